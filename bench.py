@@ -15,15 +15,22 @@ observations (whole job) per second (the Jacobian evaluations,
 which also evaluate the residual vector, are counted separately and reported
 beside it as `jacobian_evals_per_s`); LM iterations/s is reported beside it.
 
-Also reported: the one-shot C3 wall-clock (host arrays in, problem setup +
-solve + download, sfm_ba_solve -- the reference rebuilds its ceres::Problem
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only that: set-up,
+W untimed solves, the K timed solves, the outputs of the last one if
+--dump-outputs is given, and the result line.  Everything below takes runs of
+its own and is measured only with --full.
+
+With --full also reported: the per-phase times and the roofline figures (a
+profiled pass of the same solves), the CPU baseline of the same solve on the
+oracle, the one-shot C3 wall-clock (host arrays in, problem setup + solve +
+download, sfm_ba_solve -- the reference rebuilds its ceres::Problem
 per call, CTracker.cpp:672), a measured STREAM-copy bandwidth next to the
 8 TB/s peak, the frame-resident matcher (CTracker::matchFeatures, 2k x 2k
 64-B descriptors), the C5 tracker, the keyframe-sized solve, the per-frame
 PnP and the C5 pipeline end to end (KLT + PnP + triangulation + BA after
 every keyframe).
 
-Launch:  python bench.py [--gpus N --steps K --warmup W]
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
    N>1:  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 from __future__ import annotations
@@ -569,12 +576,34 @@ def factor_layout(args, world: int, strong: bool) -> int:
     return 8 if (world > 1 and strong) else 0
 
 
+def profiled_pass(ba, opts, steps: int) -> dict:
+    """Phase breakdown from a separate pass of the same solves (--full; the
+    HIP events it records stay out of the timed region).  That pass runs the
+    host-driven LM loop (the same kernels): the device-driven loop also
+    enqueues phases that its flags then skip, which would count as launches."""
+    prev_host_lm = os.environ.get("SFM_HOST_LM")
+    os.environ["SFM_HOST_LM"] = "1"
+    ba.set_profiling(True)
+    for _ in range(steps):
+        ba.reset()
+        ba.solve(opts)
+    ba.sync()
+    phases = ba.phase_times()
+    ba.set_profiling(False)
+    if prev_host_lm is None:
+        del os.environ["SFM_HOST_LM"]
+    else:
+        os.environ["SFM_HOST_LM"] = prev_host_lm
+    return phases
+
+
 def measure_ba(cams: int, P_total: int, p_begin: int, p_end: int, seed: int, strong: bool, args, world: int,
-               rank: int, local_rank: int, dist, comm: bool) -> dict:
+               rank: int, local_rank: int, dist, comm: bool, profile: bool, keep_outputs: bool = False) -> dict:
     """One BA workload: the scene's landmark shard [p_begin, p_end) set up
     resident, W untimed solves, then K timed solves (device reset + LM to
-    Ceres' termination) between barriers, max over ranks; then a profiled
-    pass of the same solves for the phase times."""
+    Ceres' termination) between barriers, max over ranks; with `profile`, then
+    a profiled pass of the same solves for the phase times.  `keep_outputs`
+    downloads what the last timed solve left (after the clock has stopped)."""
     import torch
     import sfm_amd
     from sfm_amd import scene as S
@@ -611,10 +640,10 @@ def measure_ba(cams: int, P_total: int, p_begin: int, p_end: int, seed: int, str
         print(f"[bench] set_problem {setup_s:.2f} s, warm-up done", file=sys.stderr, flush=True)
     t0 = time.perf_counter()
     iters = evals = jevals = 0
-    last = None
+    last = last_trace = None
     for _ in range(args.steps):
         ba.reset()
-        sm, _ = ba.solve(opts)
+        sm, last_trace = ba.solve(opts)
         iters += sm.num_iterations
         evals += sm.num_residual_evaluations
         jevals += sm.num_jacobian_evaluations
@@ -627,28 +656,19 @@ def measure_ba(cams: int, P_total: int, p_begin: int, p_end: int, seed: int, str
         elapsed = float(t.item())
     if rank == 0:
         print(f"[bench] timed: {elapsed / max(1, args.steps) * 1e3:.3f} ms per solve", file=sys.stderr, flush=True)
-    # phase breakdown from a separate pass of the same solves (the HIP events
-    # it records stay out of the timed region above).  That pass runs the
-    # host-driven LM loop (the same kernels): the device-driven loop also
-    # enqueues phases that its flags then skip, which would count as launches
-    prev_host_lm = os.environ.get("SFM_HOST_LM")
-    os.environ["SFM_HOST_LM"] = "1"
-    ba.set_profiling(True)
-    for _ in range(args.steps):
-        ba.reset()
-        ba.solve(opts)
-    ba.sync()
-    phases = ba.phase_times()
-    ba.set_profiling(False)
-    if prev_host_lm is None:
-        del os.environ["SFM_HOST_LM"]
-    else:
-        os.environ["SFM_HOST_LM"] = prev_host_lm
+    outputs = None
+    if keep_outputs:
+        rot, t, X = ba.parameters()
+        outputs = {"rot": rot, "t": t, "X": X, "summary": last, "trace": last_trace}
+    phases = {}
+    if profile:
+        phases = profiled_pass(ba, opts, args.steps)
     n_obs_total = VIEWS * P_total   # every point has VIEWS observations
     res_only = evals - jevals       # residual-only (candidate) evaluations
     return {"ba": ba, "sc": sc, "elapsed": elapsed, "iters": iters, "evals": evals, "jevals": jevals, "last": last,
             "phases": phases, "setup_s": setup_s, "n_obs_total": n_obs_total, "n_pts_total": P_total,
-            "res_only": res_only, "value": n_obs_total * res_only / elapsed, "strong": strong, "dist_pt": dist_pt}
+            "res_only": res_only, "value": n_obs_total * res_only / elapsed, "strong": strong, "dist_pt": dist_pt,
+            "outputs": outputs}
 
 
 def ba_summary(m: dict, args, world: int) -> dict:
@@ -666,7 +686,7 @@ def ba_summary(m: dict, args, world: int) -> dict:
         "jacobian_evals_per_solve": m["jevals"] / args.steps,
         "final_cost": last.final_cost if last else None,
         "set_problem_s": round(m["setup_s"], 4),
-        "phase_ms_per_solve": {k: round(v["ms"] / args.steps, 4) for k, v in phases.items()},
+        **({"phase_ms_per_solve": {k: round(v["ms"] / args.steps, 4) for k, v in phases.items()}} if phases else {}),
         "workload": {"cams": sc.n_cams, "points": m["n_pts_total"], "observations": m["n_obs_total"],
                      "points_per_gpu": sc.n_pts, "obs_per_gpu": sc.n_obs, "views_per_point": VIEWS,
                      "parallelism": f"landmark-sharded x{world}" if world > 1 else "single GPU",
@@ -677,11 +697,49 @@ def ba_summary(m: dict, args, world: int) -> dict:
     }
 
 
+DUMP_X_BYTES = 48 << 20   # the parameter blocks beside it are small: below 64 MB in all
+DUMP_SUMMARY_FIELDS = ("termination_type", "num_iterations", "num_successful_steps", "num_unsuccessful_steps",
+                       "num_invalid_steps", "num_residual_evaluations", "num_jacobian_evaluations", "num_linear_solves",
+                       "initial_cost", "final_cost")
+DUMP_TRACE_FIELDS = ("iteration", "step_is_valid", "step_is_successful", "cost", "cost_change", "gradient_max_norm",
+                     "step_norm", "relative_decrease", "trust_region_radius")
+
+
+def dump_outputs(dirname: str, outputs: dict, world: int, rank: int) -> None:
+    """--dump-outputs: what the last timed solve handed back, as float64 .npy
+    files: the adjusted parameter blocks (rot, t: cameras, replicated; X: this
+    rank's landmark shard), the summary's counts and costs and the iteration
+    trace (no wall-clock fields: two runs of one build write equal files).  An
+    X above DUMP_X_BYTES / world is cut to a fixed seeded sample of its rows."""
+    os.makedirs(dirname, exist_ok=True)
+    X = outputs["X"]
+    cap = DUMP_X_BYTES // world // X[0].nbytes
+    if X.shape[0] > cap:
+        X = X[np.sort(np.random.default_rng(SEED).choice(X.shape[0], cap, replace=False))]
+    np.save(os.path.join(dirname, "X.npy" if world == 1 else f"X_rank{rank}.npy"), X)
+    if rank != 0:
+        return
+    np.save(os.path.join(dirname, "rot.npy"), outputs["rot"])
+    np.save(os.path.join(dirname, "t.npy"), outputs["t"])
+    sm = outputs["summary"]
+    np.save(os.path.join(dirname, "summary.npy"),
+            np.array([getattr(sm, k) for k in DUMP_SUMMARY_FIELDS], dtype=np.float64))
+    np.save(os.path.join(dirname, "trace.npy"),
+            np.array([[it[k] for k in DUMP_TRACE_FIELDS] for it in outputs["trace"]],
+                     dtype=np.float64).reshape(-1, len(DUMP_TRACE_FIELDS)))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: phase times and roofline (a profiled pass), STREAM copy, the one-shot "
+                         "solve, the CPU baselines, the tracker / matcher / keyframe / PnP / pipeline / BRISK legs and, "
+                         "at N>1, the weak-scaling workload (the --no-* options below drop single parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed solve returned (rot, t, X, summary, trace) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--pts-per-gpu", type=int, default=0,
                     help="weak scaling: this many points per rank (default at N=1: C3's 200k)")
@@ -689,13 +747,14 @@ def main() -> int:
     ap.add_argument("--total-pts", type=int, default=0,
                     help="strong scaling: this many points in total, split into landmark shards over the ranks "
                          "(BASELINE config C4: --cams 2000 --total-pts 1000000; the default headline at N>1)")
-    ap.add_argument("--phases", action="store_true", help="print the per-phase breakdown to stderr")
+    ap.add_argument("--phases", action="store_true",
+                    help="print the per-phase breakdown to stderr (runs the profiled pass, as --full does)")
     ap.add_argument("--no-tracker", action="store_true", help="skip the C5 tracker / matcher / keyframe legs")
     ap.add_argument("--no-oneshot", action="store_true", help="skip the one-shot C3 leg")
     ap.add_argument("--no-stream-copy", action="store_true",
                     help="skip the STREAM-copy reference (kernel traces of the BA kernels alone)")
     ap.add_argument("--c4-n1", action="store_true",
-                    help="N=1: also measure BASELINE C4 on this GPU (the N=1 point of the strong-scaling curve the "
+                    help="N=1, with --full: also measure BASELINE C4 on this GPU (the N=1 point of the strong-scaling curve the "
                          "N>1 lines report; off by default so that a kernel trace of the default command holds the "
                          "C3 headline's kernels only)")
     ap.add_argument("--dist-pt", type=int, default=-1,
@@ -706,6 +765,10 @@ def main() -> int:
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check: ranks rendezvous and report the world, no GPU call")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.c4_n1 and not args.full:
+        ap.error("--c4-n1 is a part of --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(sys.argv[1:])
@@ -751,9 +814,61 @@ def main() -> int:
     else:
         per = P_total // world
         p_begin, p_end = rank * per, (rank + 1) * per
-    m = measure_ba(cams, P_total, p_begin, p_end, seed, strong, args, world, rank, local_rank, dist, args.comm)
-    ba, sc, phases = m["ba"], m["sc"], m["phases"]
+    m = measure_ba(cams, P_total, p_begin, p_end, seed, strong, args, world, rank, local_rank, dist, args.comm,
+                   profile=args.full or args.phases, keep_outputs=bool(args.dump_outputs))
     head = ba_summary(m, args, world)
+
+    wl = head.pop("workload")
+    if strong:
+        wname = (f"{cams} cams / {P_total} points / {m['n_obs_total']} obs in total"
+                 + (" (BASELINE C4)" if (cams, P_total) == C4 else "")
+                 + ", landmark-sharded over the ranks (strong scaling): full BA solve (LM + DENSE_SCHUR, "
+                   "Ceres default options)")
+    else:
+        wname = ("C3 per GPU" if (cams, P_total // world) == (CAMS, PTS_PER_GPU) else
+                 f"{cams} cams / {P_total // world} points per GPU") + \
+                ": full BA solve (LM + DENSE_SCHUR, Ceres default options)"
+    out = {
+        "metric": "BA iterations/sec + residual-evals/sec (cams x pts x obs); 1/2/4/8 GPU",
+        "value": head.pop("value"),
+        "unit": "residual-evals/s (obs x evaluations)",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": head.pop("ms_per_step"),
+        "higher_is_better": True,
+        "scaling": head.pop("scaling"),
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (seeded object-scanning scene, SURVEY.md §8d; K from main/main.cpp:47-50)",
+        "config": dict({"workload": wname}, **wl),
+    }
+    out.update(head)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, m["outputs"], world, rank)
+    ba = m["ba"]
+    if args.full:
+        ba = full_report(out, m, args, world, rank, local_rank, dist, explicit)
+    else:
+        out["cpu_baseline"] = None
+    if args.phases and rank == 0:
+        print(json.dumps(m["phases"], indent=1), file=sys.stderr)
+    if rank == 0:
+        print(json.dumps(out))
+    if ba is not None:
+        ba.close()
+    if world > 1:
+        dist.destroy_process_group()
+    return 0
+
+
+def full_report(out: dict, m: dict, args, world: int, rank: int, local_rank: int, dist, explicit: bool):
+    """--full: everything beside the headline, added to the result line `out`:
+    the roofline figures of the profiled pass, the second workload at N > 1,
+    STREAM copy, the one-shot solve, C4 at N = 1 (--c4-n1), the CPU baseline
+    and the tracker / matcher / keyframe / PnP / pipeline / BRISK legs.
+    Returns the headline's solver handle, or None once a leg has closed it."""
+    ba, sc, phases = m["ba"], m["sc"], m["phases"]
 
     jac = phases["jacobian"]
     # The solve's Jacobian pass is record-free (cost + U_c/b_c partials only;
@@ -826,39 +941,13 @@ def main() -> int:
                      "mfma_busy_frac")}
     roofline = roof_chol if dominant == "cholesky" else roof_jac
 
-    wl = head.pop("workload")
-    if strong:
-        wname = (f"{cams} cams / {P_total} points / {m['n_obs_total']} obs in total"
-                 + (" (BASELINE C4)" if (cams, P_total) == C4 else "")
-                 + ", landmark-sharded over the ranks (strong scaling): full BA solve (LM + DENSE_SCHUR, "
-                   "Ceres default options)")
-    else:
-        wname = ("C3 per GPU" if (cams, P_total // world) == (CAMS, PTS_PER_GPU) else
-                 f"{cams} cams / {P_total // world} points per GPU") + \
-                ": full BA solve (LM + DENSE_SCHUR, Ceres default options)"
-    out = {
-        "metric": "BA iterations/sec + residual-evals/sec (cams x pts x obs); 1/2/4/8 GPU",
-        "value": head.pop("value"),
-        "unit": "residual-evals/s (obs x evaluations)",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": head.pop("ms_per_step"),
-        "higher_is_better": True,
-        "scaling": head.pop("scaling"),
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (seeded object-scanning scene, SURVEY.md §8d; K from main/main.cpp:47-50)",
-        "config": dict({"workload": wname}, **wl),
-    }
-    out.update(head)
     out.update({"roofline": roofline, "roofline_jacobian": roof_jac, "roofline_jacobian_records": roof_jac_rec,
                 "roofline_cholesky": roof_chol})
     if world > 1 and not explicit:
         # weak scaling beside the strong headline: C3 per rank
         ba.close()
         mw = measure_ba(CAMS, PTS_PER_GPU * world, rank * PTS_PER_GPU, (rank + 1) * PTS_PER_GPU, SEED, False,
-                        args, world, rank, local_rank, dist, False)
+                        args, world, rank, local_rank, dist, False, profile=True)
         wk = ba_summary(mw, args, world)
         wk["workload"] = dict({"workload": "C3 per GPU (weak scaling): full BA solve"}, **wk["workload"])
         out["weak_c3_per_gpu"] = wk
@@ -874,7 +963,8 @@ def main() -> int:
         # the N = 1 point of the C4 strong-scaling curve (N > 1 lines report C4)
         if ba is not None:
             ba.close()
-        m4 = measure_ba(C4[0], C4[1], 0, C4[1], SEED + 1, True, args, 1, 0, local_rank, dist, False)
+        m4 = measure_ba(C4[0], C4[1], 0, C4[1], SEED + 1, True, args, 1, 0, local_rank, dist, False,
+                        profile=True)
         c4 = ba_summary(m4, args, 1)
         c4["workload"] = dict({"workload": "BASELINE C4 on one GPU (the N=1 point of the strong-scaling curve)"},
                               **c4["workload"])
@@ -912,15 +1002,7 @@ def main() -> int:
                           ("brisk", lambda: brisk_leg(local_rank, cb))):
             print(f"[bench] leg {name}", file=sys.stderr, flush=True)
             out[name] = leg()
-    if args.phases and rank == 0:
-        print(json.dumps(phases, indent=1), file=sys.stderr)
-    if rank == 0:
-        print(json.dumps(out))
-    if ba is not None:
-        ba.close()
-    if world > 1:
-        dist.destroy_process_group()
-    return 0
+    return ba
 
 
 if __name__ == "__main__":

@@ -171,7 +171,8 @@ def c4_n1_phases():
     """Phase times of a C4 solve on this GPU (bench.measure_ba, 3 solves)."""
     import bench
     args = argparse.Namespace(steps=3, warmup=1)
-    m = bench.measure_ba(2000, 1_000_000, 0, 1_000_000, bench.SEED + 1, True, args, 1, 0, 0, None, False)
+    m = bench.measure_ba(2000, 1_000_000, 0, 1_000_000, bench.SEED + 1, True, args, 1, 0, 0, None, False,
+                         profile=True)
     m["ba"].close()
     ph = {k: v["ms"] / 3 for k, v in m["phases"].items()}
     return m["elapsed"] / 3, ph, m["iters"] / 3
