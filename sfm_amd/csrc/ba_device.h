@@ -21,11 +21,19 @@ constexpr int kEU = 4;
 constexpr int kCamR = 36;
 // Per-camera reduction record: U (21, packed upper 6x6), b_c (6), pad.
 constexpr int kUcam = 28;
+// Per-camera record of the one-pass point-major back substitution
+// (k_backsub_pm; written by k_cam_update, copied to LDS as it stands):
+// R 9 | t 3 | K 5 | omega 3 | tau 3 | R_new 9 | t_new 3 | first-order flag |
+// pad (an odd stride: a wave's 64 cameras spread over all LDS banks).
+constexpr int kCamPM = 37;
+constexpr int kCamPMMax = 512;  // cameras whose records fit the 160-KB LDS
 // Per-point record: V (6 packed lower), b_p (3), pad | L (6), z (3), pad.
 constexpr int kPtV = 10;
 constexpr int kPtL = 10;
 // Per-point Schur record (k_schur_pts): X (3), Jacobi scale (3), L (6), 1/l_ii (3), pad: 128 B.
 constexpr int kPtS = 16;
+// Per-point record of k_schur_pairs_rot: X (3), G_p = diag(s_p) L_p^-T (G00 G01 G02 G11 G12 G22), pad: 128 B.
+constexpr int kPtG = 16;
 // Cholesky tile size.
 constexpr int kNB = 64;
 // Threads per workgroup of the observation / point kernels.
@@ -105,6 +113,8 @@ struct DevProblem {
   // per-iteration work arrays
   double* camR = nullptr;     // [C][36]
   double* camRn = nullptr;    // [C][12] candidate R (9) + t (3)
+  double* campm = nullptr;    // [C][kCamPM] k_backsub_pm's camera records (large reduced systems with
+                              // C <= kCamPMMax; nullptr: the three-pass back substitution)
   double* jrec = nullptr;     // [N_pad][20] at camera-major position (J_X 6 | r 2 | J_c 12): evaluate API only,
                               // allocated on first use (the solve writes no records)
   double* eu = nullptr;       // [N][kEU] back substitution pass A output (point-major), or
@@ -145,6 +155,8 @@ struct DevProblem {
                               // nullptr: plain block order, small systems)
   int64_t n_bslots = 0;
   double* ptS = nullptr;      // [P][kPtS] X 3, scale 3, l10 l20 l21, 1/l_ii 3, z 3, pad
+  double* ptG = nullptr;      // [P][16] X 3, G_p = diag(s_p) L_p^-T (6, upper), pad: k_schur_pairs_rot's record
+                              // (large reduced systems; nullptr: k_schur_pts and ptS alone)
   int32_t schur_pts_sub = 8;  // lanes per block (8, 16, 32 or 64; C3: 1.07 / 1.09 / 1.21 / 1.49 ms per solve)
   bool schur_wg_blocks = false;  // one block per 4-wave workgroup (small systems with long pair lists)
   // per-wave diagonal-block / rhs partials from k_obs_prep_rc ([N_pad/64][27])
@@ -200,7 +212,13 @@ void launch_pad_init(const DevProblem& d, hipStream_t s);
 void launch_pack_upper(const DevProblem& d, bool unpack, hipStream_t s);
 // dst = scale * src unless *gate == 0 (gate may be nullptr)
 void launch_gated_copy(const double* src, double* dst, int64_t n, double scale, const int32_t* gate, hipStream_t s);
-void launch_cam_update(const DevProblem& d, bool count_norm, hipStream_t s);
+// pm: also write the camera records of the one-pass back substitution (campm)
+void launch_cam_update(const DevProblem& d, bool count_norm, hipStream_t s, bool pm = false);
+// whether a step's back substitution runs as the one point-major pass
+// (k_backsub_pm: cameras and points both variable, records allocated)
+inline bool backsub_pm(const DevProblem& d, bool cams_var, bool pts_var) {
+  return d.campm && cams_var && pts_var && d.P > 0 && d.N_pad > 0;
+}
 // small systems (C <= 64): the point pass and the camera sums + finalisation
 // (k_cam_sum_finalize's work) in one launch; false when not applicable
 bool launch_point_eval_with_cams(const DevProblem& d, int mode, bool count_grad, hipStream_t s);

@@ -564,12 +564,15 @@ __global__ __launch_bounds__(kThreads * kGroups) void k_point_eval_lds(int P, in
 // With ptS != nullptr it also writes the point's 128-B record for the
 // camera-side passes (X 3 | Jacobi scale 3 | l10 l20 l21 | 1/l_ii 3 | z 3 |
 // pad): everything obs_recompute and k_schur_pts read of a point, one line.
+// With ptG != nullptr (large reduced systems) also k_schur_pairs_rot's
+// record: X and G_p = diag(s_p) L^-T.
 __global__ __launch_bounds__(kThreads) void k_point_factor(int P, const double* __restrict__ ptV,
                                                            const double* __restrict__ diag_p, double radius,
                                                            double* __restrict__ ptL, double* __restrict__ part_bad,
                                                            const double* __restrict__ X,
                                                            const double* __restrict__ scale_p,
-                                                           double* __restrict__ ptS, const int* __restrict__ gate, const double* __restrict__ radius_dev) {
+                                                           double* __restrict__ ptS, const int* __restrict__ gate, const double* __restrict__ radius_dev,
+                                                           double* __restrict__ ptG) {
   if (gate && *gate == 0) return;  // device LM loop: phase skipped
   if (radius_dev) radius = *radius_dev;  // the device LM loop's current radius
   __shared__ double sh[4];
@@ -596,6 +599,16 @@ __global__ __launch_bounds__(kThreads) void k_point_factor(int P, const double* 
       st2(o, x[0], x[1]); st2(o + 2, x[2], sp[0]); st2(o + 4, sp[1], sp[2]);
       st2(o + 6, l10, l20); st2(o + 8, l21, 1.0 / l00); st2(o + 10, 1.0 / l11, 1.0 / l22);
       st2(o + 12, z0, z1); st2(o + 14, z2, 0.0);
+    }
+    if (ptG) {
+      // k_schur_pairs_rot's record: X and G_p = diag(s_p) L^-T (upper triangular)
+      const double* x = X + 3 * size_t(p);
+      const double* sp = scale_p + 3 * size_t(p);
+      const double i00 = 1.0 / l00, i11 = 1.0 / l11, i22 = 1.0 / l22;
+      const double li10 = -l10 * i00 * i11, li21 = -l21 * i11 * i22, li20 = -(l20 * i00 + l21 * li10) * i22;
+      double* o = ptG + size_t(kPtG) * p;
+      st2(o, x[0], x[1]); st2(o + 2, x[2], sp[0] * i00); st2(o + 4, sp[0] * li10, sp[0] * li20);
+      st2(o + 6, sp[1] * i11, sp[1] * li21); st2(o + 8, sp[2] * i22, 0.0);
     }
   }
   const double r = block_reduce(bad, sh, true);
@@ -1149,78 +1162,192 @@ __global__ __launch_bounds__(kThreads, 3) void k_schur_pts(int64_t n_slots, cons
   }
 }
 
-// A register-lighter form of k_schur_pts (built to be
-// measured; SFM_SCHUR_HALVES=1): two passes over every pair list, pass kHalf
-// accumulating only rows 3 kHalf .. 3 kHalf + 2 of the 6x6 block (18 sums
-// instead of 36, 36 VGPRs fewer), at __launch_bounds__(kThreads, 4) for a
-// fourth wave per SIMD.  Pass 1's rows [H Q_2 | H] need no Q_1; pass 0 does
-// everything but half of the accumulation.  Every entry takes the full
-// kernel's operations in its order, and the lane reduction pairs lanes in the
-// same tree, so S is bitwise the one-pass kernel's.
-template <int kSub, int kHalf>
-__global__ __launch_bounds__(kThreads, 4) void k_schur_pts_half(int64_t n_slots, const int2* __restrict__ blk,
-                                                             const int32_t* __restrict__ seg,
-                                                             const int32_t* __restrict__ bpts,
-                                                             const double* __restrict__ ptS,
-                                                             const double* __restrict__ camR,
-                                                             const double* __restrict__ cam,
-                                                             const double* __restrict__ Kc,
-                                                             const double* __restrict__ scale_c, double* __restrict__ S,
-                                                             int ld, const int32_t* __restrict__ bperm,
-                                                             const int* __restrict__ gate) {
-  if (gate && *gate == 0) return;
+// k_schur_pairs_rot: k_schur_pts<kSub, 1> for large reduced systems, with the
+// rotation columns taken from the ROTATED point.  With [j_k]x = dR_k R^T,
+// dR_k X = j_k x y (y = R X), i.e. Q = [dR_0 X | dR_1 X | dR_2 X] = -[y]x J
+// with J = [j_0 j_1 j_2], and a pair's [Q_1 | I]^T H [Q_2 | I] becomes
+//   [ J_1^T ([y_1]x H [y_2]x^T) J_2   J_1^T ([y_1]x H) ]
+//   [        (H [y_2]x^T) J_2                  H        ]
+// The lane sums the four 3x3 quadrants in parentheses (cross products of H's
+// rows and columns: ~80 operations per pair against ~150 for Q_1, Q_2, H Q_2
+// and the products), and applies J_1^T and J_2 once per block, before the
+// lane reduction.  In the loop a camera costs 15 LDS doubles (R, t, fx, sk,
+// fy) and a flag instead of 50.  A camera whose dR/dw is exactly [e_k]x (the
+// first-order branch of rotation()) is flagged: J = I and y = X there, which
+// is that branch's Q exactly.  The point record (ptG, written by
+// k_point_factor beside ptS) holds X and G_p = diag(s_p) L_p^-T (upper
+// triangular), so M = (A R) G_p: 80 B of one 128-B line per pair.
+// Entry i (row-major, 0..8) of [e_k]x = d([w]x)/dw_k: +1 at (k+2, k+1), -1 at
+// (k+1, k+2), indices mod 3 -- what rotation()'s first-order branch stores as
+// dR/dw_k.  A camera whose 27 dR/dw entries equal these is a first-order
+// camera, for k_schur_pairs_rot's staging and for cam_pm_pack alike.
+__device__ __forceinline__ double skew_basis_entry(int k, int i) {
+  const int r = i / 3, q = i % 3;
+  return (r == (k + 2) % 3 && q == (k + 1) % 3) ? 1.0 : (r == (k + 1) % 3 && q == (k + 2) % 3) ? -1.0 : 0.0;
+}
+constexpr int kCamSR = 32;  // R 9 | t 3 | fx sk fy | flag | J 9 (row-major) | scale 6 | pad
+
+// The wave's kPer blocks staged together: lane l serves block q = l % kPer
+// with its kSub = 64 / kPer lanes j = l / kPer.  Every lane runs every load on
+// clamped indices, and the values a select picks from are made opaque first
+// (the compiler otherwise sinks each load into a branch with a wait of its
+// own: ~5 serial L2 round trips per block), so the loads of all blocks are in
+// flight together.
+template <int kSub>
+__device__ __forceinline__ void stage_cams_rot(double* cs_wave, int cx, int cy, const double* __restrict__ camR,
+                                               const double* __restrict__ cam, const double* __restrict__ Kc,
+                                               const double* __restrict__ scale_c, int l) {
   constexpr int kPer = 64 / kSub;
-  __shared__ __attribute__((aligned(16))) double cst[kThreads / 64][kPer][2 * kCamS];
+  const int q = l % kPer, j = l / kPer;
+  // first-order cameras: dR/dw_k == [e_k]x, entry by entry; this lane checks
+  // entries j, j + kSub, .. of the two cameras' 54, then the block's lanes
+  // are combined through one ballot per side
+  bool ok0 = true, ok1 = true;
+#pragma unroll
+  for (int idx0 = 0; idx0 < 54; idx0 += kSub) {
+    const int idx = min(idx0 + j, 53);
+    const int side = idx >= 27, en = idx - 27 * side;
+    const bool ok = camR[size_t(kCamR) * (side ? cy : cx) + 9 + en] == skew_basis_entry(en / 9, en % 9);
+    ok0 = ok0 & (bool(side) | ok);  // (bitwise: no branch around the load)
+    ok1 = ok1 & (!side | ok);
+  }
+  unsigned long long mask = 0;  // the lanes of block q
+#pragma unroll
+  for (int t = 0; t < kSub; ++t) mask |= 1ull << (kPer * t);
+  mask <<= q;
+  const bool fo0 = (__ballot(ok0) & mask) == mask, fo1 = (__ballot(ok1) & mask) == mask;
+#pragma unroll
+  for (int i0 = 0; i0 < 64; i0 += kSub) {
+    const int i = i0 + j, side = i >> 5, hl = i & 31;
+    const int c = side ? cy : cx;
+    const bool fo = side ? fo1 : fo0;
+    const double* cr = camR + size_t(kCamR) * c;
+    // entries 16..24: J[r][k] = j_k[r] = (W_k[a][b] - W_k[b][a]) / 2, W_k = dR_k R^T, (a, b) = (r + 2, r + 1) mod 3
+    const int e = min(max(hl - 16, 0), 8);
+    const int r = e / 3, k = e % 3, a = (r + 2) % 3, b = (r + 1) % 3;
+    const double* D = cr + 9 + 9 * k;
+    // (after unrolling a compile-time fact: whether any lane's entry of this round is one of J's)
+    const bool round_has_j = kSub >= 32 || ((i0 & 31) + kSub - 1 >= 16 && (i0 & 31) <= 24);
+    double wab = 0.0, wba = 0.0;
+    if (round_has_j) {
+      wab = D[3 * a] * cr[3 * b] + D[3 * a + 1] * cr[3 * b + 1] + D[3 * a + 2] * cr[3 * b + 2];
+      wba = D[3 * b] * cr[3 * a] + D[3 * b + 1] * cr[3 * a + 1] + D[3 * b + 2] * cr[3 * a + 2];
+    }
+    asm("" : "+v"(wab), "+v"(wba));  // (not volatile: opaque, yet free to be scheduled)
+    double jv = fo ? (r == k ? 1.0 : 0.0) : 0.5 * (wab - wba);
+    // entries 0..14 and 25..30: copies
+    const double* src = hl < 9 ? cr + hl
+                      : hl < 12 ? cam + 6 * size_t(c) + 3 + (hl - 9)
+                      : hl < 15 ? Kc + 5 * size_t(c) + (hl == 14 ? 3 : hl - 12)
+                      : (hl >= 25 && hl < 31) ? scale_c + 6 * size_t(c) + (hl - 25) : cr;
+    asm("" : "+v"(src));
+    double pv = *src;
+    asm("" : "+v"(jv), "+v"(pv));
+    const double v = hl == 15 ? (fo ? 1.0 : 0.0) : (hl >= 16 && hl < 25) ? jv : pv;
+    if (hl < 31) cs_wave[(2 * q + side) * kCamSR + hl] = v;
+  }
+}
+
+// One side of a pair: y (the rotated point, or X for a first-order camera),
+// M = (A R) G_p (2x3, rows m | n) and A's coefficients (a0 a1 a2 | b1 b2).
+__device__ __forceinline__ void pair_side_rot(const double* cs, const double Xp[3], const double G[6], double y[3],
+                                              double M[6], double ab[5]) {
+  const double fx = cs[12], sk = cs[13], fy = cs[14];
+  const double y0 = cs[0] * Xp[0] + cs[1] * Xp[1] + cs[2] * Xp[2];
+  const double y1 = cs[3] * Xp[0] + cs[4] * Xp[1] + cs[5] * Xp[2];
+  const double y2 = cs[6] * Xp[0] + cs[7] * Xp[1] + cs[8] * Xp[2];
+  const double pc0 = y0 + cs[9], pc1 = y1 + cs[10], pc2 = y2 + cs[11];
+  const double iz = srcp(shared_div(pc2)), xp = pc0 * iz, yp = pc1 * iz;  // (iz bitwise 1.0 / pc2)
+  const double a0 = fx * iz, a1 = sk * iz, a2 = -(fx * xp + sk * yp) * iz;
+  const double b1 = fy * iz, b2 = -fy * yp * iz;
+  ab[0] = a0; ab[1] = a1; ab[2] = a2; ab[3] = b1; ab[4] = b2;
+  const bool fo = cs[15] != 0.0;
+  y[0] = fo ? Xp[0] : y0; y[1] = fo ? Xp[1] : y1; y[2] = fo ? Xp[2] : y2;
+  double e[6];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    e[j] = a0 * cs[j] + a1 * cs[3 + j] + a2 * cs[6 + j];
+    e[3 + j] = b1 * cs[3 + j] + b2 * cs[6 + j];
+  }
+  M[0] = e[0] * G[0]; M[1] = e[0] * G[1] + e[1] * G[3]; M[2] = e[0] * G[2] + e[1] * G[4] + e[2] * G[5];
+  M[3] = e[3] * G[0]; M[4] = e[3] * G[1] + e[4] * G[3]; M[5] = e[3] * G[2] + e[4] * G[4] + e[5] * G[5];
+}
+
+template <int kSub>
+__global__ __launch_bounds__(kThreads, 2) void k_schur_pairs_rot(int64_t n_slots, const int2* __restrict__ blk,
+                                                              const int32_t* __restrict__ seg,
+                                                              const int32_t* __restrict__ bpts,
+                                                              const double* __restrict__ ptG,
+                                                              const double* __restrict__ camR,
+                                                              const double* __restrict__ cam,
+                                                              const double* __restrict__ Kc,
+                                                              const double* __restrict__ scale_c,
+                                                              double* __restrict__ S, int ld,
+                                                              const int32_t* __restrict__ bperm,
+                                                              const int* __restrict__ gate, int* __restrict__ tile_cnt,
+                                                              int nbt) {
+  if (gate && *gate == 0) return;  // device LM loop: phase skipped
+  constexpr int kPer = 64 / kSub;  // blocks per wave
+  __shared__ __attribute__((aligned(16))) double cst[kThreads / 64][kPer][2 * kCamSR];
   const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, g = l / kSub, sl = l % kSub;
   const int64_t wb = (int64_t(blockIdx.x) * (kThreads / 64) + wv) * kPer;
+  // (block order, empty slots and the clamped, one-step-ahead index loads: as k_schur_pts)
   auto slot_blk = [&](int64_t k) -> int32_t { return k < n_slots ? (bperm ? bperm[k] : int32_t(k)) : -1; };
   const int32_t bs = slot_blk(wb + g);
   const bool own = bs >= 0;
   const int64_t b = own ? bs : 0;
   const int2 cc = blk[b];
-  double* cs1 = cst[wv][g];
-  double* cs2 = cs1 + kCamS;
-#pragma unroll
-  for (int q = 0; q < kPer; ++q) {
-    const int32_t bq = slot_blk(wb + q);
+  const double* cs1 = cst[wv][g];
+  const double* cs2 = cs1 + kCamSR;
+  {
+    const int32_t bq = slot_blk(wb + l % kPer);
     const int2 cq = blk[bq >= 0 ? bq : 0];
-    stage_cam(cst[wv][q], cq.x, camR, cam, Kc, scale_c, l);
-    stage_cam(cst[wv][q] + kCamS, cq.y, camR, cam, Kc, scale_c, l);
+    stage_cams_rot<kSub>(&cst[wv][0][0], cq.x, cq.y, camR, cam, Kc, scale_c, l);
   }
   wave_lds_sync();
   const int kb = seg[b], ke = own ? seg[b + 1] : kb;
-  double acc[18];
+  double acc[36];  // row-major 6x6: [y1]x H [y2]x^T | [y1]x H ; H [y2]x^T | H
 #pragma unroll
-  for (int e = 0; e < 18; ++e) acc[e] = 0.0;
+  for (int e = 0; e < 36; ++e) acc[e] = 0.0;
   int len = ke - kb;
 #pragma unroll
   for (int off = kSub; off < 64; off <<= 1) len = max(len, __shfl_xor(len, off));
-  int p_nx = bpts[kb + sl < ke ? kb + sl : 0];
+  // The record gather runs one step ahead, its index two steps ahead: a
+  // step's five 16-B loads are issued together at the top of the step before
+  // and waited for once (the empty asm below materialises all ten values).
+  int p_nx = bpts[kb + sl + kSub < ke ? kb + sl + kSub : 0];
+  double2 n0, n1, n2, n3, n4;
+  {
+    const double* r = ptG + size_t(kPtG) * bpts[kb + sl < ke ? kb + sl : 0];
+    n0 = ld2(r); n1 = ld2(r + 2); n2 = ld2(r + 4); n3 = ld2(r + 6); n4 = ld2(r + 8);
+  }
   for (int k0 = 0; k0 < len; k0 += kSub) {
-    asm volatile("" ::: "memory");
+    double2 x0 = n0, x1 = n1, x2 = n2, x3 = n3, x4 = n4;
+    asm volatile("" : "+v"(x0.x), "+v"(x0.y), "+v"(x1.x), "+v"(x1.y), "+v"(x2.x), "+v"(x2.y), "+v"(x3.x), "+v"(x3.y),
+                 "+v"(x4.x), "+v"(p_nx));
     const int k = kb + k0 + sl;
     const bool valid = k < ke;
-    const int p = p_nx;
-    p_nx = bpts[k + kSub < ke ? k + kSub : 0];
-    const double* r = ptS + size_t(kPtS) * p;
-    double q[12];
-#pragma unroll
-    for (int f = 0; f < 12; f += 2) {
-      const double2 x = ld2(r + f);
-      q[f] = x.x; q[f + 1] = x.y;
+    {
+      const double* r = ptG + size_t(kPtG) * p_nx;
+      n0 = ld2(r); n1 = ld2(r + 2); n2 = ld2(r + 4); n3 = ld2(r + 6); n4 = ld2(r + 8);
     }
-    const double Xp[3] = {q[0], q[1], q[2]}, sp[3] = {q[3], q[4], q[5]};
-    const double Lp[6] = {q[6], q[7], q[8], q[9], q[10], q[11]};
-    double M1[6], ab1[5], M2[6], ab2[5];
-    pair_side_m(cs1, Xp, sp, Lp, M1, ab1);
-    pair_side_m(cs2, Xp, sp, Lp, M2, ab2);
+    p_nx = bpts[k + 2 * kSub < ke ? k + 2 * kSub : 0];
+    // (fences: the loads above stay here, and each camera's constants are
+    // read from LDS where they are used, not hoisted into live registers)
+    asm volatile("" ::: "memory");
+    const double Xp[3] = {x0.x, x0.y, x1.x};
+    const double G[6] = {x1.y, x2.x, x2.y, x3.x, x3.y, x4.x};
+    double M1[6], ab1[5], y1[3], M2[6], ab2[5], y2[3];
+    pair_side_rot(cs1, Xp, G, y1, M1, ab1);
+    asm volatile("" ::: "memory");
+    pair_side_rot(cs2, Xp, G, y2, M2, ab2);
     asm volatile("" ::: "memory");
     const double w = valid ? 1.0 : 0.0;
     const double g00 = (M1[0] * M2[0] + M1[1] * M2[1] + M1[2] * M2[2]) * w;
     const double g01 = (M1[0] * M2[3] + M1[1] * M2[4] + M1[2] * M2[5]) * w;
     const double g10 = (M1[3] * M2[0] + M1[4] * M2[1] + M1[5] * M2[2]) * w;
     const double g11 = (M1[3] * M2[3] + M1[4] * M2[4] + M1[5] * M2[5]) * w;
-    double H[3][3];
+    double H[3][3];  // A_1^T G A_2
     {
       const double t00 = g00 * ab2[0], t01 = g00 * ab2[1] + g01 * ab2[3], t02 = g00 * ab2[2] + g01 * ab2[4];
       const double t10 = g10 * ab2[0], t11 = g10 * ab2[1] + g11 * ab2[3], t12 = g10 * ab2[2] + g11 * ab2[4];
@@ -1228,60 +1355,80 @@ __global__ __launch_bounds__(kThreads, 4) void k_schur_pts_half(int64_t n_slots,
       H[1][0] = ab1[1] * t00 + ab1[3] * t10; H[1][1] = ab1[1] * t01 + ab1[3] * t11; H[1][2] = ab1[1] * t02 + ab1[3] * t12;
       H[2][0] = ab1[2] * t00 + ab1[4] * t10; H[2][1] = ab1[2] * t01 + ab1[4] * t11; H[2][2] = ab1[2] * t02 + ab1[4] * t12;
     }
-    double HQ[3][3];
+    // Kx = [y1]x H: column v is y1 x H[:, v]
+    double Kx[3][3];
 #pragma unroll
-    for (int kq = 0; kq < 3; ++kq) {
-      const double* D = cs2 + 9 + 9 * kq;
-      const double q0 = D[0] * Xp[0] + D[1] * Xp[1] + D[2] * Xp[2];
-      const double q1 = D[3] * Xp[0] + D[4] * Xp[1] + D[5] * Xp[2];
-      const double q2 = D[6] * Xp[0] + D[7] * Xp[1] + D[8] * Xp[2];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) HQ[i][kq] = H[i][0] * q0 + H[i][1] * q1 + H[i][2] * q2;
+    for (int v = 0; v < 3; ++v) {
+      Kx[0][v] = y1[1] * H[2][v] - y1[2] * H[1][v];
+      Kx[1][v] = y1[2] * H[0][v] - y1[0] * H[2][v];
+      Kx[2][v] = y1[0] * H[1][v] - y1[1] * H[0][v];
     }
-    if (kHalf == 0) {
+    // A [y2]x^T: row u is y2 x A[u, :]
 #pragma unroll
-      for (int u = 0; u < 3; ++u) {
-        const double* D = cs1 + 9 + 9 * u;
-        const double q0 = D[0] * Xp[0] + D[1] * Xp[1] + D[2] * Xp[2];
-        const double q1 = D[3] * Xp[0] + D[4] * Xp[1] + D[5] * Xp[2];
-        const double q2 = D[6] * Xp[0] + D[7] * Xp[1] + D[8] * Xp[2];
+    for (int u = 0; u < 3; ++u) {
+      acc[6 * u + 0] += y2[1] * Kx[u][2] - y2[2] * Kx[u][1];
+      acc[6 * u + 1] += y2[2] * Kx[u][0] - y2[0] * Kx[u][2];
+      acc[6 * u + 2] += y2[0] * Kx[u][1] - y2[1] * Kx[u][0];
+      acc[6 * u + 3] += Kx[u][0]; acc[6 * u + 4] += Kx[u][1]; acc[6 * u + 5] += Kx[u][2];
+      acc[6 * (3 + u) + 0] += y2[1] * H[u][2] - y2[2] * H[u][1];
+      acc[6 * (3 + u) + 1] += y2[2] * H[u][0] - y2[0] * H[u][2];
+      acc[6 * (3 + u) + 2] += y2[0] * H[u][1] - y2[1] * H[u][0];
+      acc[6 * (3 + u) + 3] += H[u][0]; acc[6 * (3 + u) + 4] += H[u][1]; acc[6 * (3 + u) + 5] += H[u][2];
+    }
+  }
+  // once per block: rows 0..2 <- J_1^T rows, then columns 0..2 <- columns J_2
+  {
+    const double* J1 = cs1 + 16;
+    const double* J2 = cs2 + 16;
 #pragma unroll
-        for (int v = 0; v < 3; ++v) {
-          acc[6 * u + v] += q0 * HQ[0][v] + q1 * HQ[1][v] + q2 * HQ[2][v];
-          acc[6 * u + 3 + v] += q0 * H[0][v] + q1 * H[1][v] + q2 * H[2][v];
-        }
-      }
-    } else {
+    for (int v = 0; v < 6; ++v) {
+      const double a0 = acc[v], a1 = acc[6 + v], a2 = acc[12 + v];
 #pragma unroll
-      for (int u = 0; u < 3; ++u)
+      for (int k = 0; k < 3; ++k) acc[6 * k + v] = J1[k] * a0 + J1[3 + k] * a1 + J1[6 + k] * a2;
+    }
 #pragma unroll
-        for (int v = 0; v < 3; ++v) {
-          acc[6 * u + v] += HQ[u][v];
-          acc[6 * u + 3 + v] += H[u][v];
-        }
+    for (int u = 0; u < 6; ++u) {
+      const double a0 = acc[6 * u], a1 = acc[6 * u + 1], a2 = acc[6 * u + 2];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) acc[6 * u + k] = a0 * J2[k] + a1 * J2[3 + k] + a2 * J2[6 + k];
     }
   }
   double v32[32];
 #pragma unroll
-  for (int e = 0; e < 32; ++e) v32[e] = e < 18 ? acc[e] : 0.0;
+  for (int e = 0; e < 32; ++e) v32[e] = acc[e];
   seg_reduce32<kSub>(v32, l);
+  const double t32 = seg_sum<kSub>(acc[32]), t33 = seg_sum<kSub>(acc[33]), t34 = seg_sum<kSub>(acc[34]),
+               t35 = seg_sum<kSub>(acc[35]);
   if (own) {
+    // (a diagonal block: same-camera duplicate pairs only, added to k_schur_diag_sum's)
     double* Sb = S + size_t(6 * cc.x) * ld + 6 * size_t(cc.y);
     const bool add = cc.x == cc.y;
-    const double* sc1 = cst[wv][g] + 44;
-    const double* sc2 = sc1 + kCamS;
+    const double* sc1 = cs1 + 25;
+    const double* sc2 = cs2 + 25;
     auto put = [&](int e, double v) {
       double* q = Sb + size_t(e / 6) * ld + e % 6;
       v = v * sc1[e / 6] * sc2[e % 6];
-      *q = add ? *q - v : -v;
+      v = add ? *q - v : -v;
+      // overlapped with the factorisation: write-through, counted per tile
+      if (tile_cnt) __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else *q = v;
     };
     constexpr int kR = kSub >= 32 ? 1 : 32 / kSub;
     if (kSub == 64) {
-      if (!(sl & 1) && (sl >> 1) < 18) put(18 * kHalf + (sl >> 1), v32[0]);
+      if (!(sl & 1)) put(sl >> 1, v32[0]);
     } else {
 #pragma unroll
-      for (int r = 0; r < kR; ++r)
-        if (kR * sl + r < 18) put(18 * kHalf + kR * sl + r, v32[r]);
+      for (int r = 0; r < kR; ++r) put(kR * sl + r, v32[r]);
+    }
+    if (sl < 4) put(32 + sl, sl == 0 ? t32 : sl == 1 ? t33 : sl == 2 ? t34 : t35);
+  }
+  if (tile_cnt) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (as k_schur_pts: the block is out, then counted)
+    if (own && sl == 0) {
+      const int r0 = 6 * cc.y, c0 = 6 * cc.x;
+      for (int I = r0 / 64; I <= (r0 + 5) / 64; ++I)
+        for (int J = c0 / 64; J <= (c0 + 5) / 64; ++J)
+          __hip_atomic_fetch_add(tile_cnt + I * nbt + J, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
 }
@@ -1348,16 +1495,64 @@ __global__ void k_pad_init(double* __restrict__ S, int ld, int n, int* __restric
 
 // ---------------------------------------------------------------------------
 // Camera candidate: delta = -y (scaled space), dx = s * delta.
+// Camera c's record for k_backsub_pm (kCamPM doubles).  With [j_k]x = dR_k
+// R^T the rotation columns of the Jacobian are dR_k X = j_k x (R X), so
+//   e_o = J_c,o y_c = A_o (omega x (R X) + tau),
+//   omega = sum_k s_k y_k j_k,  tau = s_t o y_t
+// (A_o = dr/dpc): 6 doubles per camera instead of dR/dw's 27.  A camera whose
+// dR/dw is exactly [e_k]x (the first-order branch of rotation(): R X is
+// X + w x X there, and dR_k X = e_k x X) is flagged: omega = s_w o y_w and the
+// cross product takes X itself, which is that branch's e_o exactly.
+__device__ __forceinline__ void cam_pm_pack(int c, const double* __restrict__ camR, const double* __restrict__ cam,
+                                            const double* __restrict__ Kc, const double* __restrict__ ysol,
+                                            const double* __restrict__ scale_c, const double* camRn,
+                                            double* __restrict__ campm) {
+  const double* cr = camR + size_t(kCamR) * c;
+  double* o = campm + size_t(kCamPM) * c;
+  double R[9], sy[6];
+  for (int i = 0; i < 9; ++i) R[i] = cr[i];
+  for (int k = 0; k < 6; ++k) sy[k] = scale_c[6 * c + k] * ysol[6 * c + k];
+  bool first_order = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int i = 0; i < 9; ++i)  // (bitwise &: all 27 loads together, no branch and wait per entry)
+      first_order = first_order & (cr[9 + 9 * k + i] == skew_basis_entry(k, i));
+  double om[3] = {sy[0], sy[1], sy[2]};
+  if (!first_order) {
+    om[0] = om[1] = om[2] = 0.0;
+    for (int k = 0; k < 3; ++k) {
+      const double* D = cr + 9 + 9 * k;
+      double W[9];  // dR_k R^T: skew up to rounding, its antisymmetric part taken
+      for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) W[3 * i + j] = D[3 * i] * R[3 * j] + D[3 * i + 1] * R[3 * j + 1] + D[3 * i + 2] * R[3 * j + 2];
+      om[0] += 0.5 * (W[7] - W[5]) * sy[k];
+      om[1] += 0.5 * (W[2] - W[6]) * sy[k];
+      om[2] += 0.5 * (W[3] - W[1]) * sy[k];
+    }
+  }
+  for (int i = 0; i < 9; ++i) o[i] = R[i];
+  for (int i = 0; i < 3; ++i) o[9 + i] = cam[6 * c + 3 + i];
+  for (int i = 0; i < 5; ++i) o[12 + i] = Kc[5 * size_t(c) + i];
+  for (int i = 0; i < 3; ++i) { o[17 + i] = om[i]; o[20 + i] = sy[3 + i]; }
+  for (int i = 0; i < 12; ++i) o[23 + i] = camRn[12 * size_t(c) + i];  // (this thread's own stores, cam_update_one)
+  o[35] = first_order ? 1.0 : 0.0;
+  o[36] = 0.0;
+}
+
 __global__ __launch_bounds__(kThreads) void k_cam_update(int C, const double* __restrict__ cam,
                                                          const double* __restrict__ ysol,
                                                          const double* __restrict__ scale_c,
                                                          double* __restrict__ cam_new, double* __restrict__ camRn,
-                                                         double* __restrict__ part_step, double* __restrict__ part_bad, const int* __restrict__ gate) {
+                                                         double* __restrict__ part_step, double* __restrict__ part_bad, const int* __restrict__ gate,
+                                                         const double* __restrict__ camR, const double* __restrict__ Kc,
+                                                         double* __restrict__ campm) {
   if (gate && *gate == 0) return;  // device LM loop: phase skipped
   __shared__ double sh[4];
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   double st = 0.0, bad = 0.0;
   if (c < C) cam_update_one(c, cam, ysol, scale_c, cam_new, camRn, st, bad);
+  if (c < C && campm) cam_pm_pack(c, camR, cam, Kc, ysol, scale_c, camRn, campm);
   const double rs = block_reduce(st, sh, false);
   if (threadIdx.x == 0 && part_step) part_step[blockIdx.x] = rs;
   const double rb = block_reduce(bad, sh, true);
@@ -1566,6 +1761,139 @@ __global__ __launch_bounds__(kThreads) void k_backsub_c(const int32_t* __restric
   if (threadIdx.x == 0) part_cost[blockIdx.x] = r;
 }
 
+// Passes A, B and C as ONE point-major launch (large reduced systems with
+// C <= kCamPMMax, both blocks variable): one lane per point,
+// every camera's record (cam_pm_pack, kCamPM doubles) in LDS.  The lane's
+// first loop over its observations recomputes the residual, J_X and
+// e = A (omega x (R X) + tau) and sums h = sum J_X^T e and the observations'
+// model term; then s = L^-1 h is pass A's sum of u, and y_p, the point's
+// model term, X_new and the step follow as in k_backsub_b; its second loop is
+// the candidate residual at (R_new, t_new, X_new).  No eu: 64 MB written and
+// read back at C3, and two launches, less.  Organised as
+// k_point_eval_lds<512, 2>: group g of 256 threads stands for the 256-point
+// block blockIdx.x * kGroups + g and reduces its own four waves in order.
+template <int kGroups>
+__global__ __launch_bounds__(kThreads * kGroups) void k_backsub_pm(
+    int P, int C, const int32_t* __restrict__ pt_off, const int32_t* __restrict__ cam_pm,
+    const double* __restrict__ uv_pm, const double* __restrict__ campm, const double* __restrict__ ptL,
+    const double* __restrict__ ptV, const double* __restrict__ scale_p, const double* __restrict__ X,
+    double* __restrict__ X_new, double* __restrict__ ypt, double* __restrict__ part_model,
+    double* __restrict__ part_model_pt, double* __restrict__ part_step, double* __restrict__ part_bad,
+    double* __restrict__ part_cost, const int* __restrict__ gate) {
+  if (gate && *gate == 0) return;  // device LM loop: phase skipped
+  __shared__ double sh[4 * kGroups];
+  __shared__ double cst[kCamPMMax * kCamPM];
+  for (int i = threadIdx.x; i < C * kCamPM; i += blockDim.x) cst[i] = campm[i];
+  __syncthreads();
+  const int nbp = (P + kThreads - 1) / kThreads;
+  const int grp = int(threadIdx.x) / kThreads, tg = int(threadIdx.x) % kThreads;
+  const int vb = int(blockIdx.x) * kGroups + grp;  // the 256-thread block this group stands for
+  const int p = vb * kThreads + tg;
+  double model = 0.0, model_pt = 0.0, st = 0.0, bad = 0.0, ncost = 0.0;
+  if (p < P) {
+    const double Xp[3] = {X[3 * size_t(p)], X[3 * size_t(p) + 1], X[3 * size_t(p) + 2]};
+    const double sp[3] = {scale_p[3 * size_t(p)], scale_p[3 * size_t(p) + 1], scale_p[3 * size_t(p) + 2]};
+    const int q0 = pt_off[p], q1 = pt_off[p + 1];
+    // the next observation's camera index and uv are loaded one step ahead
+    int c_n = q0 < q1 ? cam_pm[q0] : 0;
+    double2 uv_n = q0 < q1 ? ld2(uv_pm + 2 * size_t(q0)) : make_double2(0.0, 0.0);
+    double h0 = 0.0, h1 = 0.0, h2 = 0.0;  // sum J_X^T e
+    for (int q = q0; q < q1; ++q) {
+      const double* k = cst + kCamPM * c_n;
+      const double2 uvo = uv_n;
+      if (q + 1 < q1) {
+        c_n = cam_pm[q + 1];
+        uv_n = ld2(uv_pm + 2 * size_t(q + 1));
+      }
+      const double y0 = k[0] * Xp[0] + k[1] * Xp[1] + k[2] * Xp[2];
+      const double y1 = k[3] * Xp[0] + k[4] * Xp[1] + k[5] * Xp[2];
+      const double y2 = k[6] * Xp[0] + k[7] * Xp[1] + k[8] * Xp[2];
+      const double pc0 = y0 + k[9], pc1 = y1 + k[10], pc2 = y2 + k[11];
+      const double fx = k[12], sk = k[13], cx = k[14], fy = k[15], cy = k[16];
+      const double iz = srcp(shared_div(pc2)), xp = pc0 * iz, yp = pc1 * iz;  // (iz bitwise 1.0 / pc2)
+      const double r0 = fx * xp + sk * yp + cx - uvo.x;
+      const double r1 = fy * yp + cy - uvo.y;
+      const double a0 = fx * iz, a1 = sk * iz, a2 = -(fx * xp + sk * yp) * iz;
+      const double b1 = fy * iz, b2 = -fy * yp * iz;
+      // e = A (omega x yt + tau), yt = R X (X for a first-order camera)
+      const bool fo = k[35] != 0.0;
+      const double t0 = fo ? Xp[0] : y0, t1 = fo ? Xp[1] : y1, t2 = fo ? Xp[2] : y2;
+      const double d0 = k[18] * t2 - k[19] * t1 + k[20];
+      const double d1 = k[19] * t0 - k[17] * t2 + k[21];
+      const double d2 = k[17] * t1 - k[18] * t0 + k[22];
+      const double e0 = a0 * d0 + a1 * d1 + a2 * d2, e1 = b1 * d1 + b2 * d2;
+      model += e0 * r0 + e1 * r1 - 0.5 * (e0 * e0 + e1 * e1);
+      // J_X = A R, Jacobi-scaled
+      h0 += ((a0 * k[0] + a1 * k[3] + a2 * k[6]) * e0 + (b1 * k[3] + b2 * k[6]) * e1) * sp[0];
+      h1 += ((a0 * k[1] + a1 * k[4] + a2 * k[7]) * e0 + (b1 * k[4] + b2 * k[7]) * e1) * sp[1];
+      h2 += ((a0 * k[2] + a1 * k[5] + a2 * k[8]) * e0 + (b1 * k[5] + b2 * k[8]) * e1) * sp[2];
+    }
+    const double* L = ptL + size_t(kPtL) * p;
+    const double l00 = L[0], l10 = L[1], l11 = L[2], l20 = L[3], l21 = L[4], l22 = L[5];
+    // s = L^-1 h (pass A's sum of u = M^T e), w = z - s, y_p = L^-T w
+    const double s0 = h0 / l00, s1 = (h1 - l10 * s0) / l11, s2 = (h2 - l20 * s0 - l21 * s1) / l22;
+    const double w0 = L[6] - s0, w1 = L[7] - s1, w2 = L[8] - s2;
+    const double yp2 = w2 / l22;
+    const double yp1 = (w1 - l21 * yp2) / l11;
+    const double yp0 = (w0 - l10 * yp1 - l20 * yp2) / l00;
+    if (!isfinite(yp0) || !isfinite(yp1) || !isfinite(yp2)) bad = 1.0;
+    {  // the point's model term (k_backsub_b's; its h_p is h itself)
+      const double* v = ptV + size_t(kPtV) * p;
+      const double yVy = v[0] * yp0 * yp0 + v[2] * yp1 * yp1 + v[5] * yp2 * yp2 +
+                         2.0 * (v[1] * yp0 * yp1 + v[3] * yp0 * yp2 + v[4] * yp1 * yp2);
+      model_pt = yp0 * (v[6] - h0) + yp1 * (v[7] - h1) + yp2 * (v[8] - h2) - 0.5 * yVy;
+    }
+    const double ys[3] = {yp0, yp1, yp2};
+    double Xn[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      Xn[j] = Xp[j] + sp[j] * (-ys[j]);
+      const double dd = Xp[j] - Xn[j];
+      st += dd * dd;
+      X_new[3 * size_t(p) + j] = Xn[j];
+      ypt[3 * size_t(p) + j] = ys[j];
+    }
+    // candidate residual at (R_new, t_new, X_new): the same observations again
+    c_n = q0 < q1 ? cam_pm[q0] : 0;
+    uv_n = q0 < q1 ? ld2(uv_pm + 2 * size_t(q0)) : make_double2(0.0, 0.0);
+    for (int q = q0; q < q1; ++q) {
+      const double* k = cst + kCamPM * c_n;
+      const double2 uvo = uv_n;
+      if (q + 1 < q1) {
+        c_n = cam_pm[q + 1];
+        uv_n = ld2(uv_pm + 2 * size_t(q + 1));
+      }
+      const double* Rn = k + 23;
+      double pc[3];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) pc[j] = Rn[3 * j] * Xn[0] + Rn[3 * j + 1] * Xn[1] + Rn[3 * j + 2] * Xn[2] + Rn[9 + j];
+      const SharedDiv dz = shared_div(pc[2]);  // (bitwise the two divisions)
+      const double xp = sdiv(dz, pc[0]), ypj = sdiv(dz, pc[1]);
+      const double rn0 = k[12] * xp + k[13] * ypj + k[14] - uvo.x;
+      const double rn1 = k[15] * ypj + k[16] - uvo.y;
+      ncost += 0.5 * (rn0 * rn0 + rn1 * rn1);
+    }
+  }
+  // block_reduce per group: its four waves' values combined in wave order
+  const int w = int(threadIdx.x) >> 6, l = int(threadIdx.x) & 63;
+  auto group_reduce = [&](double v, bool is_max, double* __restrict__ part) {
+    v = is_max ? wave_max(v) : wave_sum(v);
+    __syncthreads();
+    if (l == 0) sh[w] = v;
+    __syncthreads();
+    if (tg == 0 && vb < nbp) {
+      double r = sh[4 * grp];
+      for (int i = 1; i < 4; ++i) r = is_max ? fmax(r, sh[4 * grp + i]) : r + sh[4 * grp + i];
+      part[vb] = r;
+    }
+  };
+  group_reduce(model, false, part_model);
+  group_reduce(model_pt, false, part_model_pt);
+  group_reduce(st, false, part_step);
+  group_reduce(bad, true, part_bad);
+  group_reduce(ncost, false, part_cost);
+}
+
 // Fixed-order final reduction of one partial slot.
 // Several fixed-order reductions in one launch (workgroup i = job i), and
 // the Cholesky failure flag copied next to the scalars (an int in the slot
@@ -1672,7 +2000,8 @@ void launch_point_eval(const DevProblem& d, int mode, bool reuse_diag, hipStream
 }
 void launch_point_factor(const DevProblem& d, double radius, hipStream_t s) {
   if (d.P) k_point_factor<<<blocks_for(d.P, kThreads), kThreads, 0, s>>>(d.P, d.ptV, d.diag_p, radius, d.ptL,
-                                                                         slot(d, kPBad), d.X, d.scale_p, d.ptS, d.gate, d.radius_dev);
+                                                                         slot(d, kPBad), d.X, d.scale_p, d.ptS, d.gate, d.radius_dev,
+                                                                         d.ptG);
 }
 void launch_point_prep(const DevProblem& d, double radius, hipStream_t s) {
   launch_point_factor(d, radius, s);
@@ -1720,19 +2049,15 @@ void launch_schur_offdiag(const DevProblem& d, int* tile_cnt, hipStream_t s) {
                                                                     bperm, d.gate, tile_cnt, d.nblk, DiagFold{});
     return;
   }
-  static const bool halves = [] {
-    const char* e = std::getenv("SFM_SCHUR_HALVES");
-    return e && e[0] == '1';
-  }();
-  if (halves && !tile_cnt) {
-#define SFM_PTS_H(S_, H_)                                                                                       \
-  k_schur_pts_half<S_, H_><<<nb, kThreads, 0, s>>>(n_slots, d.blk, d.seg, d.bpts, d.ptS, d.camR, d.cam, d.Kc, \
-                                                   d.scale_c, d.S, d.ld, bperm, d.gate)
-    if (sub == 8) { SFM_PTS_H(8, 0); SFM_PTS_H(8, 1); }
-    else if (sub == 16) { SFM_PTS_H(16, 0); SFM_PTS_H(16, 1); }
-    else if (sub == 32) { SFM_PTS_H(32, 0); SFM_PTS_H(32, 1); }
-    else { SFM_PTS_H(64, 0); SFM_PTS_H(64, 1); }
-#undef SFM_PTS_H
+  if (d.ptG) {  // large reduced systems: the rotated-point form (k_point_factor wrote ptG)
+#define SFM_ROT(S_)                                                                                              \
+  k_schur_pairs_rot<S_><<<nb, kThreads, 0, s>>>(n_slots, d.blk, d.seg, d.bpts, d.ptG, d.camR, d.cam, d.Kc, d.scale_c, \
+                                                d.S, d.ld, bperm, d.gate, tile_cnt, d.nblk)
+    if (sub == 8) SFM_ROT(8);
+    else if (sub == 16) SFM_ROT(16);
+    else if (sub == 32) SFM_ROT(32);
+    else SFM_ROT(64);
+#undef SFM_ROT
     return;
   }
   if (sub == 8) SFM_PTS(8);
@@ -1756,16 +2081,24 @@ void launch_pad_init(const DevProblem& d, hipStream_t s) {
   const int n_y = (d.n + kNB - 1) / kNB * kNB;
   k_pad_init<<<d.ld, 64, 0, s>>>(d.S, d.ld, d.n, d.fail, reinterpret_cast<unsigned long long*>(d.ysol), n_y, d.gate);
 }
-void launch_cam_update(const DevProblem& d, bool count_norm, hipStream_t s) {
+void launch_cam_update(const DevProblem& d, bool count_norm, hipStream_t s, bool pm) {
   k_cam_update<<<blocks_for(d.C, kThreads), kThreads, 0, s>>>(d.C, d.cam, d.ysol, d.scale_c, d.cam_new, d.camRn,
                                                              count_norm ? slot(d, kPStepCam) : nullptr,
-                                                             slot(d, kPBadCam), d.gate);
+                                                             slot(d, kPBadCam), d.gate, d.camR, d.Kc,
+                                                             pm ? d.campm : nullptr);
 }
 void launch_cam_solve(const DevProblem& d, double radius, hipStream_t s) {
   (void)hipMemsetAsync(d.fail, 0, sizeof(int), s);
   if (d.C) k_cam_solve<<<blocks_for(d.C, kThreads), kThreads, 0, s>>>(d.C, d.Ucam, d.diag_c, radius, d.ysol, d.fail, d.gate, d.radius_dev);
 }
 void launch_point_backsub(const DevProblem& d, hipStream_t s, bool cams_var, bool pts_var) {
+  if (backsub_pm(d, cams_var, pts_var)) {  // one point-major pass (launch_cam_update wrote campm)
+    constexpr int kG = 4;  // one 1024-thread workgroup per CU (its LDS copy is up to 148 KB)
+    k_backsub_pm<kG><<<blocks_for(d.P, kG * kThreads), kG * kThreads, 0, s>>>(
+        d.P, d.C, d.pt_off, d.cam_pm, d.uv_pm, d.campm, d.ptL, d.ptV, d.scale_p, d.X, d.X_new, d.ypt,
+        slot(d, kPModel), slot(d, kPModelPt), slot(d, kPStepPt), slot(d, kPBadBack), slot(d, kPNewCost), d.gate);
+    return;
+  }
   // cameras constant (STRUCT_ONLY): e = J_c y_c = 0 and u = 0
   if (d.N_pad && cams_var)
     k_backsub_a_rc<<<obs_xcd_blocks(d), kThreads, 0, s>>>(d.jgrp, d.jchunks, d.cm_p, d.uv_cm, d.cam_obs, d.camR,

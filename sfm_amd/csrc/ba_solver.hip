@@ -1091,9 +1091,14 @@ int compute_step_enqueue(sfm_ba_handle* h, double radius) {
     }
     hipMemsetAsync(d.ysol, 0, sizeof(double) * 6 * size_t(d.C), s);
   }
-  if (!cam_done) launch_cam_update(d, h->rank == 0 && h->mode != SFM_BA_STRUCT_ONLY, s);
+  // large reduced systems: the back substitution as one point-major pass
+  // (k_backsub_pm), its camera records written by k_cam_update
+  // (cam_done: a one-workgroup factor, never a system with campm)
+  const bool cams_var = h->mode != SFM_BA_STRUCT_ONLY, pts_var = h->mode != SFM_BA_POSE_ONLY;
+  const bool pm = backsub_pm(d, cams_var, pts_var);
+  if (!cam_done) launch_cam_update(d, h->rank == 0 && cams_var, s, pm);
   mark_begin(h, kPhBacksub);
-  launch_point_backsub(d, s, h->mode != SFM_BA_STRUCT_ONLY, h->mode != SFM_BA_POSE_ONLY);
+  launch_point_backsub(d, s, cams_var, pts_var);
   mark_end(h);
   if (d.P == 0) {
     const int slots[] = {kPModel, kPModelPt, kPNewCost, kPStepPt, kPBadBack, kPBad};
@@ -1101,8 +1106,9 @@ int compute_step_enqueue(sfm_ba_handle* h, double radius) {
   }
   if (h->rank != 0 || h->mode == SFM_BA_STRUCT_ONLY)
     hipMemsetAsync(d.partials + size_t(kPStepCam) * d.max_blocks, 0, sizeof(double) * nbC, s);
-  const int nbI = d.N_pad ? obs_xcd_blocks(d) : 1;  // k_backsub_a_rc / k_backsub_c grid
-  const int nbB = d.P ? pt_xcd_blocks(d) : 1;       // k_backsub_b grid
+  // (k_backsub_pm: every partial per 256-point block)
+  const int nbI = pm ? nbP : d.N_pad ? obs_xcd_blocks(d) : 1;  // k_backsub_a_rc / k_backsub_c grid
+  const int nbB = pm ? nbP : d.P ? pt_xcd_blocks(d) : 1;       // k_backsub_b grid
   ReduceBatch rb;
   rb.add(kPModel, nbI, 0, kModelChange);
   rb.add(kPNewCost, nbI, 0, kNewCost);
@@ -2037,6 +2043,10 @@ constexpr int64_t kDeferredUvMinObs = 262144;
   ALLOC(d.diag_p, 3 * size_t(P));
   ALLOC(d.camR, size_t(kCamR) * C);
   ALLOC(d.camRn, 12 * size_t(C));
+  // the one-pass back substitution, on the large path (the XCD-ordered Schur
+  // blocks) while every camera's record fits the LDS
+  d.campm = nullptr;
+  if (d.n_blk > kSchurXcdMinBlocks && C <= kCamPMMax) ALLOC(d.campm, size_t(kCamPM) * C);
   // pass A stores u at the camera-major position it runs at (coalesced) and
   // pass B gathers it through pos[]: 85 + 31 -> 60 + 41 us per C3 iteration
   // against the point-major scatter (SFM_EU_CM=0), S and steps bitwise equal
@@ -2049,6 +2059,8 @@ constexpr int64_t kDeferredUvMinObs = 262144;
   ALLOC(d.ptV, size_t(kPtV) * P);
   ALLOC(d.ptL, size_t(kPtL) * P);
   ALLOC(d.ptS, size_t(kPtS) * std::max(1, P));
+  d.ptG = nullptr;
+  if (d.n_blk > kSchurXcdMinBlocks) ALLOC(d.ptG, size_t(kPtG) * std::max(1, P));
   ALLOC(d.Ucam, size_t(kUcam) * C);
   ALLOC(d.jpart, 27 * std::max<size_t>(1, size_t(npad / 64)));
   ALLOC(d.dpart, 27 * std::max<size_t>(1, size_t(npad / 64)));
