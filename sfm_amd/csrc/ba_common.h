@@ -128,11 +128,12 @@ __device__ void rotation(const double w[3], double R[9], double* dR) {
 // small systems): x_new = x - scale * y, the step's squared length and a
 // non-finite flag accumulated into st / bad, the new pose and its rotation
 // matrix (camRn: R 9 | t 3).
-__device__ __forceinline__ void cam_update_one(int c, const double* __restrict__ cam, const double* __restrict__ ysol,
-                                               const double* __restrict__ scale_c, double* __restrict__ cam_new,
-                                               double* __restrict__ camRn, double& st, double& bad) {
+// cam_update_vals: the values alone (xn: the new pose, rn: R 9 | t 3), for a
+// caller that keeps them (k_backsub_pm builds its camera records from them).
+__device__ __forceinline__ void cam_update_vals(int c, const double* __restrict__ cam, const double* __restrict__ ysol,
+                                                const double* __restrict__ scale_c, double xn[6], double rn[12],
+                                                double& st, double& bad) {
 #pragma clang fp contract(fast)  // (as rotation(): k_cam_update and k_chol_small must agree bitwise)
-  double xn[6];
   for (int k = 0; k < 6; ++k) {
     const double y = ysol[6 * c + k];
     if (!isfinite(y)) bad = 1.0;
@@ -140,13 +141,18 @@ __device__ __forceinline__ void cam_update_one(int c, const double* __restrict__
     xn[k] = cam[6 * c + k] + dx;
     const double d = cam[6 * c + k] - xn[k];
     st += d * d;
-    cam_new[6 * c + k] = xn[k];
   }
-  double R[9];
-  rotation(xn, R, nullptr);
+  rotation(xn, rn, nullptr);
+  rn[9] = xn[3]; rn[10] = xn[4]; rn[11] = xn[5];
+}
+__device__ __forceinline__ void cam_update_one(int c, const double* __restrict__ cam, const double* __restrict__ ysol,
+                                               const double* __restrict__ scale_c, double* __restrict__ cam_new,
+                                               double* __restrict__ camRn, double& st, double& bad) {
+  double xn[6], rn[12];
+  cam_update_vals(c, cam, ysol, scale_c, xn, rn, st, bad);
+  for (int k = 0; k < 6; ++k) cam_new[6 * c + k] = xn[k];
   double* o = camRn + 12 * size_t(c);
-  for (int i = 0; i < 9; ++i) o[i] = R[i];
-  o[9] = xn[3]; o[10] = xn[4]; o[11] = xn[5];
+  for (int i = 0; i < 12; ++i) o[i] = rn[i];
 }
 // Wave sums of 32 values at once by recursive halving (reduce-scatter): at
 // each of the 5 exchange distances 32..2 a lane keeps half of its values and

@@ -113,8 +113,8 @@ struct DevProblem {
   // per-iteration work arrays
   double* camR = nullptr;     // [C][36]
   double* camRn = nullptr;    // [C][12] candidate R (9) + t (3)
-  double* campm = nullptr;    // [C][kCamPM] k_backsub_pm's camera records (large reduced systems with
-                              // C <= kCamPMMax; nullptr: the three-pass back substitution)
+  bool pm_backsub = false;    // large reduced systems with C <= kCamPMMax: the back substitution is
+                              // k_backsub_pm's one pass (its camera records, kCamPM doubles each, live in LDS)
   double* jrec = nullptr;     // [N_pad][20] at camera-major position (J_X 6 | r 2 | J_c 12): evaluate API only,
                               // allocated on first use (the solve writes no records)
   double* eu = nullptr;       // [N][kEU] back substitution pass A output (point-major), or
@@ -199,8 +199,13 @@ void launch_cam_finalize(const DevProblem& d, int mode, bool reuse_diag, bool co
 // (unsharded: no U_c all-reduce between them); gradient partials per camera
 void launch_cam_sum_finalize(const DevProblem& d, int mode, bool count_grad, hipStream_t s);
 // mode 0: unscaled pass -> scale_p; mode 1: V, b, diag (if !reuse), gradient, x-norm
-void launch_point_eval(const DevProblem& d, int mode, bool reuse_diag, hipStream_t s);
+// factor (mode 1): the pass also does launch_point_factor's work for the coming step's radius
+void launch_point_eval(const DevProblem& d, int mode, bool reuse_diag, hipStream_t s, bool factor = false,
+                       double radius = 0.0);
+// launch_point_factor + launch_obs_prep
 void launch_point_prep(const DevProblem& d, double radius, hipStream_t s);
+// the per-wave diagonal-block / rhs partials (k_obs_prep_rc; reads the point records)
+void launch_obs_prep(const DevProblem& d, hipStream_t s);
 void launch_point_factor(const DevProblem& d, double radius, hipStream_t s);
 void launch_schur(const DevProblem& d, double radius, bool add_diag, hipStream_t s);
 // its two parts: the diagonal blocks + rhs (k_schur_diag_sum) and the
@@ -208,21 +213,27 @@ void launch_schur(const DevProblem& d, double radius, bool add_diag, hipStream_t
 // factorisation, blocks counted per 64x64 tile as they land)
 void launch_schur_diag(const DevProblem& d, double radius, bool add_diag, hipStream_t s);
 void launch_schur_offdiag(const DevProblem& d, int* tile_cnt, hipStream_t s);
+// launch_cam_sum_finalize (mode 1, with the gradient partials) and
+// launch_schur_diag in one launch (after launch_obs_prep, in the evaluation)
+void launch_cam_sum_diag(const DevProblem& d, double radius, bool add_diag, hipStream_t s);
 void launch_pad_init(const DevProblem& d, hipStream_t s);
 void launch_pack_upper(const DevProblem& d, bool unpack, hipStream_t s);
 // dst = scale * src unless *gate == 0 (gate may be nullptr)
 void launch_gated_copy(const double* src, double* dst, int64_t n, double scale, const int32_t* gate, hipStream_t s);
-// pm: also write the camera records of the one-pass back substitution (campm)
-void launch_cam_update(const DevProblem& d, bool count_norm, hipStream_t s, bool pm = false);
+// (not on the one-pass back substitution's path: k_backsub_pm takes the camera step itself)
+void launch_cam_update(const DevProblem& d, bool count_norm, hipStream_t s);
 // whether a step's back substitution runs as the one point-major pass
-// (k_backsub_pm: cameras and points both variable, records allocated)
+// (k_backsub_pm: cameras and points both variable, on the large path)
 inline bool backsub_pm(const DevProblem& d, bool cams_var, bool pts_var) {
-  return d.campm && cams_var && pts_var && d.P > 0 && d.N_pad > 0;
+  return d.pm_backsub && cams_var && pts_var && d.P > 0 && d.N_pad > 0;
 }
 // small systems (C <= 64): the point pass and the camera sums + finalisation
 // (k_cam_sum_finalize's work) in one launch; false when not applicable
 bool launch_point_eval_with_cams(const DevProblem& d, int mode, bool count_grad, hipStream_t s);
-void launch_point_backsub(const DevProblem& d, hipStream_t s, bool cams_var = true, bool pts_var = true);
+// with backsub_pm the one pass takes the camera step too (launch_cam_update's
+// work, count_norm as there: no launch_cam_update before it)
+void launch_point_backsub(const DevProblem& d, hipStream_t s, bool cams_var = true, bool pts_var = true,
+                          bool count_norm = false);
 // grid of the XCD-ordered observation passes (k_obs_prep_rc, k_backsub_a_rc):
 // one workgroup per 4 chunks, a multiple of 8 (one point slice per XCD)
 inline int obs_xcd_blocks(const DevProblem& d) {

@@ -329,7 +329,8 @@ struct CamFold {
   int mode, C;
   double* part_grad;
 };
-__device__ __forceinline__ void cam_sum_body(int c, int t, const CamFold& f) {
+// Returns the wave's reduce-scatter (lane 2e: entry e of U_c | b_c).
+__device__ __forceinline__ double cam_sum_body(int c, int t, const CamFold& f) {
   const int w0 = f.cam_rng[2 * c] / 64, w1 = (f.cam_rng[2 * c + 1] + 63) / 64;
   double v[32];
 #pragma unroll
@@ -355,6 +356,7 @@ __device__ __forceinline__ void cam_sum_body(int c, int t, const CamFold& f) {
 #pragma unroll
   for (int off = 4; off > 0; off >>= 1) g = fmax(g, __shfl_xor(g, off));
   if (t == 0 && f.part_grad) f.part_grad[c] = g;
+  return sum;
 }
 
 __global__ __launch_bounds__(64) void k_cam_sum_finalize(const CamFold f, const int* __restrict__ gate) {
@@ -400,13 +402,63 @@ struct CamView {
   int sR, sT, sK;
 };
 
+// Point p's factorisation for one trust-region radius (k_point_factor's
+// arithmetic, also run by the mode-1 point pass on the values it holds):
+// V_p + D_p^2 = L L^T, z = L^-1 b_p -> ptL; with ptS / ptG the point's
+// records for the camera-side passes.  v: V 6 | b 3.  Returns 1.0 for a
+// non-positive pivot.
+__device__ __forceinline__ double point_factor_body(int p, const double v[9], const double dg[3], double radius,
+                                                    const double x[3], const double sp[3], double* __restrict__ ptL,
+                                                    double* __restrict__ ptS, double* __restrict__ ptG) {
+  double bad = 0.0;
+  double D[3];
+  for (int k = 0; k < 3; ++k) { const double d = sqrt(dg[k] / radius); D[k] = d * d; }
+  const double V00 = v[0] + D[0], V10 = v[1], V11 = v[2] + D[1], V20 = v[3], V21 = v[4], V22 = v[5] + D[2];
+  const double l00 = sqrt(V00);
+  const double l10 = V10 / l00, l20 = V20 / l00;
+  const double l11 = sqrt(V11 - l10 * l10);
+  const double l21 = (V21 - l20 * l10) / l11;
+  const double l22 = sqrt(V22 - l20 * l20 - l21 * l21);
+  if (!(l00 > 0.0) || !(l11 > 0.0) || !(l22 > 0.0)) bad = 1.0;
+  const double z0 = v[6] / l00, z1 = (v[7] - l10 * z0) / l11, z2 = (v[8] - l20 * z0 - l21 * z1) / l22;
+  double* L = ptL + size_t(kPtL) * p;
+  st2(L, l00, l10); st2(L + 2, l11, l20); st2(L + 4, l21, l22); st2(L + 6, z0, z1); st2(L + 8, z2, 0.0);
+  if (ptS) {
+    double* o = ptS + size_t(kPtS) * p;
+    st2(o, x[0], x[1]); st2(o + 2, x[2], sp[0]); st2(o + 4, sp[1], sp[2]);
+    st2(o + 6, l10, l20); st2(o + 8, l21, 1.0 / l00); st2(o + 10, 1.0 / l11, 1.0 / l22);
+    st2(o + 12, z0, z1); st2(o + 14, z2, 0.0);
+  }
+  if (ptG) {
+    // k_schur_pairs_rot's record: X and G_p = diag(s_p) L^-T (upper triangular)
+    const double i00 = 1.0 / l00, i11 = 1.0 / l11, i22 = 1.0 / l22;
+    const double li10 = -l10 * i00 * i11, li21 = -l21 * i11 * i22, li20 = -(l20 * i00 + l21 * li10) * i22;
+    double* o = ptG + size_t(kPtG) * p;
+    st2(o, x[0], x[1]); st2(o + 2, x[2], sp[0] * i00); st2(o + 4, sp[0] * li10, sp[0] * li20);
+    st2(o + 6, sp[1] * i11, sp[1] * li21); st2(o + 8, sp[2] * i22, 0.0);
+  }
+  return bad;
+}
+
+// What the mode-1 point pass needs to go on to the point's factorisation
+// (ptL == nullptr: it does not).  The radius is the coming step's: it
+// changes only in the step's decision, so an evaluation already has it.
+struct PointFold {
+  double radius;
+  const double* radius_dev;
+  double* ptL;
+  double* ptS;
+  double* ptG;
+  double* part_bad;
+};
+
 __device__ __forceinline__ void point_eval_body(int p, const int32_t* __restrict__ pt_off,
                                                 const int32_t* __restrict__ cam_pm,
                                                 const double* __restrict__ uv_pm, const CamView cv,
                                                 const double* __restrict__ X, double* __restrict__ scale_p,
                                                 double* __restrict__ diag_p, double* __restrict__ ptV,
                                                 double min_diag, double max_diag, int mode, int reuse, double& g,
-                                                double& xn) {
+                                                double& xn, const PointFold& pf, double& bad) {
   double V[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
   const double Xp[3] = {X[3 * size_t(p)], X[3 * size_t(p) + 1], X[3 * size_t(p) + 2]};
   double sp[3] = {1.0, 1.0, 1.0};
@@ -459,6 +511,17 @@ __device__ __forceinline__ void point_eval_body(int p, const int32_t* __restrict
     }
     double* o = ptV + size_t(kPtV) * p;
     st2(o, V[0], V[1]); st2(o + 2, V[2], V[3]); st2(o + 4, V[4], V[5]); st2(o + 6, b[0], b[1]); st2(o + 8, b[2], 0.0);
+    if (pf.ptL) {
+      // k_point_factor's inputs as it loads them (opaque: the factor's
+      // arithmetic contracts as in the stand-alone kernel, bitwise)
+      double fv[9] = {V[0], V[1], V[2], V[3], V[4], V[5], b[0], b[1], b[2]};
+      double fd[3], fx[3] = {Xp[0], Xp[1], Xp[2]}, fs[3] = {sp[0], sp[1], sp[2]};
+      for (int k = 0; k < 3; ++k) fd[k] = reuse ? diag_p[3 * size_t(p) + k] : fmin(fmax(cn[k], min_diag), max_diag);
+      double radius = pf.radius_dev ? *pf.radius_dev : pf.radius;
+      asm volatile("" : "+v"(fv[0]), "+v"(fv[1]), "+v"(fv[2]), "+v"(fv[3]), "+v"(fv[4]), "+v"(fv[5]), "+v"(fv[6]),
+                        "+v"(fv[7]), "+v"(fv[8]), "+v"(fd[0]), "+v"(fd[1]), "+v"(fd[2]), "+v"(radius));
+      bad = point_factor_body(p, fv, fd, radius, fx, fs, pf.ptL, pf.ptS, pf.ptG);
+    }
   }
 }
 
@@ -472,19 +535,25 @@ __global__ __launch_bounds__(kThreads) void k_point_eval_rc(int P, const int32_t
                                                             double* __restrict__ scale_p, double* __restrict__ diag_p,
                                                             double* __restrict__ ptV, double min_diag, double max_diag,
                                                             int mode, int reuse, double* __restrict__ part_grad,
-                                                            double* __restrict__ part_xn, const int* __restrict__ gate) {
+                                                            double* __restrict__ part_xn, const int* __restrict__ gate,
+                                                            const PointFold pf) {
   if (gate && *gate == 0) return;  // device LM loop: phase skipped
   __shared__ double sh[4];
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  double g = 0.0, xn = 0.0;
+  double g = 0.0, xn = 0.0, bad = 0.0;
+  const CamView cv{camR, cam + 3, Kc, kCamR, 6, 5};
   if (p < P)
-    point_eval_body(p, pt_off, cam_pm, uv_pm, CamView{camR, cam + 3, Kc, kCamR, 6, 5}, X, scale_p, diag_p, ptV,
-                    min_diag, max_diag, mode, reuse, g, xn);
+    point_eval_body(p, pt_off, cam_pm, uv_pm, cv, X, scale_p, diag_p, ptV, min_diag, max_diag, mode, reuse, g, xn, pf,
+                    bad);
   if (mode == 1) {
     const double rg = block_reduce(g, sh, true);
     if (threadIdx.x == 0) part_grad[blockIdx.x] = rg;
     const double rx = block_reduce(xn, sh, false);
     if (threadIdx.x == 0) part_xn[blockIdx.x] = rx;
+    if (pf.ptL) {  // k_point_factor's flag partial
+      const double rb = block_reduce(bad, sh, true);
+      if (threadIdx.x == 0) pf.part_bad[blockIdx.x] = rb;
+    }
   }
 }
 
@@ -513,7 +582,7 @@ __global__ __launch_bounds__(kThreads * kGroups) void k_point_eval_lds(int P, in
                                                              double* __restrict__ ptV, double min_diag, double max_diag,
                                                              int mode, int reuse, double* __restrict__ part_grad,
                                                              double* __restrict__ part_xn, const int* __restrict__ gate,
-                                                             const CamFold cf) {
+                                                             const CamFold cf, const PointFold pf) {
   if (gate && *gate == 0) return;  // device LM loop: phase skipped
   static_assert(kGroups == 1 || kMaxC > 64, "the camera fold runs with one group per workgroup");
   const int nbp = (P + kThreads - 1) / kThreads;
@@ -532,14 +601,21 @@ __global__ __launch_bounds__(kThreads * kGroups) void k_point_eval_lds(int P, in
   const int grp = int(threadIdx.x) / kThreads, tg = int(threadIdx.x) % kThreads;
   const int vb = int(blockIdx.x) * kGroups + grp;  // the 256-thread block this group stands for
   const int p = vb * kThreads + tg;
-  double g = 0.0, xn = 0.0;
+  double g = 0.0, xn = 0.0, bad = 0.0;
+  const CamView cv{cst, cst + 9, cst + 12, kCamE, kCamE, kCamE};
   if (p < P)
-    point_eval_body(p, pt_off, cam_pm, uv_pm, CamView{cst, cst + 9, cst + 12, kCamE, kCamE, kCamE}, X, scale_p,
-                    diag_p, ptV, min_diag, max_diag, mode, reuse, g, xn);
+    point_eval_body(p, pt_off, cam_pm, uv_pm, cv, X, scale_p, diag_p, ptV, min_diag, max_diag, mode, reuse, g, xn, pf,
+                    bad);
   if (mode == 1) {
     // block_reduce per group: its four waves' values combined in wave order
+    // (the factor's flag rides with the gradient norm: a max of 0 / 1 flags)
     const int w = int(threadIdx.x) >> 6, l = int(threadIdx.x) & 63;
+    __shared__ double shb[4 * kGroups];
     const double wg = wave_max(g), wx = wave_sum(xn);
+    if (pf.ptL) {
+      const double wb = wave_max(bad);
+      if (l == 0) shb[w] = wb;
+    }
     if (l == 0) sh[w] = wg;
     __syncthreads();
     double rg = 0.0;
@@ -555,6 +631,11 @@ __global__ __launch_bounds__(kThreads * kGroups) void k_point_eval_lds(int P, in
       for (int i = 1; i < 4; ++i) rx = rx + sh[4 * grp + i];
       part_grad[vb] = rg;
       part_xn[vb] = rx;
+      if (pf.ptL) {
+        double rb = shb[4 * grp];
+        for (int i = 1; i < 4; ++i) rb = fmax(rb, shb[4 * grp + i]);
+        pf.part_bad[vb] = rb;
+      }
     }
   }
 }
@@ -579,37 +660,13 @@ __global__ __launch_bounds__(kThreads) void k_point_factor(int P, const double* 
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   double bad = 0.0;
   if (p < P) {
-    const double* v = ptV + size_t(kPtV) * p;
-    double D[3];
-    for (int k = 0; k < 3; ++k) { const double d = sqrt(diag_p[3 * size_t(p) + k] / radius); D[k] = d * d; }
-    const double V00 = v[0] + D[0], V10 = v[1], V11 = v[2] + D[1], V20 = v[3], V21 = v[4], V22 = v[5] + D[2];
-    const double l00 = sqrt(V00);
-    const double l10 = V10 / l00, l20 = V20 / l00;
-    const double l11 = sqrt(V11 - l10 * l10);
-    const double l21 = (V21 - l20 * l10) / l11;
-    const double l22 = sqrt(V22 - l20 * l20 - l21 * l21);
-    if (!(l00 > 0.0) || !(l11 > 0.0) || !(l22 > 0.0)) bad = 1.0;
-    const double z0 = v[6] / l00, z1 = (v[7] - l10 * z0) / l11, z2 = (v[8] - l20 * z0 - l21 * z1) / l22;
-    double* L = ptL + size_t(kPtL) * p;
-    st2(L, l00, l10); st2(L + 2, l11, l20); st2(L + 4, l21, l22); st2(L + 6, z0, z1); st2(L + 8, z2, 0.0);
-    if (ptS) {
-      double* o = ptS + size_t(kPtS) * p;
-      const double* x = X + 3 * size_t(p);
-      const double* sp = scale_p + 3 * size_t(p);
-      st2(o, x[0], x[1]); st2(o + 2, x[2], sp[0]); st2(o + 4, sp[1], sp[2]);
-      st2(o + 6, l10, l20); st2(o + 8, l21, 1.0 / l00); st2(o + 10, 1.0 / l11, 1.0 / l22);
-      st2(o + 12, z0, z1); st2(o + 14, z2, 0.0);
-    }
-    if (ptG) {
-      // k_schur_pairs_rot's record: X and G_p = diag(s_p) L^-T (upper triangular)
-      const double* x = X + 3 * size_t(p);
-      const double* sp = scale_p + 3 * size_t(p);
-      const double i00 = 1.0 / l00, i11 = 1.0 / l11, i22 = 1.0 / l22;
-      const double li10 = -l10 * i00 * i11, li21 = -l21 * i11 * i22, li20 = -(l20 * i00 + l21 * li10) * i22;
-      double* o = ptG + size_t(kPtG) * p;
-      st2(o, x[0], x[1]); st2(o + 2, x[2], sp[0] * i00); st2(o + 4, sp[0] * li10, sp[0] * li20);
-      st2(o + 6, sp[1] * i11, sp[1] * li21); st2(o + 8, sp[2] * i22, 0.0);
-    }
+    const double* vp = ptV + size_t(kPtV) * p;
+    const double v[9] = {vp[0], vp[1], vp[2], vp[3], vp[4], vp[5], vp[6], vp[7], vp[8]};
+    const double dg[3] = {diag_p[3 * size_t(p)], diag_p[3 * size_t(p) + 1], diag_p[3 * size_t(p) + 2]};
+    double x[3] = {0.0, 0.0, 0.0}, sp[3] = {0.0, 0.0, 0.0};
+    if (ptS || ptG)
+      for (int k = 0; k < 3; ++k) { x[k] = X[3 * size_t(p) + k]; sp[k] = scale_p[3 * size_t(p) + k]; }
+    bad = point_factor_body(p, v, dg, radius, x, sp, ptL, ptS, ptG);
   }
   const double r = block_reduce(bad, sh, true);
   if (threadIdx.x == 0) part_bad[blockIdx.x] = r;
@@ -813,12 +870,16 @@ __global__ __launch_bounds__(kThreads) void k_backsub_a_rc(const int32_t* __rest
 // Camera c's diagonal block and rhs (64 lanes t of one wave; no barrier):
 // k_schur_diag_sum's body, also run by k_schur_pts<64, 4> for a small
 // system's diagonal blocks (one launch fewer per LM iteration).
+// kRegs: the lane's U_c entry (uq) and LM diagonal entry (dgu) come in
+// registers (k_cam_sum_diag, which has just summed them) instead of from
+// Ucam / diag_c.
+template <bool kRegs = false>
 __device__ __forceinline__ void schur_diag_body(int c, int C, int t, const int32_t* __restrict__ cam_rng,
                                                 const double* __restrict__ dpart, const double* __restrict__ Ucam,
                                                 const double* __restrict__ diag_c, double radius, int add_diag,
                                                 double* __restrict__ S, int ld, int n, int init,
                                                 int* __restrict__ fail, unsigned long long* __restrict__ ysol,
-                                                int n_y) {
+                                                int n_y, double uq = 0.0, double dgu = 0.0) {
   // k_pad_init folded in (one launch fewer per LM iteration): the identity
   // padding below row n of this camera's six columns and y's sentinel
   // there; the last camera also takes columns n.. (the identity block, the
@@ -860,8 +921,8 @@ __device__ __forceinline__ void schur_diag_body(int c, int C, int t, const int32
     double* sp = S + size_t(6 * c + u) * ld + 6 * size_t(c) + vv;
     double val = (init ? 0.0 : *sp) - tot;  // init: before the off-diagonal launch (k_schur_pts adds its part)
     if (add_diag) {
-      val += Ucam[size_t(kUcam) * c + q];
-      if (u == vv) { const double dd = sqrt(diag_c[6 * size_t(c) + u] / radius); val += dd * dd; }
+      val += kRegs ? uq : Ucam[size_t(kUcam) * c + q];
+      if (u == vv) { const double dd = sqrt((kRegs ? dgu : diag_c[6 * size_t(c) + u]) / radius); val += dd * dd; }
     }
     *sp = val;
   } else if (t < 42) {
@@ -1449,6 +1510,25 @@ __global__ __launch_bounds__(64) void k_schur_diag_sum(const int32_t* __restrict
                   fail, ysol, n_y);
 }
 
+// k_cam_sum_finalize's and k_schur_diag_sum's jobs in one launch, in that
+// order per camera (the evaluation of an unsharded STRUCT_AND_POSE solve,
+// where k_obs_prep_rc has already run for the coming step's radius): the
+// U_c and LM-diagonal entries the diagonal block adds go from the first sum
+// to the second by shuffle, the values the stand-alone kernel loads.
+__global__ __launch_bounds__(64) void k_cam_sum_diag(const CamFold f, const DiagFold df, double* __restrict__ S, int ld,
+                                                     const int* __restrict__ gate) {
+  if (gate && *gate == 0) return;  // device LM loop: phase skipped
+  const int c = blockIdx.x, t = threadIdx.x;
+  const double sum = cam_sum_body(c, t, f);
+  const int tu = t < 36 ? t / 6 : 0, tv = t < 36 ? t % 6 : 0;
+  double uq = __shfl(sum, 2 * up6(tu, tv));
+  double dgu = fmin(fmax(__shfl(sum, 2 * up6(tu, tu)), f.min_diag), f.max_diag);
+  double radius = df.radius_dev ? *df.radius_dev : df.radius;
+  asm volatile("" : "+v"(uq), "+v"(dgu), "+v"(radius));  // (opaque, as the loads they stand for)
+  schur_diag_body<true>(c, df.C, t, df.cam_rng, df.dpart, nullptr, nullptr, radius, df.add_diag, S, ld, df.n, 1,
+                        df.fail, df.ysol, df.n_y, uq, dgu);
+}
+
 // Packed form of the reduced system for the cross-rank all-reduce: row i
 // of the row-major upper triangle, columns i..n (the rhs column n
 // included), at offset i(n+1) - i(i-1)/2.  Half the bytes of the full ld^2
@@ -1505,19 +1585,19 @@ __global__ void k_pad_init(double* __restrict__ S, int ld, int n, int* __restric
 // cross product takes X itself, which is that branch's e_o exactly.
 __device__ __forceinline__ void cam_pm_pack(int c, const double* __restrict__ camR, const double* __restrict__ cam,
                                             const double* __restrict__ Kc, const double* __restrict__ ysol,
-                                            const double* __restrict__ scale_c, const double* camRn,
-                                            double* __restrict__ campm) {
+                                            const double* __restrict__ scale_c, double* __restrict__ o) {
+  // o: the camera's record (LDS); its candidate part (23..34) is the caller's
   const double* cr = camR + size_t(kCamR) * c;
-  double* o = campm + size_t(kCamPM) * c;
   double R[9], sy[6];
   for (int i = 0; i < 9; ++i) R[i] = cr[i];
   for (int k = 0; k < 6; ++k) sy[k] = scale_c[6 * c + k] * ysol[6 * c + k];
   bool first_order = true;
-#pragma unroll
+  // (bitwise &: no branch and wait per entry; nine loads at a time: k_backsub_pm
+  // has 128 registers per lane, and all 27 together spill)
+#pragma unroll 1
   for (int k = 0; k < 3; ++k)
 #pragma unroll
-    for (int i = 0; i < 9; ++i)  // (bitwise &: all 27 loads together, no branch and wait per entry)
-      first_order = first_order & (cr[9 + 9 * k + i] == skew_basis_entry(k, i));
+    for (int i = 0; i < 9; ++i) first_order = first_order & (cr[9 + 9 * k + i] == skew_basis_entry(k, i));
   double om[3] = {sy[0], sy[1], sy[2]};
   if (!first_order) {
     om[0] = om[1] = om[2] = 0.0;
@@ -1535,7 +1615,6 @@ __device__ __forceinline__ void cam_pm_pack(int c, const double* __restrict__ ca
   for (int i = 0; i < 3; ++i) o[9 + i] = cam[6 * c + 3 + i];
   for (int i = 0; i < 5; ++i) o[12 + i] = Kc[5 * size_t(c) + i];
   for (int i = 0; i < 3; ++i) { o[17 + i] = om[i]; o[20 + i] = sy[3 + i]; }
-  for (int i = 0; i < 12; ++i) o[23 + i] = camRn[12 * size_t(c) + i];  // (this thread's own stores, cam_update_one)
   o[35] = first_order ? 1.0 : 0.0;
   o[36] = 0.0;
 }
@@ -1544,15 +1623,12 @@ __global__ __launch_bounds__(kThreads) void k_cam_update(int C, const double* __
                                                          const double* __restrict__ ysol,
                                                          const double* __restrict__ scale_c,
                                                          double* __restrict__ cam_new, double* __restrict__ camRn,
-                                                         double* __restrict__ part_step, double* __restrict__ part_bad, const int* __restrict__ gate,
-                                                         const double* __restrict__ camR, const double* __restrict__ Kc,
-                                                         double* __restrict__ campm) {
+                                                         double* __restrict__ part_step, double* __restrict__ part_bad, const int* __restrict__ gate) {
   if (gate && *gate == 0) return;  // device LM loop: phase skipped
   __shared__ double sh[4];
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   double st = 0.0, bad = 0.0;
   if (c < C) cam_update_one(c, cam, ysol, scale_c, cam_new, camRn, st, bad);
-  if (c < C && campm) cam_pm_pack(c, camR, cam, Kc, ysol, scale_c, camRn, campm);
   const double rs = block_reduce(st, sh, false);
   if (threadIdx.x == 0 && part_step) part_step[blockIdx.x] = rs;
   const double rb = block_reduce(bad, sh, true);
@@ -1761,6 +1837,28 @@ __global__ __launch_bounds__(kThreads) void k_backsub_c(const int32_t* __restric
   if (threadIdx.x == 0) part_cost[blockIdx.x] = r;
 }
 
+// What k_backsub_pm needs to take the camera step itself (k_cam_update's
+// inputs and outputs, and the constants of the camera records).
+struct CamStepFold {
+  const double* cam; const double* ysol; const double* scale_c; const double* camR; const double* Kc;
+  double* cam_new; double* camRn; double* part_step; double* part_bad;
+};
+
+// Camera c's step and its record o (LDS) from the solved y: k_cam_update's
+// two routines.  The candidate goes into the record (and, store, to cam_new /
+// camRn) before the packing starts, so it is not held in registers across it.
+__device__ __forceinline__ void cam_step_record(int c, const CamStepFold& cu, double* o, bool store, double& st,
+                                                double& bad) {
+  double xn[6], rn[12];
+  cam_update_vals(c, cu.cam, cu.ysol, cu.scale_c, xn, rn, st, bad);
+  if (store) {
+    for (int k = 0; k < 6; ++k) cu.cam_new[6 * c + k] = xn[k];
+    for (int i = 0; i < 12; ++i) cu.camRn[12 * size_t(c) + i] = rn[i];
+  }
+  for (int i = 0; i < 12; ++i) o[23 + i] = rn[i];
+  cam_pm_pack(c, cu.camR, cu.cam, cu.Kc, cu.ysol, cu.scale_c, o);
+}
+
 // Passes A, B and C as ONE point-major launch (large reduced systems with
 // C <= kCamPMMax, both blocks variable): one lane per point,
 // every camera's record (cam_pm_pack, kCamPM doubles) in LDS.  The lane's
@@ -1775,20 +1873,50 @@ __global__ __launch_bounds__(kThreads) void k_backsub_c(const int32_t* __restric
 template <int kGroups>
 __global__ __launch_bounds__(kThreads * kGroups) void k_backsub_pm(
     int P, int C, const int32_t* __restrict__ pt_off, const int32_t* __restrict__ cam_pm,
-    const double* __restrict__ uv_pm, const double* __restrict__ campm, const double* __restrict__ ptL,
+    const double* __restrict__ uv_pm, const double* __restrict__ ptL,
     const double* __restrict__ ptV, const double* __restrict__ scale_p, const double* __restrict__ X,
     double* __restrict__ X_new, double* __restrict__ ypt, double* __restrict__ part_model,
     double* __restrict__ part_model_pt, double* __restrict__ part_step, double* __restrict__ part_bad,
-    double* __restrict__ part_cost, const int* __restrict__ gate) {
+    double* __restrict__ part_cost, const int* __restrict__ gate, const CamStepFold cu) {
   if (gate && *gate == 0) return;  // device LM loop: phase skipped
+  static_assert(kThreads * kGroups >= kCamPMMax, "one thread per camera record");
   __shared__ double sh[4 * kGroups];
   __shared__ double cst[kCamPMMax * kCamPM];
-  for (int i = threadIdx.x; i < C * kCamPM; i += blockDim.x) cst[i] = campm[i];
-  __syncthreads();
   const int nbp = (P + kThreads - 1) / kThreads;
   const int grp = int(threadIdx.x) / kThreads, tg = int(threadIdx.x) % kThreads;
   const int vb = int(blockIdx.x) * kGroups + grp;  // the 256-thread block this group stands for
   const int p = vb * kThreads + tg;
+  {
+    // k_cam_update's work (no launch of its own on this path): thread c
+    // builds camera c's record in LDS from the solved y with the routines
+    // k_cam_update uses; workgroup 0 also writes the candidate (cam_new,
+    // camRn) and the step / flag partials, group g standing for
+    // k_cam_update's 256-camera block g.
+    const int c = int(threadIdx.x);
+    double cst_ = 0.0, cbad = 0.0;
+    if (c < C) cam_step_record(c, cu, cst + kCamPM * c, blockIdx.x == 0, cst_, cbad);
+    if (blockIdx.x == 0) {  // (uniform per workgroup) block_reduce per group, as below
+      const int w = int(threadIdx.x) >> 6, l = int(threadIdx.x) & 63;
+      const int nbc = (C + kThreads - 1) / kThreads;
+      const double ws = wave_sum(cst_), wb = wave_max(cbad);
+      if (l == 0) sh[w] = ws;
+      __syncthreads();
+      if (tg == 0 && grp < nbc && cu.part_step) {
+        double r = sh[4 * grp];
+        for (int i = 1; i < 4; ++i) r = r + sh[4 * grp + i];
+        cu.part_step[grp] = r;
+      }
+      __syncthreads();
+      if (l == 0) sh[w] = wb;
+      __syncthreads();
+      if (tg == 0 && grp < nbc) {
+        double r = sh[4 * grp];
+        for (int i = 1; i < 4; ++i) r = fmax(r, sh[4 * grp + i]);
+        cu.part_bad[grp] = r;
+      }
+    }
+  }
+  __syncthreads();
   double model = 0.0, model_pt = 0.0, st = 0.0, bad = 0.0, ncost = 0.0;
   if (p < P) {
     const double Xp[3] = {X[3 * size_t(p)], X[3 * size_t(p) + 1], X[3 * size_t(p) + 2]};
@@ -1964,7 +2092,7 @@ bool launch_point_eval_with_cams(const DevProblem& d, int mode, bool count_grad,
   k_point_eval_lds<64><<<nb, kThreads, 0, s>>>(d.P, d.C, d.pt_off, d.cam_pm, d.uv_pm, d.camR, d.cam, d.Kc, d.X,
                                                d.scale_p, d.diag_p, d.ptV, d.min_diag, d.max_diag, mode, 0,
                                                slot(d, kPGradPt), slot(d, kPXNormPt), d.gate,
-                                               cam_fold(d, mode, count_grad));
+                                               cam_fold(d, mode, count_grad), PointFold{});
   return true;
 }
 void launch_cam_finalize(const DevProblem& d, int mode, bool reuse_diag, bool count_grad, hipStream_t s) {
@@ -1977,25 +2105,28 @@ static bool env_flag_k(const char* name) {
   const char* v = std::getenv(name);
   return v && v[0] == '1';
 }
-void launch_point_eval(const DevProblem& d, int mode, bool reuse_diag, hipStream_t s) {
+void launch_point_eval(const DevProblem& d, int mode, bool reuse_diag, hipStream_t s, bool factor, double radius) {
   if (d.P == 0) return;
   const int nb = blocks_for(d.P, kThreads);
+  // factor (mode 1): the pass goes on to k_point_factor's work for the coming step's radius
+  const PointFold pf = factor && mode == 1 ? PointFold{radius, d.radius_dev, d.ptL, d.ptS, d.ptG, slot(d, kPBad)}
+                                           : PointFold{};
   // camera constants from LDS while they fit (C3: 500 cameras, 68 KB)
 #define SFM_PE_LDS(M_)                                                                                              \
   k_point_eval_lds<M_><<<nb, kThreads, 0, s>>>(d.P, d.C, d.pt_off, d.cam_pm, d.uv_pm, d.camR, d.cam, d.Kc, d.X,      \
                                                d.scale_p, d.diag_p, d.ptV, d.min_diag, d.max_diag, mode,           \
                                                reuse_diag ? 1 : 0, slot(d, kPGradPt), slot(d, kPXNormPt), d.gate,    \
-                                               CamFold{})
+                                               CamFold{}, pf)
   if (d.C <= 64) SFM_PE_LDS(64);
   else if (d.C <= 512 && !env_flag_k("SFM_PE_GROUPS1"))
     k_point_eval_lds<512, 2><<<blocks_for(d.P, 2 * kThreads), 2 * kThreads, 0, s>>>(
         d.P, d.C, d.pt_off, d.cam_pm, d.uv_pm, d.camR, d.cam, d.Kc, d.X, d.scale_p, d.diag_p, d.ptV, d.min_diag,
-        d.max_diag, mode, reuse_diag ? 1 : 0, slot(d, kPGradPt), slot(d, kPXNormPt), d.gate, CamFold{});
+        d.max_diag, mode, reuse_diag ? 1 : 0, slot(d, kPGradPt), slot(d, kPXNormPt), d.gate, CamFold{}, pf);
   else if (d.C <= 512) SFM_PE_LDS(512);
   else
     k_point_eval_rc<<<nb, kThreads, 0, s>>>(d.P, d.pt_off, d.cam_pm, d.uv_pm, d.camR, d.cam, d.Kc, d.X, d.scale_p,
                                             d.diag_p, d.ptV, d.min_diag, d.max_diag, mode, reuse_diag ? 1 : 0,
-                                            slot(d, kPGradPt), slot(d, kPXNormPt), d.gate);
+                                            slot(d, kPGradPt), slot(d, kPXNormPt), d.gate, pf);
 #undef SFM_PE_LDS
 }
 void launch_point_factor(const DevProblem& d, double radius, hipStream_t s) {
@@ -2005,6 +2136,9 @@ void launch_point_factor(const DevProblem& d, double radius, hipStream_t s) {
 }
 void launch_point_prep(const DevProblem& d, double radius, hipStream_t s) {
   launch_point_factor(d, radius, s);
+  launch_obs_prep(d, s);
+}
+void launch_obs_prep(const DevProblem& d, hipStream_t s) {
   if (d.N_pad)
     k_obs_prep_rc<<<obs_xcd_blocks(d), kThreads, 0, s>>>(d.jgrp, d.jchunks, d.cm_p, d.uv_cm, d.cam_obs, d.camR, d.cam,
                                                          d.Kc, d.scale_c, d.ptS, d.dpart, d.gate);
@@ -2024,6 +2158,12 @@ void launch_schur(const DevProblem& d, double radius, bool add_diag, hipStream_t
   }
   launch_schur_diag(d, radius, add_diag, s);
   launch_schur_offdiag(d, nullptr, s);
+}
+void launch_cam_sum_diag(const DevProblem& d, double radius, bool add_diag, hipStream_t s) {
+  if (!d.C) return;
+  const DiagFold f{d.cam_rng, d.dpart, d.Ucam, d.diag_c, radius, d.radius_dev, add_diag ? 1 : 0, d.C, d.n,
+                   (d.n + kNB - 1) / kNB * kNB, d.fail, reinterpret_cast<unsigned long long*>(d.ysol)};
+  k_cam_sum_diag<<<d.C, 64, 0, s>>>(cam_fold(d, 1, true), f, d.S, d.ld, d.gate);
 }
 void launch_schur_diag(const DevProblem& d, double radius, bool add_diag, hipStream_t s) {
   if (d.C)
@@ -2081,22 +2221,23 @@ void launch_pad_init(const DevProblem& d, hipStream_t s) {
   const int n_y = (d.n + kNB - 1) / kNB * kNB;
   k_pad_init<<<d.ld, 64, 0, s>>>(d.S, d.ld, d.n, d.fail, reinterpret_cast<unsigned long long*>(d.ysol), n_y, d.gate);
 }
-void launch_cam_update(const DevProblem& d, bool count_norm, hipStream_t s, bool pm) {
+void launch_cam_update(const DevProblem& d, bool count_norm, hipStream_t s) {
   k_cam_update<<<blocks_for(d.C, kThreads), kThreads, 0, s>>>(d.C, d.cam, d.ysol, d.scale_c, d.cam_new, d.camRn,
                                                              count_norm ? slot(d, kPStepCam) : nullptr,
-                                                             slot(d, kPBadCam), d.gate, d.camR, d.Kc,
-                                                             pm ? d.campm : nullptr);
+                                                             slot(d, kPBadCam), d.gate);
 }
 void launch_cam_solve(const DevProblem& d, double radius, hipStream_t s) {
   (void)hipMemsetAsync(d.fail, 0, sizeof(int), s);
   if (d.C) k_cam_solve<<<blocks_for(d.C, kThreads), kThreads, 0, s>>>(d.C, d.Ucam, d.diag_c, radius, d.ysol, d.fail, d.gate, d.radius_dev);
 }
-void launch_point_backsub(const DevProblem& d, hipStream_t s, bool cams_var, bool pts_var) {
-  if (backsub_pm(d, cams_var, pts_var)) {  // one point-major pass (launch_cam_update wrote campm)
+void launch_point_backsub(const DevProblem& d, hipStream_t s, bool cams_var, bool pts_var, bool count_norm) {
+  if (backsub_pm(d, cams_var, pts_var)) {  // one point-major pass, the camera step included
     constexpr int kG = 4;  // one 1024-thread workgroup per CU (its LDS copy is up to 148 KB)
     k_backsub_pm<kG><<<blocks_for(d.P, kG * kThreads), kG * kThreads, 0, s>>>(
-        d.P, d.C, d.pt_off, d.cam_pm, d.uv_pm, d.campm, d.ptL, d.ptV, d.scale_p, d.X, d.X_new, d.ypt,
-        slot(d, kPModel), slot(d, kPModelPt), slot(d, kPStepPt), slot(d, kPBadBack), slot(d, kPNewCost), d.gate);
+        d.P, d.C, d.pt_off, d.cam_pm, d.uv_pm, d.ptL, d.ptV, d.scale_p, d.X, d.X_new, d.ypt,
+        slot(d, kPModel), slot(d, kPModelPt), slot(d, kPStepPt), slot(d, kPBadBack), slot(d, kPNewCost), d.gate,
+        CamStepFold{d.cam, d.ysol, d.scale_c, d.camR, d.Kc, d.cam_new, d.camRn,
+                    count_norm ? slot(d, kPStepCam) : nullptr, slot(d, kPBadCam)});
     return;
   }
   // cameras constant (STRUCT_ONLY): e = J_c y_c = 0 and u = 0

@@ -59,6 +59,11 @@ enum Phase { kPhJac = 0, kPhCamRed, kPhPtEval, kPhPtPrep, kPhSchur, kPhChol, kPh
 // device LM loop state (k_lm_decide / k_lm_post; see "device-driven LM loop")
 struct LmCtl {
   int32_t run_step, run_eval, done, termination, error;
+  // The evaluation prepares the coming step (prep_fold, from the host: step_prep_folds).  An
+  // unsuccessful or invalid step then pauses the loop (run_step = 0, prep_stale = 1): the radius
+  // changed with no evaluation to follow, and the host, which enqueues the stand-alone prep
+  // kernels only when it knows they are needed, re-arms the loop with them in front.
+  int32_t prep_fold, prep_stale;
   int32_t iteration, num_consecutive_invalid;
   int32_t n_succ, n_unsucc, n_invalid, n_resid, n_jac, n_lin, trace_len;
   double radius, decrease_factor, cost, grad_max, x_norm;
@@ -150,6 +155,17 @@ struct sfm_ba_handle {
   // candidate current (k_lm_accept folded in; its grid covers the copy)
   int accept_grid = 0;  // < 0: done by the deciding reduction (AcceptFold)
   bool accept_fold = false;
+  // The step's radius-dependent preparation (point factor, k_obs_prep_rc,
+  // diagonal blocks) folded into the evaluation (step_prep_folds): the
+  // radius changes only in the step's decision, so an evaluation prepares
+  // the coming step.  eval_radius: that step's radius (host loop; the device
+  // loop's kernels read LmCtl::radius).  prep_fresh: the prep on the device
+  // is for the current radius; set by the evaluation, cleared by an
+  // unsuccessful or invalid step (the host loop's own decision; the device
+  // loop pauses there and reports LmCtl::prep_stale), after which
+  // compute_step runs the stand-alone kernels first.
+  double eval_radius = 0.0;
+  bool prep_fresh = false;
   int n_cu = 0;  // compute units of the device (queried once)
   // Schur / Cholesky overlap (DevProblem::overlap): the factorisation's
   // stream and the two events that fork and join it
@@ -354,13 +370,14 @@ __device__ void lm_finish(LmCtl* c, int term) {
   c->done = 1;
   c->run_step = 0;
   c->run_eval = 0;
+  c->prep_stale = 0;
 }
 
 // after compute_step's reduction (scal: model change, candidate cost, step
 // norms, bad-step flags; the Cholesky failure int after the scalars)
 __device__ void lm_decide(LmCtl* c, const double* scal, sfm_ba_iteration* trace, int cap) {
 #pragma clang fp contract(off)
-  if (c->done) {
+  if (c->done || !c->run_step) {  // (or paused: the batch's remaining iterations do nothing)
     c->run_eval = 0;
     return;
   }
@@ -434,6 +451,10 @@ __device__ void lm_decide(LmCtl* c, const double* scal, sfm_ba_iteration* trace,
   c->radius = c->radius / c->decrease_factor;
   c->decrease_factor *= 2.0;
   c->run_eval = 0;
+  if (c->prep_fold) {  // no evaluation follows: the next step redoes its prep for the new radius
+    c->prep_stale = 1;
+    c->run_step = 0;
+  }
   itr.gradient_max_norm = c->grad_max;
   itr.cost = c->cost;
   itr.trust_region_radius = c->radius;
@@ -910,6 +931,18 @@ void reduce_phase(sfm_ba_handle* h, const ReduceBatch& rb, bool copy_fail, int t
   launch_reduce_batch(d, rb, copy_fail, h->stream);
 }
 
+// Whether an evaluation also prepares the coming step (unsharded
+// STRUCT_AND_POSE beyond the small systems whose camera sums ride in the
+// point pass): the point factor inside the point pass, then k_obs_prep_rc,
+// then the camera sums and the diagonal blocks in one launch.  A sharded
+// solve has a collective between the sums and their use and keeps the
+// stand-alone sequence, as do POSE_ONLY and STRUCT_ONLY.
+bool step_prep_folds(const sfm_ba_handle* h) {
+  const DevProblem& d = h->d;
+  return h->mode == SFM_BA_STRUCT_AND_POSE && !sharded(h) && d.P > 0 && d.C > 64 && d.N_pad > 0 &&
+         !d.schur_wg_blocks;
+}
+
 // Evaluate cost, Jacobian, Jacobi scale (first call), per-block normal
 // equations, LM diagonal and gradient at the current parameters.
 int evaluate_enqueue(sfm_ba_handle* h, bool first, bool jacobi_scaling) {
@@ -956,10 +989,14 @@ int evaluate_enqueue(sfm_ba_handle* h, bool first, bool jacobi_scaling) {
     launch_jacobian(d, true, s);
     mark_end(h);
   }
+  // the coming step's preparation rides along (its radius is final here)
+  const bool fold_prep = step_prep_folds(h);
   if (fold_cams) {
     mark_begin(h, kPhPtEval);
     launch_point_eval_with_cams(d, 1, true, s);
     mark_end(h);
+  } else if (fold_prep) {
+    // (the camera sums follow the point pass and k_obs_prep_rc, below)
   } else if (cams_var) {
     mark_begin(h, kPhCamRed);
     if (fuse_cam) {
@@ -978,8 +1015,17 @@ int evaluate_enqueue(sfm_ba_handle* h, bool first, bool jacobi_scaling) {
     // (done above, with the camera sums)
   } else if (pts_var) {
     mark_begin(h, kPhPtEval);
-    launch_point_eval(d, 1, false, s);
+    launch_point_eval(d, 1, false, s, fold_prep, h->eval_radius);
     mark_end(h);
+    if (fold_prep) {
+      mark_begin(h, kPhPtPrep);
+      launch_obs_prep(d, s);
+      mark_end(h);
+      mark_begin(h, kPhCamRed);
+      launch_cam_sum_diag(d, h->eval_radius, h->rank == 0, s);
+      mark_end(h);
+    }
+    h->prep_fresh = fold_prep;
   } else {
     hipMemsetAsync(d.partials + size_t(kPGradPt) * d.max_blocks, 0, sizeof(double) * nbP, s);
     hipMemsetAsync(d.partials + size_t(kPXNormPt) * d.max_blocks, 0, sizeof(double) * nbP, s);
@@ -1017,15 +1063,30 @@ int compute_step_enqueue(sfm_ba_handle* h, double radius) {
   int rc;
   const int nbP = std::max(1, blocks_for(d.P, 256)), nbC = std::max(1, blocks_for(d.C, 256));
   bool cam_done = false;  // the camera step taken by the small-system factor
+  // The evaluation prepared this step (step_prep_folds) unless an
+  // unsuccessful or invalid step changed the radius since: then the
+  // stand-alone kernels redo it.  Both loops know on the host (prep_fresh):
+  // the device loop pauses at such a step, so no launch is spent on the
+  // stand-alone kernels while every step is accepted.
+  const bool fold_prep = step_prep_folds(h);
+  const bool redo_prep = !fold_prep || !h->prep_fresh;
+  // the stand-alone prep: point factor and k_obs_prep_rc, then the diagonal blocks
+  auto point_prep = [&] {
+    if (!redo_prep) return;
+    mark_begin(h, kPhPtPrep);
+    launch_point_prep(d, radius, s);
+    mark_end(h);
+  };
+  auto schur_diag = [&] {
+    if (redo_prep) launch_schur_diag(d, radius, h->rank == 0, s);
+  };
   if (h->mode == SFM_BA_STRUCT_AND_POSE && d.overlap && d.C && !sharded(h) && !h->force_pack) {
     // Schur / Cholesky overlap: the diagonal blocks and rhs first, then the
     // factorisation on its own stream with half the CUs while k_schur_pts
     // fills the off-diagonal blocks on the other half, in camera-major order
     // (the factor's tile columns complete left to right); a helper reads an
     // S tile once k_schur_pts has counted all its camera blocks in
-    mark_begin(h, kPhPtPrep);
-    launch_point_prep(d, radius, s);
-    mark_end(h);
+    point_prep();
     if (!h->stream2) {
       HIPCHK(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
       HIPCHK(hipEventCreateWithFlags(&h->ov_ev[0], hipEventDisableTiming));
@@ -1033,7 +1094,7 @@ int compute_step_enqueue(sfm_ba_handle* h, double radius) {
     }
     const int m_schur = mark_begin(h, kPhSchur);
     HIPCHK(hipMemsetAsync(d.tile_cnt, 0, sizeof(int32_t) * size_t(d.nblk) * d.nblk, s));
-    launch_schur_diag(d, radius, h->rank == 0, s);
+    schur_diag();
     HIPCHK(hipEventRecord(h->ov_ev[0], s));
     HIPCHK(hipStreamWaitEvent(h->stream2, h->ov_ev[0], 0));
     mark_begin(h, kPhChol, h->stream2);
@@ -1047,11 +1108,14 @@ int compute_step_enqueue(sfm_ba_handle* h, double radius) {
     launch_backsolve(d, ++h->bs_epoch, s, true);
     mark_end(h);
   } else if (h->mode == SFM_BA_STRUCT_AND_POSE) {
-    mark_begin(h, kPhPtPrep);
-    launch_point_prep(d, radius, s);
-    mark_end(h);
+    point_prep();
     mark_begin(h, kPhSchur);
-    launch_schur(d, radius, h->rank == 0, s);
+    if (fold_prep) {  // (never a block-per-workgroup system: launch_schur's two parts)
+      schur_diag();
+      launch_schur_offdiag(d, nullptr, s);
+    } else {
+      launch_schur(d, radius, h->rank == 0, s);
+    }
     mark_end(h);
     // (k_schur_diag_sum also wrote the identity padding, y's sentinel and
     // the cleared failure flag; without cameras the separate launch does)
@@ -1092,13 +1156,14 @@ int compute_step_enqueue(sfm_ba_handle* h, double radius) {
     hipMemsetAsync(d.ysol, 0, sizeof(double) * 6 * size_t(d.C), s);
   }
   // large reduced systems: the back substitution as one point-major pass
-  // (k_backsub_pm), its camera records written by k_cam_update
-  // (cam_done: a one-workgroup factor, never a system with campm)
+  // (k_backsub_pm), which builds its camera records from y itself and takes
+  // the camera step in its first workgroup: no k_cam_update launch there
+  // (cam_done: a one-workgroup factor, never such a system)
   const bool cams_var = h->mode != SFM_BA_STRUCT_ONLY, pts_var = h->mode != SFM_BA_POSE_ONLY;
   const bool pm = backsub_pm(d, cams_var, pts_var);
-  if (!cam_done) launch_cam_update(d, h->rank == 0 && cams_var, s, pm);
+  if (!cam_done && !pm) launch_cam_update(d, h->rank == 0 && cams_var, s);
   mark_begin(h, kPhBacksub);
-  launch_point_backsub(d, s, cams_var, pts_var);
+  launch_point_backsub(d, s, cams_var, pts_var, h->rank == 0 && cams_var);
   mark_end(h);
   if (d.P == 0) {
     const int slots[] = {kPModel, kPModelPt, kPNewCost, kPStepPt, kPBadBack, kPBad};
@@ -1208,6 +1273,7 @@ int run_device_lm(sfm_ba_handle* h, const sfm_ba_options& opts, double* cost, sf
   c.max_radius = opts.max_trust_region_radius;
   c.min_radius = opts.min_trust_region_radius;
   c.min_rel_dec = opts.min_relative_decrease;
+  c.prep_fold = step_prep_folds(h) ? 1 : 0;
   HIPCHK(hipMemcpyAsync(h->lm_ctl, &c, sizeof(LmCtl), hipMemcpyHostToDevice, s));
   // 3 iterations first (a keyframe or C3 solve typically ends there), then 2
   // at a time: each gated iteration past the end still costs its launches
@@ -1226,6 +1292,7 @@ int run_device_lm(sfm_ba_handle* h, const sfm_ba_options& opts, double* cost, sf
   // the initial evaluation (Jacobi scaling on first use); its scalars
   // initialise the loop state on the device
   d.gate = nullptr;
+  h->eval_radius = c.radius;  // (the kernels read LmCtl::radius)
   int rc = evaluate_enqueue(h, true, jac_scaling);
   if (rc == 0 && !h->fuse_lm) k_lm_init<<<1, 1, 0, s>>>(h->lm_ctl, d.scal);
   while (rc == 0) {
@@ -1262,6 +1329,17 @@ int run_device_lm(sfm_ba_handle* h, const sfm_ba_options& opts, double* cost, sf
     timer.mark("batch synchronised");
     collect_marks(h);
     if (c.done) break;
+    if (c.prep_stale) {
+      // paused at an unsuccessful or invalid step (the rest of the batch
+      // returned at once): the next step redoes its prep for the new radius
+      h->prep_fresh = false;
+      c.prep_stale = 0;
+      c.run_step = 1;
+      if (hipMemcpyAsync(h->lm_ctl, &c, sizeof(LmCtl), hipMemcpyHostToDevice, s) != hipSuccess) {
+        rc = fail(SFM_EIO, "LM control upload failed");
+        break;
+      }
+    }
     batch = batch_next;
   }
   d.gate = nullptr;
@@ -2045,8 +2123,7 @@ constexpr int64_t kDeferredUvMinObs = 262144;
   ALLOC(d.camRn, 12 * size_t(C));
   // the one-pass back substitution, on the large path (the XCD-ordered Schur
   // blocks) while every camera's record fits the LDS
-  d.campm = nullptr;
-  if (d.n_blk > kSchurXcdMinBlocks && C <= kCamPMMax) ALLOC(d.campm, size_t(kCamPM) * C);
+  d.pm_backsub = d.n_blk > kSchurXcdMinBlocks && C <= kCamPMMax;
   // pass A stores u at the camera-major position it runs at (coalesced) and
   // pass B gathers it through pos[]: 85 + 31 -> 60 + 41 us per C3 iteration
   // against the point-major scatter (SFM_EU_CM=0), S and steps bitwise equal
@@ -2312,6 +2389,7 @@ int sfm_ba_solve_resident(sfm_ba_handle* h, const sfm_ba_options* opts_in, int32
     return 0;
   }
   double tj = now_s();
+  h->eval_radius = opts.initial_trust_region_radius;
   if ((rc = evaluate(h, true, opts.jacobi_scaling != 0))) return rc;
   sm.jacobian_time_s += now_s() - tj;
   sm.num_jacobian_evaluations++;
@@ -2407,6 +2485,7 @@ int sfm_ba_solve_resident(sfm_ba_handle* h, const sfm_ba_options* opts_in, int32
         std::swap(d.cam, d.cam_new);
         std::swap(d.X, d.X_new);
         tj = now_s();
+        h->eval_radius = radius;  // the next step's: its preparation rides in the evaluation
         if ((rc = evaluate(h, false, opts.jacobi_scaling != 0))) return rc;
         sm.jacobian_time_s += now_s() - tj;
         sm.num_jacobian_evaluations++;
@@ -2419,6 +2498,7 @@ int sfm_ba_solve_resident(sfm_ba_handle* h, const sfm_ba_options* opts_in, int32
         sm.num_unsuccessful_steps++;
         radius = radius / decrease_factor;
         decrease_factor *= 2.0;
+        h->prep_fresh = false;  // (as k_lm_decide: the next step redoes its prep for the new radius)
       }
       itr.gradient_max_norm = grad_max;
       itr.cost = cost;
