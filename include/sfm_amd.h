@@ -422,6 +422,64 @@ int sfm_pnp_ransac(int32_t device, int32_t n, const double* obj, const double* i
 int sfm_triangulate_points(int32_t device, int32_t n, const int32_t* cam0, const int32_t* cam1, const double* uv0,
                            const double* uv1, int32_t n_cams, const double* P, double* X);
 
+/* Two-view map initialisation: steps 2-5 of CSfM::init (CSfM.cpp:842-946)
+ * on the matches of the first keyframe and a later frame, in one synchronous
+ * call (one upload, one download, one host synchronisation):
+ *   findHomography(prev, curr, 0, 5.99) and findFundamentalMat(prev, curr,
+ *   FM_RANSAC, 3.84, 0.99) (:842-843), calculateHomographyScore /
+ *   calculateFundamentalScore and the model choice (:849-859, :415-469),
+ *   calculateHomographyAvgError / calculateFundamentalAvgError (:871, :894),
+ *   RtFromHomographyMatrix / RtFromEssentialMatrix (:874, :899),
+ *   triangulatePoints (:918) and GeometryUtils::filterMatches (:922).
+ * OpenCV 3.0 and GeometryUtils are absent, so the semantics are the build's
+ * restatement (tests/two_view_ref.py; PARITY with OpenCV's findFundamentalMat
+ * / findHomography and with GeometryUtils is UNPINNED): 7-point RANSAC with
+ * cv::RNG(-1) and no refit; normalised DLT plus cv::LMSolver refinement; both
+ * matrices rounded to float32 (the reference's Matx33f) and everything after
+ * them computed in fp64 on the rounded values; E = K1^T F K0 with its four
+ * (R, t); the eight Faugeras candidates of K1^-1 H K0; a cheirality vote over
+ * the surviving matches (triangulated as sfm_triangulate_points does); the
+ * final filter on the RANSAC F in either branch.
+ * Below 15 matches OpenCV switches findFundamentalMat to LMedS; that fallback
+ * is not restated: n < 15 returns SFM_OK with *model = 0. */
+typedef struct sfm_two_view_options {
+  double f_ransac_threshold; /* 3.84  CSfM.cpp:843 */
+  double f_confidence;       /* 0.99  CSfM.cpp:843 */
+  double h_score_th;         /* 5.99  CSfM.cpp:849 */
+  double h_score_gamma;      /* 5.99  CSfM.cpp:849 */
+  double f_score_th;         /* 3.84  CSfM.cpp:850 */
+  double f_score_gamma;      /* 5.99  CSfM.cpp:850 */
+  double h_ratio;            /* 0.45  CSfM.cpp:859 */
+  double max_repr_err;       /* 7     CSfM.cpp:35 (_maxReprErr) */
+  double min_good_fraction;  /* 0.9   vote: good points of the winner / surviving matches */
+  double ambiguity_ratio;    /* 0.7   vote: runner-up must stay below this share of the winner */
+  double min_parallax_deg;   /* 1.0   vote: median parallax of the winner's good points */
+  int32_t f_max_iters;       /* 1000  OpenCV's default bound (at most 2048) */
+  int32_t min_good;          /* 50    vote: least number of good points */
+} sfm_two_view_options;
+void sfm_two_view_default_options(sfm_two_view_options* o);
+
+/* pts0 / pts1 [n][2] float (the reference's _prevMatch / _currMatch), K0 / K1
+ * row-major 3x3.  Outputs (every pointer but `model` may be NULL):
+ *   *model     0 = no initialisation, 1 = homography, 2 = fundamental
+ *   H9, F9     the float32 values of the reference's Matx33f, as doubles
+ *   f_mask[n]  the RANSAC inlier mask of F
+ *   scores[2]  (s_h, s_f)
+ *   *avg_err   errHomo / errFund of the chosen branch (pixels)
+ *   R9, t3     second camera x = R X + t, |t| = 1; the first camera is the
+ *              origin (CFrame.cpp:229-235)
+ *   keep[n]    matches that survive the model's mask and the final filter
+ *   X[n][3]    triangulated points, valid where keep
+ *   *n_kept
+ * With *model = 0 R9, t3, keep, X and *n_kept are zero; H9, F9, f_mask,
+ * scores and *avg_err hold what was computed before the failing step.
+ * opts NULL = the defaults.  No device: SFM_ENODEV; non-finite input:
+ * SFM_EINVAL. */
+int sfm_two_view_init(int32_t device, int32_t n, const float* pts0, const float* pts1, const double* K0,
+                      const double* K1, const sfm_two_view_options* opts, int32_t* model, double* H9, double* F9,
+                      uint8_t* f_mask, double* scores, double* avg_err, double* R9, double* t3, uint8_t* keep,
+                      double* X, int32_t* n_kept);
+
 /* Testing hook: solve the dense SPD system A y = b (A [n][n] row-major,
  * both triangles given; only the upper triangle is read) with the device
  * Cholesky + substitution kernels used for the reduced camera system.

@@ -108,6 +108,24 @@ class GFTTParams(ctypes.Structure):
     ]
 
 
+class TwoViewOptions(ctypes.Structure):
+    _fields_ = [
+        ("f_ransac_threshold", c_double),
+        ("f_confidence", c_double),
+        ("h_score_th", c_double),
+        ("h_score_gamma", c_double),
+        ("f_score_th", c_double),
+        ("f_score_gamma", c_double),
+        ("h_ratio", c_double),
+        ("max_repr_err", c_double),
+        ("min_good_fraction", c_double),
+        ("ambiguity_ratio", c_double),
+        ("min_parallax_deg", c_double),
+        ("f_max_iters", c_int32),
+        ("min_good", c_int32),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGNATURES = {
     "sfm_abi_version": (c_int32, []),
@@ -186,6 +204,10 @@ _SIGNATURES = {
                                c_void_p, c_void_p, c_void_p, POINTER(c_int32), POINTER(c_int32)]),
     "sfm_triangulate_points": (c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
                                        c_void_p]),
+    "sfm_two_view_default_options": (None, [POINTER(TwoViewOptions)]),
+    "sfm_two_view_init": (c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(TwoViewOptions),
+                                  POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_double),
+                                  c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int32)]),
     "sfm_dense_spd_solve": (c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, POINTER(c_double),
                                     POINTER(c_int32)]),
     "sfm_bench_stream_copy": (c_int, [c_int32, c_int64, c_int32, POINTER(c_double)]),
@@ -282,10 +304,16 @@ def default_gftt_params() -> GFTTParams:
     return p
 
 
+def default_two_view_options() -> TwoViewOptions:
+    o = TwoViewOptions()
+    lib().sfm_two_view_default_options(ctypes.byref(o))
+    return o
+
+
 def device_count() -> int:
     return int(lib().sfm_device_count())
 
 
-__all__ = ["lib", "check", "ptr", "BAOptions", "BASummary", "BAIteration", "KLTParams", "GFTTParams", "SfmError",
-           "default_options", "default_klt_params", "default_gftt_params",
+__all__ = ["lib", "check", "ptr", "BAOptions", "BASummary", "BAIteration", "KLTParams", "GFTTParams", "TwoViewOptions", "SfmError",
+           "default_options", "default_klt_params", "default_gftt_params", "default_two_view_options",
            "device_count", "exported_symbols", "LIB_PATH", "c_uint8"]

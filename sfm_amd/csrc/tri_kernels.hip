@@ -12,6 +12,7 @@
 #include <string>
 #include "../../include/sfm_amd.h"
 #include "cv_linalg.h"
+#include "tri_point.h"
 
 void sfm_internal_set_error(const std::string& msg);
 
@@ -27,21 +28,11 @@ __global__ __launch_bounds__(256) void k_triangulate(int n, const int32_t* __res
   if (i >= n) return;
   const double* Pa = P + 12 * size_t(cam0[i]);
   const double* Pb = P + 12 * size_t(cam1[i]);
-  double A[4][4];
-  const double xa = uv0[2 * i], ya = uv0[2 * i + 1], xb = uv1[2 * i], yb = uv1[2 * i + 1];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    A[0][k] = xa * Pa[8 + k] - Pa[k];
-    A[1][k] = ya * Pa[8 + k] - Pa[4 + k];
-    A[2][k] = xb * Pb[8 + k] - Pb[k];
-    A[3][k] = yb * Pb[8 + k] - Pb[4 + k];
-  }
-  double U[4][4], w[4], Vt[4][4];
-  cv_svd<4, 4>(A, U, w, Vt);
-  const double h = Vt[3][3];
-  X[3 * size_t(i)] = Vt[3][0] / h;
-  X[3 * size_t(i) + 1] = Vt[3][1] / h;
-  X[3 * size_t(i) + 2] = Vt[3][2] / h;
+  double Xi[3];
+  const double h = tri_point(Pa, Pb, uv0[2 * i], uv0[2 * i + 1], uv1[2 * i], uv1[2 * i + 1], Xi);
+  X[3 * size_t(i)] = Xi[0];
+  X[3 * size_t(i) + 1] = Xi[1];
+  X[3 * size_t(i) + 2] = Xi[2];
   if (w4) w4[i] = h;
 }
 

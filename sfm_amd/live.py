@@ -27,9 +27,15 @@ bundle adjustment over all keyframes, gathered frame-major through
 CMap::getPointsInFrame as CSfM::bundleAdjustment does (CSfM.cpp:310-348),
 one-shot sfm_ba_solve, poses and points written back.
 
-Scope notes: the initial map comes from the stream's known poses of the
-first two keyframes (CSfM::init's homography / fundamental estimation is
-OpenCV's, out of scope); GeometryUtils (filterMatches, projectPoints) is not
+The initial map (CSfM::init, CSfM.cpp:802-1001): init="known" reads the
+second keyframe's pose from the stream's ground truth (the synthetic
+bootstrap); init="estimate" runs the reference's two-view initialisation on
+the matcher's matches (sfm_two_view_init, sfm_amd/init.py: homography and
+fundamental matrix, model choice, R, t, triangulation, filter) and retries on
+the next frame while it fails, the first keyframe staying (CSfM.cpp:984-1000);
+the map's scale is then the unit baseline of the first two keyframes.
+
+Scope notes: GeometryUtils (filterMatches, projectPoints) is not
 in the reference tree, so filterMatches is restated from its call site
 (CSfM.cpp:164-165) as positive depth in both keyframes and the point-to-
 epipolar-line distance <= _maxReprErr both ways; map-point and keyframe
@@ -44,7 +50,8 @@ import numpy as np
 
 from . import ba as _ba
 from .cmap import DeviceMap
-from .mapping import F_PIX, _rodrigues, triangulate_points
+from .init import two_view_init
+from .mapping import F_PIX, _rodrigues, _rodrigues_inv, triangulate_points
 from .matcher import FeatureMatcher
 from .pnp import solvePnPRansac
 
@@ -224,7 +231,13 @@ def _filter_matches(K, f0, f1, uv0, uv1, X, max_err):
 
 
 class LiveSfM:
-    def __init__(self, stream: KeypointStream | None = None, device: int = 0, init_gap: int = 5):
+    def __init__(self, stream: KeypointStream | None = None, device: int = 0, init_gap: int = 5,
+                 init: str = "known", init_options: dict | None = None):
+        if init not in ("known", "estimate"):
+            raise ValueError(f"init must be 'known' or 'estimate', not {init!r}")
+        self.init = init
+        self.init_options = dict(init_options or {})
+        self.init_log: list[dict] = []   # init="estimate": one entry per attempt
         self.stream = stream if stream is not None else KeypointStream()
         self.K = self.stream.K
         self.device = device
@@ -271,16 +284,28 @@ class LiveSfM:
             return
         self._tracking(k, pts, desc)
 
-    # ---- initial map (bootstrap: known poses of the first two keyframes) ------
+    # ---- initial map (CSfM::init) ----------------------------------------------
     def _initialise(self, k, pts, desc) -> None:
         f0 = self.kfs[0]
         f1 = _Frame(k, pts, desc)
-        f1.rot, f1.t = self.stream.pose(k)
-        self.matcher.push_frame(pts, desc)
-        i0, i1 = self.matcher.match(f0.pts, f0.desc, f1.pts, f1.desc)
-        X = triangulate_points(np.zeros(len(i0), np.int32), np.ones(len(i0), np.int32), f0.pts[i0], f1.pts[i1],
-                               np.stack([f0.P(self.K), f1.P(self.K)]), device=self.device)
-        ok = _filter_matches(self.K, f0, f1, f0.pts[i0], f1.pts[i1], X, MAX_REPR_ERR)
+        if self.init == "estimate":
+            # CSfM.cpp:823-946 on the device: no pose is read from the stream
+            i0, i1 = self.matcher.match(f0.pts, f0.desc, f1.pts, f1.desc)
+            r = two_view_init(f0.pts[i0], f1.pts[i1], self.K, self.K, device=self.device, **self.init_options)
+            self.init_log.append({"frame": k, "matches": len(i0), "model": r.model, "n_kept": r.n_kept,
+                                  "scores": r.scores.copy(), "avg_err": r.avg_err, "pts0": f0.pts[i0], "pts1": f1.pts[i1]})
+            if not r.ok:
+                return  # the first keyframe stays; the next frame tries again (CSfM.cpp:984-1000)
+            f1.rot, f1.t = _rodrigues_inv(r.R), r.t.copy()
+            self.matcher.push_frame(pts, desc)
+            ok, X = r.keep.astype(bool), r.X
+        else:
+            f1.rot, f1.t = self.stream.pose(k)
+            self.matcher.push_frame(pts, desc)
+            i0, i1 = self.matcher.match(f0.pts, f0.desc, f1.pts, f1.desc)
+            X = triangulate_points(np.zeros(len(i0), np.int32), np.ones(len(i0), np.int32), f0.pts[i0], f1.pts[i1],
+                                   np.stack([f0.P(self.K), f1.P(self.K)]), device=self.device)
+            ok = _filter_matches(self.K, f0, f1, f0.pts[i0], f1.pts[i1], X, MAX_REPR_ERR)
         i0, i1, X = i0[ok], i1[ok], X[ok]
         idx = self.map.addNewPoints(X, np.stack([i0, i1]), [f0.no, f1.no])
         self.map.addDescriptors(idx, f0.desc[i0])

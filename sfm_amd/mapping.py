@@ -18,10 +18,14 @@ bundle adjustment over all keyframes (BASELINE.json configs[4]; SURVEY.md
   STRUCT_AND_POSE) on a fresh problem gathered frame-major as
   CSfM::bundleAdjustment does (CSfM.cpp:310-348; one-shot sfm_ba_solve).
 
-Scope notes: the map is bootstrapped from the video's known
-relative pose of the first keyframe pair (the reference's initialisation,
-CSfM::init with findHomography / findFundamentalMat, is OpenCV's and out
-of scope); tracks follow the flowed LK positions (the association step of
+The map starts from the video's known relative pose of the first keyframe
+pair (init="known", the synthetic bootstrap) or from the reference's
+initialisation, CSfM::init's findHomography / findFundamentalMat step, on the
+tracks of the first keyframe (init="estimate": sfm_two_view_init,
+sfm_amd/init.py; a failed attempt keeps the first keyframe and the next frame
+tries again, and the map's scale is the unit baseline of the first pair).
+
+Scope notes: tracks follow the flowed LK positions (the association step of
 computeOpticalFlow re-anchors points to fresh detections, which ends most
 tracks within a few frames -- row T6 keeps it bit-exact on its own); the
 reprojection re-finding of CSfM.cpp:190-221 is not restated (tracks already
@@ -87,9 +91,30 @@ def _rodrigues(r):
                                                                     [-u[1], u[0], 0]])
 
 
+def _rodrigues_inv(R):
+    """the rotation vector of R (angle < pi)"""
+    R = np.asarray(R, np.float64)
+    v = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s = 0.5 * float(np.sqrt(v @ v))
+    c = min(1.0, max(-1.0, 0.5 * (float(np.trace(R)) - 1.0)))
+    if s < 1e-12:
+        return np.zeros(3)
+    return v * (np.arctan2(s, c) / (2.0 * s))
+
+
 class IncrementalMapper:
     def __init__(self, video: SyntheticVideo | None = None, device: int = 0, kf_every: int = 10,
-                 depth: float = 10.0, max_tracks: int = 500, min_track_dist: float = 10.0):
+                 depth: float = 10.0, max_tracks: int = 500, min_track_dist: float = 10.0, init: str = "known",
+                 init_options: dict | None = None):
+        if init not in ("known", "estimate"):
+            raise ValueError(f"init must be 'known' or 'estimate', not {init!r}")
+        # the second keyframe's pose: "known" = the video's ground truth (the synthetic bootstrap),
+        # "estimate" = CSfM::init's two-view initialisation on the tracks (sfm_two_view_init)
+        self.init = init
+        self.init_options = dict(init_options or {})
+        self.init_log: list[dict] = []
+        self._init_result = None
+        self._init_retry = False
         self.video = video if video is not None else SyntheticVideo()
         self.device = device
         self.kf_every = int(kf_every)
@@ -149,7 +174,7 @@ class IncrementalMapper:
                     self.pose = (r, t)
                     self.pnp_frames += 1
         self.times["pnp"] += time.perf_counter() - t1
-        if k % self.kf_every == 0:
+        if k % self.kf_every == 0 or self._init_retry:
             t2 = time.perf_counter()
             self._keyframe(k)
             self.times["keyframe"] += time.perf_counter() - t2
@@ -158,8 +183,19 @@ class IncrementalMapper:
         j = len(self.kf_frames)
         if j == 0:
             rot, t = np.zeros(3), np.zeros(3)         # CFrame.cpp:229-235: first keyframe at the origin
+        elif j == 1 and self.init == "estimate":
+            # CSfM::init (CSfM.cpp:823-946): every live track started in the first keyframe
+            from .init import two_view_init
+            r = two_view_init(self.first_uv[self.tr_id], self.tr_uv, self.K, self.K, device=self.device,
+                              **self.init_options)
+            self.init_log.append({"frame": k, "matches": len(self.tr_id), "model": r.model, "n_kept": r.n_kept})
+            self._init_retry = not r.ok
+            if not r.ok:
+                return                                # the first keyframe stays; the next frame tries again
+            self._init_result = r
+            rot, t = _rodrigues_inv(r.R), r.t.copy()
         elif j == 1:
-            rot, t = self.gt_pose(k)                  # bootstrap (CSfM::init is out of scope)
+            rot, t = self.gt_pose(k)                  # the synthetic bootstrap (init="known")
         else:
             rot, t = self.pose[0].copy(), self.pose[1].copy()
         self.kf_frames.append(k)
@@ -179,9 +215,15 @@ class IncrementalMapper:
             c1 = np.full(len(cand), j, np.int32)
             uv0 = self.first_uv[cand]
             uv1 = self.tr_uv[(self.nobs[self.tr_id] >= 2) & (self.pt_of[self.tr_id] < 0)].astype(np.float64)
-            Xn = triangulate_points(c0, c1, uv0, uv1, P, device=self.device)
-            ok = np.ones(len(cand), bool)
-            for cam, uvs in ((c0, uv0), (c1, uv1)):
+            if j == 1 and self._init_result is not None:
+                # the initialisation's own triangulation and filter (CSfM.cpp:918-946)
+                assert len(cand) == n_live
+                Xn, ok, views = self._init_result.X, self._init_result.keep.astype(bool), ()
+                self._init_result = None
+            else:
+                Xn = triangulate_points(c0, c1, uv0, uv1, P, device=self.device)
+                ok, views = np.ones(len(cand), bool), ((c0, uv0), (c1, uv1))
+            for cam, uvs in views:
                 Rm = np.stack([_rodrigues(self.kf_rot[c]) for c in range(len(self.kf_rot))])[cam]
                 Tm = np.stack(self.kf_t)[cam]
                 Xc = np.einsum("nij,nj->ni", Rm, Xn) + Tm
