@@ -1,0 +1,257 @@
+// The bundle adjuster's handle and what the files that work on it share:
+// ba_solver.hip (the LM loops, the collectives, the C ABI) and ba_problem.hip
+// (sfm_ba_set_problem).  Internal: nothing here is part of include/sfm_amd.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <map>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "ba_device.h"
+#include "ba_host_layout.h"
+#include "../../include/sfm_amd.h"
+
+// the calling thread's last error (ba_solver.hip holds it)
+void sfm_internal_set_error(const std::string& msg);
+inline int fail(int code, const std::string& msg) {
+  sfm_internal_set_error(msg);
+  return code;
+}
+
+#define HIPCHK(expr)                                                                              \
+  do {                                                                                            \
+    hipError_t e_ = (expr);                                                                       \
+    if (e_ != hipSuccess) return fail(SFM_EIO, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+enum Phase { kPhJac = 0, kPhCamRed, kPhPtEval, kPhPtPrep, kPhSchur, kPhChol, kPhBack, kPhBacksub, kPhOther, kNumPh };
+
+// device LM loop state (k_lm_decide / k_lm_post; see "device-driven LM loop")
+struct LmCtl {
+  int32_t run_step, run_eval, done, termination, error;
+  // The evaluation prepares the coming step (prep_fold, from the host: step_prep_folds).  An
+  // unsuccessful or invalid step then pauses the loop (run_step = 0, prep_stale = 1): the radius
+  // changed with no evaluation to follow, and the host, which enqueues the stand-alone prep
+  // kernels only when it knows they are needed, re-arms the loop with them in front.
+  int32_t prep_fold, prep_stale;
+  int32_t iteration, num_consecutive_invalid;
+  int32_t n_succ, n_unsucc, n_invalid, n_resid, n_jac, n_lin, trace_len;
+  double radius, decrease_factor, cost, grad_max, x_norm;
+  sfm_ba_iteration pending;  // an accepted iteration, completed after its evaluation
+  int32_t max_iter, max_invalid;
+  double ftol, gtol, ptol, max_radius, min_radius, min_rel_dec;
+  uint32_t red_count;  // workgroups of k_reduce_batch_lm done (reset by the last)
+  double init_cost, init_grad;  // the initial evaluation (k_lm_init), for the host's summary
+};
+
+struct sfm_ba_handle {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  sfm::DevProblem d;
+  int32_t mode = SFM_BA_STRUCT_AND_POSE;  // of the running solve (CTracker.h:67)
+  int32_t bs_epoch = 0;          // stamp of the last back-substitution launch (k_backsolve flags)
+  int32_t chol_epoch = 0;        // launches of the fused Cholesky since the last set_problem
+  bool force_pack = false;       // SFM_FORCE_PACK=1: exercise the packed all-reduce path on one rank (tests)
+  std::vector<std::pair<size_t, void*>> allocs;  // (bytes, buffer) of the resident problem
+  std::vector<std::pair<size_t, void*>> tmps;    // set_problem's scratch (back to the pool when it returns)
+  std::multimap<size_t, void*> pool;             // buffers of earlier problems, reused by size
+  bool has_problem = false;
+  // multi-GPU
+  ncclComm_t comm = nullptr;
+  int nranks = 1, rank = 0;
+  // host-callback collective (sfm_ba_set_host_comm: tests run the sharded
+  // path with several ranks on one GPU, where RCCL allows one rank per GPU)
+  sfm_allreduce_fn host_fn = nullptr;
+  void* host_user = nullptr;
+  std::vector<double> host_buf, host_buf2;
+  // ... with broadcast and reduce-scatter too (sfm_ba_set_host_collectives);
+  // without it the distributed factor builds both from host_fn's all-reduce
+  sfm_collective_fn coll_fn = nullptr;
+  void* coll_user = nullptr;
+  // distributed reduced-camera factor (sfm_ba_set_distributed_factor): 1-D
+  // block-cyclic column panels of dist_pt 64-column tiles; 0 = every rank
+  // factors the all-reduced system (replicated)
+  int dist_pt = 0;
+  struct DistBufs {
+    int pt = 0, nblk = 0, n = 0, nranks = 0, rank = 0;  // the layout below was made for
+    int64_t total = 0;                // doubles of all panel rectangles
+    int64_t bcast_cap = 0;            // largest broadcast (doubles)
+    std::vector<int64_t> count, poff; // per panel: rectangle doubles, offset in the panel image
+    double* send = nullptr;           // [total] this rank's partial panels (own ones: zeros)
+    double* recv = nullptr;           // [total] the other ranks' sums of the own panels
+    double* bcast = nullptr;          // [2][bcast_cap]: panel k travels in half k % 2
+    hipStream_t cstream = nullptr;    // RCCL: the collectives' own stream (look-ahead)
+    hipEvent_t ev_packed = nullptr, ev_free[2] = {nullptr, nullptr}, ev_arrived[2] = {nullptr, nullptr};
+    hipEvent_t ev_sent = nullptr;     // the partial panels are packed
+    std::vector<hipEvent_t> ev_red;   // [np] panel k's reduce has landed (owner)
+    int64_t* off_send = nullptr;      // [np] panel offset in send, -1 for own panels (device)
+    int64_t* off_recv = nullptr;      // (unused)
+  } dist;
+  // out-of-place target of the collectives enqueued inside a gated phase of
+  // the device LM loop (allreduce below); grown on demand
+  double* ar_tmp = nullptr;
+  size_t ar_tmp_cap = 0;
+  // SFM_EMULATE_IDENTICAL_RANKS=k (tests, read by sfm_ba_set_comm): every sum
+  // collective returns k times its one-rank result, i.e. the sum over k
+  // ranks holding the same shard, so a one-GPU run sees the stale-buffer
+  // hazards of a multi-rank one
+  int emulate_ranks = 1;
+  // device-driven LM loop (unsharded solves): control block, its pinned
+  // mirror and the device trace buffer (grown to the iteration cap)
+  LmCtl* lm_ctl = nullptr;
+  LmCtl* lm_ctl_host = nullptr;
+  // (pinned host memory: the deciding workgroups write the few entries
+  // straight to the host, which reads them after the batch's synchronisation)
+  sfm_ba_iteration* lm_trace = nullptr;
+  int lm_trace_cap = 0;
+  // one-shot sfm_ba_solve on a small problem: every batch's control readback
+  // also brings the parameters (cam | X) into param_host, so the final
+  // download needs no further round trip (param_host_valid until consumed)
+  bool prefetch_params = false;
+  bool param_host_valid = false;
+  double* param_host = nullptr;
+  size_t param_host_cap = 0;
+  // pinned staging for every host <-> device transfer of set_problem,
+  // get_parameters and the LM trace: a pageable copy goes through the
+  // runtime's own staging (C1: the 320-KB uv upload took 131 us, the 49-KB
+  // parameter download ~100 us), a pinned one is a single DMA.  Grown
+  // geometrically, only while the stream is idle.
+  uint8_t* stage = nullptr;
+  size_t stage_cap = 0;
+  // device LM loop without a collective: the phase reductions run the
+  // bookkeeping in their last workgroup (k_reduce_batch_lm)
+  bool fuse_lm = false;
+  // device LM loop: the evaluation's k_cam_prep also makes the accepted
+  // candidate current (k_lm_accept folded in; its grid covers the copy)
+  int accept_grid = 0;  // < 0: done by the deciding reduction (AcceptFold)
+  bool accept_fold = false;
+  // The step's radius-dependent preparation (point factor, k_obs_prep_rc,
+  // diagonal blocks) folded into the evaluation (step_prep_folds): the
+  // radius changes only in the step's decision, so an evaluation prepares
+  // the coming step.  eval_radius: that step's radius (host loop; the device
+  // loop's kernels read LmCtl::radius).  prep_fresh: the prep on the device
+  // is for the current radius; set by the evaluation, cleared by an
+  // unsuccessful or invalid step (the host loop's own decision; the device
+  // loop pauses there and reports LmCtl::prep_stale), after which
+  // compute_step runs the stand-alone kernels first.
+  double eval_radius = 0.0;
+  bool prep_fresh = false;
+  int n_cu = 0;  // compute units of the device (queried once)
+  // Schur / Cholesky overlap (DevProblem::overlap): the factorisation's
+  // stream and the two events that fork and join it
+  hipStream_t stream2 = nullptr;
+  hipEvent_t ov_ev[2] = {nullptr, nullptr};
+  // set_problem's uploads beside the layout kernels (large problems): the
+  // parameters (uev), and uv from a worker thread (uev_uv)
+  hipStream_t ustream = nullptr;
+  hipEvent_t uev = nullptr, uev_uv = nullptr;
+  // profiling
+  bool profiling = false;
+  std::vector<hipEvent_t> ev;
+  int ev_used = 0;
+  std::vector<std::pair<int, int>> ev_marks;  // (phase, event index of start); end = start + 1
+  double phase_ms[kNumPh] = {0};
+  int phase_count[kNumPh] = {0};
+};
+
+// Device buffers are taken from the handle's pool (the previous problem's
+// buffers, best fit within 2x) before hipMalloc: repeated keyframe-sized
+// solves (CSfM::bundleAdjustment after every keyframe) then allocate
+// nothing.  Contents are never assumed: set_problem initialises every
+// buffer it relies on.
+template <typename T>
+int dalloc(sfm_ba_handle* h, T** p, size_t count) {
+  if (count == 0) count = 1;
+  const size_t bytes = (count * sizeof(T) + 255) & ~size_t(255);
+  auto it = h->pool.lower_bound(bytes);
+  void* q = nullptr;
+  size_t got = bytes;
+  if (it != h->pool.end() && it->first <= 2 * bytes) {
+    q = it->second;
+    got = it->first;
+    h->pool.erase(it);
+  } else {
+    hipError_t e = hipMalloc(&q, bytes);
+    if (e != hipSuccess) return fail(SFM_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+  }
+  h->allocs.push_back({got, q});
+  *p = static_cast<T*>(q);
+  return 0;
+}
+// set_problem scratch: retired into the pool when set_problem returns after
+// its synchronisation, or -- a keyframe-sized set_problem returns without one
+// -- by the next set_problem's free_problem, which synchronises first.  So a
+// pooled buffer is never handed out while a kernel of this stream may still
+// use it: every path that moves tmps into the pool (retire_tmps) runs behind
+// a hipStreamSynchronize of the handle's stream.
+template <typename T>
+int dalloc_tmp(sfm_ba_handle* h, T** p, size_t count) {
+  const int rc = dalloc(h, p, count);
+  if (rc) return rc;
+  h->tmps.push_back(h->allocs.back());
+  h->allocs.pop_back();
+  return 0;
+}
+inline void retire_tmps(sfm_ba_handle* h) {
+  for (auto& a : h->tmps) h->pool.insert(a);
+  h->tmps.clear();
+}
+
+// The pinned staging buffer with room for `bytes` (ba_solver.hip).  Growing it
+// frees the old buffer, so nothing may still read or write it: every caller
+// has synchronised the stream (set_problem, get_parameters), and a
+// keyframe-sized set_problem, which returns with its uploads from the stage
+// still in flight, is always followed by a synchronising call before the
+// stage is written again.  The rule is checked there: a stream found busy is
+// drained first (and counted, so a test can see the rule broken).
+int stage_reserve(sfm_ba_handle* h, size_t bytes);
+using sfm::kStageMaxBytes;  // transfers above it bypass the stage (ba_host_layout.h)
+using sfm::hostlayout::StageLayout;
+
+inline void release_pool(sfm_ba_handle* h) {
+  for (auto& kv : h->pool) hipFree(kv.second);
+  h->pool.clear();
+}
+
+// Retires the problem's buffers into the pool (freed by release_pool).
+inline void free_problem(sfm_ba_handle* h) {
+  for (auto& a : h->allocs) h->pool.insert(a);
+  h->allocs.clear();
+  retire_tmps(h);
+  double* keep = h->d.scal_host;  // pinned mirror: kept for the handle's life
+  h->d = sfm::DevProblem();
+  h->d.scal_host = keep;
+  h->has_problem = false;
+}
+
+inline bool env_flag(const char* name) {
+  const char* v = std::getenv(name);
+  return v && v[0] == '1';
+}
+
+// SFM_TIMING=1: host phase times of sfm_ba_set_problem and of the device LM
+// loop's batches on stderr.
+struct HostTimer {
+  bool on = env_flag("SFM_TIMING");
+  const char* tag = "set_problem";
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  void mark(const char* what) {
+    if (!on) return;
+    const auto t1 = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "[%s] %-22s %8.3f ms\n", tag, what,
+                 std::chrono::duration<double, std::milli>(t1 - t0).count());
+    t0 = t1;
+  }
+};
+
+inline bool sharded(const sfm_ba_handle* h) { return h->comm != nullptr || h->host_fn != nullptr; }
+
+inline size_t packed_size(int n) { return size_t(n) * (n + 1) / 2 + size_t(n); }

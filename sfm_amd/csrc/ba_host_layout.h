@@ -2,7 +2,11 @@
 // keyframe-sized problems' checks and counts (k_validate's work done on the
 // host), the camera runs and wavefront chunk table, the small path's XCD
 // slice sizes and the bound of the camera-run blob staged for upload.
-// Factored out of ba_solver.hip so that the CPU sanitizer build
+// Also the decisions set_problem takes before its first device call
+// (plan_setup: which of the three regimes and four parameter routes a problem
+// takes, and where its blobs lie in the pinned stage), the small path's size
+// predicate and the Schur pass's shape.
+// Kept apart from ba_problem.hip so that the CPU sanitizer build
 // (tests/asan, `make asan`) runs exactly this code under ASan/UBSan.
 //
 // Reference: the observation / parameter-block layout is CSfM.cpp:310-341
@@ -17,10 +21,164 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 #include <vector>
 
 namespace sfm {
+
+// Transfers above this go straight from / to the caller's pageable memory:
+// the runtime pipelines its own staging copies with the DMA, where ours
+// would run them one after the other (C3 one-shot 7.4 -> 9.2 ms with the
+// 48-MB observation upload staged).
+constexpr size_t kStageMaxBytes = size_t(1) << 20;
+// observations up to which set_problem checks and counts them on the host
+constexpr int64_t kHostCheckMaxObs = 65536;
+// and from which uv (16 B each) goes up from a worker thread beside the index
+// layouts (4 MB: the thread's start-up is noise beside the copy)
+constexpr int64_t kDeferredUvMinObs = 262144;
+// Bounds of the layouts without radix sorts (ba_setup.hip small path): C <=
+// 256, at most kSmallSetupMaxChunks chunks, short point segments.
+constexpr int kSmallSetupMaxC = 256;
+constexpr int kSmallSetupMaxChunks = 2048;
+constexpr int kSmallSetupMaxPtObs = 64;
+constexpr int64_t kSmallSetupMaxObs = 64 * 1024;  // (k_small_cm_compact: 64 steps of 1024)
+// Reduced systems with more camera blocks than this take the XCD-aware
+// k_schur_pts order (C3: 125k blocks); smaller ones the plain order.
+constexpr int64_t kSchurXcdMinBlocks = 8192;
+
 namespace hostlayout {
+
+// byte offsets of a packed staging layout (256-B aligned pieces)
+struct StageLayout {
+  size_t bytes = 0;
+  size_t add(size_t n) {
+    const size_t o = bytes;
+    bytes += (n + 255) & ~size_t(255);
+    return o;
+  }
+};
+
+// Bytes the camera-run blob (cam_rng | wcam | cam_off | chunks, and on the
+// small path pt_off | the scatters' slot counters) can take, staged behind
+// the still-in-flight input blob: 2 C + (npad / 64 + 1) + (C + 1) ints, 16 B
+// per chunk (npad / 64 <= N / 64 + C chunks), P + 1 + P + C ints, padding.
+inline size_t runs_blob_bound(int C, int64_t N, int P) {
+  return 64 * (size_t(C) + 1) + 2 * size_t(N) + 8 * (size_t(P) + 1) + 4 * size_t(C) + 2048;
+}
+
+// How the parameter blob (Kc | cam | cam0 | X | X0) reaches the device.
+//   None   no cameras and no points: nothing to upload
+//   Early  host-counted problems: staged behind the camera-run blob and
+//          uploaded before the layout launches (its host copies overlap them)
+//   Side   above the stage's 1 MB: from the caller's pageable arrays on a
+//          stream of its own beside the layout kernels
+//   Late   staged after the layout round trip, which has freed the stage
+enum class ParamRoute { None, Early, Side, Late };
+
+// Everything set_problem decides before its first device call.
+//
+//   regime           observations        validation  uv upload
+//   host counts      input blob <= 1 MB  host        staged with the indices
+//   device checks    up to 262143        k_validate  in line, pageable
+//   deferred uv      from 262144         k_validate  worker thread, side stream
+//
+// The pinned stage holds up to three regions at once, none synchronised
+// against the next: the input blob [0, in_bytes), the camera-run blob
+// [il_base, il_base + il_bound) and, on the Early route, the parameter blob
+// [pl_base, pl_base + pl_bytes).
+struct SetupPlan {
+  bool host_counts = false;  // checks and counts on the host, riding in the staged input blob
+  bool stage_in = false;     // the input blob goes through the pinned stage
+  bool deferred_uv = false;  // uv from a worker thread beside the index layouts
+  size_t o_uv = 0, o_cam = 0, o_pt = 0, o_pc = 0, in_bytes = 0;  // input blob (device, and the stage's image of it)
+  size_t il_base = 0, il_bound = 0;                              // camera-run blob in the stage
+  size_t o_K = 0, o_c = 0, o_c0 = 0, o_X = 0, o_X0 = 0, pl_bytes = 0;  // parameter blob
+  size_t pl_base = 0;                                            // ... in the stage (Early)
+  ParamRoute route = ParamRoute::None;
+  size_t stage_bytes = 0;  // to reserve in the stage before the first upload
+};
+
+inline SetupPlan plan_setup(int64_t N, int C, int P, bool sync_uv) {
+  SetupPlan p;
+  // keyframe-sized problems: the checks and the camera / point counts on
+  // the host, their point counts riding in the same upload -- no validation
+  // launch and no round trip before the layout (C1: ~60 us of set_problem)
+  const bool host_check = N <= kHostCheckMaxObs;
+  StageLayout up;
+  p.o_uv = up.add(sizeof(double) * 2 * size_t(N));
+  p.o_cam = up.add(sizeof(int32_t) * size_t(N));
+  p.o_pt = up.add(sizeof(int32_t) * size_t(N));
+  p.o_pc = host_check ? up.add(sizeof(int32_t) * (size_t(P) + 1)) : 0;
+  p.in_bytes = up.bytes;
+  p.stage_in = p.in_bytes <= kStageMaxBytes;
+  p.host_counts = host_check && p.stage_in;
+  // large problems: uv uploaded beside the index layouts (SFM_SYNC_UV=1: in
+  // line, as before round 6)
+  p.deferred_uv = !p.stage_in && N >= kDeferredUvMinObs && !sync_uv;
+  // (host counts: the camera-run blob is staged AFTER the input blob, which
+  // is still in flight -- no synchronisation in between -- so the stage
+  // holds both from the start: 2 C + chunks + ... ints, bounded)
+  p.il_base = p.host_counts ? (p.in_bytes + 255) / 256 * 256 : 0;
+  p.il_bound = p.host_counts ? runs_blob_bound(C, N, P) : 0;
+  // intrinsics, the parameters and their reset copies: one blob, one DMA
+  StageLayout pl;
+  p.o_K = pl.add(sizeof(double) * 5 * size_t(C));
+  p.o_c = pl.add(sizeof(double) * 6 * size_t(C));
+  p.o_c0 = pl.add(sizeof(double) * 6 * size_t(C));
+  p.o_X = pl.add(sizeof(double) * 3 * size_t(P));
+  p.o_X0 = pl.add(sizeof(double) * 3 * size_t(P));
+  p.pl_bytes = pl.bytes;
+  p.pl_base = (p.il_base + p.il_bound + 255) / 256 * 256;
+  if (!(C || P)) p.route = ParamRoute::None;
+  else if (p.host_counts && p.pl_base + p.pl_bytes <= 4 * kStageMaxBytes) p.route = ParamRoute::Early;
+  else if (p.pl_bytes > kStageMaxBytes) p.route = ParamRoute::Side;
+  else p.route = ParamRoute::Late;
+  p.stage_bytes = std::max({p.stage_in ? p.il_base + p.il_bound : 0,
+                            p.route == ParamRoute::Early ? p.pl_base + p.pl_bytes : 0,
+                            sizeof(int32_t) * (size_t(C) + 4)});  // (the validation readback: 4 + C counts)
+  return p;
+}
+
+// The size part of the small path's predicate (the layouts without radix
+// sorts; the caller adds that the host has the counts, and SFM_SMALL_SETUP):
+// the segments fit ba_setup.hip's bounds, and C (C + 1) / 2 <=
+// kSchurXcdMinBlocks, i.e. the plain k_schur_pts block order, as the sorted
+// path takes for these sizes.
+inline bool small_setup_fits(int64_t N, int C, int P, const int32_t* n_obs_of_cam, const int32_t* n_obs_of_pt) {
+  if (!(N > 0 && N <= kSmallSetupMaxObs && C > 0 && C <= kSmallSetupMaxC &&
+        int64_t(C) * (C + 1) / 2 <= kSchurXcdMinBlocks))
+    return false;
+  int64_t nch = 0;
+  for (int c = 0; c < C; ++c) nch += (n_obs_of_cam[c] + 63) / 64;
+  if (nch > kSmallSetupMaxChunks) return false;
+  for (int p = 0; p < P; ++p)
+    if (n_obs_of_pt[p] > kSmallSetupMaxPtObs) return false;
+  return true;
+}
+
+// The Schur pass's shape from the mean pair count per camera block.  Lanes
+// per block ~ a tenth of the mean, 8..64 (measured best: C3, 72 pairs per
+// block -> 8; C1 / C2, ~460 -> 64; SFM_SCHUR_PTS_SUB forces 8 / 16 / 32 / 64).
+// Few blocks with long lists (keyframe-sized: C1 210 blocks of ~460 pairs): a
+// workgroup per block instead of a wave (SFM_SCHUR_WG=0/1 forces).  The
+// overrides are the variables' values, nullptr when unset.
+struct SchurShape {
+  int pts_sub = 8;
+  bool wg_blocks = false;
+};
+inline SchurShape schur_shape(int64_t n_pairs, int64_t n_blk, const char* pts_sub_env, const char* wg_env) {
+  SchurShape sh;
+  const double avg = n_blk ? double(n_pairs) / double(n_blk) : 0.0;
+  if (pts_sub_env) {
+    const int v = std::atoi(pts_sub_env);
+    sh.pts_sub = v == 64 ? 64 : v == 32 ? 32 : v == 8 ? 8 : 16;
+  } else {
+    while (sh.pts_sub < 64 && sh.pts_sub < avg / 10.0) sh.pts_sub *= 2;
+  }
+  sh.wg_blocks = sh.pts_sub == 64 && n_blk <= 4 * 256 && avg >= 256.0;
+  if (wg_env) sh.wg_blocks = wg_env[0] == '1' && sh.pts_sub == 64;
+  return sh;
+}
 
 // One 64-wide wavefront chunk of a camera's run (the int4 the device reads:
 // camera, first camera-major position, count, the first observation's index
@@ -171,14 +329,6 @@ inline int32_t small_slice_max(int C, const int32_t* n_obs_of_cam, const std::ve
     }
   }
   return *std::max_element(jcnt.begin(), jcnt.end());
-}
-
-// Bytes the camera-run blob (cam_rng | wcam | cam_off | chunks, and on the
-// small path pt_off | the scatters' slot counters) can take, staged behind
-// the still-in-flight input blob: 2 C + (npad / 64 + 1) + (C + 1) ints, 16 B
-// per chunk (npad / 64 <= N / 64 + C chunks), P + 1 + P + C ints, padding.
-inline size_t runs_blob_bound(int C, int64_t N, int P) {
-  return 64 * (size_t(C) + 1) + 2 * size_t(N) + 8 * (size_t(P) + 1) + 4 * size_t(C) + 2048;
 }
 
 }  // namespace hostlayout

@@ -1,9 +1,11 @@
 // Launchers of the device-side problem setup (ba_setup.hip), driven by
-// sfm_ba_set_problem (ba_solver.hip).
+// sfm_ba_set_problem (ba_problem.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
+
+#include "ba_host_layout.h"  // kSmallSetupMax*: the small path's bounds
 
 namespace sfm {
 
@@ -80,11 +82,7 @@ void launch_blk(int C, int2* blk, hipStream_t s);
 // compactions, run lengths of the camera-sorted point segments for the pair
 // lists).  fill / tmp: zeroed point counters (P) and N-item scratch.  Bounds
 // (the host checks): C <= 256, at most kSmallChunks chunks, short point
-// segments.
-constexpr int kSmallSetupMaxC = 256;
-constexpr int kSmallSetupMaxChunks = 2048;
-constexpr int kSmallSetupMaxPtObs = 64;
-constexpr int64_t kSmallSetupMaxObs = 64 * 1024;  // (k_small_cm_compact: 64 steps of 1024)
+// segments (kSmallSetupMax*, ba_host_layout.h).
 void launch_small_pm(int64_t N, const int32_t* pt, const int32_t* cam, const double* uv, const int32_t* pt_off,
                      int32_t* fill, int32_t* tmp, int32_t* order, double* uv_pm, int32_t* cam_pm, int32_t* pt_s,
                      hipStream_t s);

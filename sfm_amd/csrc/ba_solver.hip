@@ -1,5 +1,6 @@
-// Host side of the device bundle adjuster: problem layout, the Levenberg-
-// Marquardt trust-region loop and the C ABI of include/sfm_amd.h.
+// Host side of the device bundle adjuster: the Levenberg-Marquardt
+// trust-region loop and the C ABI of include/sfm_amd.h (the problem layout,
+// sfm_ba_set_problem, is ba_problem.hip's; the handle they share, ba_handle.h).
 //
 // The loop restates Ceres' TrustRegionMinimizer + LevenbergMarquardtStrategy
 // (the solver behind ceres::Solve at /root/reference/CTracker.cpp:700-701,
@@ -10,7 +11,6 @@
 #include <rccl/rccl.h>
 #include <map>
 #include <atomic>
-#include <thread>
 
 #include <algorithm>
 #include <array>
@@ -29,23 +29,16 @@
 #include "ba_setup.h"
 #include "ba_common.h"
 #include "ba_host_layout.h"
+#include "ba_handle.h"
 #include "../../include/sfm_amd.h"
 
 namespace {
 thread_local std::string g_err;
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
+std::atomic<int> g_stage_busy_regrows{0};
 }  // namespace
 
 void sfm_internal_set_error(const std::string& msg) { g_err = msg; }
 
-#define HIPCHK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return fail(SFM_EIO, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 #define NCCLCHK(expr)                                                                             \
   do {                                                                                            \
     ncclResult_t r_ = (expr);                                                                     \
@@ -54,189 +47,7 @@ void sfm_internal_set_error(const std::string& msg) { g_err = msg; }
 
 using namespace sfm;
 
-enum Phase { kPhJac = 0, kPhCamRed, kPhPtEval, kPhPtPrep, kPhSchur, kPhChol, kPhBack, kPhBacksub, kPhOther, kNumPh };
-
-// device LM loop state (k_lm_decide / k_lm_post; see "device-driven LM loop")
-struct LmCtl {
-  int32_t run_step, run_eval, done, termination, error;
-  // The evaluation prepares the coming step (prep_fold, from the host: step_prep_folds).  An
-  // unsuccessful or invalid step then pauses the loop (run_step = 0, prep_stale = 1): the radius
-  // changed with no evaluation to follow, and the host, which enqueues the stand-alone prep
-  // kernels only when it knows they are needed, re-arms the loop with them in front.
-  int32_t prep_fold, prep_stale;
-  int32_t iteration, num_consecutive_invalid;
-  int32_t n_succ, n_unsucc, n_invalid, n_resid, n_jac, n_lin, trace_len;
-  double radius, decrease_factor, cost, grad_max, x_norm;
-  sfm_ba_iteration pending;  // an accepted iteration, completed after its evaluation
-  int32_t max_iter, max_invalid;
-  double ftol, gtol, ptol, max_radius, min_radius, min_rel_dec;
-  uint32_t red_count;  // workgroups of k_reduce_batch_lm done (reset by the last)
-  double init_cost, init_grad;  // the initial evaluation (k_lm_init), for the host's summary
-};
-
-struct sfm_ba_handle {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  DevProblem d;
-  int32_t mode = SFM_BA_STRUCT_AND_POSE;  // of the running solve (CTracker.h:67)
-  int32_t bs_epoch = 0;          // stamp of the last back-substitution launch (k_backsolve flags)
-  int32_t chol_epoch = 0;        // launches of the fused Cholesky since the last set_problem
-  bool force_pack = false;       // SFM_FORCE_PACK=1: exercise the packed all-reduce path on one rank (tests)
-  std::vector<std::pair<size_t, void*>> allocs;  // (bytes, buffer) of the resident problem
-  std::vector<std::pair<size_t, void*>> tmps;    // set_problem's scratch (back to the pool when it returns)
-  std::multimap<size_t, void*> pool;             // buffers of earlier problems, reused by size
-  bool has_problem = false;
-  // multi-GPU
-  ncclComm_t comm = nullptr;
-  int nranks = 1, rank = 0;
-  // host-callback collective (sfm_ba_set_host_comm: tests run the sharded
-  // path with several ranks on one GPU, where RCCL allows one rank per GPU)
-  sfm_allreduce_fn host_fn = nullptr;
-  void* host_user = nullptr;
-  std::vector<double> host_buf, host_buf2;
-  // ... with broadcast and reduce-scatter too (sfm_ba_set_host_collectives);
-  // without it the distributed factor builds both from host_fn's all-reduce
-  sfm_collective_fn coll_fn = nullptr;
-  void* coll_user = nullptr;
-  // distributed reduced-camera factor (sfm_ba_set_distributed_factor): 1-D
-  // block-cyclic column panels of dist_pt 64-column tiles; 0 = every rank
-  // factors the all-reduced system (replicated)
-  int dist_pt = 0;
-  struct DistBufs {
-    int pt = 0, nblk = 0, n = 0, nranks = 0, rank = 0;  // the layout below was made for
-    int64_t total = 0;                // doubles of all panel rectangles
-    int64_t bcast_cap = 0;            // largest broadcast (doubles)
-    std::vector<int64_t> count, poff; // per panel: rectangle doubles, offset in the panel image
-    double* send = nullptr;           // [total] this rank's partial panels (own ones: zeros)
-    double* recv = nullptr;           // [total] the other ranks' sums of the own panels
-    double* bcast = nullptr;          // [2][bcast_cap]: panel k travels in half k % 2
-    hipStream_t cstream = nullptr;    // RCCL: the collectives' own stream (look-ahead)
-    hipEvent_t ev_packed = nullptr, ev_free[2] = {nullptr, nullptr}, ev_arrived[2] = {nullptr, nullptr};
-    hipEvent_t ev_sent = nullptr;     // the partial panels are packed
-    std::vector<hipEvent_t> ev_red;   // [np] panel k's reduce has landed (owner)
-    int64_t* off_send = nullptr;      // [np] panel offset in send, -1 for own panels (device)
-    int64_t* off_recv = nullptr;      // (unused)
-  } dist;
-  // out-of-place target of the collectives enqueued inside a gated phase of
-  // the device LM loop (allreduce below); grown on demand
-  double* ar_tmp = nullptr;
-  size_t ar_tmp_cap = 0;
-  // SFM_EMULATE_IDENTICAL_RANKS=k (tests, read by sfm_ba_set_comm): every sum
-  // collective returns k times its one-rank result, i.e. the sum over k
-  // ranks holding the same shard, so a one-GPU run sees the stale-buffer
-  // hazards of a multi-rank one
-  int emulate_ranks = 1;
-  // device-driven LM loop (unsharded solves): control block, its pinned
-  // mirror and the device trace buffer (grown to the iteration cap)
-  LmCtl* lm_ctl = nullptr;
-  LmCtl* lm_ctl_host = nullptr;
-  // (pinned host memory: the deciding workgroups write the few entries
-  // straight to the host, which reads them after the batch's synchronisation)
-  sfm_ba_iteration* lm_trace = nullptr;
-  int lm_trace_cap = 0;
-  // one-shot sfm_ba_solve on a small problem: every batch's control readback
-  // also brings the parameters (cam | X) into param_host, so the final
-  // download needs no further round trip (param_host_valid until consumed)
-  bool prefetch_params = false;
-  bool param_host_valid = false;
-  double* param_host = nullptr;
-  size_t param_host_cap = 0;
-  // pinned staging for every host <-> device transfer of set_problem,
-  // get_parameters and the LM trace: a pageable copy goes through the
-  // runtime's own staging (C1: the 320-KB uv upload took 131 us, the 49-KB
-  // parameter download ~100 us), a pinned one is a single DMA.  Grown
-  // geometrically, only while the stream is idle.
-  uint8_t* stage = nullptr;
-  size_t stage_cap = 0;
-  // device LM loop without a collective: the phase reductions run the
-  // bookkeeping in their last workgroup (k_reduce_batch_lm)
-  bool fuse_lm = false;
-  // device LM loop: the evaluation's k_cam_prep also makes the accepted
-  // candidate current (k_lm_accept folded in; its grid covers the copy)
-  int accept_grid = 0;  // < 0: done by the deciding reduction (AcceptFold)
-  bool accept_fold = false;
-  // The step's radius-dependent preparation (point factor, k_obs_prep_rc,
-  // diagonal blocks) folded into the evaluation (step_prep_folds): the
-  // radius changes only in the step's decision, so an evaluation prepares
-  // the coming step.  eval_radius: that step's radius (host loop; the device
-  // loop's kernels read LmCtl::radius).  prep_fresh: the prep on the device
-  // is for the current radius; set by the evaluation, cleared by an
-  // unsuccessful or invalid step (the host loop's own decision; the device
-  // loop pauses there and reports LmCtl::prep_stale), after which
-  // compute_step runs the stand-alone kernels first.
-  double eval_radius = 0.0;
-  bool prep_fresh = false;
-  int n_cu = 0;  // compute units of the device (queried once)
-  // Schur / Cholesky overlap (DevProblem::overlap): the factorisation's
-  // stream and the two events that fork and join it
-  hipStream_t stream2 = nullptr;
-  hipEvent_t ov_ev[2] = {nullptr, nullptr};
-  // set_problem's uploads beside the layout kernels (large problems): the
-  // parameters (uev), and uv from a worker thread (uev_uv)
-  hipStream_t ustream = nullptr;
-  hipEvent_t uev = nullptr, uev_uv = nullptr;
-  // profiling
-  bool profiling = false;
-  std::vector<hipEvent_t> ev;
-  int ev_used = 0;
-  std::vector<std::pair<int, int>> ev_marks;  // (phase, event index of start); end = start + 1
-  double phase_ms[kNumPh] = {0};
-  int phase_count[kNumPh] = {0};
-};
-
-namespace {
-
-// Device buffers are taken from the handle's pool (the previous problem's
-// buffers, best fit within 2x) before hipMalloc: repeated keyframe-sized
-// solves (CSfM::bundleAdjustment after every keyframe) then allocate
-// nothing.  Contents are never assumed: set_problem initialises every
-// buffer it relies on.
-template <typename T>
-int dalloc(sfm_ba_handle* h, T** p, size_t count) {
-  if (count == 0) count = 1;
-  const size_t bytes = (count * sizeof(T) + 255) & ~size_t(255);
-  auto it = h->pool.lower_bound(bytes);
-  void* q = nullptr;
-  size_t got = bytes;
-  if (it != h->pool.end() && it->first <= 2 * bytes) {
-    q = it->second;
-    got = it->first;
-    h->pool.erase(it);
-  } else {
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) return fail(SFM_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-  }
-  h->allocs.push_back({got, q});
-  *p = static_cast<T*>(q);
-  return 0;
-}
-// set_problem scratch: retired into the pool when set_problem returns after
-// its synchronisation, or -- a keyframe-sized set_problem returns without one
-// -- by the next set_problem's free_problem, which synchronises first.  So a
-// pooled buffer is never handed out while a kernel of this stream may still
-// use it: every path that moves tmps into the pool (retire_tmps) runs behind
-// a hipStreamSynchronize of the handle's stream.
-template <typename T>
-int dalloc_tmp(sfm_ba_handle* h, T** p, size_t count) {
-  const int rc = dalloc(h, p, count);
-  if (rc) return rc;
-  h->tmps.push_back(h->allocs.back());
-  h->allocs.pop_back();
-  return 0;
-}
-void retire_tmps(sfm_ba_handle* h) {
-  for (auto& a : h->tmps) h->pool.insert(a);
-  h->tmps.clear();
-}
-
-// The pinned staging buffer with room for `bytes`.  Growing it frees the old
-// buffer, so nothing may still read or write it: every caller has synchronised
-// the stream (set_problem, get_parameters), and a keyframe-sized set_problem,
-// which returns with its uploads from the stage still in flight, is always
-// followed by a synchronising call before the stage is written again.  The
-// rule is checked here: a stream found busy is drained first (and counted, so
-// a test can see the rule broken).
-std::atomic<int> g_stage_busy_regrows{0};
+// The pinned staging buffer with room for `bytes` (the rule it checks: ba_handle.h).
 int stage_reserve(sfm_ba_handle* h, size_t bytes) {
   if (bytes <= h->stage_cap) return 0;
   if (h->stage && hipStreamQuery(h->stream) == hipErrorNotReady) {
@@ -254,38 +65,10 @@ int stage_reserve(sfm_ba_handle* h, size_t bytes) {
   h->stage_cap = cap;
   return 0;
 }
-// Transfers above this go straight from / to the caller's pageable memory:
-// the runtime pipelines its own staging copies with the DMA, where ours
-// would run them one after the other (C3 one-shot 7.4 -> 9.2 ms with the
-// 48-MB observation upload staged).
-constexpr size_t kStageMaxBytes = size_t(1) << 20;
+
+namespace {
+
 constexpr size_t kParamPrefetchMaxBytes = size_t(1) << 20;  // one-shot solves that prefetch their parameters
-
-// byte offsets of a packed staging layout (256-B aligned pieces)
-struct StageLayout {
-  size_t bytes = 0;
-  size_t add(size_t n) {
-    const size_t o = bytes;
-    bytes += (n + 255) & ~size_t(255);
-    return o;
-  }
-};
-
-void release_pool(sfm_ba_handle* h) {
-  for (auto& kv : h->pool) hipFree(kv.second);
-  h->pool.clear();
-}
-
-// Retires the problem's buffers into the pool (freed by release_pool).
-void free_problem(sfm_ba_handle* h) {
-  for (auto& a : h->allocs) h->pool.insert(a);
-  h->allocs.clear();
-  retire_tmps(h);
-  double* keep = h->d.scal_host;  // pinned mirror: kept for the handle's life
-  h->d = DevProblem();
-  h->d.scal_host = keep;
-  h->has_problem = false;
-}
 
 // ---- phase timing (HIP events on the solver stream; read at the per-iteration sync)
 int mark_begin(sfm_ba_handle* h, int ph, hipStream_t on = nullptr) {
@@ -319,11 +102,6 @@ void collect_marks(sfm_ba_handle* h) {
   h->ev_used = 0;
 }
 
-bool env_flag(const char* name) {
-  const char* v = std::getenv(name);
-  return v && v[0] == '1';
-}
-
 // Compute units of the device: the persistent grids (fused Cholesky) size
 // themselves to one workgroup per CU (they also finish when only part of the
 // grid is resident: roles go by start order).
@@ -333,20 +111,6 @@ int device_cus(int device) {
   return prop.multiProcessorCount;
 }
 
-// SFM_TIMING=1: host phase times of sfm_ba_set_problem and of the device LM
-// loop's batches on stderr.
-struct HostTimer {
-  bool on = env_flag("SFM_TIMING");
-  const char* tag = "set_problem";
-  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  void mark(const char* what) {
-    if (!on) return;
-    const auto t1 = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[%s] %-22s %8.3f ms\n", tag, what,
-                 std::chrono::duration<double, std::milli>(t1 - t0).count());
-    t0 = t1;
-  }
-};
 
 // ---- device-driven LM loop ----
 // The trust-region bookkeeping of the host loop in sfm_ba_solve_resident,
@@ -600,15 +364,6 @@ __global__ __launch_bounds__(1024) void k_reduce_batch_lm(const double* __restri
   const double r = block_reduce(xn, sh, false);
   if (threadIdx.x == 0 && af.part_xn) af.part_xn[0] = r;
 }
-
-// Reduced systems with more camera blocks than this take the XCD-aware
-// k_schur_pts order (C3: 125k blocks); smaller ones the plain order.
-constexpr int64_t kSchurXcdMinBlocks = 8192;
-
-
-bool sharded(const sfm_ba_handle* h) { return h->comm != nullptr || h->host_fn != nullptr; }
-
-size_t packed_size(int n) { return size_t(n) * (n + 1) / 2 + size_t(n); }
 
 int allreduce(sfm_ba_handle* h, double* buf, size_t count, ncclRedOp_t op) {
   if (h->host_fn) {
@@ -1536,736 +1291,6 @@ int sfm_ba_set_host_collectives(sfm_ba_handle* h, int32_t nranks, int32_t rank, 
 int sfm_ba_set_distributed_factor(sfm_ba_handle* h, int32_t panel_tiles) {
   if (!h || panel_tiles < 0 || panel_tiles > 64) return fail(SFM_EINVAL, "panel_tiles must be in [0, 64]");
   h->dist_pt = panel_tiles;
-  return 0;
-}
-
-int sfm_ba_set_problem(sfm_ba_handle* h, int64_t n_obs, const double* obs_uv, const int32_t* cam_idx,
-                       const int32_t* pt_idx, int32_t n_cams, const double* K9, const double* rot, const double* t,
-                       int32_t n_pts, const double* X) {
-  SFM_TRACE("sfm_ba_set_problem");
-  if (!h) return fail(SFM_EINVAL, "handle is NULL");
-  if (n_obs < 0 || n_cams < 0 || n_pts < 0) return fail(SFM_EINVAL, "negative size");
-  if (n_obs > 0 && (!obs_uv || !cam_idx || !pt_idx)) return fail(SFM_EINVAL, "observation arrays are NULL");
-  if (n_cams > 0 && (!K9 || !rot || !t)) return fail(SFM_EINVAL, "camera arrays are NULL");
-  if (n_pts > 0 && !X) return fail(SFM_EINVAL, "point array is NULL");
-  if (n_obs > int64_t(INT32_MAX) - 64 * int64_t(n_cams))
-    return fail(SFM_EINVAL, "more than 2^31-1 observations per shard");
-  HostTimer timer;
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  free_problem(h);
-  DevProblem& d = h->d;
-  timer.mark("sync + free");
-  const int64_t N = n_obs;
-  const int C = n_cams, P = n_pts;
-  d.C = C; d.P = P; d.N = N;
-  hipStream_t s = h->stream;
-  int rc = 0;
-  // large problems: uv goes up from a worker thread (below); it is joined
-  // before any return (the copy writes a buffer of this call and reads the
-  // caller's array)
-  std::atomic<int> uv_state{0};     // 1: uv's copy and event are enqueued, 2: that failed
-  std::atomic<int> param_state{0};  // the same for the parameters' copies (by that worker)
-  struct Joiner {
-    std::thread t;
-    void join() {
-      if (t.joinable()) t.join();
-    }
-    ~Joiner() { join(); }  // (declared after the states: joined before they go)
-  } uv_worker;
-  // Any failure returns through here: the buffers go back to the pool.
-  auto bail = [&](int code) {
-    uv_worker.join();
-    free_problem(h);
-    return code;
-  };
-// observations up to which set_problem checks and counts them on the host
-constexpr int64_t kHostCheckMaxObs = 65536;
-// and from which uv (16 B each) goes up from a worker thread beside the index
-// layouts (4 MB: the thread's start-up is noise beside the copy)
-constexpr int64_t kDeferredUvMinObs = 262144;
-#define ALLOC(ptr, cnt) if ((rc = dalloc(h, &(ptr), (cnt)))) return bail(rc)
-#define TMP(ptr, cnt) if ((rc = dalloc_tmp(h, &(ptr), (cnt)))) return bail(rc)
-#define HCHK(expr)                                                                                \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return bail(fail(SFM_EIO, std::string(#expr) + ": " + hipGetErrorString(e_))); \
-  } while (0)
-  std::vector<int32_t> cam_cnt(size_t(C) + 4);
-  // host-checked problems with few cameras: per camera, its observations per
-  // point slice (the 8 XCD slices of k_small_chunks' key p * 8 / P) -- the
-  // chunk table's slice sizes follow from them on the host -- and the pair
-  // total's estimate (no same-camera duplicates): the small path then needs no
-  // round trip before the pair lists
-  std::vector<int32_t> cam_slice;
-  int64_t pairs_est = 0;
-  uint8_t* stg = nullptr;
-  double* in_uv = nullptr;
-  int32_t *in_cam = nullptr, *in_pt = nullptr, *cnt_p = nullptr;
-  // ---- the caller's observation arrays go up as they are (packed into the
-  // pinned stage: one DMA); the O(N) layout work runs on the device
-  // (ba_setup.hip) ----
-  // keyframe-sized problems: the checks and the camera / point counts on
-  // the host, their point counts riding in the same upload -- no validation
-  // launch and no round trip before the layout (C1: ~60 us of set_problem)
-  const bool host_check = N <= kHostCheckMaxObs;
-  StageLayout up;
-  const size_t o_uv = up.add(sizeof(double) * 2 * size_t(N)), o_cam = up.add(sizeof(int32_t) * size_t(N)),
-               o_pt = up.add(sizeof(int32_t) * size_t(N)),
-               o_pc = host_check ? up.add(sizeof(int32_t) * (size_t(P) + 1)) : 0;
-  const size_t in_bytes = up.bytes;
-  const bool stage_in = in_bytes <= kStageMaxBytes;
-  // large problems: uv uploaded beside the index layouts (SFM_SYNC_UV=1: in
-  // line, as before round 6)
-  const bool deferred_uv = !stage_in && N >= kDeferredUvMinObs && !env_flag("SFM_SYNC_UV");
-  // (host checks: the camera-run blob below is staged AFTER the input blob,
-  // which is still in flight -- no synchronisation in between -- so the
-  // stage holds both from here: 2 C + chunks + ... ints, bounded)
-  const size_t il_base = host_check && stage_in ? (in_bytes + 255) / 256 * 256 : 0;
-  const size_t il_bound = host_check && stage_in ? hostlayout::runs_blob_bound(C, N, P) : 0;
-  // intrinsics, the parameters and their reset copies: one blob, one DMA
-  StageLayout pl;
-  const size_t o_K = pl.add(sizeof(double) * 5 * size_t(C)), o_c = pl.add(sizeof(double) * 6 * size_t(C)),
-               o_c0 = pl.add(sizeof(double) * 6 * size_t(C)), o_X = pl.add(sizeof(double) * 3 * size_t(P)),
-               o_X0 = pl.add(sizeof(double) * 3 * size_t(P));
-  // host-checked problems stage it behind the camera-run blob and upload it
-  // before the layout round trip (its host copies overlap the layout kernels)
-  const size_t pl_base = (il_base + il_bound + 255) / 256 * 256;
-  const bool early_params = il_base > 0 && (C || P) && pl_base + pl.bytes <= 4 * kStageMaxBytes;
-  if ((rc = stage_reserve(h, std::max({stage_in ? il_base + il_bound : 0, early_params ? pl_base + pl.bytes : 0,
-                                        sizeof(int32_t) * (size_t(C) + 4)}))))
-    return bail(rc);
-  stg = h->stage;
-  uint8_t* in_blob = nullptr;
-  TMP(in_blob, in_bytes);
-  in_uv = reinterpret_cast<double*>(in_blob + o_uv);
-  in_cam = reinterpret_cast<int32_t*>(in_blob + o_cam);
-  in_pt = reinterpret_cast<int32_t*>(in_blob + o_pt);
-  std::vector<double> Kc(5 * size_t(C)), cam(6 * size_t(C));
-  for (int c = 0; c < C; ++c) {
-    const double* k = K9 + 9 * size_t(c);
-    Kc[5 * c] = k[0]; Kc[5 * c + 1] = k[1]; Kc[5 * c + 2] = k[2]; Kc[5 * c + 3] = k[4]; Kc[5 * c + 4] = k[5];
-    for (int j = 0; j < 3; ++j) { cam[6 * c + j] = rot[3 * c + j]; cam[6 * c + 3 + j] = t[3 * c + j]; }
-  }
-  // large problems: the parameters (above the stage's 1 MB) go up from the
-  // caller's pageable arrays on a stream of their own while the layout
-  // kernels run (with a deferred uv, from its worker, before uv) (the host's staging copies took ~0.5 ms at C3 after the
-  // layout round trip, with the device idle); the solve stream waits for them
-  // at the end of set_problem
-  const bool side_params = !early_params && (C || P) && pl.bytes > kStageMaxBytes;
-  if (side_params) {
-    uint8_t* pb = nullptr;
-    ALLOC(pb, pl.bytes);
-    d.Kc = reinterpret_cast<double*>(pb + o_K);
-    d.cam = reinterpret_cast<double*>(pb + o_c);
-    d.cam0 = reinterpret_cast<double*>(pb + o_c0);
-    d.X = reinterpret_cast<double*>(pb + o_X);
-    d.X0 = reinterpret_cast<double*>(pb + o_X0);
-    if (!h->ustream) {
-      HCHK(hipStreamCreateWithFlags(&h->ustream, hipStreamNonBlocking));
-      HCHK(hipEventCreateWithFlags(&h->uev, hipEventDisableTiming));
-    }
-  }
-  auto params_copies = [&]() -> bool {
-    hipStream_t u = h->ustream;
-    return hipMemcpyAsync(d.Kc, Kc.data(), sizeof(double) * Kc.size(), hipMemcpyHostToDevice, u) == hipSuccess &&
-           hipMemcpyAsync(d.cam, cam.data(), sizeof(double) * cam.size(), hipMemcpyHostToDevice, u) == hipSuccess &&
-           hipMemcpyAsync(d.cam0, d.cam, sizeof(double) * cam.size(), hipMemcpyDeviceToDevice, u) == hipSuccess &&
-           (!P || (hipMemcpyAsync(d.X, X, sizeof(double) * 3 * size_t(P), hipMemcpyHostToDevice, u) == hipSuccess &&
-                   hipMemcpyAsync(d.X0, d.X, sizeof(double) * 3 * size_t(P), hipMemcpyDeviceToDevice, u) ==
-                       hipSuccess)) &&
-           hipEventRecord(h->uev, u) == hipSuccess;
-  };
-  auto upload_params_side = [&]() -> int { return params_copies() ? 0 : fail(SFM_EIO, "parameter upload failed"); };
-  int32_t* err = nullptr;
-  int32_t* cnt_c = nullptr;
-  if (host_check && stage_in) {
-    // k_validate's checks and counts on the host (ba_host_layout.h)
-    hostlayout::check_and_count(N, obs_uv, cam_idx, pt_idx, C, P, C <= kSmallSetupMaxC, cam_cnt.data(),
-                                reinterpret_cast<int32_t*>(stg + o_pc), &cam_slice, &pairs_est);
-    cnt_p = reinterpret_cast<int32_t*>(in_blob + o_pc);
-    timer.mark("host checks + counts");
-  } else {
-    TMP(err, 4 + size_t(C) + 1);  // first bad observation (4) | per-camera counts (C + 1)
-    cnt_c = err + 4;
-    TMP(cnt_p, size_t(P) + 1);
-  }
-  // (host checks: the point counts ride in this upload, so it goes up even
-  // without observations -- the zero counts then reach cnt_p)
-  if ((N || host_check) && stage_in) {
-    if (N) {
-      std::memcpy(stg + o_uv, obs_uv, sizeof(double) * 2 * size_t(N));
-      std::memcpy(stg + o_cam, cam_idx, sizeof(int32_t) * size_t(N));
-      std::memcpy(stg + o_pt, pt_idx, sizeof(int32_t) * size_t(N));
-    }
-    HCHK(hipMemcpyAsync(in_blob, stg, in_bytes, hipMemcpyHostToDevice, s));
-    timer.mark("stage copy + upload");
-  } else if (N) {
-    HCHK(hipMemcpyAsync(in_cam, cam_idx, sizeof(int32_t) * size_t(N), hipMemcpyHostToDevice, s));
-    HCHK(hipMemcpyAsync(in_pt, pt_idx, sizeof(int32_t) * size_t(N), hipMemcpyHostToDevice, s));
-    if (deferred_uv) {
-      // the indices are up; uv (two thirds of the bytes) goes up from a
-      // worker thread on the side stream -- a pageable copy holds its thread
-      // until the data has left the caller's array -- while this thread lays
-      // out the indices; k_uv_layout takes it once it has landed
-      if (!h->ustream) {
-        HCHK(hipStreamCreateWithFlags(&h->ustream, hipStreamNonBlocking));
-        HCHK(hipEventCreateWithFlags(&h->uev, hipEventDisableTiming));
-      }
-      if (!h->uev_uv) HCHK(hipEventCreateWithFlags(&h->uev_uv, hipEventDisableTiming));
-      const int dev = h->device;
-      hipStream_t u = h->ustream;
-      hipEvent_t ue = h->uev_uv;
-      // (the parameters first: 5 MB the solve needs only at its start, off
-      // the copy engine before uv's layouts wait on it)
-      auto uv_job = [dev, u, ue, in_uv, obs_uv, N, side_params, &params_copies, &uv_state, &param_state]() {
-        bool ok = hipSetDevice(dev) == hipSuccess;
-        if (side_params) param_state.store(ok && params_copies() ? 1 : 2, std::memory_order_release);
-        ok = ok && hipMemcpyAsync(in_uv, obs_uv, sizeof(double) * 2 * size_t(N), hipMemcpyHostToDevice, u) ==
-                       hipSuccess &&
-             hipEventRecord(ue, u) == hipSuccess;
-        uv_state.store(ok ? 1 : 2, std::memory_order_release);
-      };
-      // (no exception crosses the C ABI: without a thread the copies run here)
-      try {
-        uv_worker.t = std::thread(uv_job);
-      } catch (...) {
-        uv_job();
-      }
-    } else {
-      HCHK(hipMemcpyAsync(in_uv, obs_uv, sizeof(double) * 2 * size_t(N), hipMemcpyHostToDevice, s));
-    }
-  }
-  // the solve stream takes uv once the worker has enqueued its copy
-  auto wait_uv = [&]() -> int {
-    uv_worker.join();
-    if (uv_state.load(std::memory_order_acquire) != 1) return fail(SFM_EIO, "observation upload failed");
-    if (hipStreamWaitEvent(s, h->uev_uv, 0) != hipSuccess) return fail(SFM_EIO, "observation upload wait failed");
-    return 0;
-  };
-  if (!(host_check && stage_in)) {
-    {
-      Fill32Set fs;
-      fs.add(err, 4 * sizeof(int32_t), uint32_t(INT32_MAX));
-      fs.add(cnt_c, sizeof(int32_t) * (size_t(C) + 1), 0);
-      fs.add(cnt_p, sizeof(int32_t) * (size_t(P) + 1), 0);
-      launch_fill32(fs, s);
-    }
-    // (deferred uv: no point counts either -- pt_off comes from the sorted keys)
-    launch_validate(N, deferred_uv ? nullptr : in_uv, in_cam, in_pt, C, P, err, cnt_c, deferred_uv ? nullptr : cnt_p, s);
-    // one round trip: the first bad observation and the per-camera counts
-    // (the host lays out the C camera runs and the wavefront chunk table);
-    // the readback lands in the stage after the upload has read it (stream order)
-    HCHK(hipMemcpyAsync(stg, err, sizeof(int32_t) * (size_t(C) + 4), hipMemcpyDeviceToHost, s));
-    HCHK(hipStreamSynchronize(s));
-    std::memcpy(cam_cnt.data(), stg, sizeof(int32_t) * (size_t(C) + 4));
-    if (deferred_uv && std::min(cam_cnt[0], cam_cnt[1]) != INT32_MAX) {
-      // a bad index: the whole check once uv is up, so the error reported is
-      // the first bad observation of any kind, as without the deferral
-      if ((rc = wait_uv())) return bail(rc);
-      launch_validate(N, in_uv, in_cam, in_pt, C, P, err, cnt_c, cnt_p, s);
-      HCHK(hipMemcpyAsync(stg, err, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, s));
-      HCHK(hipStreamSynchronize(s));
-      std::memcpy(cam_cnt.data(), stg, sizeof(int32_t) * 4);
-    }
-  }
-  timer.mark("upload + validate");
-  {
-    const int32_t e0 = cam_cnt[0], e1 = cam_cnt[1], e2 = cam_cnt[2];
-    const int32_t first = std::min({e0, e1, e2});
-    if (first != INT32_MAX) {
-      const char* what = first == e0 ? "cam_idx out of range at " : first == e1 ? "pt_idx out of range at "
-                                                                                   : "non-finite observation at ";
-      return bail(fail(SFM_EINVAL, what + std::to_string(first)));
-    }
-  }
-  // ---- camera runs: camera-major, each camera's run padded to a whole
-  // number of 64-wide wavefront chunks; the chunk table camera-major
-  // (grouped into 8 point slices on the device, one per XCD) ----
-  hostlayout::Runs runs;
-  hostlayout::camera_runs(C, cam_cnt.data() + 4, &runs);
-  const std::vector<int32_t>&cam_off = runs.cam_off, &cam_rng = runs.cam_rng, &wcam = runs.wcam;
-  const std::vector<hostlayout::Chunk>& chunks = runs.chunks;
-  const int64_t npad = runs.npad;
-  d.N_pad = npad;
-  d.n_jchunks = int32_t(chunks.size());
-  d.jac_blocks_rec = 8 * std::max(1, std::min((d.n_jchunks / 8 + 3) / 4, 128));  // multiple of 8 (one slice per XCD)
-  // the record-free pass of the solve (no 160-B stores) prefers a larger
-  // grid: 256 workgroups per XCD, 0.256 -> 0.223 ms per C3 solve
-  d.jac_blocks = 8 * std::max(1, std::min((d.n_jchunks / 8 + 3) / 4, 256));
-  if (const char* jw = std::getenv("SFM_JAC_WG_PER_XCD")) {  // tuning knob (tools/sweep_jac.sh)
-    const int v = std::atoi(jw);
-    if (v > 0) d.jac_blocks = 8 * std::max(1, std::min((d.n_jchunks / 8 + 3) / 4, v));
-  }
-  // keyframe-sized problems: the layouts without radix sorts (ba_setup.hip
-  // small path; the same arrays bit for bit), when the host has the counts
-  // and the segments fit its bounds (SFM_SMALL_SETUP=0: the sorted path)
-  // (C (C + 1) / 2 <= kSchurXcdMinBlocks: the plain k_schur_pts block order,
-  // as the sorted path takes for these sizes)
-  bool small = host_check && stage_in && N > 0 && N <= kSmallSetupMaxObs && C > 0 && C <= kSmallSetupMaxC &&
-               int64_t(C) * (C + 1) / 2 <= kSchurXcdMinBlocks;
-  if (small) {
-    const char* ss = std::getenv("SFM_SMALL_SETUP");
-    if (ss && ss[0] == '0') small = false;
-  }
-  if (small) {
-    int64_t nch_small = 0;
-    for (int c = 0; c < C; ++c) nch_small += (cam_cnt[4 + c] + 63) / 64;
-    small = nch_small <= kSmallSetupMaxChunks;
-  }
-  if (small) {
-    const int32_t* pc = reinterpret_cast<const int32_t*>(stg + o_pc);
-    for (int p = 0; p < P && small; ++p) small = pc[p] <= kSmallSetupMaxPtObs;
-  }
-  timer.mark("camera runs (host)");
-  // ---- resident arrays of the point-major and camera-major layouts ----
-  int64_t n_pairs = 0;
-  int32_t *pt_s = nullptr, *cm_order = nullptr;
-  const int32_t* pair_order = nullptr;  // the Schur pair lists' emission order (nullptr: point-major)
-  int64_t* poff = nullptr;
-  void* sort_tmp = nullptr;
-  size_t sort_bytes = 0;
-  int32_t* small_fill = nullptr;  // small path: the scatters' slot counters (P | C), zeroed in the camera-run blob
-  if (!small) ALLOC(d.pt_off, size_t(P) + 1);  // (small path: in the camera-run blob)
-  ALLOC(d.order, size_t(N));
-  ALLOC(d.uv_pm, 2 * size_t(N));
-  ALLOC(d.cam_pm, size_t(N));
-  ALLOC(d.cam_obs, size_t(npad));
-  ALLOC(d.cm_p, size_t(npad));
-  ALLOC(d.jchunks, size_t(std::max(1, d.n_jchunks)));
-  ALLOC(d.jgrp, size_t(9));
-  ALLOC(d.uv_cm, 2 * size_t(npad));
-  ALLOC(d.pos, size_t(N));
-  // scratch of the sorts
-  uint64_t *k64a = nullptr, *k64b = nullptr;
-  uint32_t *k32a = nullptr, *k32b = nullptr;
-  int32_t *iota = nullptr, *d_cam_off = nullptr, *perm = nullptr;
-  int4* ch_in = nullptr;
-  const int64_t nch = d.n_jchunks;
-  const int64_t nmax = std::max<int64_t>({N, nch, 1});
-  TMP(k64a, size_t(N));
-  TMP(k64b, size_t(N));
-  TMP(k32a, size_t(nmax));
-  TMP(k32b, size_t(nmax));
-  TMP(iota, size_t(nmax));
-  TMP(pt_s, size_t(N));
-  TMP(cm_order, size_t(N));
-  TMP(perm, size_t(std::max<int64_t>(1, nch)));
-  sort_bytes = std::max({setup_sort_bytes(N, 64), setup_sort_bytes(nmax, 32), setup_sort_bytes(P + 1, 1),
-                                setup_sort_bytes(N + 1, 2), size_t(256)});
-  {
-    uint8_t* tb = nullptr;
-    TMP(tb, sort_bytes);
-    sort_tmp = tb;
-  }
-  {
-    // the host-made camera runs and chunk table in one resident blob, one
-    // DMA from the stage (the validation readback was consumed above):
-    // cam_rng | wcam (resident), cam_off | chunks (read by the setup only)
-    StageLayout il;
-    const size_t o_rng = il.add(sizeof(int32_t) * cam_rng.size()), o_w = il.add(sizeof(int32_t) * wcam.size()),
-                 o_off = il.add(sizeof(int32_t) * cam_off.size()), o_ch = il.add(sizeof(hostlayout::Chunk) * chunks.size());
-    // small path: pt_off (the host's scan of the point counts, resident) and
-    // the zeroed slot counters of the point / camera scatters
-    const size_t o_poff = small ? il.add(sizeof(int32_t) * (size_t(P) + 1)) : 0,
-                 o_fill = small ? il.add(sizeof(int32_t) * (size_t(P) + size_t(C))) : 0;
-    if (il_base && il.bytes > il_bound) return bail(fail(SFM_EIO, "internal: camera-run blob above its bound"));
-    if ((rc = stage_reserve(h, il_base + il.bytes))) return bail(rc);  // (never regrows with il_base > 0)
-    if (early_params && il_base + il.bytes > pl_base) return bail(fail(SFM_EIO, "internal: stage layout overlap"));
-    stg = h->stage;
-    uint8_t* ib = nullptr;
-    ALLOC(ib, il.bytes);
-    uint8_t* sb = stg + il_base;
-    std::memcpy(sb + o_rng, cam_rng.data(), sizeof(int32_t) * cam_rng.size());
-    std::memcpy(sb + o_w, wcam.data(), sizeof(int32_t) * wcam.size());
-    std::memcpy(sb + o_off, cam_off.data(), sizeof(int32_t) * cam_off.size());
-    if (nch) std::memcpy(sb + o_ch, chunks.data(), sizeof(hostlayout::Chunk) * chunks.size());
-    if (small) {
-      const int32_t* pc = reinterpret_cast<const int32_t*>(stg + o_pc);
-      int32_t* po = reinterpret_cast<int32_t*>(sb + o_poff);
-      po[0] = 0;
-      for (int p = 0; p < P; ++p) po[p + 1] = po[p] + pc[p];
-      std::memset(sb + o_fill, 0, sizeof(int32_t) * (size_t(P) + size_t(C)));
-    }
-    if (deferred_uv) {
-      // uv's 32-MB DMA is on the copy engine now: this blob, on it, would
-      // wait behind it and hold up the layouts, so a kernel reads it from
-      // the pinned stage instead (il.bytes: 256-B aligned pieces)
-      void* sbd = nullptr;
-      HCHK(hipHostGetDevicePointer(&sbd, sb, 0));
-      launch_copy_from_host(ib, sbd, (il.bytes + 15) / 16 * 16, s);
-    } else {
-      HCHK(hipMemcpyAsync(ib, sb, il.bytes, hipMemcpyHostToDevice, s));
-    }
-    if (small) {
-      d.pt_off = reinterpret_cast<int32_t*>(ib + o_poff);
-      small_fill = reinterpret_cast<int32_t*>(ib + o_fill);
-    }
-    d.cam_rng = reinterpret_cast<int32_t*>(ib + o_rng);
-    d.wcam = reinterpret_cast<int32_t*>(ib + o_w);
-    d_cam_off = reinterpret_cast<int32_t*>(ib + o_off);
-    ch_in = reinterpret_cast<int4*>(ib + o_ch);
-  }
-  if (early_params) {
-    uint8_t* pb = nullptr;
-    ALLOC(pb, pl.bytes);
-    d.Kc = reinterpret_cast<double*>(pb + o_K);
-    d.cam = reinterpret_cast<double*>(pb + o_c);
-    d.cam0 = reinterpret_cast<double*>(pb + o_c0);
-    d.X = reinterpret_cast<double*>(pb + o_X);
-    d.X0 = reinterpret_cast<double*>(pb + o_X0);
-    uint8_t* ps = stg + pl_base;
-    std::memcpy(ps + o_K, Kc.data(), sizeof(double) * Kc.size());
-    std::memcpy(ps + o_c, cam.data(), sizeof(double) * cam.size());
-    std::memcpy(ps + o_c0, cam.data(), sizeof(double) * cam.size());
-    if (P) {
-      std::memcpy(ps + o_X, X, sizeof(double) * 3 * size_t(P));
-      std::memcpy(ps + o_X0, X, sizeof(double) * 3 * size_t(P));
-    }
-    HCHK(hipMemcpyAsync(pb, ps, pl.bytes, hipMemcpyHostToDevice, s));
-  }
-  int32_t* small_cnt = nullptr;  // small path: per-block pair counts
-  if (small) {
-    // the same layouts without radix sorts (ba_setup.hip small path):
-    // point-major by (point, camera, caller index), camera-major by (camera,
-    // point-major id), the chunk table by slice, the pair counts per block
-    // (seg = their exclusive sum, seg[n_blk] = the pair total)
-    d.n_blk = int64_t(C) * (C + 1) / 2;
-    ALLOC(d.seg, size_t(d.n_blk) + 1);
-    TMP(small_cnt, std::max<size_t>(1, size_t(d.n_blk)));
-    timer.mark("allocs + camera-run blob");
-    launch_small_pm(N, in_pt, in_cam, in_uv, d.pt_off, small_fill, reinterpret_cast<int32_t*>(k32a), d.order,
-                    d.uv_pm, d.cam_pm, pt_s, s);
-    launch_small_cm(N, C, d.cam_pm, d_cam_off, cm_order, s);
-    launch_fill_cm(npad, d.wcam, d.cam_rng, d_cam_off, cm_order, pt_s, d.uv_pm, d.cm_p, d.uv_cm, d.cam_obs, d.pos, s);
-    launch_small_chunks(int(nch), ch_in, cm_order, pt_s, P, d.jchunks, d.jgrp, s);
-    launch_small_pairs_count(C, d.n_blk, d_cam_off, cm_order, d.cam_pm, pt_s, d.pt_off, small_cnt, d.seg, s);
-    // (into the stage: stream order puts it after the upload that reads the stage)
-  } else {
-  timer.mark("allocs + camera-run blob");
-  // point-major order: stable sort by (point, camera)
-  launch_pm_keys(N, in_cam, in_pt, C, k64a, iota, s);
-  HCHK(sort_pairs64(sort_tmp, sort_bytes, k64a, k64b, iota, d.order, N,
-                    uint64_t(std::max(1, P)) * uint64_t(std::max(1, C)) - 1, s));
-  launch_gather_pm(N, d.order, deferred_uv ? nullptr : in_uv, in_cam, in_pt, d.uv_pm, d.cam_pm, pt_s, k32a, iota, s);
-  if (deferred_uv) launch_pt_off(P, k64b, N, C, d.pt_off, s);
-  else HCHK(exclusive_sum32(sort_tmp, sort_bytes, cnt_p, d.pt_off, int64_t(P) + 1, s));
-  // camera-major order of the point-major ids: stable sort by camera
-  HCHK(sort_pairs32(sort_tmp, sort_bytes, k32a, k32b, iota, cm_order, N, uint64_t(std::max(1, C)) - 1, s));
-  launch_fill_cm(npad, d.wcam, d.cam_rng, d_cam_off, cm_order, pt_s, deferred_uv ? nullptr : d.uv_pm, d.cm_p,
-                 d.uv_cm, d.cam_obs, d.pos, s);
-  // chunk table grouped by point slice (stable: camera-major order kept)
-  launch_chunk_keys(int(nch), ch_in, cm_order, pt_s, P, k32a, iota, s);
-  HCHK(sort_pairs32(sort_tmp, sort_bytes, k32a, k32b, iota, perm, nch, 7, s));
-  launch_chunk_gather(int(nch), perm, ch_in, k32b, d.jchunks, d.jgrp, s);
-  // Schur pair counts: the second (and last) round trip
-  int64_t* pcnt = nullptr;
-  TMP(pcnt, size_t(N) + 1);
-  TMP(poff, size_t(N) + 1);
-  // (point-major emission: the same lists; SFM_PAIRS_CM=1 emits in camera-major order)
-  pair_order = env_flag("SFM_PAIRS_CM") ? cm_order : nullptr;
-  launch_pair_count(N, pair_order, d.cam_pm, pt_s, d.pt_off, pcnt, s);
-  HCHK(exclusive_sum64(sort_tmp, sort_bytes, pcnt, poff, N + 1, s));
-  // (into the stage: stream order puts it after the upload that reads the stage)
-  if (!deferred_uv) HCHK(hipMemcpyAsync(stg, poff + N, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  }
-  if (small) {
-    // no round trip: the pair lists go into a buffer of the pair total's
-    // bound (every ordered pair of a point's observations: twice the
-    // estimate), the chunk table's slice sizes come from the host's
-    // per-camera slice counts (a camera's chunk k starts at its 64 k-th
-    // observation in point order, whose slice the counts' running sum gives)
-    n_pairs = std::max<int64_t>(1, 2 * pairs_est);
-    d.xcd_slice_max = hostlayout::small_slice_max(C, cam_cnt.data() + 4, cam_slice);
-    timer.mark("layout launches");
-  } else {
-    // and the 8 slices' chunk offsets: the observation passes size their
-    // grids by the largest slice (obs_xcd_blocks)
-    if (!deferred_uv) HCHK(hipMemcpyAsync(stg + 8, d.jgrp, 9 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    timer.mark("layout launches");
-    if (deferred_uv) {
-      // the pair total and the slice offsets read back by a kernel into the
-      // pinned stage: uv's DMA holds the copy engine (uv itself is taken
-      // after the pair lists are enqueued, which do not read it)
-      void* stg_d = nullptr;
-      HCHK(hipHostGetDevicePointer(&stg_d, stg, 0));
-      uint8_t* sd = static_cast<uint8_t*>(stg_d);
-      HostCopySet cs;
-      cs.add(sd, poff + N, sizeof(int64_t));
-      cs.add(sd + 8, d.jgrp, 9 * sizeof(int32_t));
-      launch_copy_to_host(cs, s);
-    }
-    if (side_params && !deferred_uv) {
-      if ((rc = upload_params_side())) return bail(rc);
-      timer.mark("parameter upload (side stream)");
-    }
-    HCHK(hipStreamSynchronize(s));
-    std::memcpy(&n_pairs, stg, sizeof(int64_t));
-    int32_t g[9];
-    std::memcpy(g, stg + 8, sizeof(g));
-    d.xcd_slice_max = 0;
-    for (int i = 0; i < 8; ++i) d.xcd_slice_max = std::max(d.xcd_slice_max, g[i + 1] - g[i]);
-    timer.mark("layouts (device)");
-  }
-  if (n_pairs >= int64_t(INT32_MAX)) return bail(fail(SFM_EINVAL, "too many Schur pairs for 32-bit offsets"));
-  d.n_blk = int64_t(C) * (C + 1) / 2;
-  // the Schur pass's shape below follows the mean pair count: the host's
-  // estimate on host-checked problems (either layout path, so both choose
-  // alike), else the device's count.  The estimate counts every unordered
-  // pair of a point's observations, so it undercounts when a camera sees a
-  // point twice (a same-camera pair is an ordered pair of the diagonal
-  // block); it picks the lanes per block only -- the pair buffer is sized by
-  // twice the estimate, an upper bound of the true count either way.
-  d.n_pairs = host_check && stage_in && !cam_slice.empty() ? pairs_est : n_pairs;
-  // lanes per Schur block ~ a tenth of the mean pair count, 8..64 (measured
-  // best: C3, 72 pairs per block -> 8; C1 / C2, ~460 -> 64)
-  if (const char* ss = std::getenv("SFM_SCHUR_PTS_SUB")) {
-    const int v = std::atoi(ss);
-    d.schur_pts_sub = v == 64 ? 64 : v == 32 ? 32 : v == 8 ? 8 : 16;
-  } else {
-    const double avg = d.n_blk ? double(d.n_pairs) / double(d.n_blk) : 0.0;
-    int sub = 8;
-    while (sub < 64 && sub < avg / 10.0) sub *= 2;
-    d.schur_pts_sub = sub;
-  }
-  // few blocks with long lists (keyframe-sized: C1 210 blocks of ~460
-  // pairs): a workgroup per block instead of a wave (SFM_SCHUR_WG=0/1 forces)
-  d.schur_wg_blocks = d.schur_pts_sub == 64 && d.n_blk <= 4 * 256 &&
-                      (d.n_blk ? double(d.n_pairs) / double(d.n_blk) : 0.0) >= 256.0;
-  if (const char* sw = std::getenv("SFM_SCHUR_WG")) d.schur_wg_blocks = sw[0] == '1' && d.schur_pts_sub == 64;
-  if (!d.scal_host && hipHostMalloc(&d.scal_host, sizeof(double) * (kNumScalars + 1 + 17)) != hipSuccess) {
-    d.scal_host = nullptr;
-    return bail(fail(SFM_ENOMEM, "hipHostMalloc failed"));
-  }
-  // the pinned mirror's 17-slot tail: the k_schur_pts group sizes (16), then
-  // the deferred uv's finite check (slot 16)
-  int64_t* grp_host = reinterpret_cast<int64_t*>(d.scal_host + kNumScalars + 1);
-  int32_t* uv_err_host = reinterpret_cast<int32_t*>(grp_host + 16);
-  int bperm_per = 0;
-  ALLOC(d.blk, std::max<size_t>(1, size_t(d.n_blk)));
-  if (!small) ALLOC(d.seg, size_t(d.n_blk) + 1);
-  ALLOC(d.bpts, std::max<size_t>(1, size_t(n_pairs)));
-  if (small) {
-    launch_small_pairs_fill(C, d.n_blk, d_cam_off, cm_order, d.cam_pm, pt_s, d.pt_off, d.seg, d.bpts, s);
-    launch_blk(C, d.blk, s);
-    d.bperm = nullptr;
-    d.n_bslots = d.n_blk;
-  } else {
-    uint32_t *bk_a = nullptr, *bk_b = nullptr;
-    int32_t* bv = nullptr;
-    const int64_t nk = std::max<int64_t>({n_pairs, d.n_blk, 1});
-    TMP(bk_a, size_t(nk));
-    TMP(bk_b, size_t(nk));
-    TMP(bv, size_t(nk));
-    const size_t need = std::max(setup_sort_bytes(n_pairs, 32), setup_sort_bytes(d.n_blk, 32));
-    if (need > sort_bytes) {
-      uint8_t* tb = nullptr;
-      TMP(tb, need);
-      sort_tmp = tb;
-      sort_bytes = need;
-    }
-    launch_pair_fill(N, pair_order, d.cam_pm, pt_s, d.pt_off, poff, C, bk_a, bv, s);
-    HCHK(sort_pairs32(sort_tmp, sort_bytes, bk_a, bk_b, bv, d.bpts, n_pairs, uint64_t(std::max<int64_t>(1, d.n_blk)) - 1,
-                      s));
-    launch_seg(d.n_blk, bk_b, n_pairs, d.seg, s);
-    launch_blk(C, d.blk, s);
-    // ---- k_schur_pts work order: XCD-aware (ba_setup.hip k_bperm_*).
-    // Block (c1, c2)'s pairs gather records of points camera c1 sees, so a
-    // row c1 (its blocks c2 >= c1) reads one camera's ~N/C point records
-    // (C3: ~0.5 MB).  Rows go to 8 groups of contiguous rows with equal pair
-    // totals; group x's blocks, row by row (descending pair count within a
-    // row, so a wave's blocks run lists of nearly equal length), fill
-    // workgroups x, x + 8, x + 16, ... -- the ones dealt to one XCD
-    // (round-robin placement: a speed assumption only, MI355X_MICROARCH.md),
-    // so a row's records stay in that XCD's L2 while its blocks run.  Slots
-    // past a group's end hold -1 (an empty list).  Small reduced systems
-    // (keyframe-sized solves: everything fits one L2) keep the plain block
-    // order (bperm = nullptr).  The group sizes come back with the final
-    // synchronisation of set_problem.
-    d.bperm = nullptr;
-    d.n_bslots = d.n_blk;
-    if (d.n_blk > kSchurXcdMinBlocks) {
-      const int per = 64 / d.schur_pts_sub * (kThreads / 64);
-      int32_t *sorted = nullptr, *row_x = nullptr;
-      int64_t* grp = nullptr;
-      TMP(sorted, size_t(d.n_blk));
-      TMP(row_x, size_t(C));
-      TMP(grp, 16);
-      ALLOC(d.bperm, size_t(bperm_slots_bound(d.n_blk, per)));
-      HCHK(launch_bperm(C, d.n_blk, n_pairs, d.seg, d.blk, per, bk_a, bk_b, bv, sorted, row_x, grp, sort_tmp,
-                        sort_bytes, d.bperm, s));
-      HCHK(hipMemcpyAsync(grp_host, grp, sizeof(int64_t) * 16, hipMemcpyDeviceToHost, s));
-      bperm_per = per;
-    }
-  }
-  // ---- parameters, per-iteration arrays, dense system ----
-  d.n = 6 * C;
-  d.ld = ((d.n + 1 + kNB - 1) / kNB) * kNB;
-  d.nblk = d.ld / kNB;
-  d.max_blocks = std::max({1, C, blocks_for(N, 256), blocks_for(P, 256), d.jac_blocks,
-                           d.jac_blocks_rec, blocks_for(npad, 256), obs_xcd_blocks(d), pt_xcd_blocks(d)});
-  if (!early_params && !side_params) {
-    uint8_t* pb = nullptr;
-    ALLOC(pb, pl.bytes);
-    d.Kc = reinterpret_cast<double*>(pb + o_K);
-    d.cam = reinterpret_cast<double*>(pb + o_c);
-    d.cam0 = reinterpret_cast<double*>(pb + o_c0);
-    d.X = reinterpret_cast<double*>(pb + o_X);
-    d.X0 = reinterpret_cast<double*>(pb + o_X0);
-  }
-  ALLOC(d.cam_new, 6 * size_t(C));
-  ALLOC(d.X_new, 3 * size_t(P));
-  ALLOC(d.scale_c, 6 * size_t(C));
-  ALLOC(d.scale_p, 3 * size_t(P));
-  ALLOC(d.diag_c, 6 * size_t(C));
-  ALLOC(d.diag_p, 3 * size_t(P));
-  ALLOC(d.camR, size_t(kCamR) * C);
-  ALLOC(d.camRn, 12 * size_t(C));
-  // the one-pass back substitution, on the large path (the XCD-ordered Schur
-  // blocks) while every camera's record fits the LDS
-  d.pm_backsub = d.n_blk > kSchurXcdMinBlocks && C <= kCamPMMax;
-  // pass A stores u at the camera-major position it runs at (coalesced) and
-  // pass B gathers it through pos[]: 85 + 31 -> 60 + 41 us per C3 iteration
-  // against the point-major scatter (SFM_EU_CM=0), S and steps bitwise equal
-  {
-    const char* ec = std::getenv("SFM_EU_CM");
-    d.eu_cm = !(ec && ec[0] == '0');
-  }
-  ALLOC(d.eu, size_t(kEU) * size_t(d.eu_cm ? npad : N));
-  ALLOC(d.ypt, 3 * size_t(P));
-  ALLOC(d.ptV, size_t(kPtV) * P);
-  ALLOC(d.ptL, size_t(kPtL) * P);
-  ALLOC(d.ptS, size_t(kPtS) * std::max(1, P));
-  d.ptG = nullptr;
-  if (d.n_blk > kSchurXcdMinBlocks) ALLOC(d.ptG, size_t(kPtG) * std::max(1, P));
-  ALLOC(d.Ucam, size_t(kUcam) * C);
-  ALLOC(d.jpart, 27 * std::max<size_t>(1, size_t(npad / 64)));
-  ALLOC(d.dpart, 27 * std::max<size_t>(1, size_t(npad / 64)));
-  ALLOC(d.S, size_t(d.ld) * d.ld);
-  h->force_pack = env_flag("SFM_FORCE_PACK");
-  if (sharded(h) || h->force_pack) ALLOC(d.Spack, packed_size(d.n));
-  ALLOC(d.invL, size_t(d.nblk) * kNB * kNB);
-  ALLOC(d.flags, size_t(d.nblk));
-  ALLOC(d.cflags, 2 * size_t(d.nblk) * d.nblk);
-  ALLOC(d.cticket, 5);  // task ticket, walker-role ticket, back-substitution role ticket, a panel's two
-  // Schur / Cholesky overlap (SFM_OVERLAP=1; unsharded, more than two tiles):
-  // per 64x64 tile of S the number of camera blocks (c1 <= c2, stored at
-  // rows 6 c2.., columns 6 c1..) whose 6x6 footprint touches it.  (The
-  // round-4 mode 2, a full helper grid placed as the Schur pass retires,
-  // relied on the dispatcher starting the Schur pass's workgroups first:
-  // not guaranteed, and seen to time out the factor, so removed.)
-  {
-    const char* ov = std::getenv("SFM_OVERLAP");
-    const int v = ov ? std::atoi(ov) : 0;
-    d.overlap = v > 0 && d.nblk > 2 && !sharded(h) ? 1 : 0;
-  }
-  if (d.overlap) {
-    ALLOC(d.tile_cnt, size_t(d.nblk) * d.nblk);
-    ALLOC(d.tile_exp, size_t(d.nblk) * d.nblk);
-    std::vector<int32_t> te(size_t(d.nblk) * d.nblk, 0);
-    for (int c1 = 0; c1 < C; ++c1)
-      for (int c2 = c1; c2 < C; ++c2)
-        for (int I = 6 * c2 / kNB; I <= (6 * c2 + 5) / kNB; ++I)
-          for (int J = 6 * c1 / kNB; J <= (6 * c1 + 5) / kNB; ++J) ++te[size_t(I) * d.nblk + J];
-    HCHK(hipMemcpy(d.tile_exp, te.data(), sizeof(int32_t) * te.size(), hipMemcpyHostToDevice));
-  }
-  ALLOC(d.ysol, size_t(d.ld));
-  ALLOC(d.fail, size_t(1));
-  ALLOC(d.partials, size_t(kNumPartialSlots) * d.max_blocks);
-  ALLOC(d.scal, size_t(kNumScalars) + 1);  // + the Cholesky failure int (k_reduce_batch)
-#undef ALLOC
-#undef TMP
-  release_pool(h);  // earlier problems' buffers this one did not reuse
-  if (deferred_uv) {
-    // uv (and before it the parameters) by now up or nearly: its two
-    // layouts and its finite check on the side stream, behind its copy and
-    // beside the pair lists (the index layouts they read are complete: the
-    // host synchronised on them), the check read back by a kernel with the
-    // final synchronisation
-    uv_worker.join();
-    if (uv_state.load(std::memory_order_acquire) != 1) return bail(fail(SFM_EIO, "observation upload failed"));
-    timer.mark("uv upload (worker)");
-    hipStream_t u = h->ustream;
-    launch_uv_layout(N, npad, d.order, d.wcam, d.cam_rng, d_cam_off, cm_order, in_uv, d.uv_pm, d.uv_cm, err, u);
-    void* ue_d = nullptr;
-    HCHK(hipHostGetDevicePointer(&ue_d, uv_err_host, 0));
-    HostCopySet cs;
-    cs.add(ue_d, err + 2, sizeof(int32_t));
-    launch_copy_to_host(cs, u);
-    HCHK(hipEventRecord(h->uev_uv, u));  // (the solve stream waits for it after its own fills, below)
-  }
-  if (side_params) {
-    if (small && (rc = upload_params_side())) return bail(rc);  // (the small path has no layout round trip)
-    // (deferred uv: its worker, joined above, enqueued them)
-    if (deferred_uv && param_state.load(std::memory_order_acquire) != 1)
-      return bail(fail(SFM_EIO, "parameter upload failed"));
-    HCHK(hipStreamWaitEvent(s, h->uev, 0));
-  } else if ((C || P) && !early_params) {
-    if (pl.bytes <= kStageMaxBytes) {
-      // the stage is free: the n_pairs readback synchronised the stream
-      if ((rc = stage_reserve(h, pl.bytes))) return bail(rc);
-      uint8_t* ps = h->stage;
-      std::memcpy(ps + o_K, Kc.data(), sizeof(double) * Kc.size());
-      std::memcpy(ps + o_c, cam.data(), sizeof(double) * cam.size());
-      std::memcpy(ps + o_c0, cam.data(), sizeof(double) * cam.size());
-      if (P) {
-        std::memcpy(ps + o_X, X, sizeof(double) * 3 * size_t(P));
-        std::memcpy(ps + o_X0, X, sizeof(double) * 3 * size_t(P));
-      }
-      HCHK(hipMemcpyAsync(d.Kc, ps, pl.bytes, hipMemcpyHostToDevice, s));
-    } else {
-      // (the host vectors live until the synchronisation below)
-      HCHK(hipMemcpyAsync(d.Kc, Kc.data(), sizeof(double) * Kc.size(), hipMemcpyHostToDevice, s));
-      HCHK(hipMemcpyAsync(d.cam, cam.data(), sizeof(double) * cam.size(), hipMemcpyHostToDevice, s));
-      HCHK(hipMemcpyAsync(d.cam0, d.cam, sizeof(double) * cam.size(), hipMemcpyDeviceToDevice, s));
-      if (P) {
-        HCHK(hipMemcpyAsync(d.X, X, sizeof(double) * 3 * size_t(P), hipMemcpyHostToDevice, s));
-        HCHK(hipMemcpyAsync(d.X0, d.X, sizeof(double) * 3 * size_t(P), hipMemcpyDeviceToDevice, s));
-      }
-    }
-  }
-  {
-    // the walker stores only the lower 16x16 blocks of each W_k (k_chol_fused)
-    Fill32Set fs;
-    fs.add(d.S, sizeof(double) * size_t(d.ld) * d.ld, 0);
-    fs.add(d.invL, sizeof(double) * size_t(d.nblk) * kNB * kNB, 0);
-    fs.add(d.flags, sizeof(int32_t) * size_t(d.nblk), 0);
-    fs.add(d.cflags, sizeof(int32_t) * 2 * size_t(d.nblk) * d.nblk, 0);
-    fs.add(d.cticket, 5 * sizeof(unsigned long long), 0);
-    fs.add(d.partials, sizeof(double) * size_t(kNumPartialSlots) * d.max_blocks, 0);
-    launch_fill32(fs, s);
-  }
-  h->chol_epoch = 0;
-  h->bs_epoch = 0;
-  d.n_cu = h->n_cu;
-  timer.mark("pairs + params launches");
-  // Small problems end without a synchronisation: every host-to-device copy
-  // came from the pinned stage, nothing is read back, so the pair lists and
-  // uploads run on while the caller enqueues the solve (stream order covers
-  // every reader; the scratch buffers stay out of the pool until the next
-  // set_problem's free_problem, after its synchronisation, and the stage is
-  // next written by a call that synchronises first).  Otherwise: the
-  // k_schur_pts group sizes come back, copies from pageable host memory (the
-  // caller's arrays, this call's vectors) complete, and the scratch buffers
-  // return to the pool.
-  // (SFM_SYNC_SETUP=1: always synchronise, so that a fault in a layout kernel
-  // is reported by set_problem itself, not by the next call)
-  static const bool sync_setup = env_flag("SFM_SYNC_SETUP");
-  if (deferred_uv) HCHK(hipStreamWaitEvent(s, h->uev_uv, 0));
-  if (!(small && early_params && !bperm_per) || sync_setup) {
-    HCHK(hipStreamSynchronize(s));
-    if (deferred_uv && *uv_err_host != INT32_MAX)
-      return bail(fail(SFM_EINVAL, "non-finite observation at " + std::to_string(*uv_err_host)));
-    if (bperm_per) {
-      int64_t m_max = 1;
-      for (int x = 0; x < 8; ++x) m_max = std::max<int64_t>(m_max, (grp_host[8 + x] + bperm_per - 1) / bperm_per);
-      d.n_bslots = m_max * 8 * bperm_per;
-    }
-    retire_tmps(h);
-    timer.mark("pair lists + uploads (device)");
-  }
-#undef HCHK
-  h->has_problem = true;
   return 0;
 }
 

@@ -4,9 +4,11 @@
 // Covered:
 //   * sfm_amd/csrc/ba_host_layout.h -- set_problem's host checks and counts,
 //     camera runs / chunk table, the small path's slice sizes and the camera-
-//     run blob's bound -- on the C1 scene, shuffled duplicates, an empty
-//     camera with single-view points, bad indices / non-finite uv, and the
-//     empty problem; every output checked against a naive recount;
+//     run blob's bound, the small path's size predicate -- on the C1 scene,
+//     shuffled duplicates, an empty camera with single-view points, bad
+//     indices / non-finite uv, and the empty problem; every output checked against a naive recount; and the
+//     plan of set_problem (regimes, parameter routes, the stage's regions)
+//     over a grid of sizes around every threshold, with the Schur shape;
 //   * include/sfm_ctracker_compat.hpp -- the pointer dedup / packing of
 //     bundleAdjustmentStructAndPose (CSfM.cpp:321-341 gather) and its in-place
 //     scatter-back, and the matchFeatures overload, with the C ABI answered by
@@ -169,6 +171,14 @@ static void check_layout(const Scene& s, const char* name) {
   const size_t blob = al(4 * r.cam_rng.size()) + al(4 * r.wcam.size()) + al(4 * r.cam_off.size()) +
                       al(16 * r.chunks.size()) + al(4 * (size_t(P) + 1)) + al(4 * (size_t(P) + size_t(C)));
   CHECK(blob <= sfm::hostlayout::runs_blob_bound(C, N, P));
+  // the small path's size predicate, against its bounds restated: these
+  // scenes all fit, except where a camera count is above the plain Schur order
+  {
+    bool fits = N > 0 && N <= 65536 && C > 0 && C <= 256 && int64_t(C) * (C + 1) / 2 <= 8192 && nch <= 2048;
+    for (int p = 0; p < P; ++p) fits = fits && pp[size_t(p)] <= 64;
+    CHECK(sfm::hostlayout::small_setup_fits(N, C, P, cam_cnt.data() + 4, pc.data()) == fits);
+    CHECK(fits == (N > 0 && C <= 127));
+  }
   // small path: slice sizes vs a point-order walk of every camera's run
   if (C <= 127 && P > 0) {
     CHECK(cam_slice.size() == 8 * size_t(C));
@@ -185,6 +195,105 @@ static void check_layout(const Scene& s, const char* name) {
   }
   std::printf("  %-14s N=%-7lld C=%-4d P=%-6d layout ok (%lld chunks, %lld pairs est.)\n", name, (long long)N, C, P,
               (long long)nch, (long long)pairs_est);
+}
+
+// set_problem's host plan (hostlayout::plan_setup): the invariants of the
+// stage's regions and of the routes over a grid of sizes around every
+// threshold, and rows derived from the expressions the plan replaced.
+static void check_plan() {
+  using sfm::hostlayout::ParamRoute;
+  using sfm::hostlayout::plan_setup;
+  const size_t MiB = size_t(1) << 20;
+  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+  const int64_t Ns[] = {0, 1, 43648, 43690, 43691, 65536, 65537, 262143, 262144, 2000000};
+  const int Cs[] = {0, 1, 127, 128, 256, 257, 2000};
+  const int Ps[] = {0, 1, 2000, 21800, 60000, 1000000};
+  int n = 0;
+  for (int64_t N : Ns)
+    for (int C : Cs)
+      for (int P : Ps) {
+        const auto p = plan_setup(N, C, P, false);
+        ++n;
+        // the stage's regions in use, in order, disjoint, inside the reserved
+        // bytes (the input blob only when it is staged; the camera-run blob
+        // has il_bound = 0 without host counts)
+        CHECK(p.stage_bytes >= 4 * (size_t(C) + 4));
+        if (p.stage_in) CHECK(p.in_bytes <= p.stage_bytes);
+        CHECK(p.host_counts ? p.il_base >= p.in_bytes && p.il_base + p.il_bound <= p.stage_bytes
+                            : p.il_base == 0 && p.il_bound == 0);
+        if (p.route == ParamRoute::Early)
+          CHECK(p.pl_base >= p.il_base + p.il_bound && p.pl_base + p.pl_bytes <= p.stage_bytes);
+        CHECK(p.il_base % 256 == 0 && p.pl_base % 256 == 0);
+        // the blobs' pieces, 256-B aligned; the point counts are part of the
+        // input blob up to 65536 observations, staged or not
+        CHECK(p.o_uv == 0 && p.o_cam == al(16 * size_t(N)) && p.o_pt == p.o_cam + al(4 * size_t(N)));
+        CHECK(p.o_pc == (N <= 65536 ? p.o_pt + al(4 * size_t(N)) : 0));
+        CHECK(p.in_bytes == p.o_pt + al(4 * size_t(N)) + (N <= 65536 ? al(4 * (size_t(P) + 1)) : 0));
+        CHECK(p.o_K == 0 && p.o_c == al(40 * size_t(C)) && p.o_c0 == p.o_c + al(48 * size_t(C)) &&
+              p.o_X == p.o_c0 + al(48 * size_t(C)) && p.o_X0 == p.o_X + al(24 * size_t(P)) &&
+              p.pl_bytes == p.o_X0 + al(24 * size_t(P)));
+        // exactly one route (an enum), None only without parameters
+        CHECK((p.route == ParamRoute::None) == (C == 0 && P == 0));
+        if (p.route == ParamRoute::Late) CHECK(p.pl_bytes <= MiB);
+        if (p.route == ParamRoute::Side) CHECK(p.pl_bytes > MiB);
+        if (p.route == ParamRoute::Early) CHECK(p.host_counts);
+        if (p.deferred_uv) CHECK(!p.stage_in && N >= 262144);
+        if (p.host_counts) CHECK(N <= 65536 && p.stage_in);
+        CHECK(p.stage_in == (p.in_bytes <= MiB));
+        CHECK(!plan_setup(N, C, P, true).deferred_uv);
+      }
+  struct Row {
+    int64_t N;
+    int C, P;
+    bool host_counts, deferred;
+    ParamRoute route;
+    size_t in_bytes;
+  };
+  const Row rows[] = {
+      {0, 0, 0, true, false, ParamRoute::None, 256},
+      {0, 3, 5, true, false, ParamRoute::Early, 256},
+      {20000, 20, 2000, true, false, ParamRoute::Early, 488448},
+      {43648, 1, 10, true, false, ParamRoute::Early, 1047808},
+      {43690, 1, 1, false, false, ParamRoute::Late, 1049088},
+      {18000, 130, 3000, true, false, ParamRoute::Early, 444416},
+      {30000, 256, 60000, true, false, ParamRoute::Side, 960256},
+      {44000, 12, 11000, false, false, ParamRoute::Late, 1100288},
+      {66000, 50, 22000, false, false, ParamRoute::Side, 1584384},
+      {262143, 50, 20000, false, false, ParamRoute::Late, 6291456},
+      {262144, 50, 20000, false, true, ParamRoute::Late, 6291456},
+      {264000, 100, 22000, false, true, ParamRoute::Side, 6336000},
+      {2000000, 500, 200000, false, true, ParamRoute::Side, 48000000},
+  };
+  for (const Row& r : rows) {
+    const auto p = plan_setup(r.N, r.C, r.P, false);
+    CHECK(p.host_counts == r.host_counts && p.deferred_uv == r.deferred && p.route == r.route &&
+          p.in_bytes == r.in_bytes);
+  }
+  CHECK(!plan_setup(262144, 50, 20000, true).deferred_uv);  // SFM_SYNC_UV
+  // the Schur shape at the two measured points: C3, a mean of 72 pairs per
+  // block; C1, ~460 pairs over 210 blocks
+  auto sh = sfm::hostlayout::schur_shape(72 * 125250, 125250, nullptr, nullptr);
+  CHECK(sh.pts_sub == 8 && !sh.wg_blocks);
+  sh = sfm::hostlayout::schur_shape(460 * 210, 210, nullptr, nullptr);
+  CHECK(sh.pts_sub == 64 && sh.wg_blocks);
+  sh = sfm::hostlayout::schur_shape(460 * 210, 210, "32", "1");  // the overrides: 64 lanes only take workgroup blocks
+  CHECK(sh.pts_sub == 32 && !sh.wg_blocks);
+  sh = sfm::hostlayout::schur_shape(460 * 210, 210, "7", "0");
+  CHECK(sh.pts_sub == 16 && !sh.wg_blocks);
+  CHECK(sfm::hostlayout::schur_shape(0, 0, nullptr, nullptr).pts_sub == 8);
+  // the small path's predicate at its bounds (counts made up: one camera, one point)
+  {
+    const int32_t one_cam[1] = {65536}, pt64[1] = {64}, pt65[1] = {65};
+    CHECK(sfm::hostlayout::small_setup_fits(65536, 1, 1, one_cam, pt64));
+    CHECK(!sfm::hostlayout::small_setup_fits(65536, 1, 1, one_cam, pt65));   // a point segment too long
+    CHECK(!sfm::hostlayout::small_setup_fits(65537, 1, 1, one_cam, pt64));   // too many observations
+    std::vector<int32_t> cams(127, 500);
+    CHECK(sfm::hostlayout::small_setup_fits(127 * 500, 127, 1, cams.data(), pt64));
+    cams.push_back(500);  // 128 cameras: 8256 blocks, the XCD block order
+    CHECK(!sfm::hostlayout::small_setup_fits(128 * 500, 128, 1, cams.data(), pt64));
+  }
+  std::printf("  plan: %d grid points, %zu literal rows, Schur shape, small-path bounds ok\n", n,
+              sizeof(rows) / sizeof(rows[0]));
 }
 
 struct Pt2 {
@@ -301,6 +410,9 @@ int main() {
   check_layout(none, "empty");
   Scene big = make_scene(130, 500, 8, 99);  // above the small path's 127 cameras: no slices
   check_layout(big, "C>127");
+
+  std::printf("asan: set_problem's host plan (ba_host_layout.h)\n");
+  check_plan();
 
   std::printf("asan: compat header over the oracle (gather, solve, scatter-back)\n");
   for (int mode = 0; mode < 3; ++mode) {
