@@ -6,7 +6,10 @@
 //     camera runs / chunk table, the small path's slice sizes and the camera-
 //     run blob's bound, the small path's size predicate -- on the C1 scene,
 //     shuffled duplicates, an empty camera with single-view points, bad
-//     indices / non-finite uv, and the empty problem; every output checked against a naive recount; and the
+//     indices / non-finite uv, and the empty problem; every output checked
+//     against a naive recount; a hub point seen by every camera, by some twice
+//     and three times (the pair buffer's bound 2 * pairs_est, the small
+//     path's degree limit at 64 / 65 observations); and the
 //     plan of set_problem (regimes, parameter routes, the stage's regions)
 //     over a grid of sizes around every threshold, with the Schur shape;
 //   * include/sfm_ctracker_compat.hpp -- the pointer dedup / packing of
@@ -195,6 +198,89 @@ static void check_layout(const Scene& s, const char* name) {
   }
   std::printf("  %-14s N=%-7lld C=%-4d P=%-6d layout ok (%lld chunks, %lld pairs est.)\n", name, (long long)N, C, P,
               (long long)nch, (long long)pairs_est);
+}
+
+// A duplicate-heavy input: point 0 seen once by every one of 60 cameras, then
+// again by some of them -- two cameras three times in all (degree 64), and
+// with `extra` one more camera twice (degree 65).  The small path sizes the
+// pair buffer 2 * pairs_est without a device count, so that must bound the
+// pair total by k_pair_count's rule (ba_setup.hip: for each observation, the
+// other observations of its point with camera >= its own), which pairs_est
+// itself undercounts here; and the hub's degree alone decides the small path.
+static void check_duplicate_hub(bool extra) {
+  Scene s = make_scene(60, 300, 6, 41);
+  {
+    Scene e = s;
+    e.cam.clear();
+    e.pt.clear();
+    e.uv.clear();
+    auto add = [&](int32_t c, int32_t p, double u, double v) {
+      e.cam.push_back(c);
+      e.pt.push_back(p);
+      e.uv.push_back(u);
+      e.uv.push_back(v);
+    };
+    for (size_t i = 0; i < s.cam.size(); ++i)
+      if (s.pt[i] != 0) add(s.cam[i], s.pt[i], s.uv[2 * i], s.uv[2 * i + 1]);
+    // (spread through the caller's order: every 25th observation is followed by one of the hub's)
+    std::vector<int32_t> hub;
+    for (int c = 0; c < s.C; ++c) hub.push_back(c);
+    for (int c : {3, 3, 59, 59}) hub.push_back(c);  // cameras 3 and 59 (the last) three times
+    if (extra) hub.push_back(20);                   // camera 20 twice
+    Scene m = e;
+    m.cam.clear();
+    m.pt.clear();
+    m.uv.clear();
+    size_t h = 0;
+    for (size_t i = 0; i < e.cam.size(); ++i) {
+      m.cam.push_back(e.cam[i]);
+      m.pt.push_back(e.pt[i]);
+      m.uv.push_back(e.uv[2 * i]);
+      m.uv.push_back(e.uv[2 * i + 1]);
+      if (i % 25 == 24 && h < hub.size()) {
+        m.cam.push_back(hub[hub.size() - 1 - h]);  // the repeats first, cameras descending
+        m.pt.push_back(0);
+        m.uv.push_back(100.0 + double(h));
+        m.uv.push_back(200.0 - double(h));
+        ++h;
+      }
+    }
+    CHECK(h == hub.size());
+    s = m;
+  }
+  const int C = s.C, P = s.P;
+  const int64_t N = s.N();
+  std::vector<int32_t> cam_cnt(size_t(C) + 4), pc(size_t(P) + 1);
+  std::vector<int32_t> cam_slice;
+  int64_t pairs_est = -1;
+  sfm::hostlayout::check_and_count(N, s.uv.data(), s.cam.data(), s.pt.data(), C, P, true, cam_cnt.data(), pc.data(),
+                                   &cam_slice, &pairs_est);
+  CHECK(cam_cnt[0] == INT32_MAX && cam_cnt[1] == INT32_MAX && cam_cnt[2] == INT32_MAX);
+  CHECK(pc[0] == (extra ? 65 : 64));
+  CHECK(cam_cnt[4 + 3] >= 3 && cam_cnt[4 + 59] >= 3);
+  // k_pair_count's rule, naively
+  std::vector<std::vector<int32_t>> cams_of(static_cast<size_t>(P));
+  for (int64_t i = 0; i < N; ++i) cams_of[size_t(s.pt[size_t(i)])].push_back(s.cam[size_t(i)]);
+  int64_t pairs = 0, est = 0, same = 0;
+  for (const auto& v : cams_of) {
+    for (size_t a = 0; a < v.size(); ++a)
+      for (size_t b = 0; b < v.size(); ++b)
+        if (a != b && v[b] >= v[a]) {
+          ++pairs;
+          same += v[a] == v[b];
+        }
+    est += int64_t(v.size()) * (int64_t(v.size()) - 1) / 2;
+  }
+  CHECK(est == pairs_est);
+  CHECK(same == (extra ? 14 : 12));     // a camera seen three times: 6 ordered pairs, twice: 2
+  CHECK(pairs == pairs_est + same / 2);  // the estimate undercounts by the same-camera pairs
+  CHECK(pairs > pairs_est && pairs <= 2 * pairs_est);
+  // the hub's degree alone takes the problem off the small path
+  CHECK(sfm::hostlayout::small_setup_fits(N, C, P, cam_cnt.data() + 4, pc.data()) == !extra);
+  for (int p = 1; p < P; ++p) CHECK(pc[size_t(p)] <= 6);
+  std::printf("  %-14s N=%-7lld C=%-4d P=%-6d hub degree %d: %lld pairs (%lld of one camera) <= 2 x %lld est., small path %s\n",
+              extra ? "dup-hub-65" : "dup-hub-64", (long long)N, C, P, pc[0], (long long)pairs, (long long)same,
+              (long long)pairs_est, extra ? "no" : "yes");
 }
 
 // set_problem's host plan (hostlayout::plan_setup): the invariants of the
@@ -410,6 +496,8 @@ int main() {
   check_layout(none, "empty");
   Scene big = make_scene(130, 500, 8, 99);  // above the small path's 127 cameras: no slices
   check_layout(big, "C>127");
+  check_duplicate_hub(false);
+  check_duplicate_hub(true);
 
   std::printf("asan: set_problem's host plan (ba_host_layout.h)\n");
   check_plan();
