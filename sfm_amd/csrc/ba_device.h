@@ -34,6 +34,9 @@ constexpr int kPtL = 10;
 constexpr int kPtS = 16;
 // Per-point record of k_schur_pairs_rot: X (3), G_p = diag(s_p) L_p^-T (G00 G01 G02 G11 G12 G22), pad: 128 B.
 constexpr int kPtG = 16;
+// Per-camera record of k_schur_pairs_rot's staging (one side of a block in LDS; camS):
+// R 9 | t 3 | fx sk fy | first-order flag | J 9 (row-major) | Jacobi scale 6 | pad.
+constexpr int kCamSR = 32;
 // Cholesky tile size.
 constexpr int kNB = 64;
 // Threads per workgroup of the observation / point kernels.
@@ -154,6 +157,10 @@ struct DevProblem {
   int32_t* bperm = nullptr;   // [n_bslots] k_schur_pts work order (XCD-aware row groups; -1: empty slot;
                               // nullptr: plain block order, small systems)
   int64_t n_bslots = 0;
+  int4* srec = nullptr;       // [n_bslots] with bperm: slot k's {c1, c2, seg[b], seg[b + 1]}, b = bperm[k]; c1 = -1:
+                              // empty slot (k_schur_pairs_rot_pw reads these in place of bperm -> blk -> seg)
+  int32_t schur_wgs = 0;      // its grid (SFM_SCHUR_WGS, a test knob; 0: eight workgroups per CU)
+  double* camS = nullptr;     // [C][kCamSR] with ptG: each camera's staged record (k_cam_stage_rot, once per pass)
   double* ptS = nullptr;      // [P][kPtS] X 3, scale 3, l10 l20 l21, 1/l_ii 3, z 3, pad
   double* ptG = nullptr;      // [P][16] X 3, G_p = diag(s_p) L_p^-T (6, upper), pad: k_schur_pairs_rot's record
                               // (large reduced systems; nullptr: k_schur_pts and ptS alone)

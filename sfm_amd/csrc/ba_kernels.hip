@@ -1246,7 +1246,7 @@ __device__ __forceinline__ double skew_basis_entry(int k, int i) {
   const int r = i / 3, q = i % 3;
   return (r == (k + 2) % 3 && q == (k + 1) % 3) ? 1.0 : (r == (k + 1) % 3 && q == (k + 2) % 3) ? -1.0 : 0.0;
 }
-constexpr int kCamSR = 32;  // R 9 | t 3 | fx sk fy | flag | J 9 (row-major) | scale 6 | pad
+// (kCamSR doubles per camera, ba_device.h: R 9 | t 3 | fx sk fy | flag | J 9 (row-major) | scale 6 | pad)
 
 // The wave's kPer blocks staged together: lane l serves block q = l % kPer
 // with its kSub = 64 / kPer lanes j = l / kPer.  Every lane runs every load on
@@ -1334,6 +1334,109 @@ __device__ __forceinline__ void pair_side_rot(const double* cs, const double Xp[
   M[3] = e[3] * G[0]; M[4] = e[3] * G[1] + e[4] * G[3]; M[5] = e[3] * G[2] + e[4] * G[4] + e[5] * G[5];
 }
 
+// One loop step of a lane: its pair's four quadrants added to acc (row-major
+// 6x6: [y1]x H [y2]x^T | [y1]x H ; H [y2]x^T | H).  x0..x4: the point's record.
+__device__ __forceinline__ void pairs_rot_step(const double* cs1, const double* cs2, const double2 x0,
+                                               const double2 x1, const double2 x2, const double2 x3,
+                                               const double2 x4, const bool valid, double (&acc)[36]) {
+    const double Xp[3] = {x0.x, x0.y, x1.x};
+    const double G[6] = {x1.y, x2.x, x2.y, x3.x, x3.y, x4.x};
+    double M1[6], ab1[5], y1[3], M2[6], ab2[5], y2[3];
+    pair_side_rot(cs1, Xp, G, y1, M1, ab1);
+    asm volatile("" ::: "memory");
+    pair_side_rot(cs2, Xp, G, y2, M2, ab2);
+    asm volatile("" ::: "memory");
+    const double w = valid ? 1.0 : 0.0;
+    const double g00 = (M1[0] * M2[0] + M1[1] * M2[1] + M1[2] * M2[2]) * w;
+    const double g01 = (M1[0] * M2[3] + M1[1] * M2[4] + M1[2] * M2[5]) * w;
+    const double g10 = (M1[3] * M2[0] + M1[4] * M2[1] + M1[5] * M2[2]) * w;
+    const double g11 = (M1[3] * M2[3] + M1[4] * M2[4] + M1[5] * M2[5]) * w;
+    double H[3][3];  // A_1^T G A_2
+    {
+      const double t00 = g00 * ab2[0], t01 = g00 * ab2[1] + g01 * ab2[3], t02 = g00 * ab2[2] + g01 * ab2[4];
+      const double t10 = g10 * ab2[0], t11 = g10 * ab2[1] + g11 * ab2[3], t12 = g10 * ab2[2] + g11 * ab2[4];
+      H[0][0] = ab1[0] * t00; H[0][1] = ab1[0] * t01; H[0][2] = ab1[0] * t02;
+      H[1][0] = ab1[1] * t00 + ab1[3] * t10; H[1][1] = ab1[1] * t01 + ab1[3] * t11; H[1][2] = ab1[1] * t02 + ab1[3] * t12;
+      H[2][0] = ab1[2] * t00 + ab1[4] * t10; H[2][1] = ab1[2] * t01 + ab1[4] * t11; H[2][2] = ab1[2] * t02 + ab1[4] * t12;
+    }
+    // Kx = [y1]x H: column v is y1 x H[:, v]
+    double Kx[3][3];
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+      Kx[0][v] = y1[1] * H[2][v] - y1[2] * H[1][v];
+      Kx[1][v] = y1[2] * H[0][v] - y1[0] * H[2][v];
+      Kx[2][v] = y1[0] * H[1][v] - y1[1] * H[0][v];
+    }
+    // A [y2]x^T: row u is y2 x A[u, :]
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      acc[6 * u + 0] += y2[1] * Kx[u][2] - y2[2] * Kx[u][1];
+      acc[6 * u + 1] += y2[2] * Kx[u][0] - y2[0] * Kx[u][2];
+      acc[6 * u + 2] += y2[0] * Kx[u][1] - y2[1] * Kx[u][0];
+      acc[6 * u + 3] += Kx[u][0]; acc[6 * u + 4] += Kx[u][1]; acc[6 * u + 5] += Kx[u][2];
+      acc[6 * (3 + u) + 0] += y2[1] * H[u][2] - y2[2] * H[u][1];
+      acc[6 * (3 + u) + 1] += y2[2] * H[u][0] - y2[0] * H[u][2];
+      acc[6 * (3 + u) + 2] += y2[0] * H[u][1] - y2[1] * H[u][0];
+      acc[6 * (3 + u) + 3] += H[u][0]; acc[6 * (3 + u) + 4] += H[u][1]; acc[6 * (3 + u) + 5] += H[u][2];
+    }
+}
+
+// Once per block: J_1^T and J_2 applied to the lanes' sums, the lane
+// reduction and the block's 36 stores (own: the slot holds a block).
+template <int kSub>
+__device__ __forceinline__ void pairs_rot_finish(const double* cs1, const double* cs2, double (&acc)[36],
+                                                 const bool own, const int2 cc, double* __restrict__ S, int ld,
+                                                 const int* tile_cnt, int l, int sl) {
+  // once per block: rows 0..2 <- J_1^T rows, then columns 0..2 <- columns J_2
+  {
+    const double* J1 = cs1 + 16;
+    const double* J2 = cs2 + 16;
+#pragma unroll
+    for (int v = 0; v < 6; ++v) {
+      const double a0 = acc[v], a1 = acc[6 + v], a2 = acc[12 + v];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) acc[6 * k + v] = J1[k] * a0 + J1[3 + k] * a1 + J1[6 + k] * a2;
+    }
+#pragma unroll
+    for (int u = 0; u < 6; ++u) {
+      const double a0 = acc[6 * u], a1 = acc[6 * u + 1], a2 = acc[6 * u + 2];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) acc[6 * u + k] = a0 * J2[k] + a1 * J2[3 + k] + a2 * J2[6 + k];
+    }
+  }
+  double v32[32];
+#pragma unroll
+  for (int e = 0; e < 32; ++e) v32[e] = acc[e];
+  seg_reduce32<kSub>(v32, l);
+  const double t32 = seg_sum<kSub>(acc[32]), t33 = seg_sum<kSub>(acc[33]), t34 = seg_sum<kSub>(acc[34]),
+               t35 = seg_sum<kSub>(acc[35]);
+  if (own) {
+    // (a diagonal block: same-camera duplicate pairs only, added to k_schur_diag_sum's)
+    double* Sb = S + size_t(6 * cc.x) * ld + 6 * size_t(cc.y);
+    const bool add = cc.x == cc.y;
+    const double* sc1 = cs1 + 25;
+    const double* sc2 = cs2 + 25;
+    auto put = [&](int e, double v) {
+      double* q = Sb + size_t(e / 6) * ld + e % 6;
+      v = v * sc1[e / 6] * sc2[e % 6];
+      v = add ? *q - v : -v;
+      // overlapped with the factorisation: write-through, counted per tile
+      if (tile_cnt) __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else *q = v;
+    };
+    constexpr int kR = kSub >= 32 ? 1 : 32 / kSub;
+    if (kSub == 64) {
+      if (!(sl & 1)) put(sl >> 1, v32[0]);
+    } else {
+#pragma unroll
+      for (int r = 0; r < kR; ++r) put(kR * sl + r, v32[r]);
+    }
+    if (sl < 4) put(32 + sl, sl == 0 ? t32 : sl == 1 ? t33 : sl == 2 ? t34 : t35);
+  }
+}
+
+// One group of 64 / kSub slots per wave, a workgroup's four groups once: the
+// form of the Schur / Cholesky overlap (tile_cnt, the blocks in plain order).
 template <int kSub>
 __global__ __launch_bounds__(kThreads, 2) void k_schur_pairs_rot(int64_t n_slots, const int2* __restrict__ blk,
                                                               const int32_t* __restrict__ seg,
@@ -1396,93 +1499,9 @@ __global__ __launch_bounds__(kThreads, 2) void k_schur_pairs_rot(int64_t n_slots
     // (fences: the loads above stay here, and each camera's constants are
     // read from LDS where they are used, not hoisted into live registers)
     asm volatile("" ::: "memory");
-    const double Xp[3] = {x0.x, x0.y, x1.x};
-    const double G[6] = {x1.y, x2.x, x2.y, x3.x, x3.y, x4.x};
-    double M1[6], ab1[5], y1[3], M2[6], ab2[5], y2[3];
-    pair_side_rot(cs1, Xp, G, y1, M1, ab1);
-    asm volatile("" ::: "memory");
-    pair_side_rot(cs2, Xp, G, y2, M2, ab2);
-    asm volatile("" ::: "memory");
-    const double w = valid ? 1.0 : 0.0;
-    const double g00 = (M1[0] * M2[0] + M1[1] * M2[1] + M1[2] * M2[2]) * w;
-    const double g01 = (M1[0] * M2[3] + M1[1] * M2[4] + M1[2] * M2[5]) * w;
-    const double g10 = (M1[3] * M2[0] + M1[4] * M2[1] + M1[5] * M2[2]) * w;
-    const double g11 = (M1[3] * M2[3] + M1[4] * M2[4] + M1[5] * M2[5]) * w;
-    double H[3][3];  // A_1^T G A_2
-    {
-      const double t00 = g00 * ab2[0], t01 = g00 * ab2[1] + g01 * ab2[3], t02 = g00 * ab2[2] + g01 * ab2[4];
-      const double t10 = g10 * ab2[0], t11 = g10 * ab2[1] + g11 * ab2[3], t12 = g10 * ab2[2] + g11 * ab2[4];
-      H[0][0] = ab1[0] * t00; H[0][1] = ab1[0] * t01; H[0][2] = ab1[0] * t02;
-      H[1][0] = ab1[1] * t00 + ab1[3] * t10; H[1][1] = ab1[1] * t01 + ab1[3] * t11; H[1][2] = ab1[1] * t02 + ab1[3] * t12;
-      H[2][0] = ab1[2] * t00 + ab1[4] * t10; H[2][1] = ab1[2] * t01 + ab1[4] * t11; H[2][2] = ab1[2] * t02 + ab1[4] * t12;
-    }
-    // Kx = [y1]x H: column v is y1 x H[:, v]
-    double Kx[3][3];
-#pragma unroll
-    for (int v = 0; v < 3; ++v) {
-      Kx[0][v] = y1[1] * H[2][v] - y1[2] * H[1][v];
-      Kx[1][v] = y1[2] * H[0][v] - y1[0] * H[2][v];
-      Kx[2][v] = y1[0] * H[1][v] - y1[1] * H[0][v];
-    }
-    // A [y2]x^T: row u is y2 x A[u, :]
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-      acc[6 * u + 0] += y2[1] * Kx[u][2] - y2[2] * Kx[u][1];
-      acc[6 * u + 1] += y2[2] * Kx[u][0] - y2[0] * Kx[u][2];
-      acc[6 * u + 2] += y2[0] * Kx[u][1] - y2[1] * Kx[u][0];
-      acc[6 * u + 3] += Kx[u][0]; acc[6 * u + 4] += Kx[u][1]; acc[6 * u + 5] += Kx[u][2];
-      acc[6 * (3 + u) + 0] += y2[1] * H[u][2] - y2[2] * H[u][1];
-      acc[6 * (3 + u) + 1] += y2[2] * H[u][0] - y2[0] * H[u][2];
-      acc[6 * (3 + u) + 2] += y2[0] * H[u][1] - y2[1] * H[u][0];
-      acc[6 * (3 + u) + 3] += H[u][0]; acc[6 * (3 + u) + 4] += H[u][1]; acc[6 * (3 + u) + 5] += H[u][2];
-    }
+    pairs_rot_step(cs1, cs2, x0, x1, x2, x3, x4, valid, acc);
   }
-  // once per block: rows 0..2 <- J_1^T rows, then columns 0..2 <- columns J_2
-  {
-    const double* J1 = cs1 + 16;
-    const double* J2 = cs2 + 16;
-#pragma unroll
-    for (int v = 0; v < 6; ++v) {
-      const double a0 = acc[v], a1 = acc[6 + v], a2 = acc[12 + v];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) acc[6 * k + v] = J1[k] * a0 + J1[3 + k] * a1 + J1[6 + k] * a2;
-    }
-#pragma unroll
-    for (int u = 0; u < 6; ++u) {
-      const double a0 = acc[6 * u], a1 = acc[6 * u + 1], a2 = acc[6 * u + 2];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) acc[6 * u + k] = a0 * J2[k] + a1 * J2[3 + k] + a2 * J2[6 + k];
-    }
-  }
-  double v32[32];
-#pragma unroll
-  for (int e = 0; e < 32; ++e) v32[e] = acc[e];
-  seg_reduce32<kSub>(v32, l);
-  const double t32 = seg_sum<kSub>(acc[32]), t33 = seg_sum<kSub>(acc[33]), t34 = seg_sum<kSub>(acc[34]),
-               t35 = seg_sum<kSub>(acc[35]);
-  if (own) {
-    // (a diagonal block: same-camera duplicate pairs only, added to k_schur_diag_sum's)
-    double* Sb = S + size_t(6 * cc.x) * ld + 6 * size_t(cc.y);
-    const bool add = cc.x == cc.y;
-    const double* sc1 = cs1 + 25;
-    const double* sc2 = cs2 + 25;
-    auto put = [&](int e, double v) {
-      double* q = Sb + size_t(e / 6) * ld + e % 6;
-      v = v * sc1[e / 6] * sc2[e % 6];
-      v = add ? *q - v : -v;
-      // overlapped with the factorisation: write-through, counted per tile
-      if (tile_cnt) __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else *q = v;
-    };
-    constexpr int kR = kSub >= 32 ? 1 : 32 / kSub;
-    if (kSub == 64) {
-      if (!(sl & 1)) put(sl >> 1, v32[0]);
-    } else {
-#pragma unroll
-      for (int r = 0; r < kR; ++r) put(kR * sl + r, v32[r]);
-    }
-    if (sl < 4) put(32 + sl, sl == 0 ? t32 : sl == 1 ? t33 : sl == 2 ? t34 : t35);
-  }
+  pairs_rot_finish<kSub>(cs1, cs2, acc, own, cc, S, ld, tile_cnt, l, sl);
   if (tile_cnt) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (as k_schur_pts: the block is out, then counted)
     if (own && sl == 0) {
@@ -1491,6 +1510,144 @@ __global__ __launch_bounds__(kThreads, 2) void k_schur_pairs_rot(int64_t n_slots
         for (int J = c0 / 64; J <= (c0 + 5) / 64; ++J)
           __hip_atomic_fetch_add(tile_cnt + I * nbt + J, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+  }
+}
+
+// The cameras' staged records (kCamSR doubles each, what stage_cams_rot
+// leaves in LDS for one side of a block) written out once per pass, for
+// k_schur_pairs_rot_pw: a wave stages 64 / kSub cameras as both sides of
+// 64 / kSub blocks and copies the first side out.
+template <int kSub>
+__global__ __launch_bounds__(kThreads) void k_cam_stage_rot(int C, const double* __restrict__ camR,
+                                                            const double* __restrict__ cam,
+                                                            const double* __restrict__ Kc,
+                                                            const double* __restrict__ scale_c,
+                                                            double* __restrict__ camS, const int* __restrict__ gate) {
+  if (gate && *gate == 0) return;  // device LM loop: phase skipped
+  constexpr int kPer = 64 / kSub;
+  __shared__ __attribute__((aligned(16))) double cst[kThreads / 64][kPer][2 * kCamSR];
+  const int l = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int c0 = (int(blockIdx.x) * (kThreads / 64) + wv) * kPer;
+  const int cq = min(c0 + l % kPer, C - 1);
+  stage_cams_rot<kSub>(&cst[wv][0][0], cq, cq, camR, cam, Kc, scale_c, l);
+  wave_lds_sync();
+  for (int e = l; e < kPer * kCamSR; e += 64) {
+    const int q = e / kCamSR, hl = e % kCamSR;
+    if (c0 + q < C) camS[size_t(kCamSR) * (c0 + q) + hl] = hl < kCamSR - 1 ? cst[wv][q][hl] : 0.0;
+  }
+}
+
+// The pass outside the overlap: waves that walk several groups.  The grid is
+// a few resident generations (launch_schur_offdiag); workgroup w serves list
+// w % 8 of the slot order (set_problem's XCD-aware groups: the workgroups one XCD gets under
+// round-robin placement, a speed assumption only).  A list is dealt out in
+// groups of 64 / kSub slots, the four groups of a former workgroup in a row;
+// wave j of the list's W takes groups j, j + W, j + 2 W, ..: no wave ever
+// waits for another, or for a counter.  (Groups handed out through one ticket
+// per list measured slower: profiles/schur_persistent_ab.txt.)  Per slot
+// set_problem left one record {c1, c2, kb, ke} (srec; c1 < 0: empty slot) in
+// place of the walk bperm -> blk -> seg, and k_cam_stage_rot one record per
+// camera in place of stage_cams_rot's rounds of loads.  From the top of group
+// i the wave has in flight group i + 2's slot record and group i + 1's first
+// two point indices and cameras (copied into its other LDS buffer); from the
+// end of group i's loop group i + 1's first point records, behind which group
+// i's J application, reduction and stores run.
+template <int kSub>
+__global__ __launch_bounds__(kThreads, 2) void k_schur_pairs_rot_pw(const int4* __restrict__ srec, int n_tick,
+                                                                 const int32_t* __restrict__ bpts,
+                                                                 const double* __restrict__ ptG,
+                                                                 const double* __restrict__ camS,
+                                                                 double* __restrict__ S, int ld,
+                                                                 const int* __restrict__ gate) {
+  if (gate && *gate == 0) return;  // device LM loop: phase skipped
+  constexpr int kPer = 64 / kSub, kW = kThreads / 64;
+  const int W = int(gridDim.x / 8) * kW;  // waves per list
+  __shared__ __attribute__((aligned(16))) double cst[2][kW][kPer][2 * kCamSR];
+  const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, g = l / kSub, sl = l % kSub;
+  const int xl = blockIdx.x & 7;
+  // group t of list xl: wave t % kW of the list's workgroup-sized group t / kW
+  auto load_rec = [&](int t) -> int4 {
+    int4 r = make_int4(-1, -1, 0, 0);
+    if (t < n_tick) r = srec[((int64_t(t / kW) * 8 + xl) * kW + t % kW) * kPer + g];
+    return r;
+  };
+  auto first_idx = [&](const int4 r, int& i0, int& i1) {
+    const int kb = r.x >= 0 ? r.z : 0, ke = r.x >= 0 ? r.w : 0;
+    i0 = bpts[kb + sl < ke ? kb + sl : 0];
+    i1 = bpts[kb + sl + kSub < ke ? kb + sl + kSub : 0];
+  };
+  // the group's 2 (64 / kSub) camera records, 16 B per lane and round: doubles
+  // 2 e2, 2 e2 + 1 of the wave's buffer are entries 2 e2 % 32.. of side
+  // (e2 / 16) % 2 of block e2 / 32, whose slot record lane (e2 / 32) kSub holds
+  auto stage = [&](const int4 r, int buf) {
+    double* cs_wave = &cst[buf][wv][0][0];
+#pragma unroll
+    for (int e0 = 0; e0 < kPer * kCamSR; e0 += 64) {
+      const int e2 = e0 + l;
+      const int q = min(e2 / kCamSR, kPer - 1), side = (e2 / (kCamSR / 2)) & 1, hl = 2 * (e2 % (kCamSR / 2));
+      const int c1 = __shfl(r.x, q * kSub), c2 = __shfl(r.y, q * kSub);
+      const double2 v = ld2(camS + size_t(kCamSR) * max(side ? c2 : c1, 0) + hl);
+      if (e2 < kPer * kCamSR) *reinterpret_cast<double2*>(cs_wave + (2 * q + side) * kCamSR + hl) = v;
+    }
+  };
+  // (the groups a wave holds ascend, so the first one past the end ends the wave)
+  int tA = int(blockIdx.x / 8) * kW + wv, tB = tA + W, tC = tB + W;
+  int4 rA = load_rec(tA), rB = load_rec(tB);
+  int cur = 0;
+  // the wave's first group starts in the open
+  int p_nx;
+  double2 n0, n1, n2, n3, n4;
+  {
+    int i0;
+    first_idx(rA, i0, p_nx);
+    stage(rA, 0);
+    const double* r = ptG + size_t(kPtG) * i0;
+    n0 = ld2(r); n1 = ld2(r + 2); n2 = ld2(r + 4); n3 = ld2(r + 6); n4 = ld2(r + 8);
+  }
+  wave_lds_sync();
+  while (tA < n_tick) {  // (wave-uniform)
+    const int4 rC = load_rec(tC);
+    int iB0, iB1;
+    first_idx(rB, iB0, iB1);
+    stage(rB, cur ^ 1);
+    const bool own = rA.x >= 0;
+    const int2 cc = make_int2(own ? rA.x : 0, own ? rA.y : 0);
+    const int kb = own ? rA.z : 0, ke = own ? rA.w : 0;
+    const double* cs1 = cst[cur][wv][g];
+    const double* cs2 = cs1 + kCamSR;
+    double acc[36];
+#pragma unroll
+    for (int e = 0; e < 36; ++e) acc[e] = 0.0;
+    int len = ke - kb;
+#pragma unroll
+    for (int off = kSub; off < 64; off <<= 1) len = max(len, __shfl_xor(len, off));
+    // (the loop of k_schur_pairs_rot: the record gather one step ahead, its index two)
+    for (int k0 = 0; k0 < len; k0 += kSub) {
+      double2 x0 = n0, x1 = n1, x2 = n2, x3 = n3, x4 = n4;
+      asm volatile("" : "+v"(x0.x), "+v"(x0.y), "+v"(x1.x), "+v"(x1.y), "+v"(x2.x), "+v"(x2.y), "+v"(x3.x), "+v"(x3.y),
+                   "+v"(x4.x), "+v"(p_nx));
+      const int k = kb + k0 + sl;
+      const bool valid = k < ke;
+      {
+        const double* r = ptG + size_t(kPtG) * p_nx;
+        n0 = ld2(r); n1 = ld2(r + 2); n2 = ld2(r + 4); n3 = ld2(r + 6); n4 = ld2(r + 8);
+      }
+      p_nx = bpts[k + 2 * kSub < ke ? k + 2 * kSub : 0];
+      asm volatile("" ::: "memory");
+      pairs_rot_step(cs1, cs2, x0, x1, x2, x3, x4, valid, acc);
+    }
+    // the next group's first records, then this group's end behind them
+    {
+      const double* r = ptG + size_t(kPtG) * iB0;
+      n0 = ld2(r); n1 = ld2(r + 2); n2 = ld2(r + 4); n3 = ld2(r + 6); n4 = ld2(r + 8);
+    }
+    p_nx = iB1;
+    asm volatile("" ::: "memory");
+    pairs_rot_finish<kSub>(cs1, cs2, acc, own, cc, S, ld, nullptr, l, sl);
+    wave_lds_sync();
+    tA = tB; tB = tC; tC += W;
+    rA = rB; rB = rC;
+    cur ^= 1;
   }
 }
 
@@ -2189,8 +2346,29 @@ void launch_schur_offdiag(const DevProblem& d, int* tile_cnt, hipStream_t s) {
                                                                     bperm, d.gate, tile_cnt, d.nblk, DiagFold{});
     return;
   }
+  if (d.ptG && d.srec && !tile_cnt) {  // ... with persistent waves over the slot and camera records
+    // 2 workgroups per CU are resident (2 waves per SIMD); the grid is four
+    // times that (C3: a wave walks 2 groups, the dispatcher evens out the
+    // lists' unequal groups; one resident generation of longer walks measured
+    // slower, profiles/schur_persistent_ab.txt), never more than one workgroup
+    // per workgroup-sized group of slots
+    const int64_t wg_groups = n_slots / per;  // (n_bslots: a multiple of 8 per)
+    const int grid = d.schur_wgs > 0 ? d.schur_wgs
+                                     : int(std::max<int64_t>(8, std::min<int64_t>(8 * std::max(1, d.n_cu), wg_groups)));
+    const int n_tick = int(n_slots / (8 * per)) * (kThreads / 64);  // groups per list
+    const int nbc = (d.C + per - 1) / per;
+#define SFM_ROTP(S_)                                                                                               \
+  k_cam_stage_rot<S_><<<nbc, kThreads, 0, s>>>(d.C, d.camR, d.cam, d.Kc, d.scale_c, d.camS, d.gate);               \
+  k_schur_pairs_rot_pw<S_><<<grid, kThreads, 0, s>>>(d.srec, n_tick, d.bpts, d.ptG, d.camS, d.S, d.ld, d.gate)
+    if (sub == 8) { SFM_ROTP(8); }
+    else if (sub == 16) { SFM_ROTP(16); }
+    else if (sub == 32) { SFM_ROTP(32); }
+    else { SFM_ROTP(64); }
+#undef SFM_ROTP
+    return;
+  }
   if (d.ptG) {  // large reduced systems: the rotated-point form (k_point_factor wrote ptG)
-#define SFM_ROT(S_)                                                                                              \
+#define SFM_ROT(S_)                                                                                           \
   k_schur_pairs_rot<S_><<<nb, kThreads, 0, s>>>(n_slots, d.blk, d.seg, d.bpts, d.ptG, d.camR, d.cam, d.Kc, d.scale_c, \
                                                 d.S, d.ld, bperm, d.gate, tile_cnt, d.nblk)
     if (sub == 8) SFM_ROT(8);

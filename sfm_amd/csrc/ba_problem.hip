@@ -545,6 +545,7 @@ void pair_lists_small(Setup& c) {
   launch_small_pairs_fill(c.C, d.n_blk, c.d_cam_off, c.cm_order, d.cam_pm, c.pt_s, d.pt_off, d.seg, d.bpts, c.s);
   launch_blk(c.C, d.blk, c.s);
   d.bperm = nullptr;
+  d.srec = nullptr;
   d.n_bslots = d.n_blk;
 }
 
@@ -582,16 +583,18 @@ int pair_lists_sorted(Setup& c) {
   // order (bperm = nullptr).  The group sizes come back with the final
   // synchronisation of set_problem.
   d.bperm = nullptr;
+  d.srec = nullptr;
   d.n_bslots = d.n_blk;
   if (d.n_blk > kSchurXcdMinBlocks) {
     const int per = 64 / d.schur_pts_sub * (kThreads / 64);
     int32_t *sorted = nullptr, *row_x = nullptr;
     int64_t* grp = nullptr;
     if (!(c.tmp(sorted, size_t(d.n_blk)) && c.tmp(row_x, size_t(c.C)) && c.tmp(grp, 16) &&
-          c.alloc(d.bperm, size_t(bperm_slots_bound(d.n_blk, per)))))
+          c.alloc(d.bperm, size_t(bperm_slots_bound(d.n_blk, per))) &&
+          c.alloc(d.srec, size_t(bperm_slots_bound(d.n_blk, per)))))
       return c.rc;
     HIPCHK(launch_bperm(c.C, d.n_blk, n_pairs, d.seg, d.blk, per, bk_a, bk_b, bv, sorted, row_x, grp, c.sort_tmp,
-                        c.sort_bytes, d.bperm, s));
+                        c.sort_bytes, d.bperm, d.srec, s));
     HIPCHK(hipMemcpyAsync(c.grp_host, grp, sizeof(int64_t) * 16, hipMemcpyDeviceToHost, s));
     c.bperm_per = per;
   }
@@ -620,6 +623,7 @@ int alloc_solver_arrays(Setup& c) {
   const char* ec = std::getenv("SFM_EU_CM");
   d.eu_cm = !(ec && ec[0] == '0');
   d.ptG = nullptr;
+  d.camS = nullptr;
   h->force_pack = env_flag("SFM_FORCE_PACK");
   // Schur / Cholesky overlap (SFM_OVERLAP=1; unsharded, more than two tiles):
   // per 64x64 tile of S the number of camera blocks (c1 <= c2, stored at
@@ -637,6 +641,7 @@ int alloc_solver_arrays(Setup& c) {
             c.alloc(d.ptV, size_t(kPtV) * P) && c.alloc(d.ptL, size_t(kPtL) * P) &&
             c.alloc(d.ptS, size_t(kPtS) * std::max<size_t>(1, P)) &&
             (d.n_blk <= kSchurXcdMinBlocks || c.alloc(d.ptG, size_t(kPtG) * std::max<size_t>(1, P))) &&
+            (d.n_blk <= kSchurXcdMinBlocks || c.alloc(d.camS, size_t(kCamSR) * std::max<size_t>(1, C))) &&
             c.alloc(d.Ucam, size_t(kUcam) * C) && c.alloc(d.jpart, 27 * std::max<size_t>(1, npad / 64)) &&
             c.alloc(d.dpart, 27 * std::max<size_t>(1, npad / 64)) && c.alloc(d.S, size_t(d.ld) * d.ld) &&
             (!(sharded(h) || h->force_pack) || c.alloc(d.Spack, packed_size(d.n))) &&
@@ -644,6 +649,10 @@ int alloc_solver_arrays(Setup& c) {
             c.alloc(d.cflags, 2 * tiles) &&
             c.alloc(d.cticket, 5);  // task ticket, walker-role ticket, back-substitution role ticket, a panel's two
   if (!ok) return c.rc;
+  // SFM_SCHUR_WGS (a test knob: few workgroups give each wave of k_schur_pairs_rot_pw
+  // many groups on a small problem), rounded up to the 8 lists; read per problem
+  const char* sw = std::getenv("SFM_SCHUR_WGS");
+  d.schur_wgs = sw ? std::min(1 << 16, std::max(0, std::atoi(sw)) + 7) / 8 * 8 : 0;
   if (d.overlap) {
     if (!(c.alloc(d.tile_cnt, tiles) && c.alloc(d.tile_exp, tiles))) return c.rc;
     std::vector<int32_t> te(tiles, 0);

@@ -326,13 +326,18 @@ __global__ __launch_bounds__(kT) void k_bperm_keys(int64_t n_blk, const int2* __
 __global__ __launch_bounds__(kT) void k_bperm_fill(int64_t n_blk, const int32_t* __restrict__ sorted,
                                                    const int2* __restrict__ blk, const int32_t* __restrict__ row_x,
                                                    const int64_t* __restrict__ grp, int per,
-                                                   int32_t* __restrict__ bperm) {
+                                                   const int32_t* __restrict__ seg, int32_t* __restrict__ bperm,
+                                                   int4* __restrict__ srec) {
   const int64_t p = int64_t(blockIdx.x) * kT + threadIdx.x;
   if (p >= n_blk) return;
   const int32_t b = sorted[p];
-  const int x = row_x[blk[b].x];
+  const int2 cc = blk[b];
+  const int x = row_x[cc.x];
   const int64_t i = p - grp[x];
-  bperm[((i / per) * 8 + x) * per + i % per] = b;
+  const int64_t k = ((i / per) * 8 + x) * per + i % per;
+  bperm[k] = b;
+  // the slot's record: what k_schur_pairs_rot_pw would read through bperm -> blk -> seg
+  srec[k] = make_int4(cc.x, cc.y, seg[b], seg[b + 1]);
 }
 
 // Host (pinned, device-mapped) -> device copy by a kernel, 16 B per lane
@@ -737,15 +742,16 @@ void launch_small_pairs_fill(int C, int64_t n_blk, const int32_t* cam_off, const
 int64_t bperm_slots_bound(int64_t n_blk, int per) { return std::max<int64_t>(1, (n_blk + per - 1) / per) * 8 * per; }
 hipError_t launch_bperm(int C, int64_t n_blk, int64_t n_pairs, const int32_t* seg, const int2* blk, int per,
                         uint32_t* key_a, uint32_t* key_b, int32_t* iota, int32_t* sorted, int32_t* row_x,
-                        int64_t* grp, void* sort_tmp, size_t sort_bytes, int32_t* bperm, hipStream_t s) {
+                        int64_t* grp, void* sort_tmp, size_t sort_bytes, int32_t* bperm, int4* srec, hipStream_t s) {
   hipError_t e = hipMemsetAsync(bperm, 0xFF, sizeof(int32_t) * size_t(bperm_slots_bound(n_blk, per)), s);
+  if (e == hipSuccess) e = hipMemsetAsync(srec, 0xFF, sizeof(int4) * size_t(bperm_slots_bound(n_blk, per)), s);
   if (e != hipSuccess || n_blk <= 0) return e;
   k_bperm_rows<<<1, kT, 0, s>>>(C, seg, n_pairs, n_blk, row_x, grp);
   const int cbits = 32 - bits_for(uint64_t(std::max(1, C)) - 1);
   k_bperm_keys<<<nblocks(n_blk), kT, 0, s>>>(n_blk, blk, seg, cbits, key_a, iota);
   e = sort_pairs32(sort_tmp, sort_bytes, key_a, key_b, iota, sorted, n_blk, ~uint64_t(0) >> 32, s);
   if (e != hipSuccess) return e;
-  k_bperm_fill<<<nblocks(n_blk), kT, 0, s>>>(n_blk, sorted, blk, row_x, grp, per, bperm);
+  k_bperm_fill<<<nblocks(n_blk), kT, 0, s>>>(n_blk, sorted, blk, row_x, grp, per, seg, bperm, srec);
   return hipGetLastError();
 }
 
