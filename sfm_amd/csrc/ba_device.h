@@ -6,6 +6,8 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "ba_lm.h"  // the scalar block's indices (enum Scalar) and the LM state machine
+
 namespace sfm {
 
 // Per-observation Jacobian record written by the Jacobian pass (doubles):
@@ -45,25 +47,6 @@ constexpr int kThreads = 256;
 // signalling NaN, which arithmetic never yields)
 constexpr uint32_t kYSentinelWord = 0x7FF4DEADu;
 constexpr uint64_t kYSentinel = (uint64_t(kYSentinelWord) << 32) | kYSentinelWord;
-
-// Index of scalar results (device array `scal`, doubles).
-enum Scalar {
-  kCost = 0,        // cost at current x (Jacobian pass)
-  kGradMaxCam,      // max |g| over camera params
-  kGradMaxPt,       // max |g| over point params
-  kXNorm2Cam,       // sum x^2 over cameras
-  kXNorm2Pt,        // sum x^2 over points
-  kModelChange,     // model cost change
-  kNewCost,         // cost at the candidate
-  kStep2Pt,         // sum dx^2 over points
-  kStep2Cam,        // sum dx^2 over cameras
-  kBadStep,         // > 0 if the step or candidate is non-finite / V not PD
-  kCholFail,        // reserved (the Cholesky flag is an int, fetched separately)
-  kBadCam,          // > 0 if the camera step is non-finite
-  kBadBack,         // > 0 if the point step is non-finite
-  kModelChangePt,   // point share of the model cost change (k_backsub_b; kModelChange holds the observations')
-  kNumScalars
-};
 
 // Batched scalar reductions (k_reduce_batch): job i reduces partial slot
 // `slot` over `nb` blocks (op 0 sum, 1 max) into scal[dst].

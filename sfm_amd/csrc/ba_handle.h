@@ -1,5 +1,5 @@
 // The bundle adjuster's handle and what the files that work on it share:
-// ba_solver.hip (the LM loops, the collectives, the C ABI) and ba_problem.hip
+// ba_solver.hip (the LM loop's drivers, the collectives, the C ABI) and ba_problem.hip
 // (sfm_ba_set_problem).  Internal: nothing here is part of include/sfm_amd.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,24 +33,6 @@ inline int fail(int code, const std::string& msg) {
   } while (0)
 
 enum Phase { kPhJac = 0, kPhCamRed, kPhPtEval, kPhPtPrep, kPhSchur, kPhChol, kPhBack, kPhBacksub, kPhOther, kNumPh };
-
-// device LM loop state (k_lm_decide / k_lm_post; see "device-driven LM loop")
-struct LmCtl {
-  int32_t run_step, run_eval, done, termination, error;
-  // The evaluation prepares the coming step (prep_fold, from the host: step_prep_folds).  An
-  // unsuccessful or invalid step then pauses the loop (run_step = 0, prep_stale = 1): the radius
-  // changed with no evaluation to follow, and the host, which enqueues the stand-alone prep
-  // kernels only when it knows they are needed, re-arms the loop with them in front.
-  int32_t prep_fold, prep_stale;
-  int32_t iteration, num_consecutive_invalid;
-  int32_t n_succ, n_unsucc, n_invalid, n_resid, n_jac, n_lin, trace_len;
-  double radius, decrease_factor, cost, grad_max, x_norm;
-  sfm_ba_iteration pending;  // an accepted iteration, completed after its evaluation
-  int32_t max_iter, max_invalid;
-  double ftol, gtol, ptol, max_radius, min_radius, min_rel_dec;
-  uint32_t red_count;  // workgroups of k_reduce_batch_lm done (reset by the last)
-  double init_cost, init_grad;  // the initial evaluation (k_lm_init), for the host's summary
-};
 
 struct sfm_ba_handle {
   int device = 0;
@@ -104,10 +86,11 @@ struct sfm_ba_handle {
   // ranks holding the same shard, so a one-GPU run sees the stale-buffer
   // hazards of a multi-rank one
   int emulate_ranks = 1;
-  // device-driven LM loop (unsharded solves): control block, its pinned
-  // mirror and the device trace buffer (grown to the iteration cap)
-  LmCtl* lm_ctl = nullptr;
-  LmCtl* lm_ctl_host = nullptr;
+  // device-driven LM loop: the state block (ba_lm.h; the host driver keeps
+  // its own on the stack), its pinned mirror and the trace buffer (grown to
+  // the iteration cap)
+  sfm::LmCtl* lm_ctl = nullptr;
+  sfm::LmCtl* lm_ctl_host = nullptr;
   // (pinned host memory: the deciding workgroups write the few entries
   // straight to the host, which reads them after the batch's synchronisation)
   sfm_ba_iteration* lm_trace = nullptr;
@@ -138,10 +121,10 @@ struct sfm_ba_handle {
   // radius changes only in the step's decision, so an evaluation prepares
   // the coming step.  eval_radius: that step's radius (host loop; the device
   // loop's kernels read LmCtl::radius).  prep_fresh: the prep on the device
-  // is for the current radius; set by the evaluation, cleared by an
-  // unsuccessful or invalid step (the host loop's own decision; the device
-  // loop pauses there and reports LmCtl::prep_stale), after which
-  // compute_step runs the stand-alone kernels first.
+  // is for the current radius; set by the evaluation, cleared when an
+  // unsuccessful or invalid step paused the loop (LmCtl::prep_stale, which
+  // either driver answers with lm_rearm), after which compute_step runs the
+  // stand-alone kernels first.
   double eval_radius = 0.0;
   bool prep_fresh = false;
   int n_cu = 0;  // compute units of the device (queried once)

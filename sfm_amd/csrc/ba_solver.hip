@@ -4,9 +4,11 @@
 //
 // The loop restates Ceres' TrustRegionMinimizer + LevenbergMarquardtStrategy
 // (the solver behind ceres::Solve at /root/reference/CTracker.cpp:700-701,
-// options CTracker.cpp:571-577) step for step; the
-// per-iteration arithmetic runs in the kernels of ba_kernels.hip /
-// chol_kernels.hip and only ~10 scalars cross PCIe per iteration.
+// options CTracker.cpp:571-577) step for step: its
+// bookkeeping is ba_lm.h's state machine, driven here from the device or from
+// the host; the per-iteration arithmetic runs in the kernels of
+// ba_kernels.hip / chol_kernels.hip and only ~10 scalars cross PCIe per
+// iteration.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <map>
@@ -113,167 +115,20 @@ int device_cus(int device) {
 
 
 // ---- device-driven LM loop ----
-// The trust-region bookkeeping of the host loop in sfm_ba_solve_resident,
-// restated on the device so that an unsharded solve enqueues several
-// iterations per host synchronisation.  k_lm_decide follows compute_step's
-// reductions; the accept copy (cam_new -> cam, X_new -> X: enqueued
-// iterations hold fixed pointers, where the host loop swaps them) and the
-// evaluation kernels run only when the step
-// was accepted (gate run_eval), k_lm_post completes the accepted iteration
-// after its evaluation; compute_step's kernels run only while the loop is
-// not done (gate run_step).  The arithmetic is the host loop's, operation
-// for operation (contraction off), so both loops take the same decisions.
-
-
-__device__ void lm_push(LmCtl* c, sfm_ba_iteration* trace, int cap, const sfm_ba_iteration& it) {
-  if (c->trace_len < cap) trace[c->trace_len] = it;
-  ++c->trace_len;
-}
-__device__ void lm_finish(LmCtl* c, int term) {
-  c->termination = term;
-  c->done = 1;
-  c->run_step = 0;
-  c->run_eval = 0;
-  c->prep_stale = 0;
-}
-
-// after compute_step's reduction (scal: model change, candidate cost, step
-// norms, bad-step flags; the Cholesky failure int after the scalars)
-__device__ void lm_decide(LmCtl* c, const double* scal, sfm_ba_iteration* trace, int cap) {
-#pragma clang fp contract(off)
-  if (c->done || !c->run_step) {  // (or paused: the batch's remaining iterations do nothing)
-    c->run_eval = 0;
-    return;
-  }
-  ++c->iteration;
-  sfm_ba_iteration itr;
-  itr.iteration = c->iteration;
-  itr.step_is_valid = 0;
-  itr.step_is_successful = 0;
-  itr.reserved = 0;
-  itr.cost = 0.0;
-  itr.cost_change = 0.0;
-  itr.gradient_max_norm = 0.0;
-  itr.step_norm = 0.0;
-  itr.relative_decrease = 0.0;
-  itr.trust_region_radius = 0.0;
-  c->n_lin++;
-  const int chol_fail = *reinterpret_cast<const int*>(scal + kNumScalars);
-  if (chol_fail & 6) {  // a persistent grid's hand-off timed out: the host reports it
-    c->error = chol_fail & 6;
-    lm_finish(c, SFM_FAILURE);
-    return;
-  }
-  const bool solve_ok = chol_fail == 0 && !(scal[kBadStep] > 0.0) && !(scal[kBadCam] > 0.0) && !(scal[kBadBack] > 0.0);
-  const double model_cost_change = scal[kModelChange] + scal[kModelChangePt];
-  itr.step_is_valid = (solve_ok && model_cost_change >= 0.0) ? 1 : 0;
-  if (!itr.step_is_valid) {
-    ++c->num_consecutive_invalid;
-    c->n_invalid++;
-    if (c->num_consecutive_invalid >= c->max_invalid) {
-      itr.cost = c->cost; itr.gradient_max_norm = c->grad_max; itr.trust_region_radius = c->radius;
-      lm_push(c, trace, cap, itr);
-      lm_finish(c, SFM_FAILURE);
-      return;
-    }
-    itr.cost = c->cost;
-    itr.gradient_max_norm = c->grad_max;
-  } else {
-    c->num_consecutive_invalid = 0;
-    double new_cost = scal[kNewCost];
-    if (!isfinite(new_cost)) new_cost = DBL_MAX;
-    c->n_resid++;
-    itr.step_norm = sqrt(scal[kStep2Cam] + scal[kStep2Pt]);
-    const double step_size_tolerance = c->ptol * (c->x_norm + c->ptol);
-    if (itr.step_norm <= step_size_tolerance) {
-      itr.cost = c->cost; itr.gradient_max_norm = c->grad_max; itr.trust_region_radius = c->radius;
-      lm_push(c, trace, cap, itr);
-      lm_finish(c, SFM_CONVERGENCE);
-      return;
-    }
-    itr.cost_change = c->cost - new_cost;
-    if (fabs(itr.cost_change) <= c->ftol * c->cost) {
-      itr.cost = c->cost; itr.gradient_max_norm = c->grad_max; itr.trust_region_radius = c->radius;
-      lm_push(c, trace, cap, itr);
-      lm_finish(c, SFM_CONVERGENCE);
-      return;
-    }
-    itr.relative_decrease = itr.cost_change / model_cost_change;
-    itr.step_is_successful = itr.relative_decrease > c->min_rel_dec;
-  }
-  if (itr.step_is_successful) {
-    c->n_succ++;
-    const double q = 2.0 * itr.relative_decrease - 1.0;
-    double radius = c->radius / fmax(1.0 / 3.0, 1.0 - q * q * q);
-    c->radius = fmin(c->max_radius, radius);
-    c->decrease_factor = 2.0;
-    c->pending = itr;  // cost, gradient and radius after the evaluation (k_lm_post)
-    c->run_eval = 1;
-    return;
-  }
-  c->n_unsucc++;
-  c->radius = c->radius / c->decrease_factor;
-  c->decrease_factor *= 2.0;
-  c->run_eval = 0;
-  if (c->prep_fold) {  // no evaluation follows: the next step redoes its prep for the new radius
-    c->prep_stale = 1;
-    c->run_step = 0;
-  }
-  itr.gradient_max_norm = c->grad_max;
-  itr.cost = c->cost;
-  itr.trust_region_radius = c->radius;
-  lm_push(c, trace, cap, itr);
-  if (c->radius < c->min_radius) { lm_finish(c, SFM_CONVERGENCE); return; }
-  if (c->iteration >= c->max_iter) { lm_finish(c, SFM_NO_CONVERGENCE); return; }
-}
+// The trust-region bookkeeping is ba_lm.h's (lm_init / lm_decide / lm_post on
+// an LmCtl), the same functions the host driver calls; here they run on the
+// device so that an unsharded solve enqueues several iterations per host
+// synchronisation.  k_lm_decide follows compute_step's reductions; the
+// accept copy (cam_new -> cam, X_new -> X: enqueued iterations hold fixed
+// pointers, where the host driver swaps them) and the evaluation kernels run
+// only when the step was accepted (gate run_eval), k_lm_post completes the
+// accepted iteration after its evaluation; compute_step's kernels run only
+// while the loop is not done (gate run_step).
 __global__ void k_lm_decide(LmCtl* c, const double* __restrict__ scal, sfm_ba_iteration* trace, int cap) {
   lm_decide(c, scal, trace, cap);
 }
-
-// after the accepted step's evaluation (scal: cost, gradient max norms, |x|^2)
-__device__ void lm_post(LmCtl* c, const double* scal, sfm_ba_iteration* trace, int cap) {
-#pragma clang fp contract(off)
-  if (!c->run_eval) return;
-  c->run_eval = 0;
-  c->n_jac++;
-  c->n_resid++;
-  const double cost = scal[kCost];
-  c->cost = cost;
-  if (!isfinite(cost)) { lm_finish(c, SFM_FAILURE); return; }
-  c->grad_max = fmax(scal[kGradMaxCam], scal[kGradMaxPt]);
-  c->x_norm = sqrt(scal[kXNorm2Cam] + scal[kXNorm2Pt]);
-  sfm_ba_iteration itr = c->pending;
-  itr.gradient_max_norm = c->grad_max;
-  itr.cost = cost;
-  itr.trust_region_radius = c->radius;
-  lm_push(c, trace, cap, itr);
-  if (c->grad_max <= c->gtol) { lm_finish(c, SFM_CONVERGENCE); return; }
-  if (c->iteration >= c->max_iter) { lm_finish(c, SFM_NO_CONVERGENCE); return; }
-}
 __global__ void k_lm_post(LmCtl* c, const double* __restrict__ scal, sfm_ba_iteration* trace, int cap) {
   lm_post(c, scal, trace, cap);
-}
-
-// after the initial evaluation (scal: cost, gradient max norms, |x|^2): the
-// loop state the host loop derives from its first evaluate(), so that the
-// solve needs no host round trip before the first iteration.  Error bit 8:
-// the initial cost is not finite (the host reports it).
-__device__ void lm_init(LmCtl* c, const double* scal) {
-#pragma clang fp contract(off)
-  const double cost = scal[kCost];
-  c->cost = cost;
-  c->init_cost = cost;
-  c->grad_max = fmax(scal[kGradMaxCam], scal[kGradMaxPt]);
-  c->init_grad = c->grad_max;
-  c->x_norm = sqrt(scal[kXNorm2Cam] + scal[kXNorm2Pt]);
-  if (!isfinite(cost)) {
-    c->error |= 8;
-    lm_finish(c, SFM_FAILURE);
-  } else if (c->grad_max <= c->gtol) {
-    lm_finish(c, SFM_CONVERGENCE);
-  } else if (c->max_iter <= 0) {
-    lm_finish(c, SFM_NO_CONVERGENCE);
-  }
 }
 __global__ void k_lm_init(LmCtl* c, const double* __restrict__ scal) { lm_init(c, scal); }
 
@@ -976,17 +831,124 @@ const char* invalid_option(const sfm_ba_options& o) {
   return nullptr;
 }
 
-// The device-driven LM loop of sfm_ba_solve_resident (all but the
-// host-callback collective), initial evaluation included:
-// state in LmCtl, initialised on the device from the initial evaluation
-// (k_lm_init: no host round trip before the first iteration), iterations
-// enqueued in batches (3, then 2; SFM_LM_BATCH fixes the size), the host
-// reads the control block once per batch.  The gated kernels of iterations
-// enqueued past the end return at once.  *nonfinite: the initial cost was
-// not finite (the summary is then the host loop's FAILURE).
+// ---- the LM loop's two drivers over ba_lm.h, and what they share ----
+
+// The loop state before the initial evaluation.
+LmCtl lm_start(const sfm_ba_handle* h, const sfm_ba_options& opts) {
+  LmCtl c;
+  std::memset(&c, 0, sizeof(c));
+  c.run_step = 1;
+  c.radius = opts.initial_trust_region_radius;
+  c.decrease_factor = 2.0;
+  c.max_iter = opts.max_num_iterations;
+  c.max_invalid = opts.max_num_consecutive_invalid_steps;
+  c.ftol = opts.function_tolerance;
+  c.gtol = opts.gradient_tolerance;
+  c.ptol = opts.parameter_tolerance;
+  c.max_radius = opts.max_trust_region_radius;
+  c.min_radius = opts.min_trust_region_radius;
+  c.min_rel_dec = opts.min_relative_decrease;
+  c.prep_fold = step_prep_folds(h) ? 1 : 0;
+  return c;
+}
+
+// The loop paused at an unsuccessful or invalid step (LmCtl::prep_stale): the
+// next step redoes its prep for the new radius.  Whether it re-armed the loop.
+bool lm_rearm(sfm_ba_handle* h, LmCtl* c) {
+  if (!c->prep_stale) return false;
+  h->prep_fresh = false;
+  c->prep_stale = 0;
+  c->run_step = 1;
+  return true;
+}
+
+// The finished loop's report: its error bits as messages, else the summary's
+// counters, termination and costs, and iteration 0's record followed by the
+// loop's.  *nonfinite: the initial cost was not finite (an error whose
+// summary, a FAILURE, the caller still gets).
 template <class Push>
-int run_device_lm(sfm_ba_handle* h, const sfm_ba_options& opts, double* cost, sfm_ba_summary* sm, Push& push,
-                  bool* nonfinite) {
+int lm_report(const sfm_ba_options& opts, const LmCtl& c, const sfm_ba_iteration* trace, int cap, sfm_ba_summary* sm,
+              Push& push, bool* nonfinite) {
+  if (c.error & 4) return fail(SFM_EIO, "Cholesky tile hand-off timed out (persistent grid made no progress)");
+  if (c.error & 2) return fail(SFM_EIO, "back-substitution hand-off timed out (persistent grid made no progress)");
+  sm->num_jacobian_evaluations++;  // the initial evaluation
+  sm->num_residual_evaluations++;
+  sm->initial_cost = c.init_cost;
+  sm->final_cost = c.cost;
+  if (c.error & 8) {
+    *nonfinite = true;
+    sm->termination_type = SFM_FAILURE;
+    return fail(SFM_EIO, "initial residual evaluation is not finite");
+  }
+  sfm_ba_iteration it0;
+  std::memset(&it0, 0, sizeof(it0));
+  it0.cost = c.init_cost;
+  it0.gradient_max_norm = c.init_grad;
+  it0.trust_region_radius = opts.initial_trust_region_radius;
+  it0.step_is_valid = 1;
+  it0.step_is_successful = 1;
+  push(it0);
+  const int n_tr = std::min(c.trace_len, cap);
+  for (int i = 0; i < n_tr; ++i) push(trace[i]);
+  sm->termination_type = c.termination;
+  sm->num_iterations = c.iteration;
+  sm->num_successful_steps += c.n_succ;
+  sm->num_unsuccessful_steps += c.n_unsucc;
+  sm->num_invalid_steps += c.n_invalid;
+  sm->num_residual_evaluations += c.n_resid;
+  sm->num_jacobian_evaluations += c.n_jac;
+  sm->num_linear_solves += c.n_lin;
+  return 0;
+}
+
+// The host driver (a host-callback collective, the distributed factor, whose
+// collectives are not gated, or SFM_HOST_LM=1): one phase at a time, each
+// ending in fetch_scalars, the decision taken between them.  Its own: the
+// per-phase wall times and the pointer swap that makes the candidate current.
+template <class Push>
+int run_host_lm(sfm_ba_handle* h, const sfm_ba_options& opts, sfm_ba_summary* sm, Push& push, bool* nonfinite) {
+  DevProblem& d = h->d;
+  const auto t_start = std::chrono::steady_clock::now();
+  auto now_s = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
+  LmCtl c = lm_start(h, opts);
+  std::vector<sfm_ba_iteration> trace(size_t(std::max(1, opts.max_num_iterations + 1)));
+  const int cap = int(trace.size());
+  const bool jac_scaling = opts.jacobi_scaling != 0;
+  int rc;
+  double tj = now_s();
+  h->eval_radius = c.radius;
+  if ((rc = evaluate(h, true, jac_scaling))) return rc;
+  sm->jacobian_time_s += now_s() - tj;
+  lm_init(&c, d.scal_host);
+  while (!c.done) {
+    const double tls = now_s();
+    if ((rc = compute_step(h, c.radius))) return rc;
+    sm->linear_solver_time_s += now_s() - tls;
+    lm_decide(&c, d.scal_host, trace.data(), cap);
+    lm_rearm(h, &c);
+    if (!c.run_eval) continue;
+    std::swap(d.cam, d.cam_new);
+    std::swap(d.X, d.X_new);
+    tj = now_s();
+    h->eval_radius = c.radius;  // the next step's: its preparation rides in the evaluation
+    if ((rc = evaluate(h, false, jac_scaling))) return rc;
+    sm->jacobian_time_s += now_s() - tj;
+    lm_post(&c, d.scal_host, trace.data(), cap);
+  }
+  return lm_report(opts, c, trace.data(), cap, sm, push, nonfinite);
+}
+
+// The device driver (every other solve), initial evaluation included: the
+// state block lives on the device, initialised there from the initial
+// evaluation (k_lm_init: no host round trip before the first iteration),
+// iterations enqueued in batches (3, then 2; SFM_LM_BATCH fixes the size), the
+// host reads the control block once per batch.  The gated kernels of
+// iterations enqueued past the end return at once.  With an RCCL communicator
+// the all-reduces are enqueued on the same stream and every rank decides from
+// the same reduced scalars.  (Per-phase host times stay 0 here: the phases
+// run asynchronously.)
+template <class Push>
+int run_device_lm(sfm_ba_handle* h, const sfm_ba_options& opts, sfm_ba_summary* sm, Push& push, bool* nonfinite) {
   DevProblem& d = h->d;
   hipStream_t s = h->stream;
   HostTimer timer;
@@ -1016,19 +978,7 @@ int run_device_lm(sfm_ba_handle* h, const sfm_ba_options& opts, double* cost, sf
     h->lm_trace_cap = cap;
   }
   LmCtl& c = *h->lm_ctl_host;
-  std::memset(&c, 0, sizeof(c));
-  c.run_step = 1;
-  c.radius = opts.initial_trust_region_radius;
-  c.decrease_factor = 2.0;
-  c.max_iter = opts.max_num_iterations;
-  c.max_invalid = opts.max_num_consecutive_invalid_steps;
-  c.ftol = opts.function_tolerance;
-  c.gtol = opts.gradient_tolerance;
-  c.ptol = opts.parameter_tolerance;
-  c.max_radius = opts.max_trust_region_radius;
-  c.min_radius = opts.min_trust_region_radius;
-  c.min_rel_dec = opts.min_relative_decrease;
-  c.prep_fold = step_prep_folds(h) ? 1 : 0;
+  c = lm_start(h, opts);
   HIPCHK(hipMemcpyAsync(h->lm_ctl, &c, sizeof(LmCtl), hipMemcpyHostToDevice, s));
   // 3 iterations first (a keyframe or C3 solve typically ends there), then 2
   // at a time: each gated iteration past the end still costs its launches
@@ -1084,16 +1034,10 @@ int run_device_lm(sfm_ba_handle* h, const sfm_ba_options& opts, double* cost, sf
     timer.mark("batch synchronised");
     collect_marks(h);
     if (c.done) break;
-    if (c.prep_stale) {
-      // paused at an unsuccessful or invalid step (the rest of the batch
-      // returned at once): the next step redoes its prep for the new radius
-      h->prep_fresh = false;
-      c.prep_stale = 0;
-      c.run_step = 1;
-      if (hipMemcpyAsync(h->lm_ctl, &c, sizeof(LmCtl), hipMemcpyHostToDevice, s) != hipSuccess) {
-        rc = fail(SFM_EIO, "LM control upload failed");
-        break;
-      }
+    // (paused: the rest of the batch returned at once)
+    if (lm_rearm(h, &c) && hipMemcpyAsync(h->lm_ctl, &c, sizeof(LmCtl), hipMemcpyHostToDevice, s) != hipSuccess) {
+      rc = fail(SFM_EIO, "LM control upload failed");
+      break;
     }
     batch = batch_next;
   }
@@ -1102,41 +1046,10 @@ int run_device_lm(sfm_ba_handle* h, const sfm_ba_options& opts, double* cost, sf
   h->fuse_lm = false;
   h->accept_fold = false;
   if (rc) return rc;
-  if (c.error & 4) return fail(SFM_EIO, "Cholesky tile hand-off timed out (persistent grid made no progress)");
-  if (c.error & 2) return fail(SFM_EIO, "back-substitution hand-off timed out (persistent grid made no progress)");
-  sm->num_jacobian_evaluations++;  // the initial evaluation
-  sm->num_residual_evaluations++;
-  sm->initial_cost = c.init_cost;
-  if (c.error & 8) {
-    *nonfinite = true;
-    sm->termination_type = SFM_FAILURE;
-    sm->final_cost = c.init_cost;
-    return fail(SFM_EIO, "initial residual evaluation is not finite");
-  }
-  {
-    sfm_ba_iteration it0;
-    std::memset(&it0, 0, sizeof(it0));
-    it0.cost = c.init_cost;
-    it0.gradient_max_norm = c.init_grad;
-    it0.trust_region_radius = opts.initial_trust_region_radius;
-    it0.step_is_valid = 1;
-    it0.step_is_successful = 1;
-    push(it0);
-  }
-  const int n_tr = std::min(c.trace_len, h->lm_trace_cap);
-  // (written to pinned host memory, complete at the last batch's synchronisation)
-  for (int i = 0; i < n_tr; ++i) push(h->lm_trace[i]);
-  h->param_host_valid = h->prefetch_params;
-  sm->termination_type = c.termination;
-  sm->num_iterations = c.iteration;
-  sm->num_successful_steps += c.n_succ;
-  sm->num_unsuccessful_steps += c.n_unsucc;
-  sm->num_invalid_steps += c.n_invalid;
-  sm->num_residual_evaluations += c.n_resid;
-  sm->num_jacobian_evaluations += c.n_jac;
-  sm->num_linear_solves += c.n_lin;
-  *cost = c.cost;
-  return 0;
+  // (the trace is in pinned host memory, complete at the last batch's synchronisation)
+  rc = lm_report(opts, c, h->lm_trace, h->lm_trace_cap, sm, push, nonfinite);
+  if (!rc) h->param_host_valid = h->prefetch_params;
+  return rc;
 }
 
 }  // namespace
@@ -1378,7 +1291,6 @@ int sfm_ba_solve_resident(sfm_ba_handle* h, const sfm_ba_options* opts_in, int32
   h->mode = mode;
   d.min_diag = opts.min_lm_diagonal;
   d.max_diag = opts.max_lm_diagonal;
-  int rc;
   if (!opts.jacobi_scaling) {
     std::vector<double> ones(std::max(6 * size_t(d.C), 3 * size_t(d.P)), 1.0);
     HIPCHK(hipMemcpyAsync(d.scale_c, ones.data(), sizeof(double) * 6 * d.C, hipMemcpyHostToDevice, h->stream));
@@ -1388,159 +1300,16 @@ int sfm_ba_solve_resident(sfm_ba_handle* h, const sfm_ba_options* opts_in, int32
   // Jacobian columns of the constant side vanish and its step is zero
   if (mode == SFM_BA_STRUCT_ONLY && d.C) HIPCHK(hipMemsetAsync(d.scale_c, 0, sizeof(double) * 6 * d.C, h->stream));
   if (mode == SFM_BA_POSE_ONLY && d.P) HIPCHK(hipMemsetAsync(d.scale_p, 0, sizeof(double) * 3 * d.P, h->stream));
-  double* sc = d.scal_host;
-  // (the distributed factor's panel loop runs in the host-driven loop: its
-  // collectives are not gated; at the sizes it is for, a host round trip per
-  // phase is noise)
-  if (!h->host_fn && !h->coll_fn && !(sharded(h) && h->dist_pt > 0) && !env_flag("SFM_HOST_LM")) {
-    // the same loop with its decisions on the device (k_lm_init /
-    // k_lm_decide / k_lm_post): the initial evaluation and the iterations
-    // are enqueued in batches, one host synchronisation per batch instead
-    // of two per iteration.  With an RCCL communicator the all-reduces are
-    // enqueued on the same stream and every rank decides from the same
-    // reduced scalars; only the host-callback collective (tests) needs the
-    // host loop.
-    double cost = 0.0;
-    bool nonfinite = false;
-    rc = run_device_lm(h, opts, &cost, &sm, push, &nonfinite);
-    if (rc) {
-      if (nonfinite && summary) *summary = sm;
-      return rc;
-    }
-    // (per-phase host times stay 0 here: the phases run asynchronously)
-    sm.final_cost = cost;
-    sm.wall_time_s = now_s();
-    if (summary) *summary = sm;
-    return 0;
-  }
-  double tj = now_s();
-  h->eval_radius = opts.initial_trust_region_radius;
-  if ((rc = evaluate(h, true, opts.jacobi_scaling != 0))) return rc;
-  sm.jacobian_time_s += now_s() - tj;
-  sm.num_jacobian_evaluations++;
-  sm.num_residual_evaluations++;
-  double cost = sc[kCost];
-  sm.initial_cost = cost;
-  if (!std::isfinite(cost)) {
-    sm.termination_type = SFM_FAILURE;
-    sm.final_cost = cost;
-    if (summary) *summary = sm;
-    return fail(SFM_EIO, "initial residual evaluation is not finite");
-  }
-  double grad_max = std::max(sc[kGradMaxCam], sc[kGradMaxPt]);
-  double x_norm = std::sqrt(sc[kXNorm2Cam] + sc[kXNorm2Pt]);
-  {
-    sfm_ba_iteration it0;
-    std::memset(&it0, 0, sizeof(it0));
-    it0.cost = cost;
-    it0.gradient_max_norm = grad_max;
-    it0.trust_region_radius = opts.initial_trust_region_radius;
-    it0.step_is_valid = 1;
-    it0.step_is_successful = 1;
-    push(it0);
-  }
-  if (grad_max <= opts.gradient_tolerance) {
-    sm.termination_type = SFM_CONVERGENCE;
-  } else {
-    double radius = opts.initial_trust_region_radius;
-    double decrease_factor = 2.0;
-    int num_consecutive_invalid = 0;
-    int iteration = 0;
-    while (true) {
-      if (iteration >= opts.max_num_iterations) { sm.termination_type = SFM_NO_CONVERGENCE; break; }
-      ++iteration;
-      sfm_ba_iteration itr;
-      std::memset(&itr, 0, sizeof(itr));
-      itr.iteration = iteration;
-      const double tls = now_s();
-      if ((rc = compute_step(h, radius))) return rc;
-      sm.linear_solver_time_s += now_s() - tls;
-      sm.num_linear_solves++;
-      int chol_fail = 0;
-      std::memcpy(&chol_fail, sc + kNumScalars, sizeof(int));
-      // The persistent grids' waits are bounded (roles go by start order, so
-      // a partly resident grid still progresses); a timeout reports here
-      // (INTEGRATION.md §2).
-      if (chol_fail & 4) return fail(SFM_EIO, "Cholesky tile hand-off timed out (persistent grid made no progress)");
-      if (chol_fail & 2) return fail(SFM_EIO, "back-substitution hand-off timed out (persistent grid made no progress)");
-      const bool solve_ok = chol_fail == 0 && !(sc[kBadStep] > 0.0) && !(sc[kBadCam] > 0.0) && !(sc[kBadBack] > 0.0);
-      const double model_cost_change = sc[kModelChange] + sc[kModelChangePt];
-      itr.step_is_valid = (solve_ok && model_cost_change >= 0.0) ? 1 : 0;
-      itr.step_is_successful = 0;
-      if (!itr.step_is_valid) {
-        ++num_consecutive_invalid;
-        sm.num_invalid_steps++;
-        if (num_consecutive_invalid >= opts.max_num_consecutive_invalid_steps) {
-          sm.termination_type = SFM_FAILURE;
-          itr.cost = cost; itr.gradient_max_norm = grad_max; itr.trust_region_radius = radius;
-          push(itr);
-          break;
-        }
-        itr.cost = cost;
-        itr.gradient_max_norm = grad_max;
-      } else {
-        num_consecutive_invalid = 0;
-        double new_cost = sc[kNewCost];
-        if (!std::isfinite(new_cost)) new_cost = std::numeric_limits<double>::max();
-        sm.num_residual_evaluations++;
-        itr.step_norm = std::sqrt(sc[kStep2Cam] + sc[kStep2Pt]);
-        const double step_size_tolerance = opts.parameter_tolerance * (x_norm + opts.parameter_tolerance);
-        if (itr.step_norm <= step_size_tolerance) {
-          sm.termination_type = SFM_CONVERGENCE;
-          itr.cost = cost; itr.gradient_max_norm = grad_max; itr.trust_region_radius = radius;
-          push(itr);
-          break;
-        }
-        itr.cost_change = cost - new_cost;
-        if (std::fabs(itr.cost_change) <= opts.function_tolerance * cost) {
-          sm.termination_type = SFM_CONVERGENCE;
-          itr.cost = cost; itr.gradient_max_norm = grad_max; itr.trust_region_radius = radius;
-          push(itr);
-          break;
-        }
-        itr.relative_decrease = itr.cost_change / model_cost_change;
-        itr.step_is_successful = itr.relative_decrease > opts.min_relative_decrease;
-      }
-      if (itr.step_is_successful) {
-        sm.num_successful_steps++;
-        const double q = 2.0 * itr.relative_decrease - 1.0;  // (2 rho - 1)^3, as k_lm_decide
-        radius = radius / std::max(1.0 / 3.0, 1.0 - q * q * q);
-        radius = std::min(opts.max_trust_region_radius, radius);
-        decrease_factor = 2.0;
-        std::swap(d.cam, d.cam_new);
-        std::swap(d.X, d.X_new);
-        tj = now_s();
-        h->eval_radius = radius;  // the next step's: its preparation rides in the evaluation
-        if ((rc = evaluate(h, false, opts.jacobi_scaling != 0))) return rc;
-        sm.jacobian_time_s += now_s() - tj;
-        sm.num_jacobian_evaluations++;
-        sm.num_residual_evaluations++;
-        cost = sc[kCost];
-        if (!std::isfinite(cost)) { sm.termination_type = SFM_FAILURE; break; }
-        grad_max = std::max(sc[kGradMaxCam], sc[kGradMaxPt]);
-        x_norm = std::sqrt(sc[kXNorm2Cam] + sc[kXNorm2Pt]);
-      } else {
-        sm.num_unsuccessful_steps++;
-        radius = radius / decrease_factor;
-        decrease_factor *= 2.0;
-        h->prep_fresh = false;  // (as k_lm_decide: the next step redoes its prep for the new radius)
-      }
-      itr.gradient_max_norm = grad_max;
-      itr.cost = cost;
-      itr.trust_region_radius = radius;
-      push(itr);
-      if (itr.step_is_successful) {
-        if (grad_max <= opts.gradient_tolerance) { sm.termination_type = SFM_CONVERGENCE; break; }
-      } else {
-        if (radius < opts.min_trust_region_radius) { sm.termination_type = SFM_CONVERGENCE; break; }
-      }
-    }
-    sm.num_iterations = iteration;
-  }
-  sm.final_cost = cost;
-  sm.wall_time_s = now_s();
+  // the loop's decisions on the device unless a collective needs the host
+  // between the phases (the host-callback hook; the distributed factor's
+  // panel loop: at the sizes it is for, a host round trip per phase is noise)
+  const bool host_lm = h->host_fn || h->coll_fn || (sharded(h) && h->dist_pt > 0) || env_flag("SFM_HOST_LM");
+  bool nonfinite = false;
+  const int rc = host_lm ? run_host_lm(h, opts, &sm, push, &nonfinite) : run_device_lm(h, opts, &sm, push, &nonfinite);
+  if (rc && !nonfinite) return rc;
+  if (!rc) sm.wall_time_s = now_s();
   if (summary) *summary = sm;
-  return 0;
+  return rc;
 }
 
 int sfm_ba_solve(const sfm_ba_options* opts, int32_t mode, int64_t n_obs, const double* obs_uv,

@@ -12,6 +12,10 @@
 //     path's degree limit at 64 / 65 observations); and the
 //     plan of set_problem (regimes, parameter routes, the stage's regions)
 //     over a grid of sizes around every threshold, with the Schur shape;
+//   * sfm_amd/csrc/ba_lm.h -- the LM trust-region state machine both loop
+//     drivers run: the oracle's 18 branch traces replayed through it
+//     (tests/golden/lm_replay.txt), and the branches no scene reaches from
+//     literal scalars;
 //   * include/sfm_ctracker_compat.hpp -- the pointer dedup / packing of
 //     bundleAdjustmentStructAndPose (CSfM.cpp:321-341 gather) and its in-place
 //     scatter-back, and the matchFeatures overload, with the C ABI answered by
@@ -35,6 +39,7 @@
 #include "../../include/sfm_amd.h"
 #include "../../include/sfm_ctracker_compat.hpp"
 #include "../../sfm_amd/csrc/ba_host_layout.h"
+#include "../../sfm_amd/csrc/ba_lm.h"
 
 // ---- the oracle's C entry points (oracle/*.cpp, linked in) ----
 extern "C" {
@@ -382,6 +387,274 @@ static void check_plan() {
               sizeof(rows) / sizeof(rows[0]));
 }
 
+// ---- the LM trust-region state machine (sfm_amd/csrc/ba_lm.h) ----
+using sfm::LmCtl;
+
+static LmCtl lm_ctl(int max_iter, int max_invalid, double ftol, double gtol, double ptol, double radius,
+                    double max_radius, double min_radius, double min_rel_dec) {
+  LmCtl c;
+  std::memset(&c, 0, sizeof(c));
+  c.run_step = 1;
+  c.radius = radius;
+  c.decrease_factor = 2.0;
+  c.max_iter = max_iter;
+  c.max_invalid = max_invalid;
+  c.ftol = ftol;
+  c.gtol = gtol;
+  c.ptol = ptol;
+  c.max_radius = max_radius;
+  c.min_radius = min_radius;
+  c.min_rel_dec = min_rel_dec;
+  return c;
+}
+// Ceres 1.12's defaults (sfm_ba_default_options)
+static LmCtl lm_default(int max_iter = 50) { return lm_ctl(max_iter, 5, 1e-6, 1e-10, 1e-8, 1e4, 1e16, 1e-32, 1e-3); }
+
+// a phase's scalar block: the doubles, then the Cholesky flag (an int)
+struct Scal {
+  double v[sfm::kNumScalars + 1];
+  Scal() { std::memset(v, 0, sizeof(v)); }
+  Scal& flag(int f) {
+    std::memcpy(v + sfm::kNumScalars, &f, sizeof(int));
+    return *this;
+  }
+  Scal& set(int k, double x) {
+    v[k] = x;
+    return *this;
+  }
+};
+static Scal eval_scal(double cost, double grad, double xnorm2 = 0.0) {
+  return Scal().set(sfm::kCost, cost).set(sfm::kGradMaxCam, grad).set(sfm::kXNorm2Cam, xnorm2);
+}
+static Scal step_scal(double model_change, double new_cost, double step2) {
+  return Scal().set(sfm::kModelChange, model_change).set(sfm::kNewCost, new_cost).set(sfm::kStep2Pt, step2);
+}
+static bool same_bits(double a, double b) { return std::memcmp(&a, &b, sizeof(double)) == 0; }
+
+// The oracle's traces of every branch case (tests/golden/lm_replay.txt, from
+// lm_branches.json by make_lm_replay.py) replayed through lm_init / lm_decide
+// / lm_post: each phase's scalars are rebuilt from the record the phase led
+// to, and the state machine must write the oracle's records and counters.
+static void check_lm_replay() {
+  std::FILE* f = std::fopen("../golden/lm_replay.txt", "r");
+  CHECK(f != nullptr);
+  int n_cases = 0;
+  CHECK(std::fscanf(f, "%d", &n_cases) == 1);
+  CHECK(n_cases == 18);
+  double worst_radius = 0.0;
+  for (int k = 0; k < n_cases; ++k) {
+    char name[64];
+    int n = 0, max_iter = 0, max_invalid = 0, sm[8];
+    double o[7];
+    CHECK(std::fscanf(f, " case %63s %d", name, &n) == 2 && n >= 1);
+    CHECK(std::fscanf(f, "%d %d %lf %lf %lf %lf %lf %lf %lf", &max_iter, &max_invalid, &o[0], &o[1], &o[2], &o[3], &o[4],
+                      &o[5], &o[6]) == 9);
+    for (int& s : sm) CHECK(std::fscanf(f, "%d", &s) == 1);
+    std::vector<sfm_ba_iteration> rec(static_cast<size_t>(n));
+    for (auto& r : rec) {
+      r.reserved = 0;
+      CHECK(std::fscanf(f, "%d %d %d %lf %lf %lf %lf %lf %lf", &r.iteration, &r.step_is_valid, &r.step_is_successful,
+                        &r.cost, &r.cost_change, &r.gradient_max_norm, &r.step_norm, &r.relative_decrease,
+                        &r.trust_region_radius) == 9);
+    }
+    const double ptol = o[2];
+    LmCtl c = lm_ctl(max_iter, max_invalid, o[0], o[1], ptol, o[3], o[4], o[5], o[6]);
+    // |x| is not in the trace: 0, except at the evaluation before a final
+    // record that stopped at the parameter tolerance, where |x| makes that
+    // record's step the tolerance
+    const sfm_ba_iteration& fin = rec.back();
+    const bool ptol_stop = n > 1 && fin.step_is_valid && !fin.step_is_successful && fin.cost_change == 0.0 && fin.step_norm > 0.0;
+    int last_eval = 0;
+    for (int i = 0; i < n - 1; ++i)
+      if (rec[size_t(i)].step_is_successful) last_eval = i;
+    auto xnorm2 = [&](int i) {
+      const double q = fin.step_norm / ptol;
+      return ptol_stop && i == last_eval ? q * q : 0.0;
+    };
+    std::vector<sfm_ba_iteration> out(size_t(std::max(1, max_iter + 1)));
+    const int cap = int(out.size());
+    lm_init(&c, eval_scal(rec[0].cost, rec[0].gradient_max_norm, xnorm2(0)).v);
+    CHECK(same_bits(c.init_cost, rec[0].cost) && same_bits(c.init_grad, rec[0].gradient_max_norm));
+    CHECK(same_bits(c.radius, rec[0].trust_region_radius));
+    for (int i = 1; i < n; ++i) {
+      CHECK(!c.done);
+      const sfm_ba_iteration& r = rec[size_t(i)];
+      Scal s = step_scal(r.relative_decrease != 0.0 ? r.cost_change / r.relative_decrease : 1.0, c.cost - r.cost_change,
+                         r.step_norm * r.step_norm);
+      if (!r.step_is_valid) s.flag(1);
+      lm_decide(&c, s.v, out.data(), cap);
+      CHECK(c.run_eval == r.step_is_successful);
+      if (c.run_eval) lm_post(&c, eval_scal(r.cost, r.gradient_max_norm, xnorm2(i)).v, out.data(), cap);
+    }
+    CHECK(c.done && c.error == 0);
+    CHECK(c.trace_len == n - 1);
+    for (int i = 1; i < n; ++i) {
+      const sfm_ba_iteration &a = out[size_t(i - 1)], &b = rec[size_t(i)];
+      CHECK(a.iteration == b.iteration && a.step_is_valid == b.step_is_valid && a.step_is_successful == b.step_is_successful);
+      CHECK(same_bits(a.cost, b.cost) && same_bits(a.cost_change, b.cost_change));
+      CHECK(same_bits(a.gradient_max_norm, b.gradient_max_norm) && same_bits(a.step_norm, b.step_norm));
+      CHECK(same_bits(a.relative_decrease, b.relative_decrease));
+      // (the model change is a quotient of the record's rounded numbers, so rho is the fixture's only to rounding)
+      const double d = std::fabs(a.trust_region_radius - b.trust_region_radius) / b.trust_region_radius;
+      worst_radius = std::max(worst_radius, d);
+      CHECK(d <= 1e-15);
+    }
+    // the summary the drivers make of the state (+ the initial evaluation)
+    const int got[8] = {c.termination, c.iteration, c.n_succ, c.n_unsucc, c.n_invalid, 1 + c.n_resid, 1 + c.n_jac, c.n_lin};
+    for (int j = 0; j < 8; ++j) CHECK(got[j] == sm[j]);
+  }
+  std::fclose(f);
+  std::printf("  replay: %d oracle traces reproduced (largest radius difference %.1e relative)\n", n_cases, worst_radius);
+}
+
+// The branches the scenes cannot reach, from literal scalars; the expected
+// values follow from Ceres 1.12's rules and default options (radius 1e4,
+// halved then quartered ... on rejection; radius / max(1/3, 1 - (2 rho - 1)^3)
+// on acceptance; 5 consecutive invalid steps fail).
+static void check_lm_branches() {
+  sfm_ba_iteration tr[8];
+  auto started = [&](int max_iter = 50) {
+    LmCtl c = lm_default(max_iter);
+    lm_init(&c, eval_scal(100.0, 5.0).v);
+    CHECK(!c.done && c.run_step == 1 && c.cost == 100.0 && c.grad_max == 5.0 && c.x_norm == 0.0 && c.trace_len == 0);
+    return c;
+  };
+  const Scal accept = step_scal(50.0, 50.0, 1.0);   // rho = (100 - 50) / 50 = 1
+  const Scal reject = step_scal(50.0, 150.0, 1.0);  // rho = -1
+  const double grown = 1e4 / (1.0 / 3.0);           // rho = 1: 1 - (2 rho - 1)^3 = 0 < 1/3
+  // hand-off timeouts (bits 2 and 4 of the Cholesky flag): recorded, FAILURE, no record
+  for (int bits : {2, 4, 6}) {
+    LmCtl c = started();
+    lm_decide(&c, Scal(accept).flag(bits).v, tr, 8);
+    CHECK(c.error == bits && c.done && c.termination == SFM_FAILURE && c.trace_len == 0);
+    CHECK(c.run_step == 0 && c.run_eval == 0 && c.iteration == 1 && c.n_lin == 1 && c.n_invalid == 0);
+  }
+  // a non-finite candidate cost counts as DBL_MAX: a valid step, rejected
+  for (double bad : {double(NAN), double(INFINITY), -double(INFINITY)}) {
+    LmCtl c = started();
+    lm_decide(&c, step_scal(50.0, bad, 1.0).v, tr, 8);
+    CHECK(!c.done && c.run_eval == 0 && c.run_step == 1 && c.trace_len == 1 && c.n_resid == 1 && c.n_unsucc == 1);
+    CHECK(tr[0].step_is_valid == 1 && tr[0].step_is_successful == 0 && tr[0].cost_change == 100.0 - DBL_MAX);
+    CHECK(tr[0].relative_decrease == (100.0 - DBL_MAX) / 50.0 && tr[0].cost == 100.0 && tr[0].step_norm == 1.0);
+    CHECK(tr[0].trust_region_radius == 5e3 && c.radius == 5e3 && c.decrease_factor == 4.0);
+  }
+  // an accepted step, its record completed by the evaluation ...
+  {
+    LmCtl c = started();
+    lm_decide(&c, accept.v, tr, 8);
+    CHECK(!c.done && c.run_eval == 1 && c.run_step == 1 && c.prep_stale == 0 && c.trace_len == 0 && c.n_succ == 1);
+    CHECK(c.radius == grown && c.decrease_factor == 2.0);
+    lm_post(&c, eval_scal(50.0, 4.0, 9.0).v, tr, 8);
+    CHECK(!c.done && c.run_eval == 0 && c.trace_len == 1 && c.n_jac == 1 && c.n_resid == 2 && c.x_norm == 3.0);
+    CHECK(tr[0].iteration == 1 && tr[0].step_is_valid == 1 && tr[0].step_is_successful == 1 && tr[0].cost == 50.0);
+    CHECK(tr[0].cost_change == 50.0 && tr[0].relative_decrease == 1.0 && tr[0].gradient_max_norm == 4.0);
+    CHECK(tr[0].trust_region_radius == grown);
+    // ... and lm_post without an accepted step in flight is a no-op
+    const LmCtl before = c;
+    lm_post(&c, eval_scal(1.0, 1.0).v, tr, 8);
+    CHECK(std::memcmp(&c, &before, sizeof(c)) == 0);
+  }
+  // a non-finite cost after an accepted step: FAILURE, no record
+  {
+    LmCtl c = started();
+    lm_decide(&c, accept.v, tr, 8);
+    lm_post(&c, eval_scal(NAN, 4.0).v, tr, 8);
+    CHECK(c.done && c.termination == SFM_FAILURE && c.error == 0 && c.trace_len == 0 && c.n_jac == 1 && c.n_resid == 2);
+    CHECK(std::isnan(c.cost) && c.iteration == 1);
+  }
+  // a non-finite initial cost: error bit 8
+  {
+    LmCtl c = lm_default();
+    lm_init(&c, eval_scal(INFINITY, 5.0).v);
+    CHECK(c.done && c.error == 8 && c.termination == SFM_FAILURE && c.init_cost == INFINITY && c.run_step == 0);
+  }
+  // no iterations allowed; a gradient tolerance met at once comes first
+  {
+    LmCtl c = lm_default(0);
+    lm_init(&c, eval_scal(100.0, 5.0).v);
+    CHECK(c.done && c.termination == SFM_NO_CONVERGENCE && c.iteration == 0 && c.error == 0 && c.n_lin == 0);
+    c = lm_default(0);
+    lm_init(&c, eval_scal(100.0, 1e-10).v);
+    CHECK(c.done && c.termination == SFM_CONVERGENCE && c.iteration == 0);
+  }
+  // the iteration cap reached by an accepted step (after its evaluation) and by a rejected one
+  {
+    LmCtl c = started(1);
+    lm_decide(&c, accept.v, tr, 8);
+    CHECK(!c.done && c.run_eval == 1);
+    lm_post(&c, eval_scal(50.0, 4.0).v, tr, 8);
+    CHECK(c.done && c.termination == SFM_NO_CONVERGENCE && c.trace_len == 1 && c.iteration == 1 && c.cost == 50.0);
+    c = started(1);
+    lm_decide(&c, reject.v, tr, 8);
+    CHECK(c.done && c.termination == SFM_NO_CONVERGENCE && c.trace_len == 1 && c.iteration == 1 && c.run_eval == 0);
+    CHECK(tr[0].step_is_successful == 0 && tr[0].relative_decrease == -1.0 && tr[0].trust_region_radius == 5e3);
+  }
+  // the radius clamp
+  {
+    LmCtl c = lm_ctl(50, 5, 1e-6, 1e-10, 1e-8, 1e4, 2e4, 1e-32, 1e-3);
+    lm_init(&c, eval_scal(100.0, 5.0).v);
+    lm_decide(&c, accept.v, tr, 8);
+    CHECK(c.radius == 2e4 && grown > 2e4);
+  }
+  // invalid steps: a negative model change, a failed Cholesky, each bad-step
+  // flag; the fifth in a row fails, its record with the radius unchanged
+  {
+    const Scal invalid[5] = {step_scal(-1.0, 50.0, 1.0), Scal(accept).flag(1), Scal(accept).set(sfm::kBadStep, 1.0),
+                             Scal(accept).set(sfm::kBadCam, 1.0), Scal(accept).set(sfm::kBadBack, 1.0)};
+    for (const Scal& s : invalid) {
+      LmCtl c = started();
+      lm_decide(&c, s.v, tr, 8);
+      CHECK(!c.done && c.run_eval == 0 && c.n_invalid == 1 && c.num_consecutive_invalid == 1 && c.n_unsucc == 1);
+      CHECK(c.n_resid == 0 && c.trace_len == 1 && tr[0].step_is_valid == 0 && tr[0].step_is_successful == 0);
+      CHECK(tr[0].cost == 100.0 && tr[0].cost_change == 0.0 && tr[0].step_norm == 0.0 && tr[0].trust_region_radius == 5e3);
+      lm_decide(&c, accept.v, tr, 8);  // a valid step resets the run
+      CHECK(c.num_consecutive_invalid == 0 && c.run_eval == 1);
+    }
+    LmCtl c = started();
+    for (const Scal& s : invalid) lm_decide(&c, s.v, tr, 8);
+    CHECK(c.done && c.termination == SFM_FAILURE && c.n_invalid == 5 && c.n_unsucc == 4 && c.trace_len == 5);
+    CHECK(c.radius == 1e4 / 2 / 4 / 8 / 16 && tr[4].trust_region_radius == c.radius && tr[3].trust_region_radius == c.radius);
+  }
+  // the evaluation prepares the step (prep_fold): a rejected or invalid step
+  // pauses the loop for the driver to re-arm, an accepted one does not; a call
+  // while paused, or done, only clears run_eval
+  for (const Scal& s : {reject, step_scal(-1.0, 50.0, 1.0)}) {
+    LmCtl c = started();
+    c.prep_fold = 1;
+    lm_decide(&c, s.v, tr, 8);
+    CHECK(!c.done && c.run_step == 0 && c.prep_stale == 1 && c.run_eval == 0 && c.trace_len == 1);
+    LmCtl paused = c;
+    c.run_eval = 1;
+    lm_decide(&c, accept.v, tr, 8);
+    CHECK(std::memcmp(&c, &paused, sizeof(c)) == 0);
+  }
+  {
+    LmCtl c = started();
+    c.prep_fold = 1;
+    lm_decide(&c, accept.v, tr, 8);
+    CHECK(c.run_step == 1 && c.prep_stale == 0 && c.run_eval == 1);
+    c = started(1);
+    c.prep_fold = 1;
+    lm_decide(&c, reject.v, tr, 8);  // the last iteration: done, not paused
+    CHECK(c.done && c.prep_stale == 0 && c.run_step == 0);
+    LmCtl done = c;
+    c.run_eval = 1;
+    lm_decide(&c, accept.v, tr, 8);
+    CHECK(std::memcmp(&c, &done, sizeof(c)) == 0);
+  }
+  // a trace of one record: the count goes on, the writes do not
+  {
+    std::vector<sfm_ba_iteration> one(1);
+    LmCtl c = started();
+    lm_decide(&c, reject.v, one.data(), 1);
+    lm_decide(&c, reject.v, one.data(), 1);
+    lm_decide(&c, accept.v, one.data(), 1);
+    lm_post(&c, eval_scal(50.0, 4.0).v, one.data(), 1);
+    CHECK(c.trace_len == 3 && one[0].iteration == 1 && one[0].trust_region_radius == 5e3 && c.iteration == 3);
+  }
+  std::printf("  branches: timeouts, non-finite costs, iteration cap, clamp, invalid steps, pause, trace cap ok\n");
+}
+
 struct Pt2 {
   double x, y;
 };
@@ -501,6 +774,10 @@ int main() {
 
   std::printf("asan: set_problem's host plan (ba_host_layout.h)\n");
   check_plan();
+
+  std::printf("asan: LM trust-region state machine (ba_lm.h)\n");
+  check_lm_replay();
+  check_lm_branches();
 
   std::printf("asan: compat header over the oracle (gather, solve, scatter-back)\n");
   for (int mode = 0; mode < 3; ++mode) {

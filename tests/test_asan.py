@@ -1,8 +1,12 @@
 """Host sanitizer run (CPU, no GPU): tests/asan/Makefile builds the drop-in's
 host layout code (sfm_amd/csrc/ba_host_layout.h, what sfm_ba_set_problem runs
-on the host), the compat header's gather / scatter-back and the oracle under
-AddressSanitizer + UBSan and runs them on the C1, shuffled-duplicate,
-empty-camera, bad-index and empty scenes."""
+on the host), the LM trust-region state machine both loop drivers run
+(sfm_amd/csrc/ba_lm.h), the compat header's gather / scatter-back and the
+oracle under AddressSanitizer + UBSan and runs them on the C1,
+shuffled-duplicate, empty-camera, bad-index and empty scenes (VERDICT r5 item
+8); the state machine replays the oracle's 18 branch traces
+(tests/golden/lm_replay.txt) and takes the branches no scene reaches from
+literal scalars."""
 import os
 import shutil
 import subprocess

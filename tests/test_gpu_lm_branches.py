@@ -187,7 +187,10 @@ def test_evaluate_after_solve_reports_the_current_cost():
 def test_device_loop_equals_host_loop(name, monkeypatch):
     """The device-driven LM loop (k_lm_decide / k_lm_post, iterations
     enqueued in batches) against the host-driven loop (SFM_HOST_LM=1) on
-    every branch scene: the same trace and bitwise the same parameters."""
+    every branch scene: the same trace and bitwise the same parameters.
+    Both drivers run the one state machine of sfm_amd/csrc/ba_lm.h, so this
+    guards what differs between them: the gates, the accept copy against the
+    pointer swap, the batches."""
     c = FIX[name]
     build, _, mode = L.cases()[name]
     s = build()
