@@ -156,6 +156,15 @@ struct DevProblem {
   // point-major uv and camera index (k_point_eval_rc)
   double* uv_pm = nullptr;     // [N][2]
   int32_t* cam_pm = nullptr;   // [N]
+  // the same stream wave-major, for the lane-per-point passes (k_point_eval_*,
+  // k_backsub_pm): wave w = points 64 w .. 64 w + 63 holds m_w = its largest
+  // view count slots, slot k of lane l at (woff[w] + k) * 64 + l, so a wave's
+  // loads of one step are lane-contiguous.  nullptr (the passes read uv_pm /
+  // cam_pm): no points or observations, the keyframe-sized small setup path,
+  // padding above the cap (hostlayout::wave_major_fits), or SFM_PM_WAVE_MAJOR=0
+  int32_t* woff = nullptr;     // [ceil(P / 64) + 1] exclusive sum of m_w
+  double* uv_wm = nullptr;     // [64 woff[last]][2]
+  int32_t* cam_wm = nullptr;   // [64 woff[last]] past a point's count: its last camera (0: none)
   // reductions
   double* partials = nullptr; // scratch [kNumPartialSlots][max_blocks]
   int32_t max_blocks = 0;

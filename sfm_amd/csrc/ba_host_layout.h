@@ -156,6 +156,15 @@ inline bool small_setup_fits(int64_t N, int C, int P, const int32_t* n_obs_of_ca
   return true;
 }
 
+// The wave-major copy of the point-major stream (DevProblem::uv_wm): wave w
+// of 64 consecutive points takes as many 64-lane slots as its longest point
+// has observations.  The copy is made only while its padded size 64 * slots
+// stays within 1.5 N + 64 ceil(P / 64) entries (regular visibility: exactly
+// N; one long track among short ones pads its whole wave).
+inline bool wave_major_fits(int64_t slots, int64_t N, int P) {
+  return 128 * slots <= 3 * N + 128 * ((int64_t(P) + 63) / 64);
+}
+
 // The Schur pass's shape from the mean pair count per camera block.  Lanes
 // per block ~ a tenth of the mean, 8..64 (measured best: C3, 72 pairs per
 // block -> 8; C1 / C2, ~460 -> 64; SFM_SCHUR_PTS_SUB forces 8 / 16 / 32 / 64).

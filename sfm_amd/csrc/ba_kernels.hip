@@ -452,9 +452,24 @@ struct PointFold {
   double* part_bad;
 };
 
-__device__ __forceinline__ void point_eval_body(int p, const int32_t* __restrict__ pt_off,
-                                                const int32_t* __restrict__ cam_pm,
-                                                const double* __restrict__ uv_pm, const CamView cv,
+// The point-major observation stream a lane-per-point pass walks: lane p's
+// observation k (its cnt = pt_off[p + 1] - pt_off[p] observations in
+// point-major order) at q0 + k * stride of cam / uv.  Point-major arrays
+// (cam_pm / uv_pm): q0 = pt_off[p], stride 1 -- a wave's 64 loads touch up to
+// 64 lines.  Wave-major copy (woff != nullptr; cam_wm / uv_wm, set_problem):
+// q0 = woff[p / 64] * 64 + p % 64, stride 64 -- the wave's loads of one step
+// are lane-contiguous.  The same values in the same order either way.
+struct PmStream {
+  const int32_t* pt_off; const int32_t* cam; const double* uv; const int32_t* woff;
+};
+__device__ __forceinline__ void pm_lane(const PmStream& ps, int p, size_t& q0, int& stride, int& cnt) {
+  const int a = ps.pt_off[p];
+  cnt = ps.pt_off[p + 1] - a;
+  q0 = ps.woff ? size_t(ps.woff[p >> 6]) * 64 + size_t(p & 63) : size_t(a);
+  stride = ps.woff ? 64 : 1;
+}
+
+__device__ __forceinline__ void point_eval_body(int p, const PmStream& ps, const CamView cv,
                                                 const double* __restrict__ X, double* __restrict__ scale_p,
                                                 double* __restrict__ diag_p, double* __restrict__ ptV,
                                                 double min_diag, double max_diag, int mode, int reuse, double& g,
@@ -464,16 +479,19 @@ __device__ __forceinline__ void point_eval_body(int p, const int32_t* __restrict
   double sp[3] = {1.0, 1.0, 1.0};
   if (mode == 1)
     for (int k = 0; k < 3; ++k) sp[k] = scale_p[3 * size_t(p) + k];
-  const int q0 = pt_off[p], q1 = pt_off[p + 1];
+  size_t q;
+  int qs, cnt;
+  pm_lane(ps, p, q, qs, cnt);
   // the next observation's camera index and uv are loaded one step ahead
-  int c_n = q0 < q1 ? cam_pm[q0] : 0;
-  double2 uv_n = q0 < q1 ? ld2(uv_pm + 2 * size_t(q0)) : make_double2(0.0, 0.0);
-  for (int q = q0; q < q1; ++q) {
+  int c_n = cnt > 0 ? ps.cam[q] : 0;
+  double2 uv_n = cnt > 0 ? ld2(ps.uv + 2 * q) : make_double2(0.0, 0.0);
+  for (int k = 0; k < cnt; ++k) {
     const int c = c_n;
     const double2 uvo = uv_n;
-    if (q + 1 < q1) {
-      c_n = cam_pm[q + 1];
-      uv_n = ld2(uv_pm + 2 * size_t(q + 1));
+    if (k + 1 < cnt) {
+      q += size_t(qs);
+      c_n = ps.cam[q];
+      uv_n = ld2(ps.uv + 2 * q);
     }
     const double* cr = cv.R + size_t(cv.sR) * c;
     const double* k5 = cv.K + size_t(cv.sK) * c;
@@ -525,9 +543,7 @@ __device__ __forceinline__ void point_eval_body(int p, const int32_t* __restrict
   }
 }
 
-__global__ __launch_bounds__(kThreads) void k_point_eval_rc(int P, const int32_t* __restrict__ pt_off,
-                                                            const int32_t* __restrict__ cam_pm,
-                                                            const double* __restrict__ uv_pm,
+__global__ __launch_bounds__(kThreads) void k_point_eval_rc(int P, const PmStream ps,
                                                             const double* __restrict__ camR,
                                                             const double* __restrict__ cam,
                                                             const double* __restrict__ Kc,
@@ -543,8 +559,7 @@ __global__ __launch_bounds__(kThreads) void k_point_eval_rc(int P, const int32_t
   double g = 0.0, xn = 0.0, bad = 0.0;
   const CamView cv{camR, cam + 3, Kc, kCamR, 6, 5};
   if (p < P)
-    point_eval_body(p, pt_off, cam_pm, uv_pm, cv, X, scale_p, diag_p, ptV, min_diag, max_diag, mode, reuse, g, xn, pf,
-                    bad);
+    point_eval_body(p, ps, cv, X, scale_p, diag_p, ptV, min_diag, max_diag, mode, reuse, g, xn, pf, bad);
   if (mode == 1) {
     const double rg = block_reduce(g, sh, true);
     if (threadIdx.x == 0) part_grad[blockIdx.x] = rg;
@@ -571,9 +586,7 @@ __global__ __launch_bounds__(kThreads) void k_point_eval_rc(int P, const int32_t
 // order), i.e. twice the waves per LDS copy and half the copies.
 constexpr int kCamE = 17;
 template <int kMaxC, int kGroups = 1>
-__global__ __launch_bounds__(kThreads * kGroups) void k_point_eval_lds(int P, int C, const int32_t* __restrict__ pt_off,
-                                                             const int32_t* __restrict__ cam_pm,
-                                                             const double* __restrict__ uv_pm,
+__global__ __launch_bounds__(kThreads * kGroups) void k_point_eval_lds(int P, int C, const PmStream ps,
                                                              const double* __restrict__ camR,
                                                              const double* __restrict__ cam,
                                                              const double* __restrict__ Kc,
@@ -604,8 +617,7 @@ __global__ __launch_bounds__(kThreads * kGroups) void k_point_eval_lds(int P, in
   double g = 0.0, xn = 0.0, bad = 0.0;
   const CamView cv{cst, cst + 9, cst + 12, kCamE, kCamE, kCamE};
   if (p < P)
-    point_eval_body(p, pt_off, cam_pm, uv_pm, cv, X, scale_p, diag_p, ptV, min_diag, max_diag, mode, reuse, g, xn, pf,
-                    bad);
+    point_eval_body(p, ps, cv, X, scale_p, diag_p, ptV, min_diag, max_diag, mode, reuse, g, xn, pf, bad);
   if (mode == 1) {
     // block_reduce per group: its four waves' values combined in wave order
     // (the factor's flag rides with the gradient norm: a max of 0 / 1 flags)
@@ -2029,8 +2041,7 @@ __device__ __forceinline__ void cam_step_record(int c, const CamStepFold& cu, do
 // block blockIdx.x * kGroups + g and reduces its own four waves in order.
 template <int kGroups>
 __global__ __launch_bounds__(kThreads * kGroups) void k_backsub_pm(
-    int P, int C, const int32_t* __restrict__ pt_off, const int32_t* __restrict__ cam_pm,
-    const double* __restrict__ uv_pm, const double* __restrict__ ptL,
+    int P, int C, const PmStream ps, const double* __restrict__ ptL,
     const double* __restrict__ ptV, const double* __restrict__ scale_p, const double* __restrict__ X,
     double* __restrict__ X_new, double* __restrict__ ypt, double* __restrict__ part_model,
     double* __restrict__ part_model_pt, double* __restrict__ part_step, double* __restrict__ part_bad,
@@ -2078,17 +2089,21 @@ __global__ __launch_bounds__(kThreads * kGroups) void k_backsub_pm(
   if (p < P) {
     const double Xp[3] = {X[3 * size_t(p)], X[3 * size_t(p) + 1], X[3 * size_t(p) + 2]};
     const double sp[3] = {scale_p[3 * size_t(p)], scale_p[3 * size_t(p) + 1], scale_p[3 * size_t(p) + 2]};
-    const int q0 = pt_off[p], q1 = pt_off[p + 1];
+    size_t q0, q;
+    int qs, cnt;
+    pm_lane(ps, p, q0, qs, cnt);
+    q = q0;
     // the next observation's camera index and uv are loaded one step ahead
-    int c_n = q0 < q1 ? cam_pm[q0] : 0;
-    double2 uv_n = q0 < q1 ? ld2(uv_pm + 2 * size_t(q0)) : make_double2(0.0, 0.0);
+    int c_n = cnt > 0 ? ps.cam[q] : 0;
+    double2 uv_n = cnt > 0 ? ld2(ps.uv + 2 * q) : make_double2(0.0, 0.0);
     double h0 = 0.0, h1 = 0.0, h2 = 0.0;  // sum J_X^T e
-    for (int q = q0; q < q1; ++q) {
+    for (int i = 0; i < cnt; ++i) {
       const double* k = cst + kCamPM * c_n;
       const double2 uvo = uv_n;
-      if (q + 1 < q1) {
-        c_n = cam_pm[q + 1];
-        uv_n = ld2(uv_pm + 2 * size_t(q + 1));
+      if (i + 1 < cnt) {
+        q += size_t(qs);
+        c_n = ps.cam[q];
+        uv_n = ld2(ps.uv + 2 * q);
       }
       const double y0 = k[0] * Xp[0] + k[1] * Xp[1] + k[2] * Xp[2];
       const double y1 = k[3] * Xp[0] + k[4] * Xp[1] + k[5] * Xp[2];
@@ -2139,14 +2154,16 @@ __global__ __launch_bounds__(kThreads * kGroups) void k_backsub_pm(
       ypt[3 * size_t(p) + j] = ys[j];
     }
     // candidate residual at (R_new, t_new, X_new): the same observations again
-    c_n = q0 < q1 ? cam_pm[q0] : 0;
-    uv_n = q0 < q1 ? ld2(uv_pm + 2 * size_t(q0)) : make_double2(0.0, 0.0);
-    for (int q = q0; q < q1; ++q) {
+    q = q0;
+    c_n = cnt > 0 ? ps.cam[q] : 0;
+    uv_n = cnt > 0 ? ld2(ps.uv + 2 * q) : make_double2(0.0, 0.0);
+    for (int i = 0; i < cnt; ++i) {
       const double* k = cst + kCamPM * c_n;
       const double2 uvo = uv_n;
-      if (q + 1 < q1) {
-        c_n = cam_pm[q + 1];
-        uv_n = ld2(uv_pm + 2 * size_t(q + 1));
+      if (i + 1 < cnt) {
+        q += size_t(qs);
+        c_n = ps.cam[q];
+        uv_n = ld2(ps.uv + 2 * q);
       }
       const double* Rn = k + 23;
       double pc[3];
@@ -2236,6 +2253,10 @@ void launch_jacobian(const DevProblem& d, bool scaled, hipStream_t s, bool write
 void launch_cam_reduce(const DevProblem& d, hipStream_t s) {
   if (d.C) k_cam_sum<<<d.C, 64, 0, s>>>(d.cam_rng, d.jpart, d.Ucam, d.gate);
 }
+// the wave-major copy where set_problem made one, else the point-major arrays
+static PmStream pm_stream(const DevProblem& d) {
+  return d.uv_wm ? PmStream{d.pt_off, d.cam_wm, d.uv_wm, d.woff} : PmStream{d.pt_off, d.cam_pm, d.uv_pm, nullptr};
+}
 static CamFold cam_fold(const DevProblem& d, int mode, bool count_grad) {
   return CamFold{d.cam_rng, d.jpart, d.Ucam, d.scale_c, d.diag_c, d.min_diag, d.max_diag, mode, d.C,
                  count_grad ? slot(d, kPGradCam) : nullptr};
@@ -2246,7 +2267,7 @@ void launch_cam_sum_finalize(const DevProblem& d, int mode, bool count_grad, hip
 bool launch_point_eval_with_cams(const DevProblem& d, int mode, bool count_grad, hipStream_t s) {
   if (d.P == 0 || d.C == 0 || d.C > 64) return false;
   const int nb = blocks_for(d.P, kThreads) + (d.C + kThreads / 64 - 1) / (kThreads / 64);
-  k_point_eval_lds<64><<<nb, kThreads, 0, s>>>(d.P, d.C, d.pt_off, d.cam_pm, d.uv_pm, d.camR, d.cam, d.Kc, d.X,
+  k_point_eval_lds<64><<<nb, kThreads, 0, s>>>(d.P, d.C, pm_stream(d), d.camR, d.cam, d.Kc, d.X,
                                                d.scale_p, d.diag_p, d.ptV, d.min_diag, d.max_diag, mode, 0,
                                                slot(d, kPGradPt), slot(d, kPXNormPt), d.gate,
                                                cam_fold(d, mode, count_grad), PointFold{});
@@ -2270,18 +2291,18 @@ void launch_point_eval(const DevProblem& d, int mode, bool reuse_diag, hipStream
                                            : PointFold{};
   // camera constants from LDS while they fit (C3: 500 cameras, 68 KB)
 #define SFM_PE_LDS(M_)                                                                                              \
-  k_point_eval_lds<M_><<<nb, kThreads, 0, s>>>(d.P, d.C, d.pt_off, d.cam_pm, d.uv_pm, d.camR, d.cam, d.Kc, d.X,      \
+  k_point_eval_lds<M_><<<nb, kThreads, 0, s>>>(d.P, d.C, pm_stream(d), d.camR, d.cam, d.Kc, d.X,      \
                                                d.scale_p, d.diag_p, d.ptV, d.min_diag, d.max_diag, mode,           \
                                                reuse_diag ? 1 : 0, slot(d, kPGradPt), slot(d, kPXNormPt), d.gate,    \
                                                CamFold{}, pf)
   if (d.C <= 64) SFM_PE_LDS(64);
   else if (d.C <= 512 && !env_flag_k("SFM_PE_GROUPS1"))
     k_point_eval_lds<512, 2><<<blocks_for(d.P, 2 * kThreads), 2 * kThreads, 0, s>>>(
-        d.P, d.C, d.pt_off, d.cam_pm, d.uv_pm, d.camR, d.cam, d.Kc, d.X, d.scale_p, d.diag_p, d.ptV, d.min_diag,
+        d.P, d.C, pm_stream(d), d.camR, d.cam, d.Kc, d.X, d.scale_p, d.diag_p, d.ptV, d.min_diag,
         d.max_diag, mode, reuse_diag ? 1 : 0, slot(d, kPGradPt), slot(d, kPXNormPt), d.gate, CamFold{}, pf);
   else if (d.C <= 512) SFM_PE_LDS(512);
   else
-    k_point_eval_rc<<<nb, kThreads, 0, s>>>(d.P, d.pt_off, d.cam_pm, d.uv_pm, d.camR, d.cam, d.Kc, d.X, d.scale_p,
+    k_point_eval_rc<<<nb, kThreads, 0, s>>>(d.P, pm_stream(d), d.camR, d.cam, d.Kc, d.X, d.scale_p,
                                             d.diag_p, d.ptV, d.min_diag, d.max_diag, mode, reuse_diag ? 1 : 0,
                                             slot(d, kPGradPt), slot(d, kPXNormPt), d.gate, pf);
 #undef SFM_PE_LDS
@@ -2412,7 +2433,7 @@ void launch_point_backsub(const DevProblem& d, hipStream_t s, bool cams_var, boo
   if (backsub_pm(d, cams_var, pts_var)) {  // one point-major pass, the camera step included
     constexpr int kG = 4;  // one 1024-thread workgroup per CU (its LDS copy is up to 148 KB)
     k_backsub_pm<kG><<<blocks_for(d.P, kG * kThreads), kG * kThreads, 0, s>>>(
-        d.P, d.C, d.pt_off, d.cam_pm, d.uv_pm, d.ptL, d.ptV, d.scale_p, d.X, d.X_new, d.ypt,
+        d.P, d.C, pm_stream(d), d.ptL, d.ptV, d.scale_p, d.X, d.X_new, d.ypt,
         slot(d, kPModel), slot(d, kPModelPt), slot(d, kPStepPt), slot(d, kPBadBack), slot(d, kPNewCost), d.gate,
         CamStepFold{d.cam, d.ysol, d.scale_c, d.camR, d.Kc, d.cam_new, d.camRn,
                     count_norm ? slot(d, kPStepCam) : nullptr, slot(d, kPBadCam)});

@@ -73,6 +73,11 @@ struct Setup {
   const int32_t* pair_order = nullptr;  // the Schur pair lists' emission order (nullptr: point-major)
   int64_t n_pairs = 0;                  // the pair buffer's size: the device's count, or the small path's bound
   int bperm_per = 0;                    // > 0: the XCD block order's group sizes come back with the last synchronisation
+  // the wave-major copy of the point-major stream (DevProblem::uv_wm): wanted
+  // until its slot total, back with the pair total's round trip, is above the cap
+  bool wm = false;
+  int64_t wm_slots = 0;
+  int32_t* wm_cnt = nullptr;
   // the pinned mirror's 17-slot tail: the k_schur_pts group sizes (16), then
   // the deferred uv's finite check (slot 16)
   int64_t* grp_host = nullptr;
@@ -101,6 +106,9 @@ struct Setup {
   template <typename T>
   bool tmp(T*& p, size_t count) { return (rc = dalloc_tmp(h, &p, count)) == 0; }  // back to the pool at the end
 };
+
+// waves of 64 points (the wave-major stream's woff has one more entry)
+size_t wm_waves(int P) { return (size_t(P) + 63) / 64; }
 
 // Any failure returns through here: the buffers go back to the pool.
 struct ProblemGuard {
@@ -322,6 +330,13 @@ void camera_runs(Setup& c) {
   c.small = c.plan.host_counts && !(ss && ss[0] == '0') &&
             hostlayout::small_setup_fits(c.N, c.C, c.P, c.cam_cnt.data() + 4,
                                          reinterpret_cast<const int32_t*>(c.h->stage + c.plan.o_pc));
+  // the wave-major copy of the point-major stream, for the lane-per-point
+  // passes of the solve (SFM_PM_WAVE_MAJOR=0: none, the passes read uv_pm /
+  // cam_pm).  Not on the small path: its two launches cost a keyframe-sized
+  // one-shot solve 0.02 ms of 0.49 (C1), and a stream of at most 1.3 MB gains
+  // nothing measurable from it (profiles/pm_wave_major_ab.txt)
+  const char* wm = std::getenv("SFM_PM_WAVE_MAJOR");
+  c.wm = c.N > 0 && c.P > 0 && !c.small && !(wm && wm[0] == '0');
   c.timer.mark("camera runs (host)");
 }
 
@@ -341,7 +356,8 @@ int alloc_layouts(Setup& c) {
                   c.alloc(d.jgrp, size_t(9)) && c.alloc(d.uv_cm, 2 * npad) && c.alloc(d.pos, N) &&
                   c.tmp(c.k64a, N) && c.tmp(c.k64b, N) && c.tmp(c.k32a, size_t(nmax)) && c.tmp(c.k32b, size_t(nmax)) &&
                   c.tmp(c.iota, size_t(nmax)) && c.tmp(c.pt_s, N) && c.tmp(c.cm_order, N) &&
-                  c.tmp(c.perm, size_t(std::max<int64_t>(1, nch))) && c.tmp(tb, c.sort_bytes);
+                  c.tmp(c.perm, size_t(std::max<int64_t>(1, nch))) && c.tmp(tb, c.sort_bytes) &&
+                  (!c.wm || (c.alloc(d.woff, wm_waves(c.P) + 1) && c.tmp(c.wm_cnt, wm_waves(c.P) + 1)));
   c.sort_tmp = tb;
   return ok ? 0 : c.rc;
 }
@@ -455,6 +471,7 @@ int layout_sorted(Setup& c) {
                    c.iota, s);
   if (deferred_uv) launch_pt_off(P, c.k64b, N, C, d.pt_off, s);
   else HIPCHK(exclusive_sum32(c.sort_tmp, c.sort_bytes, c.cnt_p, d.pt_off, int64_t(P) + 1, s));
+  if (c.wm) HIPCHK(launch_wm_off(P, d.pt_off, c.wm_cnt, d.woff, c.sort_tmp, c.sort_bytes, s));
   // camera-major order of the point-major ids: stable sort by camera
   HIPCHK(sort_pairs32(c.sort_tmp, c.sort_bytes, c.k32a, c.k32b, c.iota, c.cm_order, N, uint64_t(std::max(1, C)) - 1,
                       s));
@@ -483,6 +500,8 @@ int enqueue_total_readback(Setup& c) {
   if (!c.plan.deferred_uv) {
     HIPCHK(hipMemcpyAsync(stg, c.poff + c.N, sizeof(int64_t), hipMemcpyDeviceToHost, c.s));
     HIPCHK(hipMemcpyAsync(stg + 8, c.d.jgrp, 9 * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+    if (c.wm)
+      HIPCHK(hipMemcpyAsync(stg + 48, c.d.woff + wm_waves(c.P), sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
     c.timer.mark("layout launches");
     return 0;
   }
@@ -496,6 +515,7 @@ int enqueue_total_readback(Setup& c) {
   HostCopySet cs;
   cs.add(sd, c.poff + c.N, sizeof(int64_t));
   cs.add(sd + 8, c.d.jgrp, 9 * sizeof(int32_t));
+  if (c.wm) cs.add(sd + 48, c.d.woff + wm_waves(c.P), sizeof(int32_t));
   launch_copy_to_host(cs, c.s);
   return 0;
 }
@@ -507,11 +527,19 @@ int read_pair_total(Setup& c) {
   std::memcpy(g, stg + 8, sizeof(g));
   c.d.xcd_slice_max = 0;
   for (int i = 0; i < 8; ++i) c.d.xcd_slice_max = std::max(c.d.xcd_slice_max, g[i + 1] - g[i]);
+  if (c.wm) {  // the wave-major copy's slot total, and its cap
+    int32_t slots = 0;
+    std::memcpy(&slots, stg + 48, sizeof(slots));
+    c.wm_slots = slots;
+    c.wm = hostlayout::wave_major_fits(c.wm_slots, c.N, c.P);
+    if (!c.wm) c.d.woff = nullptr;  // (its buffer goes back with the problem's)
+  }
   c.timer.mark("layouts (device)");
   return 0;
 }
 
-// The Schur pass's shape, the pinned scalar mirror, the pair lists' buffers.
+// The Schur pass's shape, the pinned scalar mirror, the pair lists' buffers
+// and the wave-major stream's.
 int alloc_pair_lists(Setup& c) {
   DevProblem& d = c.d;
   if (c.n_pairs >= int64_t(INT32_MAX)) return fail(SFM_EINVAL, "too many Schur pairs for 32-bit offsets");
@@ -534,9 +562,12 @@ int alloc_pair_lists(Setup& c) {
   }
   c.grp_host = reinterpret_cast<int64_t*>(d.scal_host + kNumScalars + 1);
   c.uv_err_host = reinterpret_cast<int32_t*>(c.grp_host + 16);
+  // (and the wave-major stream's, its slot total known by now: filled once
+  // uv_pm is, layout_wave_major)
   const bool ok = c.alloc(d.blk, std::max<size_t>(1, size_t(d.n_blk))) &&
                   (c.small || c.alloc(d.seg, size_t(d.n_blk) + 1)) &&
-                  c.alloc(d.bpts, std::max<size_t>(1, size_t(c.n_pairs)));
+                  c.alloc(d.bpts, std::max<size_t>(1, size_t(c.n_pairs))) &&
+                  (!c.wm || (c.alloc(d.uv_wm, 2 * 64 * size_t(c.wm_slots)) && c.alloc(d.cam_wm, 64 * size_t(c.wm_slots))));
   return ok ? 0 : c.rc;
 }
 
@@ -668,6 +699,13 @@ int alloc_solver_arrays(Setup& c) {
   return ok ? 0 : c.rc;
 }
 
+// The wave-major copy of the point-major stream, from uv_pm / cam_pm (on st:
+// the stream that made uv_pm).
+void layout_wave_major(Setup& c, hipStream_t st) {
+  DevProblem& d = c.d;
+  if (c.wm) launch_wm_fill(c.P, d.pt_off, d.woff, d.cam_pm, d.uv_pm, d.cam_wm, d.uv_wm, st);
+}
+
 // Deferred uv, by now up or nearly (and before it the parameters): its two
 // layouts and its finite check on the side stream, behind its copy and beside
 // the pair lists (the index layouts they read are complete: the host
@@ -682,6 +720,7 @@ int layout_deferred_uv(Setup& c) {
   hipStream_t u = h->ustream;
   launch_uv_layout(c.N, d.N_pad, d.order, d.wcam, d.cam_rng, c.d_cam_off, c.cm_order, c.in_uv, d.uv_pm, d.uv_cm, c.err,
                    u);
+  layout_wave_major(c, u);
   void* ue_d = nullptr;
   HIPCHK(hipHostGetDevicePointer(&ue_d, c.uv_err_host, 0));
   HostCopySet cs;
@@ -792,6 +831,7 @@ int run_setup(Setup& c, const double* K9, const double* rot, const double* t) {
   if ((rc = alloc_solver_arrays(c))) return rc;
   release_pool(c.h);  // earlier problems' buffers this one did not reuse
   if (plan.deferred_uv && (rc = layout_deferred_uv(c))) return rc;
+  if (!plan.deferred_uv) layout_wave_major(c, c.s);
   if (side && c.small && (rc = enqueue_side_params(c))) return rc;  // Side, small path: no layout round trip to hide behind
   if ((rc = finish_params(c))) return rc;
   return finish(c);

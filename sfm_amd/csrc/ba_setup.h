@@ -66,6 +66,14 @@ void launch_uv_layout(int64_t N, int64_t N_pad, const int32_t* order, const int3
                       int32_t* err, hipStream_t s);
 // pt_off (P + 1 entries) from the sorted point-major keys point * C + camera
 void launch_pt_off(int P, const uint64_t* sorted_keys, int64_t N, int C, int32_t* pt_off, hipStream_t s);
+// Wave-major copy of the point-major stream (DevProblem::woff / uv_wm /
+// cam_wm).  launch_wm_off: m (scratch) and woff, ceil(P / 64) + 1 entries
+// each, woff[last] = the slots of 64 lanes in all; tmp as
+// setup_sort_bytes(P + 1, 1).  launch_wm_fill: every slot, from uv_pm / cam_pm.
+hipError_t launch_wm_off(int P, const int32_t* pt_off, int32_t* m, int32_t* woff, void* tmp, size_t bytes,
+                         hipStream_t s);
+void launch_wm_fill(int P, const int32_t* pt_off, const int32_t* woff, const int32_t* cam_pm, const double* uv_pm,
+                    int32_t* cam_wm, double* uv_wm, hipStream_t s);
 void launch_chunk_keys(int n, const int4* ch, const int32_t* cm_order, const int32_t* pt_s, int P, uint32_t* key,
                        int32_t* iota, hipStream_t s);
 void launch_chunk_gather(int n, const int32_t* perm, const int4* ch, const uint32_t* key, int4* out, int32_t* grp,

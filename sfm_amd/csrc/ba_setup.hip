@@ -236,6 +236,44 @@ __global__ __launch_bounds__(kT) void k_pt_off(int P, const uint64_t* __restrict
   pt_off[p] = int32_t(lo);
 }
 
+// Wave-major copy of the point-major stream (the solve's lane-per-point
+// passes): wave w = points 64 w .. 64 w + 63 takes m_w = its largest view
+// count slots of 64 lanes.  m[w] for w < n_w, m[n_w] = 0 (the scan's last
+// input); woff is their exclusive sum, woff[n_w] the total.
+__global__ __launch_bounds__(kT) void k_wm_count(int P, int n_w, const int32_t* __restrict__ pt_off,
+                                                 int32_t* __restrict__ m) {
+  const int64_t p = int64_t(blockIdx.x) * kT + threadIdx.x;
+  int32_t n = p < P ? pt_off[p + 1] - pt_off[p] : 0;
+  for (int o = 32; o; o >>= 1) n = max(n, __shfl_xor(n, o));
+  if ((threadIdx.x & 63) == 0 && (p >> 6) <= n_w) m[p >> 6] = n;
+}
+// Slot k of lane l of wave w at (woff[w] + k) * 64 + l: point 64 w + l's k-th
+// observation, in uv_pm's order; past its count the camera index repeats its
+// last one (0 for a point without observations, uv likewise), so every slot
+// is written and any slot of a wave can be loaded.
+__global__ __launch_bounds__(kT) void k_wm_fill(int P, int n_w, const int32_t* __restrict__ pt_off,
+                                                const int32_t* __restrict__ woff,
+                                                const int32_t* __restrict__ cam_pm, const double* __restrict__ uv_pm,
+                                                int32_t* __restrict__ cam_wm, double* __restrict__ uv_wm) {
+  const int64_t p = int64_t(blockIdx.x) * kT + threadIdx.x;
+  const int64_t w = p >> 6;
+  if (w >= n_w) return;
+  const int32_t q0 = p < P ? pt_off[p] : 0;
+  const int32_t n = p < P ? pt_off[p + 1] - q0 : 0;
+  const int32_t m = woff[w + 1] - woff[w];
+  size_t dst = size_t(woff[w]) * 64 + size_t(p & 63);
+  int32_t c = 0;
+  double2 u = make_double2(0.0, 0.0);
+  for (int32_t k = 0; k < m; ++k, dst += 64) {
+    if (k < n) {
+      c = cam_pm[q0 + k];
+      u = reinterpret_cast<const double2*>(uv_pm)[q0 + k];
+    }
+    cam_wm[dst] = c;
+    reinterpret_cast<double2*>(uv_wm)[dst] = u;
+  }
+}
+
 // seg[b] = first pair of block b (lower bound of b in the sorted keys).
 __global__ __launch_bounds__(kT) void k_seg(int64_t n_blk, const uint32_t* __restrict__ key, int64_t n_pairs,
                                             int32_t* __restrict__ seg) {
@@ -682,6 +720,17 @@ void launch_pair_fill(int64_t N, const int32_t* cm_order, const int32_t* cam_pm,
 }
 void launch_pt_off(int P, const uint64_t* sorted_keys, int64_t N, int C, int32_t* pt_off, hipStream_t s) {
   k_pt_off<<<nblocks(int64_t(P) + 1), kT, 0, s>>>(P, sorted_keys, N, C, pt_off);
+}
+hipError_t launch_wm_off(int P, const int32_t* pt_off, int32_t* m, int32_t* woff, void* tmp, size_t bytes,
+                         hipStream_t s) {
+  const int n_w = int((int64_t(P) + 63) / 64);
+  k_wm_count<<<nblocks(64 * int64_t(n_w) + 1), kT, 0, s>>>(P, n_w, pt_off, m);
+  return exclusive_sum32(tmp, bytes, m, woff, int64_t(n_w) + 1, s);
+}
+void launch_wm_fill(int P, const int32_t* pt_off, const int32_t* woff, const int32_t* cam_pm, const double* uv_pm,
+                    int32_t* cam_wm, double* uv_wm, hipStream_t s) {
+  const int n_w = int((int64_t(P) + 63) / 64);
+  if (n_w > 0) k_wm_fill<<<nblocks(64 * int64_t(n_w)), kT, 0, s>>>(P, n_w, pt_off, woff, cam_pm, uv_pm, cam_wm, uv_wm);
 }
 void launch_seg(int64_t n_blk, const uint32_t* key, int64_t n_pairs, int32_t* seg, hipStream_t s) {
   k_seg<<<nblocks(n_blk + 1), kT, 0, s>>>(n_blk, key, n_pairs, seg);
