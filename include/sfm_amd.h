@@ -356,6 +356,60 @@ int sfm_map_match_frame(sfm_map* h, sfm_matcher* mt, int32_t n_frames, const int
                         double max_distance, int32_t capacity, int32_t* pts3d_match, int32_t* train_match,
                         int32_t* n_matches);
 
+/* Map-point and keyframe culling (CMap.cpp:384-574, CSfM.cpp:692-752).  Every
+ * point carries CMap's _timeAlive, _kfAlive and _ptsViews and a live flag
+ * (membership of _pts3DIdx): sfm_map_add_new_points starts them at 0, 0, the
+ * frame count and live; sfm_map_add_point_matches counts one view per match.
+ * A removed point keeps its slot (sfm_map_size's n_pts never shrinks) and its
+ * coordinates, loses its observations and descriptor rows, and is refused
+ * (SFM_EINVAL) by every call but sfm_map_get_points, sfm_map_set_points and
+ * sfm_map_point_state.  Each call below makes one host synchronisation
+ * (sfm_map_n_live none), besides buffer growth. */
+/* CMap::updatePointViews (CMap.cpp:569-574): views++ per entry, repeats count. */
+int sfm_map_update_point_views(sfm_map* h, int32_t n, const int32_t* pts3d_idx);
+/* CMap::incrementMapAge (CMap.cpp:561-567): the live points only. */
+int sfm_map_increment_age(sfm_map* h, int32_t t_inc, int32_t kf_inc);
+/* CMap::getNPoints: the live points. */
+int sfm_map_n_live(sfm_map* h, int32_t* n);
+/* out [n][5]: timeAlive, kfAlive, views, observations, live. */
+int sfm_map_point_state(sfm_map* h, int32_t n, const int32_t* pts3d_idx, int32_t* out);
+/* CMap::removePointsThreshold (CMap.cpp:384-404; the reference's
+ * _kfThreshold 3, _trackThreshold 0.25f): the two rules decided on the
+ * device, with the reference's float score views / timeAlive, then
+ * CMap::removePoints.  cull_idx [capacity]: the removed points ascending,
+ * *n_cull of them; status [n_pts] (optional): -1 removed, 0 otherwise.
+ * When the count exceeds capacity nothing is removed, *n_cull is set and
+ * SFM_EINVAL is returned. */
+int sfm_map_remove_points_threshold(sfm_map* h, int32_t kf_threshold, float track_threshold, int32_t capacity,
+                                    int32_t* cull_idx, int32_t* n_cull, int32_t* status);
+/* CMap::removePoints (CMap.cpp:406-474): pts3d_idx ascending, distinct and
+ * live (SFM_EINVAL otherwise, nothing removed); status as above. */
+int sfm_map_remove_points(sfm_map* h, int32_t n, const int32_t* pts3d_idx, int32_t* status);
+/* CMap::removeFrame (CMap.cpp:483-541): for every listed point (repeats
+ * included) the observation and the descriptor row at the position where
+ * std::lower_bound ends on the point's frame list leave, with one view; then
+ * every multimap entry of the frame goes, those of unlisted points too
+ * (their observation stays in the point's own list).  Validated first: when
+ * a listed point does not hold frame_no (and a descriptor row) at that
+ * position, where the reference erases a wrong entry, SFM_EINVAL is returned
+ * and the store is unchanged. */
+int sfm_map_remove_frame(sfm_map* h, int32_t frame_no, int32_t n, const int32_t* pts3d_idx);
+/* CMap::arePointsSeenByAtLeast (CMap.cpp:544-558): *result = more than
+ * ceil(ratio n) of the entries have more than n_frames observations. */
+int sfm_map_points_seen_by_at_least(sfm_map* h, int32_t n, const int32_t* pts3d_idx, int32_t n_frames, double ratio,
+                                    int32_t* result);
+/* CSfM::cullKeyFrames (CSfM.cpp:708-752), the whole greedy loop in one call:
+ * keyframes oldest first, frame_no [n_kf], keyframe k's matched points
+ * pts[off[k] .. off[k+1]); every keyframe but the last is decided with
+ * arePointsSeenByAtLeast(list, n_frames, ratio) and, if so, removed with
+ * removeFrame; later decisions see earlier removals.  The decisions are
+ * taken on the device with no host round trip between keyframes.  culled
+ * [n_kf]: 1 removed.  On a removeFrame error (SFM_EINVAL; the message names
+ * frame and point) the earlier keyframes' removals stand, as culled reports,
+ * and the failing keyframe and those after it are untouched. */
+int sfm_map_cull_keyframes(sfm_map* h, int32_t n_kf, const int32_t* frame_no, const int32_t* off, const int32_t* pts,
+                           int32_t n_frames, double ratio, int32_t* culled);
+
 /* CSfM::tracking's pose step (CSfM.cpp:533-565) in one call, replacing
  * matchFeatures(prevIdx, currIdx) + map->getPointsAtIdx + cv::solvePnPRansac:
  * the previous frame's keypoints with a map point (prev_pt3d[n_prev], one

@@ -515,8 +515,15 @@ class MapStore {
   int status() const { return rc_; }
   sfm_map* handle() const { return h_; }
 
-  // CMap::getNPoints (CMap.cpp:114-116)
+  // CMap::getNPoints (CMap.cpp:114-116): _pts3DIdx.size(), the points still
+  // in the map (every point until something is culled)
   int getNPoints() const {
+    int32_t n = 0;
+    return h_ && sfm_map_n_live(h_, &n) == SFM_OK ? int(n) : 0;
+  }
+  // _pts3D.size(): the point slots, culled ones included (the length of
+  // removePoints' status vector)
+  int getNSlots() const {
     int32_t np = 0;
     int64_t no = 0, nd = 0;
     return h_ && sfm_map_size(h_, &np, &no, &nd) == SFM_OK ? int(np) : 0;
@@ -569,7 +576,7 @@ class MapStore {
   // over the whole vector.
   int getPointsInFrames(std::vector<int>& pts3DIdx, const std::vector<int>& frameNo) {
     if (!h_) return rc_;
-    std::vector<int32_t> out(std::max(1, getNPoints()));
+    std::vector<int32_t> out(std::max(1, getNSlots()));
     int32_t n = 0;
     const int rc = sfm_map_points_in_frames(h_, int32_t(frameNo.size()), frameNo.data(), int32_t(out.size()),
                                             out.data(), &n);
@@ -721,10 +728,104 @@ class MapStore {
     return SFM_OK;
   }
 
+  // ---- culling: CMap's _timeAlive / _kfAlive /
+  // _ptsViews / _pts3DIdx live in the store, next to the lists they judge.
+
+  // CMap's _kfThreshold / _trackThreshold (CMap.h; 3 and 0.25f)
+  void setCullThresholds(int kfThreshold, float trackThreshold) {
+    kf_threshold_ = kfThreshold;
+    track_threshold_ = trackThreshold;
+  }
+
+  // CMap::updatePointViews (CMap.cpp:569-574)
+  int updatePointViews(const std::vector<int>& pts3DIdx) {
+    if (!h_) return rc_;
+    return sfm_map_update_point_views(h_, int32_t(pts3DIdx.size()), pts3DIdx.data());
+  }
+
+  // CMap::incrementMapAge (CMap.cpp:561-567)
+  int incrementMapAge(int tIncrement, int kfIncrement) {
+    if (!h_) return rc_;
+    return sfm_map_increment_age(h_, tIncrement, kfIncrement);
+  }
+
+  // per point: timeAlive, kfAlive, views, observations, live (appended)
+  int pointState(const std::vector<int>& pts3DIdx, std::vector<int>& state) {
+    if (!h_) return rc_;
+    std::vector<int32_t> out(5 * std::max<size_t>(1, pts3DIdx.size()));
+    if (int rc = sfm_map_point_state(h_, int32_t(pts3DIdx.size()), pts3DIdx.data(), out.data())) return rc;
+    state.insert(state.end(), out.begin(), out.begin() + 5 * pts3DIdx.size());
+    return SFM_OK;
+  }
+
+  // CMap::removePointsThreshold (CMap.cpp:384-404): the culled points are
+  // appended to ptsCullIdx (ascending); newPtsIdx becomes the status vector
+  // of removePoints ([slots]: -1 culled, 0 otherwise; the reference leaves
+  // it empty when nothing is culled, here it is always sized).
+  int removePointsThreshold(std::vector<int>& ptsCullIdx, std::vector<int>& newPtsIdx) {
+    if (!h_) return rc_;
+    const int np = getNSlots();
+    std::vector<int32_t> cull(std::max(1, np)), st(std::max(1, np));
+    int32_t n = 0;
+    if (int rc = sfm_map_remove_points_threshold(h_, kf_threshold_, track_threshold_, np, cull.data(), &n, st.data()))
+      return rc;
+    ptsCullIdx.insert(ptsCullIdx.end(), cull.begin(), cull.begin() + n);
+    newPtsIdx.assign(st.begin(), st.begin() + np);
+    return SFM_OK;
+  }
+
+  // CMap::removePoints (CMap.cpp:406-474): ptsCullIdx ascending
+  int removePoints(const std::vector<int>& ptsCullIdx, std::vector<int>& ptsStatusFlag) {
+    if (!h_) return rc_;
+    const int np = getNSlots();
+    std::vector<int32_t> st(std::max(1, np));
+    if (int rc = sfm_map_remove_points(h_, int32_t(ptsCullIdx.size()), ptsCullIdx.data(), st.data())) return rc;
+    ptsStatusFlag.assign(st.begin(), st.begin() + np);
+    return SFM_OK;
+  }
+
+  // CMap::removeFrame (CMap.cpp:483-541)
+  int removeFrame(int frameNo, const std::vector<int>& framePtsIdx) {
+    if (!h_) return rc_;
+    return sfm_map_remove_frame(h_, frameNo, int32_t(framePtsIdx.size()), framePtsIdx.data());
+  }
+
+  // CMap::arePointsSeenByAtLeast (CMap.cpp:544-558); the answer in `seen`
+  int arePointsSeenByAtLeast(const std::vector<int>& pts3DIdx, int nFramesThreshold, double ratioPtsThreshold,
+                             bool& seen) {
+    if (!h_) return rc_;
+    int32_t r = 0;
+    const int rc = sfm_map_points_seen_by_at_least(h_, int32_t(pts3DIdx.size()), pts3DIdx.data(), nFramesThreshold,
+                                                   ratioPtsThreshold, &r);
+    seen = r != 0;
+    return rc;
+  }
+
+  // The loop of CSfM::cullKeyFrames (CSfM.cpp:708-752) in one device call:
+  // the keyframes oldest first (frameNo[k], matched points kfPts[k], as
+  // CFrame::getMatchedPoints gives them); culled[k] = 1 for the keyframes to
+  // erase from _kFrames.  On an error the flags of the keyframes removed
+  // before it are still set.
+  int cullKeyFrames(const std::vector<int>& frameNo, const std::vector<std::vector<int>>& kfPts,
+                    int minVisibilityFrameNo, double thresholdRate, std::vector<int>& culled) {
+    if (!h_) return rc_;
+    if (kfPts.size() != frameNo.size()) return SFM_EINVAL;
+    std::vector<int32_t> off(frameNo.size() + 1, 0), pts;
+    for (size_t k = 0; k < kfPts.size(); ++k) {
+      pts.insert(pts.end(), kfPts[k].begin(), kfPts[k].end());
+      off[k + 1] = int32_t(pts.size());
+    }
+    culled.assign(frameNo.size(), 0);
+    return sfm_map_cull_keyframes(h_, int32_t(frameNo.size()), frameNo.data(), off.data(), pts.data(),
+                                  minVisibilityFrameNo, thresholdRate, culled.data());
+  }
+
  private:
   sfm_map* h_ = nullptr;
   int rc_ = SFM_OK;
   int32_t desc_bytes_ = 64;
+  int kf_threshold_ = 3;
+  float track_threshold_ = 0.25f;
 };
 
 }  // namespace sfm_compat

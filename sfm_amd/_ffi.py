@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_int, c_int32, c_int64, c_uint8, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint8, c_uint64, c_void_p
 
 import numpy as np
 
@@ -193,6 +193,17 @@ _SIGNATURES = {
     "sfm_map_match_frame": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_int32, c_void_p, c_double, c_double, c_double, c_int32, c_void_p,
                                     c_void_p, POINTER(c_int32)]),
+    "sfm_map_update_point_views": (c_int, [c_void_p, c_int32, c_void_p]),
+    "sfm_map_increment_age": (c_int, [c_void_p, c_int32, c_int32]),
+    "sfm_map_n_live": (c_int, [c_void_p, POINTER(c_int32)]),
+    "sfm_map_point_state": (c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
+    "sfm_map_remove_points_threshold": (c_int, [c_void_p, c_int32, c_float, c_int32, c_void_p, POINTER(c_int32),
+                                                c_void_p]),
+    "sfm_map_remove_points": (c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
+    "sfm_map_remove_frame": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
+    "sfm_map_points_seen_by_at_least": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_double, POINTER(c_int32)]),
+    "sfm_map_cull_keyframes": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_double,
+                                       c_void_p]),
     "sfm_matcher_store_keyframe": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int32]),
     "sfm_matcher_match_keyframes": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
                                             c_int32, c_double, c_double, c_double, c_void_p, c_void_p,

@@ -194,6 +194,76 @@ class DeviceMap:
               "sfm_map_match_frame")
         return pm[:n.value].copy(), km[:n.value].copy()
 
+    # ---- culling (CMap.cpp:384-574, CSfM.cpp:708-752)
+    def updatePointViews(self, pts3DIdx) -> None:
+        a = np.ascontiguousarray(np.asarray(pts3DIdx, np.int32).reshape(-1))
+        check(lib().sfm_map_update_point_views(self._h, len(a), ptr(a)), "sfm_map_update_point_views")
+
+    def incrementMapAge(self, tIncrement: int, kfIncrement: int) -> None:
+        check(lib().sfm_map_increment_age(self._h, int(tIncrement), int(kfIncrement)), "sfm_map_increment_age")
+
+    def getNPoints(self) -> int:
+        n = ctypes.c_int32()
+        check(lib().sfm_map_n_live(self._h, ctypes.byref(n)), "sfm_map_n_live")
+        return n.value
+
+    def pointState(self, pts3DIdx) -> np.ndarray:
+        """int32 [n][5]: timeAlive, kfAlive, views, observations, live."""
+        a = np.ascontiguousarray(np.asarray(pts3DIdx, np.int32).reshape(-1))
+        out = np.zeros((max(1, len(a)), 5), np.int32)
+        check(lib().sfm_map_point_state(self._h, len(a), ptr(a), ptr(out)), "sfm_map_point_state")
+        return out[:len(a)].copy()
+
+    def removePointsThreshold(self, kfThreshold: int = 3, trackThreshold: float = 0.25):
+        """(culled points ascending, status [n_pts]: -1 culled, 0 otherwise)."""
+        P = self.size()[0]
+        cull = np.zeros(max(1, P), np.int32)
+        status = np.zeros(max(1, P), np.int32)
+        n = ctypes.c_int32()
+        check(lib().sfm_map_remove_points_threshold(self._h, int(kfThreshold), float(trackThreshold), P, ptr(cull),
+                                                    ctypes.byref(n), ptr(status)),
+              "sfm_map_remove_points_threshold")
+        return cull[:n.value].copy(), status[:P].copy()
+
+    def removePoints(self, ptsCullIdx) -> np.ndarray:
+        a = np.ascontiguousarray(np.asarray(ptsCullIdx, np.int32).reshape(-1))
+        P = self.size()[0]
+        status = np.zeros(max(1, P), np.int32)
+        check(lib().sfm_map_remove_points(self._h, len(a), ptr(a), ptr(status)), "sfm_map_remove_points")
+        return status[:P].copy()
+
+    def removeFrame(self, frameNo: int, framePtsIdx) -> None:
+        a = np.ascontiguousarray(np.asarray(framePtsIdx, np.int32).reshape(-1))
+        check(lib().sfm_map_remove_frame(self._h, int(frameNo), len(a), ptr(a)), "sfm_map_remove_frame")
+
+    def arePointsSeenByAtLeast(self, pts3DIdx, nFramesThreshold: int, ratioPtsThreshold: float) -> bool:
+        a = np.ascontiguousarray(np.asarray(pts3DIdx, np.int32).reshape(-1))
+        r = ctypes.c_int32()
+        check(lib().sfm_map_points_seen_by_at_least(self._h, len(a), ptr(a), int(nFramesThreshold),
+                                                    float(ratioPtsThreshold), ctypes.byref(r)),
+              "sfm_map_points_seen_by_at_least")
+        return bool(r.value)
+
+    def cullKeyFrames(self, kfs, nFrames: int = 3, ratio: float = 0.9) -> np.ndarray:
+        """CSfM::cullKeyFrames over kfs = [(frameNo, the keyframe's matched
+        points)], oldest first: the culled flag per keyframe.  On an error
+        the flags of the keyframes removed before it are in the exception's
+        `culled` attribute."""
+        fr = np.ascontiguousarray(np.array([int(f) for f, _ in kfs], np.int32))
+        lists = [np.asarray(p, np.int32).reshape(-1) for _, p in kfs]
+        off = np.zeros(len(kfs) + 1, np.int32)
+        off[1:] = np.cumsum([len(p) for p in lists])
+        pts = np.ascontiguousarray(np.concatenate(lists + [np.zeros(0, np.int32)]).astype(np.int32))
+        culled = np.zeros(max(1, len(kfs)), np.int32)
+        rc = lib().sfm_map_cull_keyframes(self._h, len(kfs), ptr(fr), ptr(off), ptr(pts), int(nFrames), float(ratio),
+                                          ptr(culled))
+        try:
+            check(rc, "sfm_map_cull_keyframes")
+        except Exception as e:
+            e.culled = culled[:len(kfs)].copy()
+            raise
+        return culled[:len(kfs)].copy()
+
     def getRepresentativeDescriptors(self, pts3DIdx, return_best: bool = False):
         a = np.ascontiguousarray(np.asarray(pts3DIdx, np.int32).reshape(-1))
         out = np.zeros((max(1, len(a)), self.desc_bytes), np.uint8)

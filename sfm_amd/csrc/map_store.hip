@@ -14,6 +14,10 @@
 //                                       has in that frame (a point matched
 //                                       twice in a frame yields 2 x 2)
 //   getRepresentativeDescriptors  CMap.cpp:345-381 (CSfM.cpp:669)
+//   updatePointViews / incrementMapAge   CMap.cpp:561-574
+//   removePointsThreshold / removePoints CMap.cpp:384-474
+//   removeFrame / arePointsSeenByAtLeast CMap.cpp:483-558
+//   CSfM::cullKeyFrames                  CSfM.cpp:708-752 (one call)
 //
 // Layout: observations are kept in global emplace order, which is taken as
 // the multimap's order within one key (the reference's container is an
@@ -23,10 +27,25 @@
 // per-point CSRs (observations, descriptor rows) are rebuilt lazily by a
 // stable radix sort after appends.  Queries are flag + stable compaction
 // (hipcub DeviceSelect), so every result keeps the reference's order.
+//
+// Culling: every point carries _timeAlive / _kfAlive / _ptsViews (int32) and
+// a live flag (membership of _pts3DIdx) beside X, every observation a flag
+// for its _frameViewsPointIdx entry: removeFrame erases ALL of a frame's
+// multimap entries but only the listed points' list entries, so the two can
+// diverge, and the frame-keyed queries read the flag while the per-point
+// lists (k_dup_count / k_dup_fill) do not.  Removals mark tombstones per
+// observation and per descriptor row and end in one stable compaction of the
+// arrays (hipcub scan + scatter), after which both CSRs are stale.  The cull
+// rules and the keyframe loop's decisions are taken on the device; each call
+// reads its results back with one host synchronisation.  A removed point
+// keeps its slot and X (indices are never renumbered); the host mirror of
+// the live flags lets the argument checks refuse it without a readback.
+// With no culling call made every flag is 1 and every query is what it was.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <string>
@@ -45,9 +64,10 @@ int mapfail(int code, const std::string& m) {
 }
 
 __global__ void k_mark_frames(int64_t n, const int32_t* __restrict__ ob_pt, const int32_t* __restrict__ ob_frame,
-                              const int32_t* __restrict__ fset, int nf, uint8_t* __restrict__ mark) {
+                              const uint8_t* __restrict__ ob_mm, const int32_t* __restrict__ fset, int nf,
+                              uint8_t* __restrict__ mark) {
   const int64_t e = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (e >= n) return;
+  if (e >= n || !ob_mm[e]) return;  // (ob_mm: the observation still has its multimap entry)
   const int f = ob_frame[e];
   int lo = 0, hi = nf;  // fset ascending
   while (lo < hi) {
@@ -57,15 +77,17 @@ __global__ void k_mark_frames(int64_t n, const int32_t* __restrict__ ob_pt, cons
   if (lo < nf && fset[lo] == f) mark[ob_pt[e]] = 1;  // idempotent plain store
 }
 
-__global__ void k_flag_frame(int64_t n, const int32_t* __restrict__ ob_frame, int f, uint8_t* __restrict__ flag) {
+__global__ void k_flag_frame(int64_t n, const int32_t* __restrict__ ob_frame, const uint8_t* __restrict__ ob_mm, int f,
+                             uint8_t* __restrict__ flag) {
   const int64_t e = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (e < n) flag[e] = ob_frame[e] == f;
+  if (e < n) flag[e] = ob_frame[e] == f && ob_mm[e];
 }
 
 // rank of each observation's frame in the query list (fr sorted by frame,
 // with the query position alongside), nf when the frame is not queried
-__global__ void k_frame_rank(int64_t n, const int32_t* __restrict__ ob_frame, const int2* __restrict__ fr, int nf,
-                             uint32_t* __restrict__ key, int32_t* __restrict__ iota) {
+__global__ void k_frame_rank(int64_t n, const int32_t* __restrict__ ob_frame, const uint8_t* __restrict__ ob_mm,
+                             const int2* __restrict__ fr, int nf, uint32_t* __restrict__ key,
+                             int32_t* __restrict__ iota) {
   const int64_t e = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (e >= n) return;
   const int f = ob_frame[e];
@@ -74,7 +96,7 @@ __global__ void k_frame_rank(int64_t n, const int32_t* __restrict__ ob_frame, co
     const int mid = (lo + hi) >> 1;
     if (fr[mid].x < f) lo = mid + 1; else hi = mid;
   }
-  key[e] = uint32_t(lo < nf && fr[lo].x == f ? fr[lo].y : nf);
+  key[e] = uint32_t(lo < nf && fr[lo].x == f && ob_mm[e] ? fr[lo].y : nf);
   iota[e] = int32_t(e);
 }
 
@@ -213,6 +235,259 @@ __global__ void k_unmark(int n, const int32_t* __restrict__ pts, uint8_t* __rest
   if (i < n) mark[pts[i]] = 0;
 }
 
+// ---- culling (CMap.cpp:384-574, CSfM.cpp:708-752)
+
+__global__ void k_fill_i32(int n, int32_t* __restrict__ v, int32_t x) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) v[i] = x;
+}
+
+// _ptsViews[idx]++ per entry; repeats count (integer adds commute)
+__global__ void k_add_views(int n, const int32_t* __restrict__ idx, int32_t* __restrict__ views) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) atomicAdd(views + idx[i], 1);
+}
+
+__global__ void k_age(int P, const uint8_t* __restrict__ live, int32_t* __restrict__ time, int32_t* __restrict__ kf,
+                      int t_inc, int kf_inc) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= P || !live[p]) return;
+  time[p] += t_inc;
+  kf[p] += kf_inc;
+}
+
+__global__ void k_point_state(int n, const int32_t* __restrict__ idx, const int32_t* __restrict__ time,
+                              const int32_t* __restrict__ kf, const int32_t* __restrict__ views,
+                              const int32_t* __restrict__ ooff, const uint8_t* __restrict__ live,
+                              int32_t* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int p = idx[i];
+  int32_t* o = out + 5 * size_t(i);
+  o[0] = time[p];
+  o[1] = kf[p];
+  o[2] = views[p];
+  o[3] = ooff[p + 1] - ooff[p];
+  o[4] = live[p];
+}
+
+// CMap::removePointsThreshold's two rules (CMap.cpp:386-399); the score is
+// the reference's float division, so timeAlive = 0 gives +inf (kept)
+__global__ void k_cull_flag(int P, const uint8_t* __restrict__ live, const int32_t* __restrict__ time,
+                            const int32_t* __restrict__ kf, const int32_t* __restrict__ views,
+                            const int32_t* __restrict__ ooff, int kf_thr, float track_thr,
+                            uint8_t* __restrict__ flag) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= P) return;
+  bool cull = false;
+  if (live[p]) {
+    const int n_obs = ooff[p + 1] - ooff[p], k = kf[p];
+    if (k >= 1 && k <= kf_thr) {
+      const float score = float(views[p]) / float(time[p]);
+      cull = n_obs < kf_thr || score < track_thr;
+    }
+    cull = cull || (n_obs < kf_thr && k > kf_thr);
+  }
+  flag[p] = cull;
+}
+
+__global__ void k_flag_list(int n, const int32_t* __restrict__ idx, uint8_t* __restrict__ flag) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) flag[idx[i]] = 1;
+}
+
+// CMap::removePoints (CMap.cpp:406-474) for the flagged points: out of
+// _pts3DIdx, every observation and descriptor row of theirs a tombstone, the
+// status -1.  Nothing happens when the count exceeds the caller's capacity
+// (n_dev NULL: no bound).
+__global__ void k_kill_points(int P, int64_t N, int64_t rows, const uint8_t* __restrict__ flag,
+                              const int32_t* __restrict__ n_dev, int capacity, const int32_t* __restrict__ ob_pt,
+                              const int32_t* __restrict__ desc_pt, uint8_t* __restrict__ live,
+                              uint8_t* __restrict__ odead, uint8_t* __restrict__ ddead, int32_t* __restrict__ status) {
+  const int64_t e = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  const bool apply = !n_dev || *n_dev <= capacity;
+  if (e < P) {
+    const bool c = flag[e] && apply;
+    if (c) live[e] = 0;
+    status[e] = c ? -1 : 0;
+  }
+  if (!apply) return;
+  if (e < N && flag[ob_pt[e]]) odead[e] = 1;
+  if (e < rows && flag[desc_pt[e]]) ddead[e] = 1;
+}
+
+__global__ void k_keep(int64_t n, const uint8_t* __restrict__ dead, int32_t* __restrict__ keep) {
+  const int64_t e = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (e < n) keep[e] = dead[e] == 0;
+}
+
+__global__ void k_compact_obs(int64_t n, const uint8_t* __restrict__ dead, const int32_t* __restrict__ pos,
+                              const int32_t* __restrict__ pt, const int32_t* __restrict__ fr,
+                              const int32_t* __restrict__ ix, const uint8_t* __restrict__ mm, int32_t* __restrict__ pt2,
+                              int32_t* __restrict__ fr2, int32_t* __restrict__ ix2, uint8_t* __restrict__ mm2) {
+  const int64_t e = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (e >= n || dead[e]) return;
+  const int q = pos[e];
+  pt2[q] = pt[e];
+  fr2[q] = fr[e];
+  ix2[q] = ix[e];
+  mm2[q] = mm[e];
+}
+
+__global__ void k_compact_desc(int64_t rows, int W, const uint8_t* __restrict__ dead, const int32_t* __restrict__ pos,
+                               const uint64_t* __restrict__ desc, const int32_t* __restrict__ dpt,
+                               uint64_t* __restrict__ desc2, int32_t* __restrict__ dpt2) {
+  const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  const int64_t r = t / W;
+  const int w = int(t % W);
+  if (r >= rows || dead[r]) return;
+  const int q = pos[r];
+  desc2[size_t(q) * W + w] = desc[size_t(r) * W + w];
+  if (w == 0) dpt2[q] = dpt[r];
+}
+
+// tot = (observations kept, descriptor rows kept)
+__global__ void k_totals(int64_t N, int64_t rows, const int32_t* __restrict__ okeep, const int32_t* __restrict__ opos,
+                         const int32_t* __restrict__ dkeep, const int32_t* __restrict__ dpos,
+                         int32_t* __restrict__ tot) {
+  tot[0] = N ? opos[N - 1] + okeep[N - 1] : 0;
+  tot[1] = rows ? dpos[rows - 1] + dkeep[rows - 1] : 0;
+}
+
+__global__ void k_nobs(int P, const int32_t* __restrict__ ooff, int32_t* __restrict__ nobs) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < P) nobs[p] = ooff[p + 1] - ooff[p];
+}
+
+// entry j (0-based) of a point's list = the j-th row of its CSR range that is
+// not a tombstone; -1 past the end
+__device__ inline int nth_live(const int32_t* row, const uint8_t* dead, int b, int e, int j) {
+  for (int q = b; q < e; ++q) {
+    const int o = row[q];
+    if (dead[o]) continue;
+    if (j-- == 0) return o;
+  }
+  return -1;
+}
+
+struct KfWalk {
+  int n_walk, mode;  // mode 0: CSfM::cullKeyFrames; 1: removeFrame (no decision); 2: the decision alone
+  int n_frames;      // arePointsSeenByAtLeast's nFramesThreshold
+  const int32_t *frame_no, *off, *pts, *thr;  // per keyframe: its number, its list pts[off[k] .. off[k+1]), ceil(ratio n)
+  const int32_t *ob_frame, *orow, *ooff, *drow, *doff;
+  uint8_t *odead, *ddead, *own;
+  int32_t *nobs, *views, *cnt, *culled, *err;  // err: (set, keyframe, point, frame)
+};
+
+// The greedy loop of CSfM::cullKeyFrames (CSfM.cpp:708-752) in one workgroup,
+// keyframe after keyframe with no host round trip: the decision of
+// CMap::arePointsSeenByAtLeast (CMap.cpp:544-558) reads only the points' list
+// lengths (nobs, kept current here), and CMap::removeFrame's per-point part
+// (CMap.cpp:486-522) touches only the listed points' own rows.  A point
+// listed k times is handled by ONE lane (the entry whose atomic count came
+// back 0) doing k removals in sequence, each with std::lower_bound's
+// bisection on the point's list as it then stands.  Removals are first
+// marked pending (2): when any entry fails the reference's unchecked
+// assumptions the keyframe's marks are withdrawn, the error is recorded and
+// the walk ends; otherwise they become tombstones (1) and the counters move.
+// The multimap erase of the culled frames and the compaction follow on a
+// full grid (k_clear_mm, compact).
+__global__ __launch_bounds__(1024) void k_walk_keyframes(KfWalk a) {
+  __shared__ int s_cnt, s_fail;
+  const int tid = threadIdx.x, T = blockDim.x;
+  for (int k = 0; k < a.n_walk; ++k) {
+    const int b = a.off[k], e = a.off[k + 1], f = a.frame_no[k];
+    if (tid == 0) { s_cnt = 0; s_fail = INT_MAX; }
+    __syncthreads();
+    bool cull = a.mode == 1;
+    if (!cull) {
+      int c = 0;
+      for (int i = b + tid; i < e; i += T) c += a.nobs[a.pts[i]] > a.n_frames;
+      for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o);
+      if ((tid & 63) == 0 && c) atomicAdd(&s_cnt, c);
+      __syncthreads();
+      cull = s_cnt > a.thr[k];
+    }
+    if (a.mode == 2 || !cull) {
+      if (tid == 0) a.culled[k] = cull;
+      __syncthreads();  // (s_cnt is read above, reset below)
+      continue;
+    }
+    // one owner per distinct point
+    for (int i = b + tid; i < e; i += T) a.own[i] = atomicAdd(a.cnt + a.pts[i], 1) == 0;
+    __syncthreads();
+    for (int i = b + tid; i < e; i += T) {
+      if (!a.own[i]) continue;
+      const int p = a.pts[i], m = atomicAdd(a.cnt + p, 0);  // (read where the adds above were made)
+      const int ob = a.ooff[p], oe = a.ooff[p + 1], db = a.doff[p], de = a.doff[p + 1];
+      int len = 0, dlen = 0;
+      for (int q = ob; q < oe; ++q) len += a.odead[a.orow[q]] == 0;
+      for (int q = db; q < de; ++q) dlen += a.ddead[a.drow[q]] == 0;
+      for (int r = 0; r < m; ++r) {
+        int first = 0, count = len;  // std::lower_bound(_frameNo[p].begin(), .end(), frameNo)
+        while (count > 0) {
+          const int step = count >> 1;
+          if (a.ob_frame[nth_live(a.orow, a.odead, ob, oe, first + step)] < f) {
+            first += step + 1;
+            count -= step + 1;
+          } else {
+            count = step;
+          }
+        }
+        const int o = first < len ? nth_live(a.orow, a.odead, ob, oe, first) : -1;
+        if (o < 0 || a.ob_frame[o] != f || dlen <= first) {
+          atomicMin(&s_fail, i);
+          break;
+        }
+        a.odead[o] = 2;
+        a.ddead[nth_live(a.drow, a.ddead, db, de, first)] = 2;
+        --len;
+        --dlen;
+      }
+    }
+    __syncthreads();
+    const int fail = s_fail;
+    for (int i = b + tid; i < e; i += T) {
+      if (!a.own[i]) continue;
+      const int p = a.pts[i];
+      int gone = 0;
+      for (int q = a.ooff[p]; q < a.ooff[p + 1]; ++q) {
+        const int o = a.orow[q];
+        if (a.odead[o] == 2) { a.odead[o] = fail == INT_MAX; ++gone; }
+      }
+      for (int q = a.doff[p]; q < a.doff[p + 1]; ++q) {
+        const int d = a.drow[q];
+        if (a.ddead[d] == 2) a.ddead[d] = fail == INT_MAX;
+      }
+      if (fail == INT_MAX) {  // _frameNo[p] shrinks, _ptsViews[p]-- per removal
+        a.nobs[p] -= gone;
+        a.views[p] -= gone;
+      }
+    }
+    __syncthreads();  // (every lane has read its own[i] and cnt)
+    for (int i = b + tid; i < e; i += T) a.cnt[a.pts[i]] = 0;
+    if (tid == 0) {
+      a.culled[k] = fail == INT_MAX;
+      if (fail != INT_MAX) { a.err[0] = 1; a.err[1] = k; a.err[2] = a.pts[fail]; a.err[3] = f; }
+    }
+    __syncthreads();
+    if (fail != INT_MAX) break;
+  }
+}
+
+// _frameViewsPointIdx.erase(frameNo) for the culled keyframes (CMap.cpp:525):
+// every surviving observation of such a frame loses its multimap entry, the
+// unlisted points' included
+__global__ void k_clear_mm(int64_t N, const int32_t* __restrict__ ob_frame, const uint8_t* __restrict__ odead, int n_kf,
+                           const int32_t* __restrict__ frame_no, const int32_t* __restrict__ culled,
+                           uint8_t* __restrict__ mm) {
+  const int64_t e = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (e >= N || odead[e]) return;
+  const int f = ob_frame[e];
+  for (int k = 0; k < n_kf; ++k)
+    if (culled[k] && frame_no[k] == f) { mm[e] = 0; return; }
+}
+
 // The queried points projected with the frame's pose (CSfM.cpp:664-668, the
 // reference's GeometryUtils::projectPoints with zero distortion, as
 // sfm_amd/live.py's _project): uv = (x / z) f + c.
@@ -253,7 +528,12 @@ struct sfm_map {
   int device = 0, desc_bytes = 0, W = 0;
   hipStream_t s = nullptr;
   DVec<int32_t> ob_pt, ob_frame, ob_idx;  // observations, emplace order
+  DVec<uint8_t> ob_mm;                     // 1: the observation's _frameViewsPointIdx entry exists
   DVec<double> X;                          // [n_pts][3]
+  DVec<int32_t> pt_time, pt_kf, pt_views;  // _timeAlive, _kfAlive, _ptsViews
+  DVec<uint8_t> pt_live;                   // 1: the point is in _pts3DIdx
+  std::vector<uint8_t> live_h;             // pt_live's host mirror (argument checks make no readback)
+  int32_t n_live = 0;
   int32_t n_pts = 0;
   DVec<uint64_t> desc;                     // [rows][W]
   DVec<int32_t> desc_pt;                   // point of each row
@@ -363,10 +643,227 @@ int build_csr(sfm_map* h, const char* tag, const int32_t* key, int64_t n, int32_
   return 0;
 }
 
+// n more entries of `value` (a byte pattern: 0, or 1 for the byte arrays)
+template <class T>
+int append_fill(sfm_map* h, DVec<T>& v, int value, int64_t n) {
+  if (int rc = grow(h, v, v.n + n)) return rc;
+  if (n && hipMemsetAsync(v.p + v.n, value, size_t(n) * sizeof(T), h->s) != hipSuccess)
+    return mapfail(SFM_EIO, "memset failed");
+  v.n += n;
+  return 0;
+}
+
+// in range and still in the map (a removed point keeps its slot and its X,
+// and is refused everywhere but sfm_map_get_points / sfm_map_set_points)
+int check_live(const sfm_map* h, int32_t n, const int32_t* idx) {
+  for (int32_t i = 0; i < n; ++i) {
+    if (idx[i] < 0 || idx[i] >= h->n_pts)
+      return mapfail(SFM_EINVAL, "point index " + std::to_string(idx[i]) + " out of range at " + std::to_string(i));
+    if (!h->live_h[size_t(idx[i])])
+      return mapfail(SFM_EINVAL, "point " + std::to_string(idx[i]) + " (at " + std::to_string(i) + ") was removed");
+  }
+  return 0;
+}
+
 int check_pts(const sfm_map* h, int32_t n, const int32_t* idx) {
   for (int32_t i = 0; i < n; ++i)
     if (idx[i] < 0 || idx[i] >= h->n_pts)
       return mapfail(SFM_EINVAL, "point index " + std::to_string(idx[i]) + " out of range at " + std::to_string(i));
+  return 0;
+}
+
+int ensure_csrs(sfm_map* h) {
+  if (!h->ocsr) {
+    if (int r = build_csr(h, "ob", h->ob_pt.p, h->ob_pt.n, &h->orow, &h->ooff)) return r;
+    h->ocsr = true;
+  }
+  if (!h->dcsr) {
+    if (int r = build_csr(h, "de", h->desc_pt.p, h->desc.n / h->W, &h->drow, &h->doff)) return r;
+    h->dcsr = true;
+  }
+  return 0;
+}
+
+// Tombstones of one culling call: per observation and per descriptor row,
+// 0 kept, 1 removed (2: pending inside k_walk_keyframes).
+struct Tomb {
+  uint8_t *odead = nullptr, *ddead = nullptr;
+};
+
+int tomb_begin(sfm_map* h, Tomb* t) {
+  int rc = 0;
+  const size_t N = size_t(h->ob_pt.n), rows = size_t(h->desc.n / h->W);
+  t->odead = static_cast<uint8_t*>(scratch(h, "odead", std::max<size_t>(N, 1), &rc));
+  t->ddead = static_cast<uint8_t*>(scratch(h, "ddead", std::max<size_t>(rows, 1), &rc));
+  if (rc) return rc;
+  (void)hipMemsetAsync(t->odead, 0, std::max<size_t>(N, 1), h->s);
+  (void)hipMemsetAsync(t->ddead, 0, std::max<size_t>(rows, 1), h->s);
+  return 0;
+}
+
+int exclusive_sum(sfm_map* h, const char* tag, const int32_t* in, int32_t* out, int n) {
+  int rc = 0;
+  size_t bytes = 0;
+  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, n, h->s);
+  void* tmp = scratch(h, tag, bytes, &rc);
+  if (rc) return rc;
+  if (hipcub::DeviceScan::ExclusiveSum(tmp, bytes, in, out, n, h->s) != hipSuccess)
+    return mapfail(SFM_EIO, "scan failed");
+  return 0;
+}
+
+// One stable compaction of the observation arrays and of desc / desc_pt past
+// the call's tombstones, enqueued on the stream: keep flags, their exclusive
+// scan (hipcub), a scatter into scratch copies, and the copies back.  tot
+// (device, 2 ints) receives the new sizes; the caller reads them with its one
+// readback and passes them to compact_done.
+int compact(sfm_map* h, const Tomb& t, int32_t* tot) {
+  int rc = 0;
+  const int64_t N = h->ob_pt.n, rows = h->desc.n / h->W;
+  const size_t n1 = size_t(std::max<int64_t>(N, 1)), r1 = size_t(std::max<int64_t>(rows, 1));
+  auto* okeep = static_cast<int32_t*>(scratch(h, "cok", sizeof(int32_t) * n1, &rc));
+  auto* opos = static_cast<int32_t*>(scratch(h, "cop", sizeof(int32_t) * n1, &rc));
+  auto* dkeep = static_cast<int32_t*>(scratch(h, "cdk", sizeof(int32_t) * r1, &rc));
+  auto* dpos = static_cast<int32_t*>(scratch(h, "cdp", sizeof(int32_t) * r1, &rc));
+  auto* pt2 = static_cast<int32_t*>(scratch(h, "cpt", sizeof(int32_t) * n1, &rc));
+  auto* fr2 = static_cast<int32_t*>(scratch(h, "cfr", sizeof(int32_t) * n1, &rc));
+  auto* ix2 = static_cast<int32_t*>(scratch(h, "cix", sizeof(int32_t) * n1, &rc));
+  auto* mm2 = static_cast<uint8_t*>(scratch(h, "cmm", n1, &rc));
+  auto* desc2 = static_cast<uint64_t*>(scratch(h, "cde", sizeof(uint64_t) * r1 * h->W, &rc));
+  auto* dpt2 = static_cast<int32_t*>(scratch(h, "cdq", sizeof(int32_t) * r1, &rc));
+  if (rc) return rc;
+  if (N) {
+    k_keep<<<grid(N), 256, 0, h->s>>>(N, t.odead, okeep);
+    if (int r = exclusive_sum(h, "cos", okeep, opos, int(N))) return r;
+  }
+  if (rows) {
+    k_keep<<<grid(rows), 256, 0, h->s>>>(rows, t.ddead, dkeep);
+    if (int r = exclusive_sum(h, "cds", dkeep, dpos, int(rows))) return r;
+  }
+  k_totals<<<1, 1, 0, h->s>>>(N, rows, okeep, opos, dkeep, dpos, tot);
+  if (N) {
+    k_compact_obs<<<grid(N), 256, 0, h->s>>>(N, t.odead, opos, h->ob_pt.p, h->ob_frame.p, h->ob_idx.p, h->ob_mm.p, pt2,
+                                             fr2, ix2, mm2);
+    (void)hipMemcpyAsync(h->ob_pt.p, pt2, sizeof(int32_t) * size_t(N), hipMemcpyDeviceToDevice, h->s);
+    (void)hipMemcpyAsync(h->ob_frame.p, fr2, sizeof(int32_t) * size_t(N), hipMemcpyDeviceToDevice, h->s);
+    (void)hipMemcpyAsync(h->ob_idx.p, ix2, sizeof(int32_t) * size_t(N), hipMemcpyDeviceToDevice, h->s);
+    (void)hipMemcpyAsync(h->ob_mm.p, mm2, size_t(N), hipMemcpyDeviceToDevice, h->s);
+  }
+  if (rows) {
+    k_compact_desc<<<grid(rows * h->W), 256, 0, h->s>>>(rows, h->W, t.ddead, dpos, h->desc.p, h->desc_pt.p, desc2,
+                                                        dpt2);
+    (void)hipMemcpyAsync(h->desc.p, desc2, sizeof(uint64_t) * size_t(rows) * h->W, hipMemcpyDeviceToDevice, h->s);
+    (void)hipMemcpyAsync(h->desc_pt.p, dpt2, sizeof(int32_t) * size_t(rows), hipMemcpyDeviceToDevice, h->s);
+  }
+  return 0;
+}
+
+void compact_done(sfm_map* h, const int32_t* tot) {
+  if (tot[0] == h->ob_pt.n && int64_t(tot[1]) * h->W == h->desc.n) return;  // nothing left: the CSRs stand
+  h->ob_pt.n = h->ob_frame.n = h->ob_idx.n = h->ob_mm.n = tot[0];
+  h->desc.n = int64_t(tot[1]) * h->W;
+  h->desc_pt.n = tot[1];
+  h->ocsr = h->dcsr = false;
+}
+
+// The flagged points' removal and the compaction, enqueued (res: count,
+// tot[2], list [P], status [P] on the device)
+int kill_and_compact(sfm_map* h, const uint8_t* flag, const int32_t* n_dev, int capacity, int32_t* res) {
+  Tomb t;
+  if (int r = tomb_begin(h, &t)) return r;
+  const int P = h->n_pts;
+  const int64_t N = h->ob_pt.n, rows = h->desc.n / h->W;
+  k_kill_points<<<grid(std::max<int64_t>({P, N, rows})), 256, 0, h->s>>>(
+      P, N, rows, flag, n_dev, capacity, h->ob_pt.p, h->desc_pt.p, h->pt_live.p, t.odead, t.ddead, res + 3 + P);
+  return compact(h, t, res + 1);
+}
+
+// CSfM::cullKeyFrames (mode 0), CMap::removeFrame (1) and
+// CMap::arePointsSeenByAtLeast (2) over the keyframes' lists: one host
+// synchronisation, the decisions and the removals on the device
+int walk_keyframes(sfm_map* h, int mode, int32_t n_kf, const int32_t* frame_no, const int32_t* off, const int32_t* pts,
+                   int32_t n_frames, double ratio, int32_t* culled) {
+  if (!h) return mapfail(SFM_EINVAL, "NULL handle");
+  if (n_kf < 0) return mapfail(SFM_EINVAL, "negative size");
+  if (n_kf == 0) return 0;
+  if (!frame_no || !off || !culled) return mapfail(SFM_EINVAL, "NULL argument");
+  if (off[0] != 0) return mapfail(SFM_EINVAL, "off[0] must be 0");
+  for (int k = 0; k < n_kf; ++k)
+    if (off[k + 1] < off[k]) return mapfail(SFM_EINVAL, "off must not decrease");
+  const int32_t total = off[n_kf];
+  if (total && !pts) return mapfail(SFM_EINVAL, "NULL point list");
+  if (int rc = check_live(h, total, pts)) return rc;
+  if (mode != 1 && !(ratio == ratio)) return mapfail(SFM_EINVAL, "ratio is NaN");
+  if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
+  if (int rc = ensure_csrs(h)) return rc;
+  int rc = 0;
+  const int P = h->n_pts;
+  const int64_t N = h->ob_pt.n;
+  // one upload: frame numbers, offsets, thresholds, lists
+  std::vector<int32_t> in(size_t(3) * n_kf + 1 + size_t(total));
+  int32_t* in_f = in.data();
+  int32_t* in_off = in_f + n_kf;
+  int32_t* in_thr = in_off + n_kf + 1;
+  int32_t* in_pts = in_thr + n_kf;
+  for (int k = 0; k < n_kf; ++k) {
+    in_f[k] = frame_no[k];
+    // int ptsThreshold = ceil(ratioPtsThreshold * pts3DIdx.size()), the product in double (CMap.cpp:546)
+    const double v = mode == 1 ? 0.0 : std::ceil(ratio * double(off[k + 1] - off[k]));
+    in_thr[k] = v >= double(INT_MAX) ? INT_MAX : v <= double(INT_MIN) ? INT_MIN : int32_t(v);
+  }
+  std::memcpy(in_off, off, sizeof(int32_t) * (size_t(n_kf) + 1));
+  if (total) std::memcpy(in_pts, pts, sizeof(int32_t) * size_t(total));
+  auto* din = static_cast<int32_t*>(scratch(h, "kin", sizeof(int32_t) * in.size(), &rc));
+  auto* res = static_cast<int32_t*>(scratch(h, "kres", sizeof(int32_t) * (size_t(n_kf) + 6), &rc));
+  auto* nobs = static_cast<int32_t*>(scratch(h, "knobs", sizeof(int32_t) * size_t(std::max(P, 1)), &rc));
+  auto* cnt = static_cast<int32_t*>(scratch(h, "kcnt", sizeof(int32_t) * size_t(std::max(P, 1)), &rc));
+  auto* own = static_cast<uint8_t*>(scratch(h, "kown", size_t(std::max(total, 1)), &rc));
+  if (rc) return rc;
+  Tomb t;
+  if (int r = tomb_begin(h, &t)) return r;
+  if (hipMemcpyAsync(din, in.data(), sizeof(int32_t) * in.size(), hipMemcpyHostToDevice, h->s) != hipSuccess)
+    return mapfail(SFM_EIO, "upload failed");
+  (void)hipMemsetAsync(res, 0, sizeof(int32_t) * (size_t(n_kf) + 6), h->s);
+  (void)hipMemsetAsync(cnt, 0, sizeof(int32_t) * size_t(std::max(P, 1)), h->s);
+  if (P) k_nobs<<<grid(P), 256, 0, h->s>>>(P, h->ooff, nobs);
+  KfWalk a;
+  a.n_walk = mode == 0 ? n_kf - 1 : n_kf;  // (the newest keyframe is never tried, CSfM.cpp:716)
+  a.mode = mode;
+  a.n_frames = n_frames;
+  a.frame_no = din;
+  a.off = din + n_kf;
+  a.thr = din + 2 * size_t(n_kf) + 1;
+  a.pts = din + 3 * size_t(n_kf) + 1;
+  a.ob_frame = h->ob_frame.p;
+  a.orow = h->orow;
+  a.ooff = h->ooff;
+  a.drow = h->drow;
+  a.doff = h->doff;
+  a.odead = t.odead;
+  a.ddead = t.ddead;
+  a.own = own;
+  a.nobs = nobs;
+  a.views = h->pt_views.p;
+  a.cnt = cnt;
+  a.culled = res;
+  a.err = res + n_kf;
+  if (a.n_walk > 0) k_walk_keyframes<<<1, 1024, 0, h->s>>>(a);
+  if (mode != 2) {
+    if (N) k_clear_mm<<<grid(N), 256, 0, h->s>>>(N, h->ob_frame.p, t.odead, n_kf, a.frame_no, res, h->ob_mm.p);
+    if (int r = compact(h, t, res + n_kf + 4)) return r;
+  }
+  int32_t* ph = pin_reserve(h, size_t(n_kf) + 6, &rc);
+  if (rc) return rc;
+  (void)hipMemcpyAsync(ph, res, sizeof(int32_t) * (size_t(n_kf) + 6), hipMemcpyDeviceToHost, h->s);
+  if (int r = sync(h)) return r;
+  if (mode != 2) compact_done(h, ph + n_kf + 4);
+  std::memcpy(culled, ph, sizeof(int32_t) * size_t(n_kf));
+  const int32_t* err = ph + n_kf;
+  if (err[0])
+    return mapfail(SFM_EINVAL, "removeFrame(" + std::to_string(err[3]) + "): point " + std::to_string(err[2]) +
+                                   " of keyframe " + std::to_string(err[1]) +
+                                   " does not hold the frame (with a descriptor row) where the bisection of its "
+                                   "frame list ends; this keyframe was left as it was");
   return 0;
 }
 
@@ -399,7 +896,8 @@ int sfm_map_destroy(sfm_map* h) {
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->s);
   for (void* p : {(void*)h->ob_pt.p, (void*)h->ob_frame.p, (void*)h->ob_idx.p, (void*)h->X.p, (void*)h->desc.p,
-                  (void*)h->desc_pt.p})
+                  (void*)h->desc_pt.p, (void*)h->ob_mm.p, (void*)h->pt_time.p, (void*)h->pt_kf.p,
+                  (void*)h->pt_views.p, (void*)h->pt_live.p})
     if (p) (void)hipFree(p);
   for (auto& e : h->scratch)
     if (e.second.first) (void)hipFree(e.second.first);
@@ -440,6 +938,15 @@ int sfm_map_add_new_points(sfm_map* h, int32_t n_pts, const double* pts3d, int32
   if (int rc = append(h, h->ob_pt, pt.data(), m)) return rc;
   if (int rc = append(h, h->ob_frame, fr.data(), m)) return rc;
   if (int rc = append(h, h->ob_idx, ix.data(), m)) return rc;
+  if (int rc = append_fill(h, h->ob_mm, 1, m)) return rc;
+  // views = the frame count, ages 0, in _pts3DIdx (CMap.cpp:36-78)
+  if (int rc = append_fill(h, h->pt_time, 0, n_pts)) return rc;
+  if (int rc = append_fill(h, h->pt_kf, 0, n_pts)) return rc;
+  if (int rc = append_fill(h, h->pt_views, 0, n_pts)) return rc;
+  if (int rc = append_fill(h, h->pt_live, 1, n_pts)) return rc;
+  if (n_frames) k_fill_i32<<<grid(n_pts), 256, 0, h->s>>>(n_pts, h->pt_views.p + h->n_pts, n_frames);
+  h->live_h.resize(size_t(h->n_pts) + n_pts, 1);
+  h->n_live += n_pts;
   if (pts3d_idx)
     for (int32_t i = 0; i < n_pts; ++i) pts3d_idx[i] = h->n_pts + i;
   h->n_pts += n_pts;
@@ -453,12 +960,14 @@ int sfm_map_add_point_matches(sfm_map* h, int32_t n, const int32_t* pts3d_idx, c
   if (n < 0) return mapfail(SFM_EINVAL, "negative size");
   if (n == 0) return 0;
   if (!pts3d_idx || !pts2d_idx) return mapfail(SFM_EINVAL, "NULL argument");
-  if (int rc = check_pts(h, n, pts3d_idx)) return rc;
+  if (int rc = check_live(h, n, pts3d_idx)) return rc;
   if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
   std::vector<int32_t> fr(size_t(n), frame_no);
   if (int rc = append(h, h->ob_pt, pts3d_idx, n)) return rc;
   if (int rc = append(h, h->ob_frame, fr.data(), n)) return rc;
   if (int rc = append(h, h->ob_idx, pts2d_idx, n)) return rc;
+  if (int rc = append_fill(h, h->ob_mm, 1, n)) return rc;
+  k_add_views<<<grid(n), 256, 0, h->s>>>(n, h->ob_pt.p + h->ob_pt.n - n, h->pt_views.p);  // _ptsViews[idx]++
   h->ocsr = false;
   return sync(h);
 }
@@ -468,7 +977,7 @@ int sfm_map_add_descriptors(sfm_map* h, int32_t n, const int32_t* pts3d_idx, con
   if (n < 0) return mapfail(SFM_EINVAL, "negative size");
   if (n == 0) return 0;
   if (!pts3d_idx || !desc) return mapfail(SFM_EINVAL, "NULL argument");
-  if (int rc = check_pts(h, n, pts3d_idx)) return rc;
+  if (int rc = check_live(h, n, pts3d_idx)) return rc;
   if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
   // rows are desc_bytes = 8 W bytes: copy as words (unaligned host bytes)
   std::vector<uint64_t> words(size_t(n) * h->W);
@@ -550,8 +1059,8 @@ int sfm_map_points_in_frames(sfm_map* h, int32_t n_frames, const int32_t* frame_
   if (rc) return rc;
   (void)hipMemcpyAsync(fset, fs.data(), sizeof(int32_t) * fs.size(), hipMemcpyHostToDevice, h->s);
   (void)hipMemsetAsync(mark, 0, size_t(P), h->s);
-  k_mark_frames<<<grid(h->ob_pt.n), 256, 0, h->s>>>(h->ob_pt.n, h->ob_pt.p, h->ob_frame.p, fset, int(fs.size()),
-                                                    mark);
+  k_mark_frames<<<grid(h->ob_pt.n), 256, 0, h->s>>>(h->ob_pt.n, h->ob_pt.p, h->ob_frame.p, h->ob_mm.p, fset,
+                                                    int(fs.size()), mark);
   hipcub::CountingInputIterator<int32_t> it(0);
   size_t bytes = 0;
   (void)hipcub::DeviceSelect::Flagged(nullptr, bytes, it, mark, out, dn, P, h->s);
@@ -586,7 +1095,7 @@ int sfm_map_points_in_frame(sfm_map* h, int32_t frame_no, int32_t capacity, int3
   auto* sel = static_cast<int32_t*>(scratch(h, "fsel", sizeof(int32_t) * size_t(N), &rc));
   auto* dn = static_cast<int32_t*>(scratch(h, "fn", sizeof(int32_t), &rc));
   if (rc) return rc;
-  k_flag_frame<<<grid(N), 256, 0, h->s>>>(N, h->ob_frame.p, frame_no, flag);
+  k_flag_frame<<<grid(N), 256, 0, h->s>>>(N, h->ob_frame.p, h->ob_mm.p, frame_no, flag);
   hipcub::CountingInputIterator<int32_t> it(0);
   size_t bytes = 0;
   (void)hipcub::DeviceSelect::Flagged(nullptr, bytes, it, flag, sel, dn, int(N), h->s);
@@ -661,7 +1170,7 @@ int sfm_map_points_in_frame_multi(sfm_map* h, int32_t n_frames, const int32_t* f
   if (rc) return rc;
   (void)hipMemcpyAsync(dfr, fr.data(), sizeof(int2) * fr.size(), hipMemcpyHostToDevice, h->s);
   (void)hipMemsetAsync(fcnt, 0, sizeof(int32_t) * (size_t(n_frames) + 1), h->s);
-  k_frame_rank<<<grid(N), 256, 0, h->s>>>(N, h->ob_frame.p, dfr, n_frames, key, iv);
+  k_frame_rank<<<grid(N), 256, 0, h->s>>>(N, h->ob_frame.p, h->ob_mm.p, dfr, n_frames, key, iv);
   k_count_keys<<<grid(N), 256, 0, h->s>>>(N, reinterpret_cast<const int32_t*>(key), fcnt);
   int bits = 1;
   while ((1 << bits) <= n_frames) ++bits;
@@ -722,7 +1231,7 @@ int sfm_map_representative_descriptors(sfm_map* h, int32_t n, const int32_t* pts
   if (!h) return mapfail(SFM_EINVAL, "NULL handle");
   if (n <= 0) return n < 0 ? mapfail(SFM_EINVAL, "negative size") : 0;
   if (!pts3d_idx || !desc_out) return mapfail(SFM_EINVAL, "NULL argument");
-  if (int rc = check_pts(h, n, pts3d_idx)) return rc;
+  if (int rc = check_live(h, n, pts3d_idx)) return rc;
   if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
   int rc = 0;
   const int64_t rows = h->desc.n / h->W;
@@ -778,7 +1287,7 @@ int sfm_map_match_frame(sfm_map* h, sfm_matcher* mt, int32_t n_frames, const int
     return mapfail(SFM_EINVAL, "NULL argument");
   if (matcher_words(mt) != h->W || matcher_device(mt) != h->device)
     return mapfail(SFM_EINVAL, "the map and the matcher differ in descriptor width or device");
-  if (int rc = check_pts(h, n_existing, existing_pts)) return rc;
+  if (int rc = check_live(h, n_existing, existing_pts)) return rc;
   const int n_cur = matcher_current_n(mt);
   if (n_cur < 0) return mapfail(SFM_EINVAL, "push the current frame to the matcher first");
   for (int i = 0; i < n_train; ++i)
@@ -820,7 +1329,8 @@ int sfm_map_match_frame(sfm_map* h, sfm_matcher* mt, int32_t n_frames, const int
   std::memcpy(h->pin + fs.size() + n_existing, train_idx, sizeof(int32_t) * size_t(n_train));
   (void)hipMemcpyAsync(fset, h->pin, sizeof(int32_t) * n_up, hipMemcpyHostToDevice, h->s);
   (void)hipMemsetAsync(mark, 0, size_t(P), h->s);
-  k_mark_frames<<<grid(h->ob_pt.n), 256, 0, h->s>>>(h->ob_pt.n, h->ob_pt.p, h->ob_frame.p, fset, int(fs.size()), mark);
+  k_mark_frames<<<grid(h->ob_pt.n), 256, 0, h->s>>>(h->ob_pt.n, h->ob_pt.p, h->ob_frame.p, h->ob_mm.p, fset,
+                                                    int(fs.size()), mark);
   if (n_existing) k_unmark<<<grid(n_existing), 256, 0, h->s>>>(n_existing, fset + fs.size(), mark);
   hipcub::CountingInputIterator<int32_t> it(0);
   size_t bytes = 0;
@@ -864,6 +1374,161 @@ int sfm_map_match_frame(sfm_map* h, sfm_matcher* mt, int32_t n_frames, const int
   }
   *n_matches = m;
   return 0;
+}
+
+// ---- culling: CMap.cpp:384-574 and CSfM::cullKeyFrames.  Every call makes
+// one host synchronisation (sfm_map_n_live none), besides buffer growth and
+// a stale CSR's rebuild, which enqueue only.
+
+int sfm_map_update_point_views(sfm_map* h, int32_t n, const int32_t* pts3d_idx) {
+  if (!h) return mapfail(SFM_EINVAL, "NULL handle");
+  if (n <= 0) return n < 0 ? mapfail(SFM_EINVAL, "negative size") : 0;
+  if (!pts3d_idx) return mapfail(SFM_EINVAL, "NULL argument");
+  if (int rc = check_live(h, n, pts3d_idx)) return rc;
+  if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
+  int rc = 0;
+  auto* di = static_cast<int32_t*>(scratch(h, "vi", sizeof(int32_t) * size_t(n), &rc));
+  if (rc) return rc;
+  if (hipMemcpyAsync(di, pts3d_idx, sizeof(int32_t) * size_t(n), hipMemcpyHostToDevice, h->s) != hipSuccess)
+    return mapfail(SFM_EIO, "upload failed");
+  k_add_views<<<grid(n), 256, 0, h->s>>>(n, di, h->pt_views.p);
+  return sync(h);
+}
+
+int sfm_map_increment_age(sfm_map* h, int32_t t_inc, int32_t kf_inc) {
+  if (!h) return mapfail(SFM_EINVAL, "NULL handle");
+  if (h->n_pts == 0) return 0;
+  if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
+  k_age<<<grid(h->n_pts), 256, 0, h->s>>>(h->n_pts, h->pt_live.p, h->pt_time.p, h->pt_kf.p, t_inc, kf_inc);
+  return sync(h);
+}
+
+int sfm_map_n_live(sfm_map* h, int32_t* n) {
+  if (!h || !n) return mapfail(SFM_EINVAL, "NULL argument");
+  *n = h->n_live;
+  return 0;
+}
+
+int sfm_map_point_state(sfm_map* h, int32_t n, const int32_t* pts3d_idx, int32_t* out) {
+  if (!h) return mapfail(SFM_EINVAL, "NULL handle");
+  if (n <= 0) return n < 0 ? mapfail(SFM_EINVAL, "negative size") : 0;
+  if (!pts3d_idx || !out) return mapfail(SFM_EINVAL, "NULL argument");
+  if (int rc = check_pts(h, n, pts3d_idx)) return rc;
+  if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
+  if (int rc = ensure_csrs(h)) return rc;
+  int rc = 0;
+  auto* di = static_cast<int32_t*>(scratch(h, "vi", sizeof(int32_t) * size_t(n), &rc));
+  auto* dout = static_cast<int32_t*>(scratch(h, "vo", sizeof(int32_t) * 5 * size_t(n), &rc));
+  if (rc) return rc;
+  if (hipMemcpyAsync(di, pts3d_idx, sizeof(int32_t) * size_t(n), hipMemcpyHostToDevice, h->s) != hipSuccess)
+    return mapfail(SFM_EIO, "upload failed");
+  k_point_state<<<grid(n), 256, 0, h->s>>>(n, di, h->pt_time.p, h->pt_kf.p, h->pt_views.p, h->ooff, h->pt_live.p,
+                                           dout);
+  if (hipMemcpyAsync(out, dout, sizeof(int32_t) * 5 * size_t(n), hipMemcpyDeviceToHost, h->s) != hipSuccess)
+    return mapfail(SFM_EIO, "download failed");
+  return sync(h);
+}
+
+int sfm_map_remove_points_threshold(sfm_map* h, int32_t kf_threshold, float track_threshold, int32_t capacity,
+                                    int32_t* cull_idx, int32_t* n_cull, int32_t* status) {
+  SFM_TRACE("sfm_map_remove_points_threshold");
+  if (!h || !n_cull) return mapfail(SFM_EINVAL, "NULL argument");
+  *n_cull = 0;
+  if (capacity < 0 || kf_threshold < 0) return mapfail(SFM_EINVAL, "negative size or threshold");
+  if (capacity && !cull_idx) return mapfail(SFM_EINVAL, "NULL output");
+  const int P = h->n_pts;
+  if (P == 0) return 0;
+  if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
+  if (int rc = ensure_csrs(h)) return rc;
+  int rc = 0;
+  const size_t nres = 3 + 2 * size_t(P);  // count, sizes after, the culled list, the status
+  auto* res = static_cast<int32_t*>(scratch(h, "cres", sizeof(int32_t) * nres, &rc));
+  auto* flag = static_cast<uint8_t*>(scratch(h, "cflag", size_t(P), &rc));
+  if (rc) return rc;
+  k_cull_flag<<<grid(P), 256, 0, h->s>>>(P, h->pt_live.p, h->pt_time.p, h->pt_kf.p, h->pt_views.p, h->ooff,
+                                         kf_threshold, track_threshold, flag);
+  hipcub::CountingInputIterator<int32_t> it(0);
+  size_t bytes = 0;
+  (void)hipcub::DeviceSelect::Flagged(nullptr, bytes, it, flag, res + 3, res, P, h->s);
+  void* tmp = scratch(h, "csel", bytes, &rc);
+  if (rc) return rc;
+  if (hipcub::DeviceSelect::Flagged(tmp, bytes, it, flag, res + 3, res, P, h->s) != hipSuccess)
+    return mapfail(SFM_EIO, "select failed");
+  if (int r = kill_and_compact(h, flag, res, capacity, res)) return r;
+  int32_t* ph = pin_reserve(h, nres, &rc);
+  if (rc) return rc;
+  (void)hipMemcpyAsync(ph, res, sizeof(int32_t) * nres, hipMemcpyDeviceToHost, h->s);
+  if (int r = sync(h)) return r;
+  const int32_t n = ph[0];
+  *n_cull = n;
+  if (n > capacity)  // (the device saw the same comparison and removed nothing)
+    return mapfail(SFM_EINVAL, "capacity " + std::to_string(capacity) + " < " + std::to_string(n));
+  compact_done(h, ph + 1);
+  for (int32_t i = 0; i < n; ++i) {
+    cull_idx[i] = ph[3 + i];
+    h->live_h[size_t(ph[3 + i])] = 0;
+  }
+  h->n_live -= n;
+  if (status) std::memcpy(status, ph + 3 + P, sizeof(int32_t) * size_t(P));
+  return 0;
+}
+
+int sfm_map_remove_points(sfm_map* h, int32_t n, const int32_t* pts3d_idx, int32_t* status) {
+  if (!h) return mapfail(SFM_EINVAL, "NULL handle");
+  if (n < 0) return mapfail(SFM_EINVAL, "negative size");
+  if (n && !pts3d_idx) return mapfail(SFM_EINVAL, "NULL argument");
+  if (int rc = check_live(h, n, pts3d_idx)) return rc;
+  for (int32_t i = 1; i < n; ++i)
+    if (pts3d_idx[i] <= pts3d_idx[i - 1])
+      return mapfail(SFM_EINVAL, "the list must be ascending and distinct (at " + std::to_string(i) + ")");
+  const int P = h->n_pts;
+  if (n == 0) {
+    if (status && P) std::memset(status, 0, sizeof(int32_t) * size_t(P));
+    return 0;
+  }
+  if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
+  int rc = 0;
+  const size_t nres = 3 + 2 * size_t(P);
+  auto* res = static_cast<int32_t*>(scratch(h, "cres", sizeof(int32_t) * nres, &rc));
+  auto* flag = static_cast<uint8_t*>(scratch(h, "cflag", size_t(P), &rc));
+  auto* di = static_cast<int32_t*>(scratch(h, "vi", sizeof(int32_t) * size_t(n), &rc));
+  if (rc) return rc;
+  if (hipMemcpyAsync(di, pts3d_idx, sizeof(int32_t) * size_t(n), hipMemcpyHostToDevice, h->s) != hipSuccess)
+    return mapfail(SFM_EIO, "upload failed");
+  (void)hipMemsetAsync(flag, 0, size_t(P), h->s);
+  k_flag_list<<<grid(n), 256, 0, h->s>>>(n, di, flag);
+  if (int r = kill_and_compact(h, flag, nullptr, 0, res)) return r;
+  int32_t* ph = pin_reserve(h, nres, &rc);
+  if (rc) return rc;
+  (void)hipMemcpyAsync(ph + 1, res + 1, sizeof(int32_t) * (nres - 1), hipMemcpyDeviceToHost, h->s);
+  if (int r = sync(h)) return r;
+  compact_done(h, ph + 1);
+  for (int32_t i = 0; i < n; ++i) h->live_h[size_t(pts3d_idx[i])] = 0;
+  h->n_live -= n;
+  if (status) std::memcpy(status, ph + 3 + P, sizeof(int32_t) * size_t(P));
+  return 0;
+}
+
+int sfm_map_remove_frame(sfm_map* h, int32_t frame_no, int32_t n, const int32_t* pts3d_idx) {
+  if (n < 0) return mapfail(SFM_EINVAL, "negative size");
+  const int32_t off[2] = {0, n};
+  int32_t culled = 0;
+  return walk_keyframes(h, 1, 1, &frame_no, off, pts3d_idx, 0, 0.0, &culled);
+}
+
+int sfm_map_points_seen_by_at_least(sfm_map* h, int32_t n, const int32_t* pts3d_idx, int32_t n_frames, double ratio,
+                                    int32_t* result) {
+  if (!result) return mapfail(SFM_EINVAL, "NULL argument");
+  *result = 0;
+  if (n < 0) return mapfail(SFM_EINVAL, "negative size");
+  const int32_t off[2] = {0, n}, f = 0;
+  return walk_keyframes(h, 2, 1, &f, off, pts3d_idx, n_frames, ratio, result);
+}
+
+int sfm_map_cull_keyframes(sfm_map* h, int32_t n_kf, const int32_t* frame_no, const int32_t* off, const int32_t* pts,
+                           int32_t n_frames, double ratio, int32_t* culled) {
+  SFM_TRACE("sfm_map_cull_keyframes");
+  return walk_keyframes(h, 0, n_kf, frame_no, off, pts, n_frames, ratio, culled);
 }
 
 }  // extern "C"

@@ -38,8 +38,24 @@ the map's scale is then the unit baseline of the first two keyframes.
 Scope notes: GeometryUtils (filterMatches, projectPoints) is not
 in the reference tree, so filterMatches is restated from its call site
 (CSfM.cpp:164-165) as positive depth in both keyframes and the point-to-
-epipolar-line distance <= _maxReprErr both ways; map-point and keyframe
-culling (CSfM.cpp:232-246) are not restated.
+epipolar-line distance <= _maxReprErr both ways.
+
+Culling (cull=True; CSfM.cpp:232-252, 692-752, off by default): between the
+pair loop and the BA, CSfM::cullMapPoints (CMap::removePointsThreshold on
+the device map store, then CFrame::cullPoints on every keyframe, the
+previous and the current frame) and CSfM::cullKeyFrames (the whole greedy
+loop in one device call, sfm_map_cull_keyframes), the culled keyframes
+leaving self.kfs.  The counters behind the rules live in the map store:
+CMap::updatePointViews (the PnP inliers, CSfM.cpp:576, then the re-found
+points, :685) and the per-frame incrementMapAge(1, 0) (:629, lost frames
+included) are accumulated on the host and flushed in one call each at the
+start of mapping, before any point is created or removed, which equals the
+per-frame calls (points are created only by init and mapping) and adds no
+device call to the tracking path; incrementMapAge(0, 2) follows init
+(:962) and incrementMapAge(0, 1) every mapping's BA (:304).  Keyframes own a
+fixed slot of the matcher's keyframe store, taken from a counter when they
+are stored (their list position while nothing is culled); a culled
+keyframe's slot is emptied.
 """
 from __future__ import annotations
 
@@ -173,6 +189,7 @@ class _Frame:
 
     def __init__(self, no, pts, desc):
         self.no, self.pts, self.desc = no, pts, desc
+        self.slot = -1  # keyframes: the matcher's keyframe-store slot
         self.pt3d = np.full(len(pts), -1, np.int64)
         self.rot, self.t = np.zeros(3), np.zeros(3)
 
@@ -181,7 +198,7 @@ class _Frame:
 
     def copy(self):
         f = _Frame(self.no, self.pts, self.desc)
-        f.pt3d, f.rot, f.t = self.pt3d.copy(), self.rot.copy(), self.t.copy()
+        f.pt3d, f.rot, f.t, f.slot = self.pt3d.copy(), self.rot.copy(), self.t.copy(), self.slot
         return f
 
     def P(self, K):
@@ -232,7 +249,8 @@ def _filter_matches(K, f0, f1, uv0, uv1, X, max_err):
 
 class LiveSfM:
     def __init__(self, stream: KeypointStream | None = None, device: int = 0, init_gap: int = 5,
-                 init: str = "known", init_options: dict | None = None):
+                 init: str = "known", init_options: dict | None = None, cull: bool = False,
+                 cull_kf_rate: float = 0.9, min_visibility: int = 3):
         if init not in ("known", "estimate"):
             raise ValueError(f"init must be 'known' or 'estimate', not {init!r}")
         self.init = init
@@ -250,6 +268,15 @@ class LiveSfM:
         self.lost = 0
         self.ba_log: list[dict] = []
         self.stats = {"frames": 0, "tracked": 0, "pnp_inliers": 0, "map_matches": 0, "new_points": 0}
+        # CSfM::cullMapPoints / cullKeyFrames (thresholdRate, _minVisibilityFrameNo: CSfM.h:70, CSfM.cpp:50)
+        self.cull, self.cull_kf_rate, self.min_visibility = bool(cull), float(cull_kf_rate), int(min_visibility)
+        self.cull_log: list[dict] = []
+        self._views: list[np.ndarray] = []   # updatePointViews since the last mapping
+        self._age = 0                        # incrementMapAge(1, 0) since the last mapping
+        self._cur: _Frame | None = None
+        self._n_slots = 0
+        if self.cull:
+            self.stats.update({"culled_points": 0, "culled_keyframes": 0})
         self.times = {"stream": 0.0, "track": 0.0, "map_match": 0.0, "mapping": 0.0, "ba": 0.0}
         self._pending: _Frame | None = None
         # the fused device calls (SFM_LIVE_COMPOSED=1: the composed calls,
@@ -273,7 +300,7 @@ class LiveSfM:
         if not self.kfs:
             f = _Frame(k, pts, desc)
             self.kfs.append(f)                  # first keyframe at the origin (CFrame.cpp:229-235)
-            self.matcher.store_keyframe(0, pts, desc)
+            self._store_keyframe(f)
             self.matcher.push_frame(pts, desc)
             self.prev = f
             return
@@ -313,8 +340,10 @@ class LiveSfM:
         f0.pt3d[i0] = idx
         f1.pt3d[i1] = idx
         self.kfs.append(f1.copy())
-        self.matcher.store_keyframe(1, f1.pts, f1.desc)
+        self._store_keyframe(self.kfs[-1])
         self.stats["new_points"] += len(idx)
+        if self.cull:
+            self.map.incrementMapAge(0, 2)      # CSfM.cpp:962
         self._bundle_adjust()
         self.prev = f1
         self.prev.rot, self.prev.t = self.kfs[-1].rot.copy(), self.kfs[-1].t.copy()
@@ -323,6 +352,7 @@ class LiveSfM:
     def _tracking(self, k, pts, desc) -> None:
         t0 = time.perf_counter()
         cur = _Frame(k, pts, desc)
+        self._age += 1                          # CSfM.cpp:629, whatever the frame's fate
         self.matcher.push_frame(pts, desc)
         if self.fused_track:
             # matchFeatures + getPointsAtIdx + solvePnPRansac in one device call
@@ -347,6 +377,8 @@ class LiveSfM:
             ikp, ipt = cm[inl], m3[inl]
         cur.rot, cur.t = np.asarray(r, float), np.asarray(t, float)
         cur.pt3d[ikp] = ipt
+        if self.cull:
+            self._views.append(np.asarray(ipt, np.int32).copy())    # CSfM.cpp:576
         self.stats["tracked"] += 1
         self.stats["pnp_inliers"] += len(ikp)
         t1 = time.perf_counter()
@@ -356,12 +388,14 @@ class LiveSfM:
         if self._add_keyframe(cur):
             kf = cur.copy()
             self.kfs.append(kf)
-            self.matcher.store_keyframe(len(self.kfs) - 1, kf.pts, kf.desc)
+            self._store_keyframe(kf)
             m = np.flatnonzero(kf.pt3d >= 0)
             self.map.addPointMatches(kf.pt3d[m], m, kf.no)
             self.map.addDescriptors(kf.pt3d[m], kf.desc[m])
             t2 = time.perf_counter()
+            self._cur = cur
             self._mapping()
+            self._cur = None
             self.times["mapping"] += time.perf_counter() - t2
             # CSfM.cpp:261: the previous frame takes the adjusted keyframe pose
             cur.rot, cur.t = self.kfs[-1].rot.copy(), self.kfs[-1].t.copy()
@@ -381,6 +415,8 @@ class LiveSfM:
                                          cur.t, self.K, un, 0.8, 0.0, MAX_REPR_ERR)
             cur.pt3d[km] = pm
             self.stats["map_matches"] += len(pm)
+            if self.cull:
+                self._views.append(np.asarray(pm, np.int32).copy())  # CSfM.cpp:685
             return
         cov = self.map.getPointsInFrames([f.no for f in self.kfs])
         existing = np.unique(cur.pt3d[cur.pt3d >= 0])
@@ -394,6 +430,8 @@ class LiveSfM:
         mi, fi = self.matcher.match(uv, desc, cur.pts[un], cur.desc[un], 0.8, 0.0, MAX_REPR_ERR)
         cur.pt3d[un[fi]] = new[mi]
         self.stats["map_matches"] += len(mi)
+        if self.cull:
+            self._views.append(np.asarray(new[mi], np.int32).copy())
 
     def _add_keyframe(self, cur: _Frame) -> bool:
         """CSfM::addKeyFrame (CSfM.cpp:481-497)."""
@@ -404,7 +442,48 @@ class LiveSfM:
         return a and b and c
 
     # ---- CSfM::mapping -------------------------------------------------------------
+    def _store_keyframe(self, kf: _Frame) -> None:
+        kf.slot = self._n_slots
+        self._n_slots += 1
+        self.matcher.store_keyframe(kf.slot, kf.pts, kf.desc)
+
+    def _flush_counters(self) -> None:
+        """The tracked frames' updatePointViews / incrementMapAge(1, 0) since
+        the last mapping, one call each (the live set has not changed since)."""
+        if self._views:
+            v = np.concatenate(self._views)
+            if len(v):
+                self.map.updatePointViews(v)
+        self._views = []
+        if self._age:
+            self.map.incrementMapAge(self._age, 0)
+        self._age = 0
+
+    def _cull(self) -> None:
+        """CSfM::cullMapPoints, then CSfM::cullKeyFrames (CSfM.cpp:237-252)."""
+        culled_pts, status = self.map.removePointsThreshold()
+        if len(culled_pts):
+            frames = list(self.kfs)
+            for f in (self.prev, self._cur):
+                if f is not None and all(f is not g for g in frames):
+                    frames.append(f)
+            for f in frames:                    # CFrame::cullPoints
+                m = np.flatnonzero(f.pt3d >= 0)
+                f.pt3d[m[status[f.pt3d[m]] == -1]] = -1
+        lists = [(kf.no, kf.pt3d[kf.pt3d >= 0].astype(np.int32)) for kf in self.kfs]
+        culled = self.map.cullKeyFrames(lists, self.min_visibility, self.cull_kf_rate)
+        gone = [kf for kf, c in zip(self.kfs, culled) if c]
+        for kf in gone:
+            self.matcher.store_keyframe(kf.slot, np.zeros((0, 2)), np.zeros((0, self.stream.desc_bytes), np.uint8))
+        self.kfs = [kf for kf, c in zip(self.kfs, culled) if not c]
+        self.stats["culled_points"] += len(culled_pts)
+        self.stats["culled_keyframes"] += len(gone)
+        self.cull_log.append({"frame": self.frame_no, "points": np.asarray(culled_pts).copy(),
+                              "keyframes": [kf.no for kf in gone], "lists": lists})
+
     def _mapping(self) -> None:
+        if self.cull:
+            self._flush_counters()
         new_kf = self.kfs[-1]
         for i in range(len(self.kfs) - 1):
             kf = self.kfs[i]
@@ -413,7 +492,7 @@ class LiveSfM:
             if len(cu) < 2 or len(pu) < 2:
                 continue
             if self.resident_kf:
-                pi, ci = self.matcher.match_keyframes(i, pu, len(self.kfs) - 1, cu)
+                pi, ci = self.matcher.match_keyframes(kf.slot, pu, new_kf.slot, cu)
             else:
                 pi, ci = self.matcher.match(kf.pts[pu], kf.desc[pu], new_kf.pts[cu], new_kf.desc[cu])
             if not len(pi):
@@ -438,8 +517,8 @@ class LiveSfM:
                 uv, _ = _project(self.K, kj.rot, kj.t, Xf)
                 near_kf = abs(kj.no - kf.no) < abs(kj.no - new_kf.no)
                 if self.resident_kf:
-                    m0, m1 = self.matcher.match_keyframes(i if near_kf else len(self.kfs) - 1, p2 if near_kf else c2,
-                                                          j, uj, uv, 0.8, 0.0, MAX_REPR_ERR)
+                    m0, m1 = self.matcher.match_keyframes(kf.slot if near_kf else new_kf.slot, p2 if near_kf else c2,
+                                                          kj.slot, uj, uv, 0.8, 0.0, MAX_REPR_ERR)
                 else:
                     d = pdesc if near_kf else cdesc
                     m0, m1 = self.matcher.match(uv, d, kj.pts[uj], kj.desc[uj], 0.8, 0.0, MAX_REPR_ERR)
@@ -451,9 +530,13 @@ class LiveSfM:
             new_kf.pt3d[c2] = idx
             self.map.addDescriptors(idx, cdesc)
             self.stats["new_points"] += len(idx)
+        if self.cull:
+            self._cull()
         t0 = time.perf_counter()
         self._bundle_adjust()
         self.times["ba"] += time.perf_counter() - t0
+        if self.cull:
+            self.map.incrementMapAge(0, 1)      # CSfM.cpp:304
 
     def _bundle_adjust(self) -> None:
         """CSfM::bundleAdjustment over all keyframes (CSfM.cpp:300-348): per
