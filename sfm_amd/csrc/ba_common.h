@@ -178,6 +178,35 @@ __device__ __forceinline__ void swap_rows16(double& x, double& y) {  // x odd 16
   x = __hiloint2double(hi[0], lo[0]);
   y = __hiloint2double(hi[1], lo[1]);
 }
+// distance 32 for one pair of values (x = v[j], y = v[16 + j]): lanes 0..31
+// keep v[0..16), lanes 32..63 v[16..32)
+__device__ __forceinline__ double wave_sum32_first(double x, double y) {
+  swap_halves32(x, y);
+  return x + y;
+}
+// ... and the distances 16..1, from the 16 values the first exchange leaves
+// (for a caller that forms its 32 values pair by pair and so never holds
+// them all: wave_sum32_rest over wave_sum32_first(v[j], v[16 + j]) is
+// wave_sum32, operation for operation)
+__device__ __forceinline__ double wave_sum32_rest(double (&v)[16], int l) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {  // distance 16: even rows keep v[0..8), odd rows v[8..16)
+    swap_rows16(v[j], v[8 + j]);
+    v[j] = v[j] + v[8 + j];
+  }
+#pragma unroll
+  for (int h = 4; h >= 1; h >>= 1) {
+    const uint64_t m = (l & (2 * h)) ? ~0ull : 0ull;  // exchange distance 2h
+#pragma unroll
+    for (int j = 0; j < h; ++j) {
+      const uint64_t a = __builtin_bit_cast(uint64_t, v[j]), b = __builtin_bit_cast(uint64_t, v[h + j]);
+      const double keep = __builtin_bit_cast(double, (b & m) | (a & ~m));
+      const double send = __builtin_bit_cast(double, (a & m) | (b & ~m));
+      v[j] = keep + __shfl_xor(send, 2 * h);
+    }
+  }
+  return v[0] + __shfl_xor(v[0], 1);
+}
 __device__ __forceinline__ double wave_sum32(double (&v)[32], int l) {
 #pragma unroll
   for (int j = 0; j < 16; ++j) {  // distance 32: lanes 0..31 keep v[0..16), 32..63 v[16..32)

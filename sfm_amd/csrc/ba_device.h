@@ -211,10 +211,19 @@ void launch_schur(const DevProblem& d, double radius, bool add_diag, hipStream_t
 // off-diagonal blocks (k_schur_pts; tile_cnt != nullptr: overlapped with the
 // factorisation, blocks counted per 64x64 tile as they land)
 void launch_schur_diag(const DevProblem& d, double radius, bool add_diag, hipStream_t s);
-void launch_schur_offdiag(const DevProblem& d, int* tile_cnt, hipStream_t s);
+// cams_staged: camS already holds the cameras' records (launch_cam_sum_diag)
+void launch_schur_offdiag(const DevProblem& d, int* tile_cnt, hipStream_t s, bool cams_staged = false);
+// whether the Schur pair pass reads the cameras' staged records (camS)
+inline bool cam_records_used(const DevProblem& d) {
+  return d.n_blk && d.ptG && d.srec && d.camS && !d.schur_wg_blocks;
+}
 // launch_cam_sum_finalize (mode 1, with the gradient partials) and
-// launch_schur_diag in one launch (after launch_obs_prep, in the evaluation)
-void launch_cam_sum_diag(const DevProblem& d, double radius, bool add_diag, hipStream_t s);
+// launch_schur_diag in one launch (after launch_obs_prep, in the evaluation);
+// stage_cams: and k_cam_stage_rot's records, where the pair pass reads them
+void launch_cam_sum_diag(const DevProblem& d, double radius, bool add_diag, hipStream_t s, bool stage_cams = false);
+// the scaled launch_jacobian and launch_obs_prep in one camera-major pass
+// (k_jac_obs_prep; after the point pass that wrote ptS)
+void launch_jac_obs_prep(const DevProblem& d, hipStream_t s);
 void launch_pad_init(const DevProblem& d, hipStream_t s);
 void launch_pack_upper(const DevProblem& d, bool unpack, hipStream_t s);
 // dst = scale * src unless *gate == 0 (gate may be nullptr)

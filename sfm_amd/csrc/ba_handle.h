@@ -127,6 +127,14 @@ struct sfm_ba_handle {
   // stand-alone kernels first.
   double eval_radius = 0.0;
   bool prep_fresh = false;
+  // eval_fused (per solve; SFM_EVAL_SPLIT=1: off): such an evaluation runs
+  // its point pass first and then ONE camera-major pass for the scaled
+  // Jacobian sums and k_obs_prep_rc's (k_jac_obs_prep), and k_cam_sum_diag
+  // also leaves the cameras' staged records (camS).  cams_staged: it did, so
+  // the Schur pair pass skips k_cam_stage_rot -- an unsuccessful step leaves
+  // the cameras, and with them the records, as they are.
+  bool eval_fused = false;
+  bool cams_staged = false;
   int n_cu = 0;  // compute units of the device (queried once)
   // Schur / Cholesky overlap (DevProblem::overlap): the factorisation's
   // stream and the two events that fork and join it

@@ -831,6 +831,260 @@ __global__ __launch_bounds__(kThreads) void k_obs_prep_rc(const int32_t* __restr
   if (!(l & 1) && (l >> 1) < 27) dpart[size_t(i0 / 64) * 27 + (l >> 1)] = tot;
 }
 
+// ---------------------------------------------------------------------------
+// k_jac_obs_prep's arithmetic.  The compiler contracts a * b + c * d into one
+// fused multiply-add, and WHICH product goes into it depends on the code
+// around the expression: k_jacobian's and k_obs_prep_rc's source inlined into
+// a third kernel picked the other product in places and missed their bits by
+// an ulp.  So the fused kernel's sums are written out operation for operation
+// as those two kernels compile (contraction off, every fma explicit:
+// a * b + c * d is fma(a, b, c * d), a longer sum of products folds from the
+// left), for the kernel to produce their bits whatever surrounds it.
+__device__ __forceinline__ double mad2(double a, double b, double c, double d) {
+#pragma clang fp contract(off)
+  const double cd = c * d;
+  return fma(a, b, cd);
+}
+__device__ __forceinline__ double mad3(double a, double b, double c, double d, double e, double f) {
+  return fma(e, f, mad2(a, b, c, d));
+}
+// The camera side of an observation: both passes' J_c (12, jc[9] == 0) and
+// residual from the point in camera coordinates; kDiv: jac_record's form of
+// the projection (divisions), else obs_recompute's (products with 1 / z).
+// ab: a0 a1 a2 b1 b2 (d r / d pc).
+template <bool kDiv>
+__device__ __forceinline__ void obs_cam_side(const double* cr, const double* tc, const double* k, const double* sc,
+                                             const double X[3], const double Xq[3], double2 uvo, double jc[12],
+                                             double& r0, double& r1, double ab[5]) {
+#pragma clang fp contract(off)
+  const double fx = k[0], sk = k[1], cx = k[2], fy = k[3], cy = k[4];
+  const double pc0 = mad3(cr[0], X[0], cr[1], X[1], cr[2], X[2]) + tc[0];
+  const double pc1 = mad3(cr[3], X[0], cr[4], X[1], cr[5], X[2]) + tc[1];
+  const double pc2 = mad3(cr[6], X[0], cr[7], X[1], cr[8], X[2]) + tc[2];
+  const SharedDiv dz = shared_div(pc2);
+  const double iz = srcp(dz);
+  const double xp = kDiv ? sdiv(dz, pc0) : pc0 * iz, yp = kDiv ? sdiv(dz, pc1) : pc1 * iz;
+  const double s = mad2(fx, xp, sk, yp);
+  r0 = (s + cx) - uvo.x;
+  r1 = fma(fy, yp, cy) - uvo.y;
+  const double fyyp = fy * yp;
+  const double a0 = fx * iz, a1 = sk * iz, a2 = -s * iz, b1 = fy * iz, b2 = -fyyp * iz;
+  ab[0] = a0; ab[1] = a1; ab[2] = a2; ab[3] = b1; ab[4] = b2;
+#pragma unroll
+  for (int kk = 0; kk < 3; ++kk) {
+    const double* D = cr + 9 + 9 * kk;
+    const double q0 = mad3(D[0], Xq[0], D[1], Xq[1], D[2], Xq[2]);
+    const double q1 = mad3(D[3], Xq[0], D[4], Xq[1], D[5], Xq[2]);
+    const double q2 = mad3(D[6], Xq[0], D[7], Xq[1], D[8], Xq[2]);
+    jc[kk] = mad3(a0, q0, a1, q1, a2, q2) * sc[kk];
+    jc[6 + kk] = mad2(b1, q1, b2, q2) * sc[kk];
+  }
+  jc[3] = a0 * sc[3]; jc[4] = a1 * sc[4]; jc[5] = a2 * sc[5];
+  jc[9] = 0.0;        jc[10] = b1 * sc[4]; jc[11] = b2 * sc[5];
+}
+// k_jacobian's half of a chunk: the lane's cost and its share of the camera's
+// U_c (21, packed upper) and b_c (6) added to acc (lane l, cnt real observations).
+__device__ __forceinline__ double jac_half(const double* cr, const double* tc, const double* k, const double* sc,
+                                           const double X[3], double2 uvo, int cnt, int l, double (&acc)[32]) {
+#pragma clang fp contract(off)
+  double jc[12], r0, r1, ab[5];
+  obs_cam_side<true>(cr, tc, k, sc, X, X, uvo, jc, r0, r1, ab);
+  const double cl = 0.5 * mad2(r1, r1, r0, r0);  // (here the second square is the contracted one)
+  if (cnt < 64) {  // (a camera's last chunk: exact zeros from the padding lanes)
+    const bool real = l < cnt;
+#pragma unroll
+    for (int a = 0; a < 12; ++a) jc[a] = real ? jc[a] : 0.0;
+    r0 = real ? r0 : 0.0;
+    r1 = real ? r1 : 0.0;
+  }
+  int q = 0;
+#pragma unroll
+  for (int a = 0; a < 6; ++a)
+#pragma unroll
+    for (int b = a; b < 6; ++b, ++q) {
+      // (jc[9] is the constant 0: its square is folded away and the other
+      // square contracted with the sum itself)
+      if (a == 3 && b == 3) acc[q] = fma(jc[3], jc[3], acc[q]);
+      else acc[q] = acc[q] + mad2(jc[a], jc[b], jc[6 + a], jc[6 + b]);
+    }
+#pragma unroll
+  for (int a = 0; a < 6; ++a) acc[21 + a] = acc[21 + a] + mad2(jc[a], r0, jc[6 + a], r1);
+  return (l < cnt) ? cl : 0.0;
+}
+// k_obs_prep_rc's half: F = J_c^T M and the chunk's 27 sums to dst.  q: the
+// point's record (ptS); partial (wave-uniform): the chunk holds padding
+// slots, *obs < 0 in their lanes.  The 32 values go through wave_sum32's
+// exchanges with entries j and 16 + j formed and traded pair by pair: 16
+// sums live beside F instead of 32 values (the kernel carries acc as well).
+// (Row u of the packed upper triangle starts at entry up6_first(u).)
+constexpr int up6_first(int u) { return u * 6 - (u * (u - 1)) / 2; }
+constexpr int up6_row(int e) { return e >= 20 ? 5 : e >= 18 ? 4 : e >= 15 ? 3 : e >= 11 ? 2 : e >= 6 ? 1 : 0; }
+__device__ __forceinline__ void prep_half(const double* cr, const double* tc, const double* k, const double* sc,
+                                          const double q[kPtS], double2 uvo, bool partial,
+                                          const int32_t* __restrict__ obs, int l, double* __restrict__ dst) {
+#pragma clang fp contract(off)
+  const double X[3] = {q[0], q[1], q[2]}, sp[3] = {q[3], q[4], q[5]};
+  double jc[12], r0, r1, ab[5], e[6];
+  // (Xq: X again, opaque -- the dR X products are formed anew here, while pc,
+  // 1/z and a0, a1, b1 come from the Jacobian half: all of them held over
+  // that half cost the kernel its 3 waves per SIMD)
+  double Xq[3] = {X[0], X[1], X[2]};
+  asm volatile("" : "+v"(Xq[0]), "+v"(Xq[1]), "+v"(Xq[2]));
+  obs_cam_side<false>(cr, tc, k, sc, X, Xq, uvo, jc, r0, r1, ab);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {  // dr/dpc * R; J_X is this times the point's Jacobi scale
+    e[j] = mad3(ab[0], cr[j], ab[1], cr[3 + j], ab[2], cr[6 + j]);
+    e[3 + j] = mad2(ab[3], cr[3 + j], ab[4], cr[6 + j]);
+  }
+  const double l10 = q[6], l20 = q[7], l21 = q[8], i00 = q[9], i11 = q[10], i22 = q[11];
+  // M = J_X L^-T by rows; in J_X[1] - l10 M[0] and J_X[2] - l20 M[0] the scale
+  // product is the one contracted (J_X[1], J_X[2] are never rounded)
+  double M[6];
+#pragma unroll
+  for (int h = 0; h < 6; h += 3) {
+    M[h] = e[h] * sp[0] * i00;
+    const double l10m = l10 * M[h], l20m = l20 * M[h];
+    M[h + 1] = fma(e[h + 1], sp[1], -l10m) * i11;
+    M[h + 2] = fma(-l21, M[h + 1], fma(e[h + 2], sp[2], -l20m)) * i22;
+  }
+  r0 = r0 - mad3(M[0], q[12], M[1], q[13], M[2], q[14]);
+  r1 = r1 - mad3(M[3], q[12], M[4], q[13], M[5], q[14]);
+  double F[18];  // 6 x 3
+#pragma unroll
+  for (int u = 0; u < 6; ++u)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) F[3 * u + j] = mad2(jc[u], M[j], jc[6 + u], M[3 + j]);
+  if (partial) {
+    const bool real = *obs >= 0;
+#pragma unroll
+    for (int a = 0; a < 18; ++a) F[a] = real ? F[a] : 0.0;
+    r0 = real ? r0 : 0.0;
+    r1 = real ? r1 : 0.0;
+  }
+  auto entry = [&](int a) {  // (a: a constant after unrolling)
+    if (a >= 27) return 0.0;
+    if (a >= 21) return mad2(jc[a - 21], r0, jc[6 + a - 21], r1);
+    const int u = up6_row(a), w = u + (a - up6_first(u));
+    return mad3(F[3 * u], F[3 * w], F[3 * u + 1], F[3 * w + 1], F[3 * u + 2], F[3 * w + 2]);
+  };
+  double s[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) s[j] = wave_sum32_first(entry(j), entry(16 + j));
+  const double tot = wave_sum32_rest(s, l);
+  if (!(l & 1) && (l >> 1) < 27) dst[l >> 1] = tot;
+}
+
+// The scaled k_jacobian<false> and k_obs_prep_rc in one walk of the chunk
+// table (the evaluation that also prepares the coming step; the point pass,
+// which writes ptS, runs first: it reads nothing either pass produces).  The
+// grid, the XCD slice, each wave's run of chunks, the per-lane U_c / b_c sums
+// carried across a camera's chunks and the cost reduction are k_jacobian's;
+// per chunk the wave also forms k_obs_prep_rc's sums.  One index + uv stream
+// and one gather serve both: X and the Jacobi scale are ptS[0..5], copies of
+// X / scale_p (point_factor_body).  The two passes take the projection
+// differently (jac_record: divisions; obs_recompute: products with 1/z), so
+// both run, each feeding its own sums (jac_half, prep_half): every sum has
+// the bits of its stand-alone kernel.
+// Prefetch: index two chunks ahead, uv and the record's X one chunk ahead;
+// the rest of the record (the same line, in L2 since the prefetch) is
+// fetched after the Jacobian half, which needs X alone: with all 128 B held
+// a chunk ahead the kernel does not fit 3 waves per SIMD without scratch.
+__global__ __launch_bounds__(kThreads, 3) void k_jac_obs_prep(const int32_t* __restrict__ grp_off,
+                                                           const int4* __restrict__ chunks,
+                                                           const int32_t* __restrict__ cm_p,
+                                                           const double* __restrict__ uv_cm,
+                                                           const int32_t* __restrict__ cam_obs,
+                                                           const double* __restrict__ Kc,
+                                                           const double* __restrict__ cam,
+                                                           const double* __restrict__ camR,
+                                                           const double* __restrict__ scale_c,
+                                                           const double* __restrict__ ptS,
+                                                           double* __restrict__ part_cost, double* __restrict__ jpart,
+                                                           double* __restrict__ dpart, const int* __restrict__ gate) {
+  if (gate && *gate == 0) return;  // device LM loop: phase skipped
+  __shared__ double sh[4];
+  const int l = threadIdx.x & 63;
+  const int wv = wave_uniform(threadIdx.x >> 6);
+  // (k_jacobian's split: slice blockIdx.x % 8, one contiguous run per wave)
+  const int grp = blockIdx.x & 7;
+  const int nbg = (int(gridDim.x) - 1 - grp) / 8 + 1;
+  const int nw = nbg * (kThreads / 64);
+  const int wi = (blockIdx.x >> 3) * (kThreads / 64) + wv;
+  const int g0 = grp_off[grp], glen = grp_off[grp + 1] - g0;
+  int t = g0 + int(int64_t(glen) * wi / nw);
+  const int n_chunks = g0 + int(int64_t(glen) * (wi + 1) / nw);  // end of this wave's run
+  double cost = 0.0;
+  auto chunk_at = [&](int tt) { return chunks[tt < n_chunks ? tt : t]; };
+  int p_cur = 0, p_nxt = 0;                   // point index of chunks t, t + 1
+  double2 uv_cur = make_double2(0.0, 0.0);    // chunk t
+  double Xc[3] = {0.0, 0.0, 1.0};            // X of chunk t
+  auto ld_x = [&](int p, double (&x)[3]) {
+    const double* rp = ptS + size_t(kPtS) * p;
+    const double2 a = ld2(rp);
+    x[0] = a.x; x[1] = a.y; x[2] = rp[2];
+  };
+  if (t < n_chunks) {
+    const int64_t i = int64_t(chunks[t].y) + l;
+    p_cur = cm_p[i];
+    uv_cur = ld2(uv_cm + 2 * i);
+    p_nxt = cm_p[int64_t(chunk_at(t + 1).y) + l];
+    ld_x(p_cur, Xc);
+  }
+  // (as k_jacobian: no outstanding prologue loads at the loop entry)
+  asm volatile("" : "+v"(Xc[0]), "+v"(Xc[1]), "+v"(Xc[2]), "+v"(uv_cur.x), "+v"(uv_cur.y), "+v"(p_cur), "+v"(p_nxt));
+  double acc[32];  // this lane's share of the current camera's U_c (21) and b_c (6)
+#pragma unroll
+  for (int e = 0; e < 32; ++e) acc[e] = 0.0;
+  for (; t < n_chunks; ++t) {
+    const int4 ch = chunks[t];
+    const int c = ch.x, cnt = ch.z;
+    const int64_t ib = ch.y;
+    // ---- issue: chunk t+1's X and uv and chunk t+2's index ----
+    double Xn[3];
+    ld_x(p_nxt, Xn);
+    const int4 ch_n = chunk_at(t + 1);
+    const double2 uv_nxt = ld2(uv_cm + 2 * (int64_t(ch_n.y) + l));
+    const int p_nn = cm_p[int64_t(chunk_at(t + 2).y) + l];
+    // camera data: wave-uniform -> scalar loads
+    const double* cr = camR + size_t(kCamR) * c;
+    const double* k = Kc + 5 * size_t(c);
+    const double* tc = cam + 6 * size_t(c) + 3;
+    const double* sc = scale_c + 6 * size_t(c);
+    // ---- chunk t, the Jacobian half: cost and U_c / b_c ----
+    cost += jac_half(cr, tc, k, sc, Xc, uv_cur, cnt, l, acc);
+    // the rest of the point's record (the line came with X a chunk ago),
+    // issued ahead of the camera's reduction and store
+    double q[kPtS];
+    {
+      const double* rp = ptS + size_t(kPtS) * p_cur;
+      q[0] = Xc[0]; q[1] = Xc[1]; q[2] = Xc[2]; q[3] = rp[3];
+#pragma unroll
+      for (int f = 4; f < kPtS; f += 2) {
+        const double2 x = ld2(rp + f);
+        q[f] = x.x; q[f + 1] = x.y;
+      }
+    }
+    {
+      double tot = 0.0;
+      if (t + 1 >= n_chunks || ch_n.x != c) {  // wave-uniform
+        tot = wave_sum32(acc, l);
+#pragma unroll
+        for (int e = 0; e < 32; ++e) acc[e] = 0.0;
+      }
+      if (!(l & 1) && (l >> 1) < 27) jpart[size_t(ib / 64) * 27 + (l >> 1)] = tot;
+    }
+    // ---- chunk t, the step-prep half: the diagonal block / rhs sums ----
+    prep_half(cr, tc, k, sc, q, uv_cur, cnt < 64, cam_obs + (ib + l), l, dpart + size_t(ib / 64) * 27);
+#pragma unroll
+    for (int f = 0; f < 3; ++f) Xc[f] = Xn[f];
+    uv_cur = uv_nxt;
+    p_cur = p_nxt;
+    p_nxt = p_nn;
+  }
+  const double r = block_reduce(cost, sh, false);
+  if (threadIdx.x == 0) part_cost[blockIdx.x] = r;
+}
+
 // Back substitution pass A (see k_backsub_b): e = J_c y_c, u = M^T e, and
 // the observation's share of the model cost change (J, M recomputed); the
 // chunks in the XCD-aware order of k_obs_prep_rc.
@@ -1684,10 +1938,22 @@ __global__ __launch_bounds__(64) void k_schur_diag_sum(const int32_t* __restrict
 // where k_obs_prep_rc has already run for the coming step's radius): the
 // U_c and LM-diagonal entries the diagonal block adds go from the first sum
 // to the second by shuffle, the values the stand-alone kernel loads.
+// camS != nullptr: the wave also leaves its camera's staged record for
+// k_schur_pairs_rot_pw (k_cam_stage_rot's job, stage_cams_rot's arithmetic:
+// the record depends on the camera and its Jacobi scale alone, both final
+// here and unchanged until the next accepted step's evaluation).
 __global__ __launch_bounds__(64) void k_cam_sum_diag(const CamFold f, const DiagFold df, double* __restrict__ S, int ld,
-                                                     const int* __restrict__ gate) {
+                                                     const int* __restrict__ gate, const double* __restrict__ camR,
+                                                     const double* __restrict__ cam, const double* __restrict__ Kc,
+                                                     double* __restrict__ camS) {
   if (gate && *gate == 0) return;  // device LM loop: phase skipped
   const int c = blockIdx.x, t = threadIdx.x;
+  if (camS) {
+    __shared__ __attribute__((aligned(16))) double cst[2 * kCamSR];
+    stage_cams_rot<64>(cst, c, c, camR, cam, Kc, f.scale_c, t);  // (both sides: this camera)
+    wave_lds_sync();
+    if (t < kCamSR) camS[size_t(kCamSR) * c + t] = t < kCamSR - 1 ? cst[t] : 0.0;
+  }
   const double sum = cam_sum_body(c, t, f);
   const int tu = t < 36 ? t / 6 : 0, tv = t < 36 ? t % 6 : 0;
   double uq = __shfl(sum, 2 * up6(tu, tv));
@@ -2316,6 +2582,10 @@ void launch_point_prep(const DevProblem& d, double radius, hipStream_t s) {
   launch_point_factor(d, radius, s);
   launch_obs_prep(d, s);
 }
+void launch_jac_obs_prep(const DevProblem& d, hipStream_t s) {
+  k_jac_obs_prep<<<d.jac_blocks, kThreads, 0, s>>>(d.jgrp, d.jchunks, d.cm_p, d.uv_cm, d.cam_obs, d.Kc, d.cam, d.camR,
+                                                   d.scale_c, d.ptS, slot(d, kPCost), d.jpart, d.dpart, d.gate);
+}
 void launch_obs_prep(const DevProblem& d, hipStream_t s) {
   if (d.N_pad)
     k_obs_prep_rc<<<obs_xcd_blocks(d), kThreads, 0, s>>>(d.jgrp, d.jchunks, d.cm_p, d.uv_cm, d.cam_obs, d.camR, d.cam,
@@ -2337,11 +2607,12 @@ void launch_schur(const DevProblem& d, double radius, bool add_diag, hipStream_t
   launch_schur_diag(d, radius, add_diag, s);
   launch_schur_offdiag(d, nullptr, s);
 }
-void launch_cam_sum_diag(const DevProblem& d, double radius, bool add_diag, hipStream_t s) {
+void launch_cam_sum_diag(const DevProblem& d, double radius, bool add_diag, hipStream_t s, bool stage_cams) {
   if (!d.C) return;
   const DiagFold f{d.cam_rng, d.dpart, d.Ucam, d.diag_c, radius, d.radius_dev, add_diag ? 1 : 0, d.C, d.n,
                    (d.n + kNB - 1) / kNB * kNB, d.fail, reinterpret_cast<unsigned long long*>(d.ysol)};
-  k_cam_sum_diag<<<d.C, 64, 0, s>>>(cam_fold(d, 1, true), f, d.S, d.ld, d.gate);
+  k_cam_sum_diag<<<d.C, 64, 0, s>>>(cam_fold(d, 1, true), f, d.S, d.ld, d.gate, d.camR, d.cam, d.Kc,
+                                    stage_cams && cam_records_used(d) ? d.camS : nullptr);
 }
 void launch_schur_diag(const DevProblem& d, double radius, bool add_diag, hipStream_t s) {
   if (d.C)
@@ -2352,7 +2623,7 @@ void launch_schur_diag(const DevProblem& d, double radius, bool add_diag, hipStr
 // tile_cnt != nullptr: overlapped with k_chol_fused (compute_step_enqueue):
 // the blocks in their plain order (camera-major: the factor's tile columns
 // complete left to right) and counted per tile
-void launch_schur_offdiag(const DevProblem& d, int* tile_cnt, hipStream_t s) {
+void launch_schur_offdiag(const DevProblem& d, int* tile_cnt, hipStream_t s, bool cams_staged) {
   if (!d.n_blk) return;
   const int64_t n_slots = tile_cnt ? d.n_blk : d.n_bslots;
   const int32_t* bperm = tile_cnt ? nullptr : d.bperm;
@@ -2379,7 +2650,8 @@ void launch_schur_offdiag(const DevProblem& d, int* tile_cnt, hipStream_t s) {
     const int n_tick = int(n_slots / (8 * per)) * (kThreads / 64);  // groups per list
     const int nbc = (d.C + per - 1) / per;
 #define SFM_ROTP(S_)                                                                                               \
-  k_cam_stage_rot<S_><<<nbc, kThreads, 0, s>>>(d.C, d.camR, d.cam, d.Kc, d.scale_c, d.camS, d.gate);               \
+  if (!cams_staged)                                                                                                \
+    k_cam_stage_rot<S_><<<nbc, kThreads, 0, s>>>(d.C, d.camR, d.cam, d.Kc, d.scale_c, d.camS, d.gate);             \
   k_schur_pairs_rot_pw<S_><<<grid, kThreads, 0, s>>>(d.srec, n_tick, d.bpts, d.ptG, d.camS, d.S, d.ld, d.gate)
     if (sub == 8) { SFM_ROTP(8); }
     else if (sub == 16) { SFM_ROTP(16); }

@@ -569,9 +569,17 @@ int evaluate_enqueue(sfm_ba_handle* h, bool first, bool jacobi_scaling) {
   if (h->accept_grid > 0) launch_cam_prep_accept(d, cams_var, h->accept_grid, s);
   else if (h->accept_grid == 0) launch_cam_prep(d, d.cam, cams_var, s);
   // accept_grid < 0: done by the deciding workgroup (AcceptFold)
-  mark_begin(h, kPhJac);
-  launch_jacobian(d, !first || !jacobi_scaling ? true : false, s);
-  mark_end(h);
+  // the coming step's preparation rides along (its radius is final here);
+  // eval_fused: the scaled Jacobian pass is then k_jac_obs_prep's first half,
+  // after the point pass below (which reads nothing the Jacobian pass writes)
+  const bool fold_prep = step_prep_folds(h);
+  const bool fused = fold_prep && h->eval_fused && pts_var;
+  const bool unscaled_first = first && jacobi_scaling;
+  if (unscaled_first || !fused) {
+    mark_begin(h, kPhJac);
+    launch_jacobian(d, !unscaled_first, s);
+    mark_end(h);
+  }
   // unsharded: the U_c sums and their finalisation in one launch
   const bool fuse_cam = !sharded(h);
   // small systems (C <= 64): the camera sums ride in the point pass's launch
@@ -595,12 +603,12 @@ int evaluate_enqueue(sfm_ba_handle* h, bool first, bool jacobi_scaling) {
       }
       if (pts_var) launch_point_eval(d, 0, false, s);
     }
-    mark_begin(h, kPhJac);
-    launch_jacobian(d, true, s);
-    mark_end(h);
+    if (!fused) {
+      mark_begin(h, kPhJac);
+      launch_jacobian(d, true, s);
+      mark_end(h);
+    }
   }
-  // the coming step's preparation rides along (its radius is final here)
-  const bool fold_prep = step_prep_folds(h);
   if (fold_cams) {
     mark_begin(h, kPhPtEval);
     launch_point_eval_with_cams(d, 1, true, s);
@@ -629,11 +637,13 @@ int evaluate_enqueue(sfm_ba_handle* h, bool first, bool jacobi_scaling) {
     mark_end(h);
     if (fold_prep) {
       mark_begin(h, kPhPtPrep);
-      launch_obs_prep(d, s);
+      if (fused) launch_jac_obs_prep(d, s);
+      else launch_obs_prep(d, s);
       mark_end(h);
       mark_begin(h, kPhCamRed);
-      launch_cam_sum_diag(d, h->eval_radius, h->rank == 0, s);
+      launch_cam_sum_diag(d, h->eval_radius, h->rank == 0, s, fused);
       mark_end(h);
+      h->cams_staged = fused && cam_records_used(d);
     }
     h->prep_fresh = fold_prep;
   } else {
@@ -722,7 +732,7 @@ int compute_step_enqueue(sfm_ba_handle* h, double radius) {
     mark_begin(h, kPhSchur);
     if (fold_prep) {  // (never a block-per-workgroup system: launch_schur's two parts)
       schur_diag();
-      launch_schur_offdiag(d, nullptr, s);
+      launch_schur_offdiag(d, nullptr, s, h->cams_staged);
     } else {
       launch_schur(d, radius, h->rank == 0, s);
     }
@@ -1304,6 +1314,9 @@ int sfm_ba_solve_resident(sfm_ba_handle* h, const sfm_ba_options* opts_in, int32
   // between the phases (the host-callback hook; the distributed factor's
   // panel loop: at the sizes it is for, a host round trip per phase is noise)
   const bool host_lm = h->host_fn || h->coll_fn || (sharded(h) && h->dist_pt > 0) || env_flag("SFM_HOST_LM");
+  // (after h->mode: step_prep_folds reads it)
+  h->eval_fused = step_prep_folds(h) && !env_flag("SFM_EVAL_SPLIT");
+  h->cams_staged = false;
   bool nonfinite = false;
   const int rc = host_lm ? run_host_lm(h, opts, &sm, push, &nonfinite) : run_device_lm(h, opts, &sm, push, &nonfinite);
   if (rc && !nonfinite) return rc;
