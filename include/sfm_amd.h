@@ -639,6 +639,58 @@ int sfm_klt_detect_time(sfm_klt_handle* h, double* ms);
 int sfm_good_features_to_track(int32_t device, const uint8_t* grey, int32_t width, int32_t height, int32_t stride,
                                const sfm_gftt_params* params, float* pts, int32_t capacity, int32_t* n_pts);
 
+/* ---- Camera front end: colour frames, lens undistortion, Kopt ---------------
+ * The reference is constructed as CSfM(K, imSize, d) and every frame passes
+ * CFrame::setFrame (cvtColor(.., CV_RGB2GRAY), CFrame.cpp:156-164) and
+ * CFrame::setKeyPoints (undistortPoints(_pts_dist, _pts, _K, _d, _Kopt),
+ * CFrame.cpp:203-227) with _Kopt = getOptimalNewCameraMatrix(_K, _d, _imSize,
+ * 0) (CFrame.cpp:33).  OpenCV is not available to this project: the
+ * arithmetic is its restatement of OpenCV 3.0 (tests/camera_ref.py), held
+ * bit for bit against that restatement -- parity with OpenCV unpinned.
+ * Everything here is opt-in: without a camera every other call behaves as
+ * before.  Note that Kopt != K even for d = 0 (the (W-1)/W factor of
+ * getOptimalNewCameraMatrix), so a "zero" camera is not a no-op. */
+typedef struct sfm_camera {
+  double K9[9];    /* row-major; only fx, fy, cx, cy are used */
+  double Kopt9[9]; /* filled by sfm_camera_init */
+  double d[8];     /* k1 k2 p1 p2 k3 k4 k5 k6; missing values 0 */
+  int32_t n_d;     /* 0, 4, 5 or 8 */
+  int32_t width, height;
+  int32_t reserved;
+} sfm_camera;
+/* Host only (no GPU needed).  d holds n_d in {0, 4, 5, 8} coefficients.
+ * SFM_EINVAL: any other n_d, non-finite input, fx or fy <= 0, a size < 2. */
+int sfm_camera_init(sfm_camera* cam, const double* K9, const double* d, int32_t n_d, int32_t width, int32_t height);
+/* cv::undistortPoints(_pts_dist, _pts, _K, _d, _Kopt): pts_dist, pts
+ * [n][2] double; five fixed iterations per point, fp64, one lane per point.
+ * n = 0 succeeds without touching the device; arguments are validated first. */
+int sfm_undistort_points(int32_t device, const sfm_camera* cam, int32_t n, const double* pts_dist, double* pts);
+/* cvtColor(.., CV_RGB2GRAY) of an 8-bit 3-channel image (row stride in bytes,
+ * >= 3 * w) into grey [h][w]: g = (c0*4899 + c1*9617 + c2*1868 + 8192) >> 14,
+ * c0 the first channel in memory. */
+int sfm_rgb_to_grey(int32_t device, const uint8_t* rgb, int32_t w, int32_t h, int32_t stride, uint8_t* grey);
+/* CFrame::setFrame for the KLT handle: sfm_klt_push_frame of the converted
+ * frame, with one upload (the colour frame) and the conversion on the device,
+ * written straight into the handle's level-0 slot. */
+int sfm_klt_push_frame_rgb(sfm_klt_handle* h, const uint8_t* rgb, int32_t stride);
+/* CTracker::setCurrentFrame + detectFeatures + CFrame::setKeyPoints in one
+ * call.  img is 8-bit with 1 or 3 channels, cam->width x cam->height, row
+ * stride in bytes.  klt (optional): the frame becomes the handle's current
+ * frame (pyramid included) and BRISK runs on that resident frame.  mt
+ * (optional): the result becomes the matcher's current frame exactly as
+ * sfm_matcher_push_frame(pts, pts_distorted = keypoints, desc) would make
+ * it, device to device.  Outputs as sfm_brisk_detect_describe plus pts
+ * [capacity][2], the undistorted positions, all in the detector's one packed
+ * download; no host synchronisation or copy beyond the detector's own.
+ * Without klt and mt the current HIP device is used.
+ * More than `capacity` keypoints: SFM_EINVAL with *n_out = the count, and the
+ * matcher is not advanced (a KLT handle has taken the frame by then, as after
+ * sfm_klt_push_frame).  SFM_EINVAL also when mt, klt and cam disagree on
+ * device, descriptor width (64 bytes) or frame size. */
+int sfm_frame_detect(sfm_matcher* mt, sfm_klt_handle* klt, const uint8_t* img, int32_t channels, int32_t stride,
+                     const sfm_camera* cam, int32_t threshold, int32_t octaves, int32_t capacity, float* kps,
+                     int32_t* octave, uint8_t* desc, double* pts, int32_t* n_out);
+
 /* Synthetic scenes, host-only.  Points [p_begin, p_end) of a
  * scene with n_pts_total points; every camera is returned.  Observations are
  * sorted by (point, camera); pt_idx is relative to p_begin.

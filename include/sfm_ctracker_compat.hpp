@@ -828,6 +828,54 @@ class MapStore {
   float track_threshold_ = 0.25f;
 };
 
+// The camera of CFrame (/root/reference/CFrame.cpp:33, 203-227).  In place of
+//   _Kopt = getOptimalNewCameraMatrix(_K, _d, _imSize, 0);
+//   undistortPoints(_pts_dist, _pts, _K, _d, _Kopt);
+// write
+//   sfm_compat::getOptimalNewCameraMatrix(_K, _d, _imSize, _Kopt);
+//   sfm_compat::undistortPoints(_pts_dist, _pts, _K, _d, _Kopt);
+// Matx33 needs .val[9], Size .width/.height, Point2 .x/.y; d is the
+// vector<double> of 0, 4, 5 or 8 coefficients the reference holds.  OpenCV's
+// arithmetic is restated (sfm_amd.h), parity with OpenCV unpinned.  Both
+// return the ABI code; on an error the outputs are left as they were.
+template <class Matx33, class Size>
+inline int getOptimalNewCameraMatrix(const Matx33& K, const std::vector<double>& d, const Size& imSize, Matx33& Kopt) {
+  sfm_camera cam;
+  double K9[9];
+  for (int m = 0; m < 9; ++m) K9[m] = K.val[m];
+  const int rc = sfm_camera_init(&cam, K9, d.empty() ? nullptr : d.data(), int32_t(d.size()), int32_t(imSize.width),
+                                 int32_t(imSize.height));
+  if (rc != SFM_OK) return rc;
+  for (int m = 0; m < 9; ++m) Kopt.val[m] = cam.Kopt9[m];
+  return SFM_OK;
+}
+
+template <class Point2, class Matx33>
+inline int undistortPoints(const std::vector<Point2>& ptsDist, std::vector<Point2>& pts, const Matx33& K,
+                           const std::vector<double>& d, const Matx33& Kopt, int device = 0) {
+  if (d.size() > 8) return SFM_EINVAL;
+  // (the image size does not enter undistortPoints; Kopt is the caller's)
+  sfm_camera cam = {};
+  for (int m = 0; m < 9; ++m) { cam.K9[m] = K.val[m]; cam.Kopt9[m] = Kopt.val[m]; }
+  for (size_t m = 0; m < d.size(); ++m) cam.d[m] = d[m];
+  cam.n_d = int32_t(d.size());
+  cam.width = cam.height = 2;
+  const size_t n = ptsDist.size();
+  std::vector<double> in(2 * n), out(2 * n);
+  for (size_t i = 0; i < n; ++i) {
+    in[2 * i] = ptsDist[i].x;
+    in[2 * i + 1] = ptsDist[i].y;
+  }
+  const int rc = sfm_undistort_points(device, &cam, int32_t(n), in.data(), out.data());
+  if (rc != SFM_OK) return rc;
+  pts.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    pts[i].x = out[2 * i];
+    pts[i].y = out[2 * i + 1];
+  }
+  return SFM_OK;
+}
+
 }  // namespace sfm_compat
 
 #endif  // SFM_CTRACKER_COMPAT_HPP_

@@ -126,6 +126,19 @@ class TwoViewOptions(ctypes.Structure):
     ]
 
 
+class CameraStruct(ctypes.Structure):
+    """sfm_camera."""
+    _fields_ = [
+        ("K9", c_double * 9),
+        ("Kopt9", c_double * 9),
+        ("d", c_double * 8),
+        ("n_d", c_int32),
+        ("width", c_int32),
+        ("height", c_int32),
+        ("reserved", c_int32),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGNATURES = {
     "sfm_abi_version": (c_int32, []),
@@ -242,6 +255,12 @@ _SIGNATURES = {
     "sfm_klt_detect_time": (c_int, [c_void_p, POINTER(c_double)]),
     "sfm_good_features_to_track": (c_int, [c_int32, c_void_p, c_int32, c_int32, c_int32, POINTER(GFTTParams),
                                            c_void_p, c_int32, POINTER(c_int32)]),
+    "sfm_camera_init": (c_int, [POINTER(CameraStruct), c_void_p, c_void_p, c_int32, c_int32, c_int32]),
+    "sfm_undistort_points": (c_int, [c_int32, POINTER(CameraStruct), c_int32, c_void_p, c_void_p]),
+    "sfm_rgb_to_grey": (c_int, [c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "sfm_klt_push_frame_rgb": (c_int, [c_void_p, c_void_p, c_int32]),
+    "sfm_frame_detect": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(CameraStruct), c_int32,
+                                 c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int32)]),
     "sfm_scene_default_intrinsics": (None, [c_void_p]),
     "sfm_scene_generate": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_uint64, c_double, c_double,
                                    c_double, c_double] + [c_void_p] * 10),
@@ -325,6 +344,6 @@ def device_count() -> int:
     return int(lib().sfm_device_count())
 
 
-__all__ = ["lib", "check", "ptr", "BAOptions", "BASummary", "BAIteration", "KLTParams", "GFTTParams", "TwoViewOptions", "SfmError",
+__all__ = ["lib", "check", "ptr", "BAOptions", "BASummary", "BAIteration", "KLTParams", "GFTTParams", "TwoViewOptions", "CameraStruct", "SfmError",
            "default_options", "default_klt_params", "default_gftt_params", "default_two_view_options",
            "device_count", "exported_symbols", "LIB_PATH", "c_uint8"]

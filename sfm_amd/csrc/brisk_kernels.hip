@@ -26,6 +26,7 @@
 #include <vector>
 #include "sfm_trace.h"
 #include "../../include/sfm_amd.h"
+#include "frame_internal.h"
 
 void sfm_internal_set_error(const std::string& msg);  // ba_solver.hip
 
@@ -798,6 +799,7 @@ struct BriskWork {
   // the per-keypoint outputs before: BRISK 1.0 -> 0.74 ms per frame)
   void* host = nullptr;
   size_t host_cap = 0;
+  hipEvent_t installed = nullptr;  // end of the last hand-off's reads of the packed buffer
   void* pinned(size_t bytes, int* rc) {
     if (host_cap < bytes) {
       const size_t cap = std::max(bytes, 2 * host_cap);
@@ -888,12 +890,16 @@ extern "C" int sfm_brisk_describe(int32_t device, const uint8_t* img, int32_t w,
 // BRISK on an 8-bit frame that is either in host memory (uploaded here) or
 // already resident on the device (sfm_klt_brisk_detect_describe: the KLT
 // handle's current frame, copied device to device).
+// With fx (sfm_frame_detect, frame_kernels.hip) the host image may be
+// 3-channel or strided, the keypoints are undistorted into the same packed
+// download, and the result is handed to a matcher device to device.
 namespace sfm {
 int brisk_detect_describe_impl(int32_t device, const uint8_t* img, bool img_on_device, int32_t w, int32_t h,
                                int32_t threshold, int32_t octaves, int32_t capacity, float* kps, int32_t* octave,
-                               uint8_t* desc, int32_t* n_out) {
+                               uint8_t* desc, int32_t* n_out, const FrameExtras* fx) {
   if (!n_out) return bfail(SFM_EINVAL, "n_out is NULL");
   *n_out = 0;
+  if (fx && ((capacity && !fx->pts) || (fx->mt && !desc))) return bfail(SFM_EINVAL, "NULL argument");
   if (w < 8 || h < 8 || threshold < 1 || threshold > 255 || octaves < 0 || 2 * octaves > kMaxLayers || capacity < 0)
     return bfail(SFM_EINVAL, "bad sizes (w, h >= 8; threshold 1..255; octaves 0..8)");
   if (!img || (capacity && (!kps || !octave))) return bfail(SFM_EINVAL, "NULL argument");
@@ -927,6 +933,17 @@ int brisk_detect_describe_impl(int32_t device, const uint8_t* img, bool img_on_d
   if (rc) return rc;
   if (img_on_device) {
     if (hipMemcpy(limg, img, size_t(w) * h, hipMemcpyDeviceToDevice) != hipSuccess)
+      return bfail(SFM_EIO, "frame copy failed");
+  } else if (fx && fx->channels == 3) {
+    // CFrame::setFrame: the colour rows as the caller holds them in one
+    // upload, grey written straight into layer 0
+    const size_t bytes = size_t(h - 1) * fx->stride + 3 * size_t(w);
+    auto* rgb = static_cast<uint8_t*>(W->get(16, bytes, &rc));
+    if (rc) return rc;
+    if (hipMemcpy(rgb, img, bytes, hipMemcpyHostToDevice) != hipSuccess) return bfail(SFM_EIO, "frame copy failed");
+    launch_rgb_to_grey(nullptr, rgb, w, h, fx->stride, limg);
+  } else if (fx && fx->stride != w) {
+    if (hipMemcpy2D(limg, w, img, fx->stride, w, h, hipMemcpyHostToDevice) != hipSuccess)
       return bfail(SFM_EIO, "frame copy failed");
   } else if (hipMemcpy(limg, img, size_t(w) * h, hipMemcpyHostToDevice) != hipSuccess) {
     return bfail(SFM_EIO, "frame copy failed");
@@ -971,15 +988,23 @@ int brisk_detect_describe_impl(int32_t device, const uint8_t* img, bool img_on_d
   int32_t n = 0;
   if (hipMemcpy(&n, cnt, sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return bfail(SFM_EIO, "kernel failed");
   if (n > cap_c) return bfail(SFM_EIO, "candidate buffer overflow");
-  if (n == 0) return 0;
+  if (n == 0) {
+    if (fx && fx->mt) {  // an empty frame still becomes the current one
+      hipStream_t ms = nullptr;
+      return frame_install(fx->mt, 0, 0, nullptr, nullptr, nullptr, nullptr, &ms);
+    }
+    return 0;
+  }
   // BRISK's order: layer, then row-major (stable radix sort on the key)
   auto* key = static_cast<unsigned long long*>(W->get(4, sizeof(unsigned long long) * 2 * size_t(n), &rc));
   auto* idx = static_cast<int32_t*>(W->get(5, sizeof(int32_t) * 2 * size_t(n), &rc));
   // every per-keypoint output in one buffer (descriptors first, 16-B
   // aligned), downloaded by one copy: desc | kp3 | resp | layer | keep | angle
+  // (| undistorted positions, 16-B aligned, for sfm_frame_detect)
   const int n_bytes = desc ? ((P->n_short + 127) / 128) * 16 : 0;
   const size_t o_kp = size_t(n) * n_bytes, o_resp = o_kp + 12 * size_t(n), o_lay = o_resp + 4 * size_t(n),
-               o_keep = o_lay + 4 * size_t(n), o_ang = o_keep + 4 * size_t(n), out_bytes = o_ang + 4 * size_t(n);
+               o_keep = o_lay + 4 * size_t(n), o_ang = o_keep + 4 * size_t(n), o_und = (o_ang + 4 * size_t(n) + 15) & ~size_t(15),
+               out_bytes = fx ? o_und + 16 * size_t(n) : o_ang + 4 * size_t(n);
   auto* ob = static_cast<uint8_t*>(W->get(6, out_bytes, &rc));
   if (rc) return rc;
   auto* kp3 = reinterpret_cast<float*>(ob + o_kp);
@@ -1002,8 +1027,11 @@ int brisk_detect_describe_impl(int32_t device, const uint8_t* img, bool img_on_d
     integral_image(limg, w, h, ii, band);
     k_brisk_describe<<<n, 64>>>(limg, w, h, ii, *P, kp3, n, keep, ang, ob);
   }
+  auto* und = reinterpret_cast<double*>(ob + o_und);
+  if (fx) launch_undistort_kp3(nullptr, fx->lens, kp3, n, und);
   // one download of the packed outputs (without descriptors: kp3 | resp | layer)
-  const size_t dl_off = desc ? 0 : o_kp, dl_bytes = desc ? out_bytes : o_keep - o_kp;
+  // (with fx, whose tail is the undistorted positions: through to the end)
+  const size_t dl_off = desc ? 0 : o_kp, dl_bytes = fx ? out_bytes - dl_off : (desc ? out_bytes : o_keep - o_kp);
   auto* hb = static_cast<uint8_t*>(W->pinned(out_bytes, &rc));
   if (rc) return rc;
   if (hipMemcpy(hb + dl_off, ob + dl_off, dl_bytes, hipMemcpyDeviceToHost) != hipSuccess)
@@ -1014,6 +1042,26 @@ int brisk_detect_describe_impl(int32_t device, const uint8_t* img, bool img_on_d
   const int32_t* hkeep = desc ? reinterpret_cast<const int32_t*>(hb + o_keep) : nullptr;
   const float* hang = desc ? reinterpret_cast<const float*>(hb + o_ang) : nullptr;
   const uint8_t* hd = hb;
+  const double* hu = reinterpret_cast<const double*>(hb + o_und);
+  if (fx && fx->mt) {
+    // the hand-off: the packed buffer becomes the matcher's current frame on
+    // the matcher's stream (the download above left the buffer complete)
+    // while the host fills the caller's arrays below; the detector's next
+    // write of the buffer waits for that, the host does not.  A frame that
+    // does not fit the caller's arrays is refused before anything is swapped.
+    if (n_bytes != 64) return bfail(SFM_EINVAL, "the hand-off needs 64-byte descriptors");
+    int kept = 0;
+    for (int k = 0; k < n; ++k) kept += hkeep[k] != 0;
+    if (kept <= capacity) {
+      hipStream_t ms = nullptr;
+      if ((rc = frame_install(fx->mt, n, kept, ob, kp3, und, reinterpret_cast<const int32_t*>(ob + o_keep), &ms)))
+        return rc;
+      if (!W->installed && hipEventCreateWithFlags(&W->installed, hipEventDisableTiming) != hipSuccess)
+        return bfail(SFM_EIO, "hipEventCreate failed");
+      if (hipEventRecord(W->installed, ms) != hipSuccess || hipStreamWaitEvent(nullptr, W->installed, 0) != hipSuccess)
+        return bfail(SFM_EIO, "stream ordering failed");
+    }
+  }
   int m = 0;
   for (int k = 0; k < n; ++k) {
     if (hkeep && !hkeep[k]) continue;
@@ -1022,6 +1070,7 @@ int brisk_detect_describe_impl(int32_t device, const uint8_t* img, bool img_on_d
       o[0] = hk[3 * k]; o[1] = hk[3 * k + 1]; o[2] = hk[3 * k + 2]; o[3] = hang ? hang[k] : -1.0f; o[4] = hr[k];
       octave[m] = hl[k];
       if (desc) std::memcpy(desc + size_t(m) * 64, hd + size_t(k) * n_bytes, 64);
+      if (fx) { fx->pts[2 * size_t(m)] = hu[2 * size_t(k)]; fx->pts[2 * size_t(m) + 1] = hu[2 * size_t(k) + 1]; }
     }
     ++m;
   }
@@ -1035,5 +1084,5 @@ extern "C" int sfm_brisk_detect_describe(int32_t device, const uint8_t* img, int
                                          int32_t octaves, int32_t capacity, float* kps, int32_t* octave,
                                          uint8_t* desc, int32_t* n_out) {
   SFM_TRACE("sfm_brisk_detect_describe");
-  return brisk_detect_describe_impl(device, img, false, w, h, threshold, octaves, capacity, kps, octave, desc, n_out);
+  return brisk_detect_describe_impl(device, img, false, w, h, threshold, octaves, capacity, kps, octave, desc, n_out, nullptr);
 }

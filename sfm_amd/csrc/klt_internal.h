@@ -11,9 +11,12 @@ struct KltFrame {
   int w, h;
   hipStream_t stream;
   void** gftt_slot;    // detector state owned by the handle
+  int device;
 };
 
 // 0, or SFM_EINVAL when no frame has been pushed.
 int sfm_internal_klt_frame(sfm_klt_handle* h, KltFrame* out);
+// Size and device alone (valid before the first frame).
+int sfm_internal_klt_size(sfm_klt_handle* h, KltFrame* out);
 // Frees a detector state (called from sfm_klt_destroy).
 void sfm_internal_gftt_free(void* state);

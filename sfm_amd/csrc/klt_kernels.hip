@@ -327,12 +327,7 @@ int pyramid_levels(int w, int h, int max_level, int win) {
 
 }  // namespace
 
-namespace sfm {
-// brisk_kernels.hip
-int brisk_detect_describe_impl(int32_t device, const uint8_t* img, bool img_on_device, int32_t w, int32_t h,
-                               int32_t threshold, int32_t octaves, int32_t capacity, float* kps, int32_t* octave,
-                               uint8_t* desc, int32_t* n_out);
-}  // namespace sfm
+#include "frame_internal.h"  // brisk_detect_describe_impl, launch_rgb_to_grey
 
 struct sfm_klt_handle {
   int device = 0;
@@ -343,6 +338,8 @@ struct sfm_klt_handle {
   size_t img_off[kMaxLv + 1] = {}, pix_total = 0;
   uint8_t* img[2] = {nullptr, nullptr};
   short2* dxy[2] = {nullptr, nullptr};
+  uint8_t* rgb = nullptr;  // upload stage of a 3-channel frame (push_frame_rgb), grow-only
+  size_t rgb_cap = 0;
   int n_frames = 0;  // frames pushed so far
   int cur = 0;       // slot of the current frame (prev = cur ^ 1)
   // point buffers
@@ -419,6 +416,58 @@ float ms_between(hipEvent_t a, hipEvent_t b) {
 
 }  // namespace
 
+namespace sfm {
+// sfm_klt_push_frame (channels 1) and CFrame::setFrame's cvtColor in front of
+// it (channels 3: one upload of the colour frame, converted on the device
+// straight into the level-0 slot).
+int klt_push_frame_any(sfm_klt_handle* h, const uint8_t* src, int32_t stride, int channels) {
+  if (!h || !src) return kfail(SFM_EINVAL, "NULL argument");
+  if (stride < channels * h->w) return kfail(SFM_EINVAL, channels == 1 ? "stride < width" : "stride < 3 * width");
+  hipSetDevice(h->device);
+  const int slot = h->n_frames == 0 ? 0 : (h->cur ^ 1);
+  hipStream_t s = h->stream;
+  if (channels == 1) {
+    // Synchronous with respect to the caller's buffer (pageable source; a
+    // pinned stage measured no faster for the 0.9-MB frame: the runtime
+    // pipelines its staging copies with the DMA).
+    if (hipMemcpy2DAsync(h->img[slot], h->w, src, stride, h->w, h->h, hipMemcpyHostToDevice, s) != hipSuccess)
+      return kfail(SFM_EIO, "frame upload failed");
+  } else {
+    // the rows as the caller holds them, in one copy; the last row ends at
+    // its 3 * w bytes
+    const size_t bytes = size_t(h->h - 1) * stride + 3 * size_t(h->w);
+    if (h->rgb_cap < bytes) {
+      if (h->rgb) hipFree(h->rgb);
+      h->rgb = nullptr;
+      h->rgb_cap = 0;
+      if (hipMalloc(reinterpret_cast<void**>(&h->rgb), bytes) != hipSuccess)
+        return kfail(SFM_ENOMEM, "hipMalloc failed (klt colour stage)");
+      h->rgb_cap = bytes;
+    }
+    if (hipMemcpyAsync(h->rgb, src, bytes, hipMemcpyHostToDevice, s) != hipSuccess)
+      return kfail(SFM_EIO, "frame upload failed");
+    launch_rgb_to_grey(s, h->rgb, h->w, h->h, stride, h->img[slot]);
+  }
+  hipEventRecord(h->ev[0], s);
+  for (int l = 1; l <= h->levels; ++l) {
+    dim3 g((h->lw[l] + 31) / 32, (h->lh[l] + 7) / 8);
+    k_pyr_down<<<g, 256, 0, s>>>(h->img[slot] + h->img_off[l - 1], h->lw[l - 1], h->lh[l - 1],
+                                 h->img[slot] + h->img_off[l], h->lw[l], h->lh[l]);
+  }
+  for (int l = 0; l <= h->levels; ++l) {
+    dim3 g((h->lw[l] + 31) / 32, (h->lh[l] + 7) / 8);
+    k_scharr<<<g, 256, 0, s>>>(h->img[slot] + h->img_off[l], h->lw[l], h->lh[l], h->dxy[slot] + h->img_off[l]);
+  }
+  hipEventRecord(h->ev[1], s);
+  if (hipGetLastError() != hipSuccess) return kfail(SFM_EIO, "pyramid launch failed");
+  if (hipStreamSynchronize(s) != hipSuccess) return kfail(SFM_EIO, "pyramid build failed");
+  h->cur = slot;
+  ++h->n_frames;
+  h->timed_push = true;
+  return 0;
+}
+}  // namespace sfm
+
 extern "C" {
 
 void sfm_klt_default_params(sfm_klt_params* p) {
@@ -486,6 +535,7 @@ int sfm_klt_destroy(sfm_klt_handle* h) {
     if (h->img[s]) hipFree(h->img[s]);
     if (h->dxy[s]) hipFree(h->dxy[s]);
   }
+  if (h->rgb) hipFree(h->rgb);
   void* bufs[] = {h->d_prev, h->d_next, h->d_status, h->d_slot, h->d_out, h->d_curr, h->d_key, h->d_first};
   for (void* b : bufs)
     if (b) hipFree(b);
@@ -501,33 +551,12 @@ int32_t sfm_klt_num_levels(const sfm_klt_handle* h) { return h ? h->levels + 1 :
 
 int sfm_klt_push_frame(sfm_klt_handle* h, const uint8_t* grey, int32_t stride) {
   SFM_TRACE("sfm_klt_push_frame");
-  if (!h || !grey) return kfail(SFM_EINVAL, "NULL argument");
-  if (stride < h->w) return kfail(SFM_EINVAL, "stride < width");
-  hipSetDevice(h->device);
-  const int slot = h->n_frames == 0 ? 0 : (h->cur ^ 1);
-  hipStream_t s = h->stream;
-  // Synchronous with respect to the caller's buffer (pageable source; a
-  // pinned stage measured no faster for the 0.9-MB frame: the runtime
-  // pipelines its staging copies with the DMA).
-  if (hipMemcpy2DAsync(h->img[slot], h->w, grey, stride, h->w, h->h, hipMemcpyHostToDevice, s) != hipSuccess)
-    return kfail(SFM_EIO, "frame upload failed");
-  hipEventRecord(h->ev[0], s);
-  for (int l = 1; l <= h->levels; ++l) {
-    dim3 g((h->lw[l] + 31) / 32, (h->lh[l] + 7) / 8);
-    k_pyr_down<<<g, 256, 0, s>>>(h->img[slot] + h->img_off[l - 1], h->lw[l - 1], h->lh[l - 1],
-                                 h->img[slot] + h->img_off[l], h->lw[l], h->lh[l]);
-  }
-  for (int l = 0; l <= h->levels; ++l) {
-    dim3 g((h->lw[l] + 31) / 32, (h->lh[l] + 7) / 8);
-    k_scharr<<<g, 256, 0, s>>>(h->img[slot] + h->img_off[l], h->lw[l], h->lh[l], h->dxy[slot] + h->img_off[l]);
-  }
-  hipEventRecord(h->ev[1], s);
-  if (hipGetLastError() != hipSuccess) return kfail(SFM_EIO, "pyramid launch failed");
-  if (hipStreamSynchronize(s) != hipSuccess) return kfail(SFM_EIO, "pyramid build failed");
-  h->cur = slot;
-  ++h->n_frames;
-  h->timed_push = true;
-  return 0;
+  return sfm::klt_push_frame_any(h, grey, stride, 1);
+}
+
+int sfm_klt_push_frame_rgb(sfm_klt_handle* h, const uint8_t* rgb, int32_t stride) {
+  SFM_TRACE("sfm_klt_push_frame_rgb");
+  return sfm::klt_push_frame_any(h, rgb, stride, 3);
 }
 
 int sfm_klt_brisk_detect_describe(sfm_klt_handle* h, int32_t threshold, int32_t octaves, int32_t capacity,
@@ -538,7 +567,7 @@ int sfm_klt_brisk_detect_describe(sfm_klt_handle* h, int32_t threshold, int32_t 
   // (push_frame left its stream drained; this keeps any later use ordered)
   if (hipStreamSynchronize(h->stream) != hipSuccess) return kfail(SFM_EIO, "klt stream failed");
   return sfm::brisk_detect_describe_impl(h->device, h->img[h->cur], true, h->w, h->h, threshold, octaves, capacity,
-                                         kps, octave, desc, n_out);
+                                         kps, octave, desc, n_out, nullptr);
 }
 
 int sfm_klt_get_level(sfm_klt_handle* h, int32_t which, int32_t level, uint8_t* img, int16_t* dxy, int32_t* w,
@@ -670,5 +699,15 @@ int sfm_internal_klt_frame(sfm_klt_handle* h, KltFrame* out) {
   out->h = h->lh[0];
   out->stream = h->stream;
   out->gftt_slot = &h->gftt;
+  out->device = h->device;
+  return 0;
+}
+
+int sfm_internal_klt_size(sfm_klt_handle* h, KltFrame* out) {
+  if (!h || !out) return kfail(SFM_EINVAL, "NULL argument");
+  *out = KltFrame{};
+  out->w = h->lw[0];
+  out->h = h->lh[0];
+  out->device = h->device;
   return 0;
 }

@@ -38,6 +38,7 @@
 #include "sfm_trace.h"
 #include "../../include/sfm_amd.h"
 #include "ordered_compact.h"
+#include "frame_internal.h"
 
 void sfm_internal_set_error(const std::string& msg);  // ba_solver.hip
 
@@ -431,6 +432,43 @@ int matcher_match_current_dev(sfm_matcher* h, hipEvent_t after, const uint64_t* 
 int matcher_current_n(const sfm_matcher* h) { return h->frames_pushed < 1 ? -1 : h->frame[h->cur].n; }
 int matcher_words(const sfm_matcher* h) { return h->W; }
 int matcher_device(const sfm_matcher* h) { return h->device; }
+int matcher_desc_bytes(const sfm_matcher* h) { return h->desc_bytes; }
+
+// For sfm_frame_detect (frame_kernels.hip): sfm_matcher_push_frame in two
+// halves around a device-side fill.  begin sizes the slot push_frame would
+// overwrite (the previous frame's: call it only once the new frame is known
+// to be accepted) for m keypoints, laid out as push_frame does; commit is
+// the prev/curr swap.
+int matcher_install_begin(sfm_matcher* h, int n, int m, MatchSlot* out) {
+  if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
+  MatchFrame& f = h->frame[h->cur ^ 1];
+  if (f.cap < size_t(std::max(m, 1))) {
+    hipStreamSynchronize(h->stream);
+    hipFree(f.desc);
+    f.desc = nullptr; f.pts = f.ptsd = nullptr;
+    f.cap = size_t(std::max(m, 1024)) * 3 / 2;
+    if (hipMalloc(&f.desc, f.cap * (h->W * 8 + 32)) != hipSuccess) {
+      f.cap = 0;
+      return mfail(SFM_ENOMEM, "hipMalloc failed (matcher frame)");
+    }
+  }
+  int rc = 0;
+  out->scratch = dbuf<int>(h, "install", size_t(n) + 1, &rc);
+  if (rc) return rc;
+  out->desc = f.desc;
+  out->pts = reinterpret_cast<double*>(f.desc + size_t(m) * h->W);
+  out->ptsd = out->pts + 2 * size_t(m);
+  out->stream = h->stream;
+  return 0;
+}
+void matcher_install_commit(sfm_matcher* h, int m) {
+  h->cur ^= 1;
+  MatchFrame& f = h->frame[h->cur];
+  f.n = m;
+  f.pts = reinterpret_cast<double*>(f.desc + size_t(m) * h->W);
+  f.ptsd = f.pts + 2 * size_t(m);
+  ++h->frames_pushed;
+}
 }  // namespace sfm
 
 extern "C" {

@@ -56,5 +56,34 @@ __global__ __launch_bounds__(1024) void k_compact_slots(int n0, const int* __res
   if (threadIdx.x == 0) *count = base;
 }
 
+// Ordered compaction of plain keep flags (the BRISK descriptor's border
+// rule, k_brisk_describe): src[pos] = i for the pos-th kept i, in order;
+// *count = the number kept.  One workgroup of 16 waves, 1024 flags a step: a
+// ballot orders the flags inside a wave, the 16 wave totals order the waves.
+__global__ __launch_bounds__(1024) void k_compact_keep(int n, const int* __restrict__ keep, int* __restrict__ src,
+                                                       int* __restrict__ count) {
+  __shared__ int wave_sum[16];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int base = 0;  // the same in every thread
+  for (int c0 = 0; c0 < n; c0 += 1024) {
+    const int i = c0 + threadIdx.x;
+    const bool f = i < n && keep[i] != 0;
+    const unsigned long long b = __ballot(f);
+    if (lane == 0) wave_sum[wv] = __popcll(b);
+    __syncthreads();
+    int off = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) {
+      const int s = wave_sum[w];
+      off += w < wv ? s : 0;
+      tot += s;
+    }
+    if (f) src[base + off + __popcll(b & ((1ull << lane) - 1ull))] = i;
+    base += tot;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *count = base;
+}
+
 }  // namespace
 }  // namespace sfm

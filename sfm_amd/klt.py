@@ -58,6 +58,15 @@ class KLTTracker:
             raise ValueError(f"frame shape {g.shape} != {(self.height, self.width)}")
         check(lib().sfm_klt_push_frame(self._h, ptr(g), self.width), "sfm_klt_push_frame")
 
+    def push_frame_rgb(self, img: np.ndarray) -> None:
+        """CFrame::setFrame: push_frame of cvtColor(img, CV_RGB2GRAY), with the
+        colour frame uploaded once and converted on the device
+        (sfm_klt_push_frame_rgb); img uint8 [h][w][3]."""
+        c = np.ascontiguousarray(img, dtype=np.uint8)
+        if c.shape != (self.height, self.width, 3):
+            raise ValueError(f"frame shape {c.shape} != {(self.height, self.width, 3)}")
+        check(lib().sfm_klt_push_frame_rgb(self._h, ptr(c), 3 * self.width), "sfm_klt_push_frame_rgb")
+
     def level(self, which: int, level: int):
         """(image u8 [h][w], derivatives int16 [h][w][2]) of a pyramid level of
         the previous (which=0) or current (which=1) frame."""

@@ -92,10 +92,20 @@ class KeypointStream:
 
     def __init__(self, n_landmarks: int = 15000, seed: int = 7, p_detect: float = 0.85, bit_noise: int = 8,
                  spurious: float = 0.15, px_sigma: float = 0.3, step: float = 0.0196, desc_bytes: int = 64,
-                 lifetime=(40, 100), horizon: int = 400):
+                 lifetime=(40, 100), horizon: int = 400, dist=None):
         rng = np.random.default_rng(seed)
         self.w, self.h = 1280, 720
         self.K = np.array([[F_PIX, 0.0, 640.0], [0.0, F_PIX, 360.0], [0.0, 0.0, 1.0]])
+        # dist (lens coefficients k1 k2 p1 p2 [k3 [k4 k5 k6]]): the camera
+        # above gets that lens.  The landmarks are still seen by a pinhole
+        # camera, now the camera's Kopt (stream.K), and the keypoints returned
+        # are those pixels pushed through the forward lens model into the
+        # lens's own image: what a detector on the distorted frames reports.
+        self.camera = None
+        if dist is not None:
+            from .camera import Camera
+            self.camera = Camera(self.K, dist, (self.w, self.h))
+            self.K = self.camera.Kopt.copy()
         self.L = np.column_stack([rng.uniform(-6.0, 14.0, n_landmarks), rng.uniform(-4.0, 4.0, n_landmarks),
                                   rng.uniform(8.0, 14.0, n_landmarks)])
         self.D = rng.integers(0, 256, size=(n_landmarks, desc_bytes), dtype=np.uint8)
@@ -115,7 +125,10 @@ class KeypointStream:
         rng = np.random.default_rng((self.seed, k))
         r, t = self.pose(k)
         Xc = self.L @ _rodrigues(r).T + t
-        uv = Xc[:, :2] / Xc[:, 2:3] * F_PIX + self.K[:2, 2]
+        if self.camera is None:
+            uv = Xc[:, :2] / Xc[:, 2:3] * F_PIX + self.K[:2, 2]
+        else:
+            uv = Xc[:, :2] / Xc[:, 2:3] * np.array([self.K[0, 0], self.K[1, 1]]) + self.K[:2, 2]
         vis = (Xc[:, 2] > 0.5) & (uv[:, 0] >= 16) & (uv[:, 0] < self.w - 16) & (uv[:, 1] >= 16) & \
               (uv[:, 1] < self.h - 16) & (self.birth <= k) & (k < self.death) & (rng.random(len(uv)) < self.p_detect)
         lid = np.flatnonzero(vis)
@@ -130,6 +143,8 @@ class KeypointStream:
         desc = np.vstack([desc, rng.integers(0, 256, size=(ns, self.desc_bytes), dtype=np.uint8)])
         lid = np.concatenate([lid, np.full(ns, -1)])
         perm = rng.permutation(len(lid))
+        if self.camera is not None:
+            pts = self.camera.distort(pts)
         return pts[perm], desc[perm], lid[perm]
 
 
@@ -187,8 +202,9 @@ class _Frame:
     """CFrame: keypoints (undistorted), descriptors, 3D index per keypoint
     (-1: unmatched), pose."""
 
-    def __init__(self, no, pts, desc):
+    def __init__(self, no, pts, desc, ptsd=None):
         self.no, self.pts, self.desc = no, pts, desc
+        self.ptsd = ptsd    # distorted positions (CFrame::_pts_dist) when the loop has a camera
         self.slot = -1  # keyframes: the matcher's keyframe-store slot
         self.pt3d = np.full(len(pts), -1, np.int64)
         self.rot, self.t = np.zeros(3), np.zeros(3)
@@ -197,7 +213,7 @@ class _Frame:
         return int((self.pt3d >= 0).sum())
 
     def copy(self):
-        f = _Frame(self.no, self.pts, self.desc)
+        f = _Frame(self.no, self.pts, self.desc, self.ptsd)
         f.pt3d, f.rot, f.t, f.slot = self.pt3d.copy(), self.rot.copy(), self.t.copy(), self.slot
         return f
 
@@ -250,14 +266,20 @@ def _filter_matches(K, f0, f1, uv0, uv1, X, max_err):
 class LiveSfM:
     def __init__(self, stream: KeypointStream | None = None, device: int = 0, init_gap: int = 5,
                  init: str = "known", init_options: dict | None = None, cull: bool = False,
-                 cull_kf_rate: float = 0.9, min_visibility: int = 3):
+                 cull_kf_rate: float = 0.9, min_visibility: int = 3, camera=None):
         if init not in ("known", "estimate"):
             raise ValueError(f"init must be 'known' or 'estimate', not {init!r}")
         self.init = init
         self.init_options = dict(init_options or {})
         self.init_log: list[dict] = []   # init="estimate": one entry per attempt
         self.stream = stream if stream is not None else KeypointStream()
-        self.K = self.stream.K
+        # camera (sfm_amd.camera.Camera, CSfM(K, imSize, d)): process() takes
+        # distorted pixels, undistorts them on the device and works in the
+        # Kopt image throughout; None: detector output is taken as undistorted
+        self.camera = camera
+        self.K = camera.Kopt if camera is not None else self.stream.K
+        self._installed = False    # process_image: the matcher already holds the current frame
+        self._front = None
         self.device = device
         self.init_gap = int(init_gap)
         self.matcher = FeatureMatcher(self.stream.desc_bytes, device=device)
@@ -295,26 +317,61 @@ class LiveSfM:
             self.process(k, pts, desc)
 
     def process(self, k: int, pts, desc) -> None:
+        if self.camera is None:
+            self._process(k, pts, desc, None)
+            return
+        # CFrame::setKeyPoints: undistortPoints(_pts_dist, _pts, _K, _d, _Kopt)
+        ptsd = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 2)
+        self._process(k, self.camera.undistort(ptsd, device=self.device), desc, ptsd)
+
+    def process_image(self, k: int, img) -> None:
+        """process() from the frame itself (8-bit grey or 3-channel): grey
+        conversion, BRISK and the undistortion in one device call
+        (sfm_frame_detect), whose result is already the matcher's current
+        frame when the loop gets to it."""
+        if self.camera is None:
+            raise ValueError("process_image needs a camera")
+        if self._front is None:
+            from .camera import FrameFrontEnd
+            th = getattr(self.stream, "threshold", 60)
+            oc = getattr(self.stream, "octaves", 6)
+            self._front = FrameFrontEnd(self.camera, matcher=self.matcher, threshold=th, octaves=oc)
+        kps, _, desc, pts = self._front.detect(img)
+        self._installed = True
+        try:
+            self._process(k, pts, desc, kps[:, :2].astype(np.float64))
+        finally:
+            self._installed = False
+
+    def _push_current(self, pts, desc, ptsd) -> None:
+        """sfm_matcher_push_frame of the frame being processed, unless
+        process_image has installed it on the device already."""
+        if self._installed:
+            self._installed = False
+            return
+        self.matcher.push_frame(pts, desc, ptsd)
+
+    def _process(self, k: int, pts, desc, ptsd) -> None:
         self.frame_no = k
         self.stats["frames"] += 1
         if not self.kfs:
-            f = _Frame(k, pts, desc)
+            f = _Frame(k, pts, desc, ptsd)
             self.kfs.append(f)                  # first keyframe at the origin (CFrame.cpp:229-235)
             self._store_keyframe(f)
-            self.matcher.push_frame(pts, desc)
+            self._push_current(pts, desc, ptsd)
             self.prev = f
             return
         if len(self.kfs) == 1:
             if k < self.init_gap:
                 return
-            self._initialise(k, pts, desc)
+            self._initialise(k, pts, desc, ptsd)
             return
-        self._tracking(k, pts, desc)
+        self._tracking(k, pts, desc, ptsd)
 
     # ---- initial map (CSfM::init) ----------------------------------------------
-    def _initialise(self, k, pts, desc) -> None:
+    def _initialise(self, k, pts, desc, ptsd=None) -> None:
         f0 = self.kfs[0]
-        f1 = _Frame(k, pts, desc)
+        f1 = _Frame(k, pts, desc, ptsd)
         if self.init == "estimate":
             # CSfM.cpp:823-946 on the device: no pose is read from the stream
             i0, i1 = self.matcher.match(f0.pts, f0.desc, f1.pts, f1.desc)
@@ -324,11 +381,11 @@ class LiveSfM:
             if not r.ok:
                 return  # the first keyframe stays; the next frame tries again (CSfM.cpp:984-1000)
             f1.rot, f1.t = _rodrigues_inv(r.R), r.t.copy()
-            self.matcher.push_frame(pts, desc)
+            self._push_current(pts, desc, ptsd)
             ok, X = r.keep.astype(bool), r.X
         else:
             f1.rot, f1.t = self.stream.pose(k)
-            self.matcher.push_frame(pts, desc)
+            self._push_current(pts, desc, ptsd)
             i0, i1 = self.matcher.match(f0.pts, f0.desc, f1.pts, f1.desc)
             X = triangulate_points(np.zeros(len(i0), np.int32), np.ones(len(i0), np.int32), f0.pts[i0], f1.pts[i1],
                                    np.stack([f0.P(self.K), f1.P(self.K)]), device=self.device)
@@ -349,11 +406,11 @@ class LiveSfM:
         self.prev.rot, self.prev.t = self.kfs[-1].rot.copy(), self.kfs[-1].t.copy()
 
     # ---- CSfM::tracking ----------------------------------------------------------
-    def _tracking(self, k, pts, desc) -> None:
+    def _tracking(self, k, pts, desc, ptsd=None) -> None:
         t0 = time.perf_counter()
-        cur = _Frame(k, pts, desc)
+        cur = _Frame(k, pts, desc, ptsd)
         self._age += 1                          # CSfM.cpp:629, whatever the frame's fate
-        self.matcher.push_frame(pts, desc)
+        self._push_current(pts, desc, ptsd)
         if self.fused_track:
             # matchFeatures + getPointsAtIdx + solvePnPRansac in one device call
             # (sfm_track_pnp); the composed form below is the test's reference
@@ -366,7 +423,7 @@ class LiveSfM:
         if nm < MIN_FEATURES:
             # lost: keep matching against the previous frame (no swap)
             self.lost += 1
-            self.matcher.push_frame(self.prev.pts, self.prev.desc)
+            self.matcher.push_frame(self.prev.pts, self.prev.desc, self.prev.ptsd)
             self.times["track"] += time.perf_counter() - t0
             return
         self.lost = 0
