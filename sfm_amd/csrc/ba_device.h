@@ -6,7 +6,8 @@
 #include <algorithm>
 #include <cstdint>
 
-#include "ba_lm.h"  // the scalar block's indices (enum Scalar) and the LM state machine
+#include "ba_lm.h"    // the scalar block's indices (enum Scalar) and the LM state machine
+#include "ba_plan.h"  // which kernel variant each pass runs (ProblemPlan, SolvePlan)
 
 namespace sfm {
 
@@ -27,8 +28,7 @@ constexpr int kUcam = 28;
 // (k_backsub_pm; written by k_cam_update, copied to LDS as it stands):
 // R 9 | t 3 | K 5 | omega 3 | tau 3 | R_new 9 | t_new 3 | first-order flag |
 // pad (an odd stride: a wave's 64 cameras spread over all LDS banks).
-constexpr int kCamPM = 37;
-constexpr int kCamPMMax = 512;  // cameras whose records fit the 160-KB LDS
+constexpr int kCamPM = 37;  // (kCamPMMax of them fit the 160-KB LDS: ba_plan.h)
 // Per-point record: V (6 packed lower), b_p (3), pad | L (6), z (3), pad.
 constexpr int kPtV = 10;
 constexpr int kPtL = 10;
@@ -60,6 +60,7 @@ struct ReduceBatch {
 };
 
 struct DevProblem {
+  ProblemPlan plan;          // set_problem's decisions (ba_plan.h); the arrays below exist as it says
   int32_t C = 0, P = 0;      // cameras (global), points (this shard)
   int64_t N = 0;             // observations (this shard)
   // structure (point-major observation order; within a point by camera,
@@ -76,11 +77,9 @@ struct DevProblem {
   // Schur / Cholesky overlap (compute_step_enqueue): per 64x64 tile of S the
   // camera blocks landed so far and the count that completes it
   int32_t* tile_cnt = nullptr;  // [nblk * nblk], zeroed before each Schur pass
-  int32_t* tile_exp = nullptr;  // [nblk * nblk], from set_problem
-  int32_t overlap = 0;          // k_chol_fused waits on tile_cnt (and leaves CUs to k_schur_pts)
+  int32_t* tile_exp = nullptr;  // [nblk * nblk], from set_problem (both with plan.overlap: k_chol_fused
+                                // waits on tile_cnt and leaves CUs to k_schur_pts)
   int32_t* jgrp = nullptr;     // [9] chunk-table offsets of the 8 point slices (one per XCD)
-  int32_t jac_blocks = 1;      // persistent grid of k_jacobian in the solve (cost partials)
-  int32_t jac_blocks_rec = 1;  // ... of the record-writing variant (evaluate API, bench roofline)
   double* uv_cm = nullptr;     // [N_pad][2] uv in camera-major order
   int32_t* pos = nullptr;      // [N] camera-major position of point-major observation q
   double* Kc = nullptr;        // [C][5] fx skew cx fy cy
@@ -99,13 +98,10 @@ struct DevProblem {
   // per-iteration work arrays
   double* camR = nullptr;     // [C][36]
   double* camRn = nullptr;    // [C][12] candidate R (9) + t (3)
-  bool pm_backsub = false;    // large reduced systems with C <= kCamPMMax: the back substitution is
-                              // k_backsub_pm's one pass (its camera records, kCamPM doubles each, live in LDS)
   double* jrec = nullptr;     // [N_pad][20] at camera-major position (J_X 6 | r 2 | J_c 12): evaluate API only,
                               // allocated on first use (the solve writes no records)
   double* eu = nullptr;       // [N][kEU] back substitution pass A output (point-major), or
-                              // [N_pad][kEU] at camera-major positions (eu_cm)
-  bool eu_cm = false;
+                              // [N_pad][kEU] at camera-major positions (plan.eu_cm)
   double* ypt = nullptr;      // [P][3] point steps y_p (scaled space)
   int32_t* wcam = nullptr;    // [N_pad / 64] camera of each camera-major wavefront (runs padded to 64)
   double* ptV = nullptr;      // [P][10]
@@ -138,17 +134,14 @@ struct DevProblem {
   int32_t* seg = nullptr;     // [n_blk + 1]
   int32_t* bpts = nullptr;    // [n_pairs]
   int32_t* bperm = nullptr;   // [n_bslots] k_schur_pts work order (XCD-aware row groups; -1: empty slot;
-                              // nullptr: plain block order, small systems)
+                              // nullptr: plain block order, without plan.xcd_block_order)
   int64_t n_bslots = 0;
   int4* srec = nullptr;       // [n_bslots] with bperm: slot k's {c1, c2, seg[b], seg[b + 1]}, b = bperm[k]; c1 = -1:
                               // empty slot (k_schur_pairs_rot_pw reads these in place of bperm -> blk -> seg)
-  int32_t schur_wgs = 0;      // its grid (SFM_SCHUR_WGS, a test knob; 0: eight workgroups per CU)
   double* camS = nullptr;     // [C][kCamSR] with ptG: each camera's staged record (k_cam_stage_rot, once per pass)
   double* ptS = nullptr;      // [P][kPtS] X 3, scale 3, l10 l20 l21, 1/l_ii 3, z 3, pad
   double* ptG = nullptr;      // [P][16] X 3, G_p = diag(s_p) L_p^-T (6, upper), pad: k_schur_pairs_rot's record
-                              // (large reduced systems; nullptr: k_schur_pts and ptS alone)
-  int32_t schur_pts_sub = 8;  // lanes per block (8, 16, 32 or 64; C3: 1.07 / 1.09 / 1.21 / 1.49 ms per solve)
-  bool schur_wg_blocks = false;  // one block per 4-wave workgroup (small systems with long pair lists)
+                              // (plan.large_system; nullptr: k_schur_pts and ptS alone)
   // per-wave diagonal-block / rhs partials from k_obs_prep_rc ([N_pad/64][27])
   double* dpart = nullptr;
   // per-chunk U_c / b_c partials from k_jacobian ([N_pad/64][27])
@@ -159,9 +152,8 @@ struct DevProblem {
   // the same stream wave-major, for the lane-per-point passes (k_point_eval_*,
   // k_backsub_pm): wave w = points 64 w .. 64 w + 63 holds m_w = its largest
   // view count slots, slot k of lane l at (woff[w] + k) * 64 + l, so a wave's
-  // loads of one step are lane-contiguous.  nullptr (the passes read uv_pm /
-  // cam_pm): no points or observations, the keyframe-sized small setup path,
-  // padding above the cap (hostlayout::wave_major_fits), or SFM_PM_WAVE_MAJOR=0
+  // loads of one step are lane-contiguous.  With plan.wave_major; nullptr
+  // otherwise (the passes read uv_pm / cam_pm)
   int32_t* woff = nullptr;     // [ceil(P / 64) + 1] exclusive sum of m_w
   double* uv_wm = nullptr;     // [64 woff[last]][2]
   int32_t* cam_wm = nullptr;   // [64 woff[last]] past a point's count: its last camera (0: none)
@@ -186,6 +178,9 @@ enum PartialSlot {
 };
 
 // ---- launchers (ba_kernels.hip) ----
+// Which kernel a launcher starts is its variant argument's or the problem
+// plan's say (ba_plan.h holds the conditions, once); a size of zero launches
+// nothing.
 void launch_cam_prep(const DevProblem& d, double* cam, bool count_norm, hipStream_t s);
 // the device LM loop's accept folded in: cam_new -> cam, X_new -> X (grid >= the copy's workgroups)
 void launch_cam_prep_accept(const DevProblem& d, bool count_norm, int grid, hipStream_t s);
@@ -199,27 +194,24 @@ void launch_cam_finalize(const DevProblem& d, int mode, bool reuse_diag, bool co
 void launch_cam_sum_finalize(const DevProblem& d, int mode, bool count_grad, hipStream_t s);
 // mode 0: unscaled pass -> scale_p; mode 1: V, b, diag (if !reuse), gradient, x-norm
 // factor (mode 1): the pass also does launch_point_factor's work for the coming step's radius
-void launch_point_eval(const DevProblem& d, int mode, bool reuse_diag, hipStream_t s, bool factor = false,
-                       double radius = 0.0);
+void launch_point_eval(const DevProblem& d, PointPass v, int mode, bool reuse_diag, hipStream_t s,
+                       bool factor = false, double radius = 0.0);
 // launch_point_factor + launch_obs_prep
 void launch_point_prep(const DevProblem& d, double radius, hipStream_t s);
 // the per-wave diagonal-block / rhs partials (k_obs_prep_rc; reads the point records)
 void launch_obs_prep(const DevProblem& d, hipStream_t s);
 void launch_point_factor(const DevProblem& d, double radius, hipStream_t s);
-void launch_schur(const DevProblem& d, double radius, bool add_diag, hipStream_t s);
+// the diagonal blocks + rhs and the pair pass, not overlapped (WgBlocks: in one launch)
+void launch_schur(const DevProblem& d, PairPass v, double radius, bool add_diag, hipStream_t s);
 // its two parts: the diagonal blocks + rhs (k_schur_diag_sum) and the
-// off-diagonal blocks (k_schur_pts; tile_cnt != nullptr: overlapped with the
-// factorisation, blocks counted per 64x64 tile as they land)
+// off-diagonal blocks (overlapped: beside the factorisation, the blocks in
+// their plain order and counted per 64x64 tile in tile_cnt as they land)
 void launch_schur_diag(const DevProblem& d, double radius, bool add_diag, hipStream_t s);
 // cams_staged: camS already holds the cameras' records (launch_cam_sum_diag)
-void launch_schur_offdiag(const DevProblem& d, int* tile_cnt, hipStream_t s, bool cams_staged = false);
-// whether the Schur pair pass reads the cameras' staged records (camS)
-inline bool cam_records_used(const DevProblem& d) {
-  return d.n_blk && d.ptG && d.srec && d.camS && !d.schur_wg_blocks;
-}
+void launch_schur_offdiag(const DevProblem& d, PairPass v, bool overlapped, hipStream_t s, bool cams_staged = false);
 // launch_cam_sum_finalize (mode 1, with the gradient partials) and
 // launch_schur_diag in one launch (after launch_obs_prep, in the evaluation);
-// stage_cams: and k_cam_stage_rot's records, where the pair pass reads them
+// stage_cams: and k_cam_stage_rot's records (SolvePlan::stage_cams)
 void launch_cam_sum_diag(const DevProblem& d, double radius, bool add_diag, hipStream_t s, bool stage_cams = false);
 // the scaled launch_jacobian and launch_obs_prep in one camera-major pass
 // (k_jac_obs_prep; after the point pass that wrote ptS)
@@ -228,47 +220,27 @@ void launch_pad_init(const DevProblem& d, hipStream_t s);
 void launch_pack_upper(const DevProblem& d, bool unpack, hipStream_t s);
 // dst = scale * src unless *gate == 0 (gate may be nullptr)
 void launch_gated_copy(const double* src, double* dst, int64_t n, double scale, const int32_t* gate, hipStream_t s);
-// (not on the one-pass back substitution's path: k_backsub_pm takes the camera step itself)
+// (not with Backsub::OnePass: k_backsub_pm takes the camera step itself)
 void launch_cam_update(const DevProblem& d, bool count_norm, hipStream_t s);
-// whether a step's back substitution runs as the one point-major pass
-// (k_backsub_pm: cameras and points both variable, on the large path)
-inline bool backsub_pm(const DevProblem& d, bool cams_var, bool pts_var) {
-  return d.pm_backsub && cams_var && pts_var && d.P > 0 && d.N_pad > 0;
-}
-// small systems (C <= 64): the point pass and the camera sums + finalisation
-// (k_cam_sum_finalize's work) in one launch; false when not applicable
-bool launch_point_eval_with_cams(const DevProblem& d, int mode, bool count_grad, hipStream_t s);
-// with backsub_pm the one pass takes the camera step too (launch_cam_update's
-// work, count_norm as there: no launch_cam_update before it)
-void launch_point_backsub(const DevProblem& d, hipStream_t s, bool cams_var = true, bool pts_var = true,
+// CamSums::InPointPass: the point pass and the camera sums + finalisation
+// (k_cam_sum_finalize's work) in one launch
+void launch_point_eval_with_cams(const DevProblem& d, int mode, bool count_grad, hipStream_t s);
+// OnePass takes the camera step too (launch_cam_update's work, count_norm as
+// there: no launch_cam_update before it)
+void launch_point_backsub(const DevProblem& d, Backsub v, hipStream_t s, bool cams_var = true, bool pts_var = true,
                           bool count_norm = false);
-// grid of the XCD-ordered observation passes (k_obs_prep_rc, k_backsub_a_rc):
-// one workgroup per 4 chunks, a multiple of 8 (one point slice per XCD)
-inline int obs_xcd_blocks(const DevProblem& d) {
-  // one wave per chunk of the LARGEST slice (slices differ by ~5% at C3; a
-  // grid sized by the mean left the largest slice's excess chunks to a
-  // second round of waves: 45.6 -> 50.0 us for k_obs_prep_rc)
-  const int64_t per = d.xcd_slice_max > 0 ? (int64_t(d.xcd_slice_max) + 3) / 4
-                                          : ((d.N_pad / 64 + 3) / 4 + 7) / 8;
-  return int(8 * std::max<int64_t>(1, per));
-}
-// grid of the XCD-ordered point pass of the back substitution (k_backsub_b):
-// workgroup b serves point slice b % 8 -- the points whose observations the
-// XCD-ordered passes ran on XCD b % 8 -- in blocks of kThreads points
-inline int pt_xcd_blocks(const DevProblem& d) {
-  const int64_t per_slice = (int64_t(d.P) + 7) / 8;
-  return int(8 * std::max<int64_t>(1, (per_slice + kThreads - 1) / kThreads));
-}
+// grids of the XCD-ordered observation passes and of the back substitution's point pass (ba_plan.h)
+inline int obs_xcd_blocks(const DevProblem& d) { return obs_xcd_blocks(d.N_pad, d.xcd_slice_max); }
+inline int pt_xcd_blocks(const DevProblem& d) { return pt_xcd_blocks(d.P); }
 void launch_cam_solve(const DevProblem& d, double radius, hipStream_t s);
 // sum (op 0) or max (op 1) of `nb` partials in slot into scal[dst]
 void launch_reduce(const DevProblem& d, int slot, int nb, int op, int dst, hipStream_t s);
 void launch_reduce_batch(const DevProblem& d, const ReduceBatch& b, bool copy_fail, hipStream_t s);
-int blocks_for(int64_t n, int threads);
 
 // ---- dense Cholesky (chol_kernels.hip) ----
 // cam_step >= 0: a small system's one-workgroup factor also takes the
 // camera step (k_cam_update; cam_step > 0: with its step-length partial);
-// returns whether it did.  overlap: d.overlap when the factor runs beside
+// returns whether it did.  overlap: plan.overlap when the factor runs beside
 // k_schur_pts (its helpers then await tile_cnt and take the overlap's grid),
 // 0 otherwise -- only the overlapped branch zeroes and fills tile_cnt
 bool launch_cholesky(const DevProblem& d, int epoch, hipStream_t s, bool clear_fail = true, int cam_step = -1,

@@ -38,10 +38,13 @@ struct sfm_ba_handle {
   int device = 0;
   hipStream_t stream = nullptr;
   sfm::DevProblem d;
-  int32_t mode = SFM_BA_STRUCT_AND_POSE;  // of the running solve (CTracker.h:67)
   int32_t bs_epoch = 0;          // stamp of the last back-substitution launch (k_backsolve flags)
   int32_t chol_epoch = 0;        // launches of the fused Cholesky since the last set_problem
-  bool force_pack = false;       // SFM_FORCE_PACK=1: exercise the packed all-reduce path on one rank (tests)
+  // ba_plan.h: the switches (the problem's half read by set_problem, the
+  // solve's by each solve) and the running solve's plan; the problem's plan
+  // lies with the problem (d.plan)
+  sfm::SolveKnobs knobs;
+  sfm::SolvePlan plan;
   std::vector<std::pair<size_t, void*>> allocs;  // (bytes, buffer) of the resident problem
   std::vector<std::pair<size_t, void*>> tmps;    // set_problem's scratch (back to the pool when it returns)
   std::multimap<size_t, void*> pool;             // buffers of earlier problems, reused by size
@@ -109,15 +112,11 @@ struct sfm_ba_handle {
   // geometrically, only while the stream is idle.
   uint8_t* stage = nullptr;
   size_t stage_cap = 0;
-  // device LM loop without a collective: the phase reductions run the
-  // bookkeeping in their last workgroup (k_reduce_batch_lm)
-  bool fuse_lm = false;
   // device LM loop: the evaluation's k_cam_prep also makes the accepted
   // candidate current (k_lm_accept folded in; its grid covers the copy)
   int accept_grid = 0;  // < 0: done by the deciding reduction (AcceptFold)
-  bool accept_fold = false;
   // The step's radius-dependent preparation (point factor, k_obs_prep_rc,
-  // diagonal blocks) folded into the evaluation (step_prep_folds): the
+  // diagonal blocks) folded into the evaluation (plan.prep_folded): the
   // radius changes only in the step's decision, so an evaluation prepares
   // the coming step.  eval_radius: that step's radius (host loop; the device
   // loop's kernels read LmCtl::radius).  prep_fresh: the prep on the device
@@ -127,16 +126,13 @@ struct sfm_ba_handle {
   // stand-alone kernels first.
   double eval_radius = 0.0;
   bool prep_fresh = false;
-  // eval_fused (per solve; SFM_EVAL_SPLIT=1: off): such an evaluation runs
-  // its point pass first and then ONE camera-major pass for the scaled
-  // Jacobian sums and k_obs_prep_rc's (k_jac_obs_prep), and k_cam_sum_diag
-  // also leaves the cameras' staged records (camS).  cams_staged: it did, so
-  // the Schur pair pass skips k_cam_stage_rot -- an unsuccessful step leaves
-  // the cameras, and with them the records, as they are.
-  bool eval_fused = false;
+  // cams_staged: the evaluation's k_cam_sum_diag left the cameras' staged
+  // records (plan.stage_cams), so the Schur pair pass skips k_cam_stage_rot --
+  // an unsuccessful step leaves the cameras, and with them the records, as
+  // they are.
   bool cams_staged = false;
   int n_cu = 0;  // compute units of the device (queried once)
-  // Schur / Cholesky overlap (DevProblem::overlap): the factorisation's
+  // Schur / Cholesky overlap (DevProblem::plan.overlap): the factorisation's
   // stream and the two events that fork and join it
   hipStream_t stream2 = nullptr;
   hipEvent_t ov_ev[2] = {nullptr, nullptr};
@@ -223,10 +219,7 @@ inline void free_problem(sfm_ba_handle* h) {
   h->has_problem = false;
 }
 
-inline bool env_flag(const char* name) {
-  const char* v = std::getenv(name);
-  return v && v[0] == '1';
-}
+using sfm::env_flag;  // (ba_plan.h)
 
 // SFM_TIMING=1: host phase times of sfm_ba_set_problem and of the device LM
 // loop's batches on stderr.

@@ -170,23 +170,33 @@ inline bool wave_major_fits(int64_t slots, int64_t N, int P) {
 // block -> 8; C1 / C2, ~460 -> 64; SFM_SCHUR_PTS_SUB forces 8 / 16 / 32 / 64).
 // Few blocks with long lists (keyframe-sized: C1 210 blocks of ~460 pairs): a
 // workgroup per block instead of a wave (SFM_SCHUR_WG=0/1 forces).  The
-// overrides are the variables' values, nullptr when unset.
+// overrides are the variables' values, nullptr when unset, or those values
+// parsed (what ba_plan.h's SolveKnobs keeps): pts_sub_forced 0 and wg_forced
+// -1 when unset.
 struct SchurShape {
   int pts_sub = 8;
   bool wg_blocks = false;
 };
-inline SchurShape schur_shape(int64_t n_pairs, int64_t n_blk, const char* pts_sub_env, const char* wg_env) {
+inline int schur_pts_sub_forced(const char* v) {
+  if (!v) return 0;
+  const int n = std::atoi(v);
+  return n == 64 ? 64 : n == 32 ? 32 : n == 8 ? 8 : 16;
+}
+inline int schur_wg_forced(const char* v) { return v ? (v[0] == '1' ? 1 : 0) : -1; }
+inline SchurShape schur_shape(int64_t n_pairs, int64_t n_blk, int pts_sub_forced, int wg_forced) {
   SchurShape sh;
   const double avg = n_blk ? double(n_pairs) / double(n_blk) : 0.0;
-  if (pts_sub_env) {
-    const int v = std::atoi(pts_sub_env);
-    sh.pts_sub = v == 64 ? 64 : v == 32 ? 32 : v == 8 ? 8 : 16;
+  if (pts_sub_forced) {
+    sh.pts_sub = pts_sub_forced;
   } else {
     while (sh.pts_sub < 64 && sh.pts_sub < avg / 10.0) sh.pts_sub *= 2;
   }
   sh.wg_blocks = sh.pts_sub == 64 && n_blk <= 4 * 256 && avg >= 256.0;
-  if (wg_env) sh.wg_blocks = wg_env[0] == '1' && sh.pts_sub == 64;
+  if (wg_forced >= 0) sh.wg_blocks = wg_forced == 1 && sh.pts_sub == 64;
   return sh;
+}
+inline SchurShape schur_shape(int64_t n_pairs, int64_t n_blk, const char* pts_sub_env, const char* wg_env) {
+  return schur_shape(n_pairs, n_blk, schur_pts_sub_forced(pts_sub_env), schur_wg_forced(wg_env));
 }
 
 // One 64-wide wavefront chunk of a camera's run (the int4 the device reads:

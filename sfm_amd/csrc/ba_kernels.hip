@@ -17,6 +17,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 #include "ba_device.h"
 #include "ba_common.h"
 
@@ -2493,7 +2494,7 @@ __global__ __launch_bounds__(1024) void k_reduce(const double* __restrict__ src,
 
 }  // namespace
 
-int blocks_for(int64_t n, int threads) { return int((n + threads - 1) / threads); }
+// ---- launchers: the variant to start is the caller's plan's (ba_plan.h) ----
 
 static inline double* slot(const DevProblem& d, int s) { return d.partials + size_t(s) * d.max_blocks; }
 
@@ -2508,11 +2509,11 @@ void launch_cam_prep_accept(const DevProblem& d, bool count_norm, int grid, hipS
 void launch_jacobian(const DevProblem& d, bool scaled, hipStream_t s, bool write_records) {
   // the record-writing variant (evaluate API) runs on its own, smaller grid
   if (write_records)
-    k_jacobian<true><<<d.jac_blocks_rec, kThreads, 0, s>>>(d.jgrp, d.jchunks, d.cm_p, d.uv_cm, d.Kc, d.cam, d.camR,
+    k_jacobian<true><<<d.plan.jac_blocks_rec, kThreads, 0, s>>>(d.jgrp, d.jchunks, d.cm_p, d.uv_cm, d.Kc, d.cam, d.camR,
                                                            d.X, d.scale_c, d.scale_p, scaled ? 1 : 0, d.jrec,
                                                            slot(d, kPCost), d.jpart, d.gate);
   else
-    k_jacobian<false><<<d.jac_blocks, kThreads, 0, s>>>(d.jgrp, d.jchunks, d.cm_p, d.uv_cm, d.Kc, d.cam, d.camR, d.X,
+    k_jacobian<false><<<d.plan.jac_blocks, kThreads, 0, s>>>(d.jgrp, d.jchunks, d.cm_p, d.uv_cm, d.Kc, d.cam, d.camR, d.X,
                                                         d.scale_c, d.scale_p, scaled ? 1 : 0, d.jrec, slot(d, kPCost),
                                                         d.jpart, d.gate);
 }
@@ -2521,7 +2522,7 @@ void launch_cam_reduce(const DevProblem& d, hipStream_t s) {
 }
 // the wave-major copy where set_problem made one, else the point-major arrays
 static PmStream pm_stream(const DevProblem& d) {
-  return d.uv_wm ? PmStream{d.pt_off, d.cam_wm, d.uv_wm, d.woff} : PmStream{d.pt_off, d.cam_pm, d.uv_pm, nullptr};
+  return d.plan.wave_major ? PmStream{d.pt_off, d.cam_wm, d.uv_wm, d.woff} : PmStream{d.pt_off, d.cam_pm, d.uv_pm, nullptr};
 }
 static CamFold cam_fold(const DevProblem& d, int mode, bool count_grad) {
   return CamFold{d.cam_rng, d.jpart, d.Ucam, d.scale_c, d.diag_c, d.min_diag, d.max_diag, mode, d.C,
@@ -2530,47 +2531,44 @@ static CamFold cam_fold(const DevProblem& d, int mode, bool count_grad) {
 void launch_cam_sum_finalize(const DevProblem& d, int mode, bool count_grad, hipStream_t s) {
   if (d.C) k_cam_sum_finalize<<<d.C, 64, 0, s>>>(cam_fold(d, mode, count_grad), d.gate);
 }
-bool launch_point_eval_with_cams(const DevProblem& d, int mode, bool count_grad, hipStream_t s) {
-  if (d.P == 0 || d.C == 0 || d.C > 64) return false;
+void launch_point_eval_with_cams(const DevProblem& d, int mode, bool count_grad, hipStream_t s) {
   const int nb = blocks_for(d.P, kThreads) + (d.C + kThreads / 64 - 1) / (kThreads / 64);
   k_point_eval_lds<64><<<nb, kThreads, 0, s>>>(d.P, d.C, pm_stream(d), d.camR, d.cam, d.Kc, d.X,
                                                d.scale_p, d.diag_p, d.ptV, d.min_diag, d.max_diag, mode, 0,
                                                slot(d, kPGradPt), slot(d, kPXNormPt), d.gate,
                                                cam_fold(d, mode, count_grad), PointFold{});
-  return true;
 }
 void launch_cam_finalize(const DevProblem& d, int mode, bool reuse_diag, bool count_grad, hipStream_t s) {
   k_cam_finalize<<<blocks_for(d.C, kThreads), kThreads, 0, s>>>(d.C, d.Ucam, d.scale_c, d.diag_c, d.min_diag, d.max_diag, mode,
                                                                reuse_diag ? 1 : 0,
                                                                count_grad ? slot(d, kPGradCam) : nullptr, d.gate);
 }
-// A/B switch, read once (SFM_PE_GROUPS1=1: the 256-thread point pass).
-static bool env_flag_k(const char* name) {
-  const char* v = std::getenv(name);
-  return v && v[0] == '1';
-}
-void launch_point_eval(const DevProblem& d, int mode, bool reuse_diag, hipStream_t s, bool factor, double radius) {
+void launch_point_eval(const DevProblem& d, PointPass v, int mode, bool reuse_diag, hipStream_t s, bool factor,
+                       double radius) {
   if (d.P == 0) return;
   const int nb = blocks_for(d.P, kThreads);
   // factor (mode 1): the pass goes on to k_point_factor's work for the coming step's radius
   const PointFold pf = factor && mode == 1 ? PointFold{radius, d.radius_dev, d.ptL, d.ptS, d.ptG, slot(d, kPBad)}
                                            : PointFold{};
-  // camera constants from LDS while they fit (C3: 500 cameras, 68 KB)
-#define SFM_PE_LDS(M_)                                                                                              \
+#define SFM_PE_LDS(M_)                                                                                            \
   k_point_eval_lds<M_><<<nb, kThreads, 0, s>>>(d.P, d.C, pm_stream(d), d.camR, d.cam, d.Kc, d.X,      \
                                                d.scale_p, d.diag_p, d.ptV, d.min_diag, d.max_diag, mode,           \
                                                reuse_diag ? 1 : 0, slot(d, kPGradPt), slot(d, kPXNormPt), d.gate,    \
                                                CamFold{}, pf)
-  if (d.C <= 64) SFM_PE_LDS(64);
-  else if (d.C <= 512 && !env_flag_k("SFM_PE_GROUPS1"))
-    k_point_eval_lds<512, 2><<<blocks_for(d.P, 2 * kThreads), 2 * kThreads, 0, s>>>(
-        d.P, d.C, pm_stream(d), d.camR, d.cam, d.Kc, d.X, d.scale_p, d.diag_p, d.ptV, d.min_diag,
-        d.max_diag, mode, reuse_diag ? 1 : 0, slot(d, kPGradPt), slot(d, kPXNormPt), d.gate, CamFold{}, pf);
-  else if (d.C <= 512) SFM_PE_LDS(512);
-  else
-    k_point_eval_rc<<<nb, kThreads, 0, s>>>(d.P, pm_stream(d), d.camR, d.cam, d.Kc, d.X, d.scale_p,
-                                            d.diag_p, d.ptV, d.min_diag, d.max_diag, mode, reuse_diag ? 1 : 0,
-                                            slot(d, kPGradPt), slot(d, kPXNormPt), d.gate, pf);
+  switch (v) {
+    case PointPass::Lds64: SFM_PE_LDS(64); break;
+    case PointPass::Lds512x2:
+      k_point_eval_lds<512, 2><<<blocks_for(d.P, 2 * kThreads), 2 * kThreads, 0, s>>>(
+          d.P, d.C, pm_stream(d), d.camR, d.cam, d.Kc, d.X, d.scale_p, d.diag_p, d.ptV, d.min_diag,
+          d.max_diag, mode, reuse_diag ? 1 : 0, slot(d, kPGradPt), slot(d, kPXNormPt), d.gate, CamFold{}, pf);
+      break;
+    case PointPass::Lds512: SFM_PE_LDS(512); break;
+    case PointPass::Rc:
+      k_point_eval_rc<<<nb, kThreads, 0, s>>>(d.P, pm_stream(d), d.camR, d.cam, d.Kc, d.X, d.scale_p,
+                                              d.diag_p, d.ptV, d.min_diag, d.max_diag, mode, reuse_diag ? 1 : 0,
+                                              slot(d, kPGradPt), slot(d, kPXNormPt), d.gate, pf);
+      break;
+  }
 #undef SFM_PE_LDS
 }
 void launch_point_factor(const DevProblem& d, double radius, hipStream_t s) {
@@ -2583,7 +2581,7 @@ void launch_point_prep(const DevProblem& d, double radius, hipStream_t s) {
   launch_obs_prep(d, s);
 }
 void launch_jac_obs_prep(const DevProblem& d, hipStream_t s) {
-  k_jac_obs_prep<<<d.jac_blocks, kThreads, 0, s>>>(d.jgrp, d.jchunks, d.cm_p, d.uv_cm, d.cam_obs, d.Kc, d.cam, d.camR,
+  k_jac_obs_prep<<<d.plan.jac_blocks, kThreads, 0, s>>>(d.jgrp, d.jchunks, d.cm_p, d.uv_cm, d.cam_obs, d.Kc, d.cam, d.camR,
                                                    d.scale_c, d.ptS, slot(d, kPCost), d.jpart, d.dpart, d.gate);
 }
 void launch_obs_prep(const DevProblem& d, hipStream_t s) {
@@ -2591,12 +2589,12 @@ void launch_obs_prep(const DevProblem& d, hipStream_t s) {
     k_obs_prep_rc<<<obs_xcd_blocks(d), kThreads, 0, s>>>(d.jgrp, d.jchunks, d.cm_p, d.uv_cm, d.cam_obs, d.camR, d.cam,
                                                          d.Kc, d.scale_c, d.ptS, d.dpart, d.gate);
 }
-void launch_schur(const DevProblem& d, double radius, bool add_diag, hipStream_t s) {
+void launch_schur(const DevProblem& d, PairPass v, double radius, bool add_diag, hipStream_t s) {
   // diagonal blocks + rhs first (k_obs_prep_rc's per-wave partials), then
   // the off-diagonal blocks, which add a block's same-camera duplicate pairs;
   // a small system's block-per-workgroup pass does the first part itself
   // (DiagFold: the workgroup of each diagonal block)
-  if (d.schur_wg_blocks && d.n_blk && d.C) {
+  if (v == PairPass::WgBlocks && d.C) {
     const DiagFold f{d.cam_rng, d.dpart, d.Ucam, d.diag_c, radius, d.radius_dev, add_diag ? 1 : 0, d.C, d.n,
                      (d.n + kNB - 1) / kNB * kNB, d.fail, reinterpret_cast<unsigned long long*>(d.ysol)};
     k_schur_pts<64, kThreads / 64><<<int(d.n_bslots), kThreads, 0, s>>>(d.n_bslots, d.blk, d.seg, d.bpts, d.ptS,
@@ -2605,14 +2603,14 @@ void launch_schur(const DevProblem& d, double radius, bool add_diag, hipStream_t
     return;
   }
   launch_schur_diag(d, radius, add_diag, s);
-  launch_schur_offdiag(d, nullptr, s);
+  launch_schur_offdiag(d, v, false, s);
 }
 void launch_cam_sum_diag(const DevProblem& d, double radius, bool add_diag, hipStream_t s, bool stage_cams) {
   if (!d.C) return;
   const DiagFold f{d.cam_rng, d.dpart, d.Ucam, d.diag_c, radius, d.radius_dev, add_diag ? 1 : 0, d.C, d.n,
                    (d.n + kNB - 1) / kNB * kNB, d.fail, reinterpret_cast<unsigned long long*>(d.ysol)};
   k_cam_sum_diag<<<d.C, 64, 0, s>>>(cam_fold(d, 1, true), f, d.S, d.ld, d.gate, d.camR, d.cam, d.Kc,
-                                    stage_cams && cam_records_used(d) ? d.camS : nullptr);
+                                    stage_cams ? d.camS : nullptr);
 }
 void launch_schur_diag(const DevProblem& d, double radius, bool add_diag, hipStream_t s) {
   if (d.C)
@@ -2620,62 +2618,66 @@ void launch_schur_diag(const DevProblem& d, double radius, bool add_diag, hipStr
                                         d.n, 1, d.gate, d.radius_dev, d.fail,
                                         reinterpret_cast<unsigned long long*>(d.ysol), (d.n + kNB - 1) / kNB * kNB);
 }
-// tile_cnt != nullptr: overlapped with k_chol_fused (compute_step_enqueue):
-// the blocks in their plain order (camera-major: the factor's tile columns
-// complete left to right) and counted per tile
-void launch_schur_offdiag(const DevProblem& d, int* tile_cnt, hipStream_t s, bool cams_staged) {
+// f(lanes per block as a compile-time constant)
+template <class F>
+static void with_sub(int sub, F&& f) {
+  if (sub == 8) f(std::integral_constant<int, 8>{});
+  else if (sub == 16) f(std::integral_constant<int, 16>{});
+  else if (sub == 32) f(std::integral_constant<int, 32>{});
+  else f(std::integral_constant<int, 64>{});
+}
+// overlapped with k_chol_fused (compute_step_enqueue): the blocks in their
+// plain order (camera-major: the factor's tile columns complete left to
+// right) and counted per tile
+void launch_schur_offdiag(const DevProblem& d, PairPass v, bool overlapped, hipStream_t s, bool cams_staged) {
   if (!d.n_blk) return;
-  const int64_t n_slots = tile_cnt ? d.n_blk : d.n_bslots;
-  const int32_t* bperm = tile_cnt ? nullptr : d.bperm;
-  const int sub = d.schur_pts_sub, per = 64 / sub * (kThreads / 64);
+  int* tile_cnt = overlapped ? d.tile_cnt : nullptr;
+  const int64_t n_slots = overlapped ? d.n_blk : d.n_bslots;
+  const int32_t* bperm = overlapped ? nullptr : d.bperm;
+  const int sub = d.plan.schur_pts_sub, per = 64 / sub * (kThreads / 64);
   const int nb = int((n_slots + per - 1) / per);
-#define SFM_PTS(S_)                                                                                           \
-  k_schur_pts<S_><<<nb, kThreads, 0, s>>>(n_slots, d.blk, d.seg, d.bpts, d.ptS, d.camR, d.cam, d.Kc, d.scale_c, \
-                                          d.S, d.ld, bperm, d.gate, tile_cnt, d.nblk, DiagFold{})
-  if (d.schur_wg_blocks) {  // small systems: one block per workgroup
-    k_schur_pts<64, kThreads / 64><<<int(n_slots), kThreads, 0, s>>>(n_slots, d.blk, d.seg, d.bpts, d.ptS,
-                                                                    d.camR, d.cam, d.Kc, d.scale_c, d.S, d.ld,
-                                                                    bperm, d.gate, tile_cnt, d.nblk, DiagFold{});
-    return;
+  switch (v) {
+    case PairPass::WgBlocks:  // small systems: one block per workgroup
+      k_schur_pts<64, kThreads / 64><<<int(n_slots), kThreads, 0, s>>>(n_slots, d.blk, d.seg, d.bpts, d.ptS,
+                                                                      d.camR, d.cam, d.Kc, d.scale_c, d.S, d.ld,
+                                                                      bperm, d.gate, tile_cnt, d.nblk, DiagFold{});
+      break;
+    case PairPass::Pts:
+      with_sub(sub, [&](auto S) {
+        k_schur_pts<decltype(S)::value><<<nb, kThreads, 0, s>>>(n_slots, d.blk, d.seg, d.bpts, d.ptS, d.camR, d.cam,
+                                                                d.Kc, d.scale_c, d.S, d.ld, bperm, d.gate, tile_cnt,
+                                                                d.nblk, DiagFold{});
+      });
+      break;
+    case PairPass::Rot:  // large reduced systems: the rotated-point form (k_point_factor wrote ptG)
+      with_sub(sub, [&](auto S) {
+        k_schur_pairs_rot<decltype(S)::value><<<nb, kThreads, 0, s>>>(n_slots, d.blk, d.seg, d.bpts, d.ptG, d.camR,
+                                                                      d.cam, d.Kc, d.scale_c, d.S, d.ld, bperm, d.gate,
+                                                                      tile_cnt, d.nblk);
+      });
+      break;
+    case PairPass::RotPersistent: {  // ... with persistent waves over the slot and camera records
+      // 2 workgroups per CU are resident (2 waves per SIMD); the grid is four
+      // times that (C3: a wave walks 2 groups, the dispatcher evens out the
+      // lists' unequal groups; one resident generation of longer walks measured
+      // slower, profiles/schur_persistent_ab.txt), never more than one workgroup
+      // per workgroup-sized group of slots
+      const int64_t wg_groups = n_slots / per;  // (n_bslots: a multiple of 8 per)
+      const int grid = d.plan.schur_wgs > 0
+                           ? d.plan.schur_wgs
+                           : int(std::max<int64_t>(8, std::min<int64_t>(8 * std::max(1, d.n_cu), wg_groups)));
+      const int n_tick = int(n_slots / (8 * per)) * (kThreads / 64);  // groups per list
+      const int nbc = (d.C + per - 1) / per;
+      with_sub(sub, [&](auto S) {
+        if (!cams_staged)
+          k_cam_stage_rot<decltype(S)::value><<<nbc, kThreads, 0, s>>>(d.C, d.camR, d.cam, d.Kc, d.scale_c, d.camS,
+                                                                       d.gate);
+        k_schur_pairs_rot_pw<decltype(S)::value><<<grid, kThreads, 0, s>>>(d.srec, n_tick, d.bpts, d.ptG, d.camS,
+                                                                           d.S, d.ld, d.gate);
+      });
+      break;
+    }
   }
-  if (d.ptG && d.srec && !tile_cnt) {  // ... with persistent waves over the slot and camera records
-    // 2 workgroups per CU are resident (2 waves per SIMD); the grid is four
-    // times that (C3: a wave walks 2 groups, the dispatcher evens out the
-    // lists' unequal groups; one resident generation of longer walks measured
-    // slower, profiles/schur_persistent_ab.txt), never more than one workgroup
-    // per workgroup-sized group of slots
-    const int64_t wg_groups = n_slots / per;  // (n_bslots: a multiple of 8 per)
-    const int grid = d.schur_wgs > 0 ? d.schur_wgs
-                                     : int(std::max<int64_t>(8, std::min<int64_t>(8 * std::max(1, d.n_cu), wg_groups)));
-    const int n_tick = int(n_slots / (8 * per)) * (kThreads / 64);  // groups per list
-    const int nbc = (d.C + per - 1) / per;
-#define SFM_ROTP(S_)                                                                                               \
-  if (!cams_staged)                                                                                                \
-    k_cam_stage_rot<S_><<<nbc, kThreads, 0, s>>>(d.C, d.camR, d.cam, d.Kc, d.scale_c, d.camS, d.gate);             \
-  k_schur_pairs_rot_pw<S_><<<grid, kThreads, 0, s>>>(d.srec, n_tick, d.bpts, d.ptG, d.camS, d.S, d.ld, d.gate)
-    if (sub == 8) { SFM_ROTP(8); }
-    else if (sub == 16) { SFM_ROTP(16); }
-    else if (sub == 32) { SFM_ROTP(32); }
-    else { SFM_ROTP(64); }
-#undef SFM_ROTP
-    return;
-  }
-  if (d.ptG) {  // large reduced systems: the rotated-point form (k_point_factor wrote ptG)
-#define SFM_ROT(S_)                                                                                           \
-  k_schur_pairs_rot<S_><<<nb, kThreads, 0, s>>>(n_slots, d.blk, d.seg, d.bpts, d.ptG, d.camR, d.cam, d.Kc, d.scale_c, \
-                                                d.S, d.ld, bperm, d.gate, tile_cnt, d.nblk)
-    if (sub == 8) SFM_ROT(8);
-    else if (sub == 16) SFM_ROT(16);
-    else if (sub == 32) SFM_ROT(32);
-    else SFM_ROT(64);
-#undef SFM_ROT
-    return;
-  }
-  if (sub == 8) SFM_PTS(8);
-  else if (sub == 16) SFM_PTS(16);
-  else if (sub == 32) SFM_PTS(32);
-  else SFM_PTS(64);
-#undef SFM_PTS
 }
 void launch_pack_upper(const DevProblem& d, bool unpack, hipStream_t s) {
   if (d.n == 0) return;
@@ -2701,8 +2703,10 @@ void launch_cam_solve(const DevProblem& d, double radius, hipStream_t s) {
   (void)hipMemsetAsync(d.fail, 0, sizeof(int), s);
   if (d.C) k_cam_solve<<<blocks_for(d.C, kThreads), kThreads, 0, s>>>(d.C, d.Ucam, d.diag_c, radius, d.ysol, d.fail, d.gate, d.radius_dev);
 }
-void launch_point_backsub(const DevProblem& d, hipStream_t s, bool cams_var, bool pts_var, bool count_norm) {
-  if (backsub_pm(d, cams_var, pts_var)) {  // one point-major pass, the camera step included
+void launch_point_backsub(const DevProblem& d, Backsub v, hipStream_t s, bool cams_var, bool pts_var,
+                          bool count_norm) {
+  const bool eu_cm = d.plan.eu_cm;
+  if (v == Backsub::OnePass) {  // one point-major pass, the camera step included
     constexpr int kG = 4;  // one 1024-thread workgroup per CU (its LDS copy is up to 148 KB)
     k_backsub_pm<kG><<<blocks_for(d.P, kG * kThreads), kG * kThreads, 0, s>>>(
         d.P, d.C, pm_stream(d), d.ptL, d.ptV, d.scale_p, d.X, d.X_new, d.ypt,
@@ -2714,14 +2718,14 @@ void launch_point_backsub(const DevProblem& d, hipStream_t s, bool cams_var, boo
   // cameras constant (STRUCT_ONLY): e = J_c y_c = 0 and u = 0
   if (d.N_pad && cams_var)
     k_backsub_a_rc<<<obs_xcd_blocks(d), kThreads, 0, s>>>(d.jgrp, d.jchunks, d.cm_p, d.uv_cm, d.cam_obs, d.camR,
-                                                          d.cam, d.Kc, d.scale_c, d.ptS, d.ysol, d.eu, d.eu_cm ? 1 : 0,
+                                                          d.cam, d.Kc, d.scale_c, d.ptS, d.ysol, d.eu, eu_cm ? 1 : 0,
                                                           slot(d, kPModel), d.gate);
   else if (d.N_pad) {
-    (void)hipMemsetAsync(d.eu, 0, sizeof(double) * 4 * size_t(d.eu_cm ? d.N_pad : d.N), s);
+    (void)hipMemsetAsync(d.eu, 0, sizeof(double) * 4 * size_t(eu_cm ? d.N_pad : d.N), s);
     (void)hipMemsetAsync(slot(d, kPModel), 0, sizeof(double) * size_t(obs_xcd_blocks(d)), s);
   }
   if (d.P && pts_var) {
-    k_backsub_b<<<pt_xcd_blocks(d), kThreads, 0, s>>>(d.P, d.pt_off, d.eu, d.eu_cm ? d.pos : nullptr,
+    k_backsub_b<<<pt_xcd_blocks(d), kThreads, 0, s>>>(d.P, d.pt_off, d.eu, eu_cm ? d.pos : nullptr,
                                                                d.ptL, d.ptV, d.scale_p,
                                                                d.X, d.X_new, d.ypt, slot(d, kPStepPt),
                                                                slot(d, kPBadBack), slot(d, kPModelPt), d.gate);

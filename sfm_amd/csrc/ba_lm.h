@@ -47,7 +47,7 @@ enum Scalar {
 // is not finite.  The driver reports them.
 struct LmCtl {
   int32_t run_step, run_eval, done, termination, error;
-  // The evaluation prepares the coming step (prep_fold, from the driver: step_prep_folds).  An
+  // The evaluation prepares the coming step (prep_fold, from the driver: SolvePlan::prep_folded).  An
   // unsuccessful or invalid step then pauses the loop (run_step = 0, prep_stale = 1): the radius
   // changed with no evaluation to follow, and the driver, which enqueues the stand-alone prep
   // kernels only when it knows they are needed, re-arms the loop with them in front.

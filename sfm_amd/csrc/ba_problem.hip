@@ -55,7 +55,9 @@ struct Setup {
   std::vector<int32_t> cam_slice;
   int64_t pairs_est = 0;
   hostlayout::Runs runs;
-  bool small = false;  // the layouts without radix sorts (ba_setup.hip small path)
+  // what d.plan (ba_plan.h: the small path, the wave-major stream, the Schur
+  // pass's shape, ...) is made from, filled in as the passes learn it
+  ProblemShape shape;
 
   // device scratch (h->tmps) and pieces of resident blobs the setup alone reads
   uint8_t* in_blob = nullptr;
@@ -73,10 +75,8 @@ struct Setup {
   const int32_t* pair_order = nullptr;  // the Schur pair lists' emission order (nullptr: point-major)
   int64_t n_pairs = 0;                  // the pair buffer's size: the device's count, or the small path's bound
   int bperm_per = 0;                    // > 0: the XCD block order's group sizes come back with the last synchronisation
-  // the wave-major copy of the point-major stream (DevProblem::uv_wm): wanted
-  // until its slot total, back with the pair total's round trip, is above the cap
-  bool wm = false;
-  int64_t wm_slots = 0;
+  // the wave-major copy of the point-major stream (DevProblem::uv_wm; wanted
+  // until its slot total, back with the pair total's round trip, is above the cap)
   int32_t* wm_cnt = nullptr;
   // the pinned mirror's 17-slot tail: the k_schur_pts group sizes (16), then
   // the deferred uv's finite check (slot 16)
@@ -109,6 +109,11 @@ struct Setup {
 
 // waves of 64 points (the wave-major stream's woff has one more entry)
 size_t wm_waves(int P) { return (size_t(P) + 63) / 64; }
+
+// The problem's plan from what the setup knows so far: after the camera runs
+// (the counts that come back from the layouts still open), and again once
+// the pair count and the wave-major slot total are in.
+void plan_from_shape(Setup& c) { c.d.plan = plan_problem(c.shape, sharded(c.h), c.h->knobs); }
 
 // Any failure returns through here: the buffers go back to the pool.
 struct ProblemGuard {
@@ -315,28 +320,21 @@ void camera_runs(Setup& c) {
   hostlayout::camera_runs(c.C, c.cam_cnt.data() + 4, &c.runs);
   d.N_pad = c.runs.npad;
   d.n_jchunks = int32_t(c.runs.chunks.size());
-  d.jac_blocks_rec = 8 * std::max(1, std::min((d.n_jchunks / 8 + 3) / 4, 128));  // multiple of 8 (one slice per XCD)
-  // the record-free pass of the solve (no 160-B stores) prefers a larger
-  // grid: 256 workgroups per XCD, 0.256 -> 0.223 ms per C3 solve
-  d.jac_blocks = 8 * std::max(1, std::min((d.n_jchunks / 8 + 3) / 4, 256));
-  if (const char* jw = std::getenv("SFM_JAC_WG_PER_XCD")) {  // tuning knob (tools/sweep_jac.sh)
-    const int v = std::atoi(jw);
-    if (v > 0) d.jac_blocks = 8 * std::max(1, std::min((d.n_jchunks / 8 + 3) / 4, v));
-  }
-  // keyframe-sized problems: the layouts without radix sorts (the same arrays
-  // bit for bit), when the host has the counts and the segments fit the small
-  // path's bounds (SFM_SMALL_SETUP=0: the sorted path)
-  const char* ss = std::getenv("SFM_SMALL_SETUP");
-  c.small = c.plan.host_counts && !(ss && ss[0] == '0') &&
-            hostlayout::small_setup_fits(c.N, c.C, c.P, c.cam_cnt.data() + 4,
-                                         reinterpret_cast<const int32_t*>(c.h->stage + c.plan.o_pc));
-  // the wave-major copy of the point-major stream, for the lane-per-point
-  // passes of the solve (SFM_PM_WAVE_MAJOR=0: none, the passes read uv_pm /
-  // cam_pm).  Not on the small path: its two launches cost a keyframe-sized
-  // one-shot solve 0.02 ms of 0.49 (C1), and a stream of at most 1.3 MB gains
-  // nothing measurable from it (profiles/pm_wave_major_ab.txt)
-  const char* wm = std::getenv("SFM_PM_WAVE_MAJOR");
-  c.wm = c.N > 0 && c.P > 0 && !c.small && !(wm && wm[0] == '0');
+  // The plan so far: the Jacobian passes' grids; keyframe-sized problems take
+  // the layouts without radix sorts (the same arrays bit for bit) when the
+  // host has the counts and the segments fit the small path's bounds; the
+  // others want the wave-major copy of the point-major stream
+  ProblemShape& sh = c.shape;
+  sh.C = c.C;
+  sh.P = c.P;
+  sh.N = c.N;
+  sh.N_pad = d.N_pad;
+  sh.n_jchunks = d.n_jchunks;
+  sh.host_counts = c.plan.host_counts;
+  sh.small_fits = c.plan.host_counts &&
+                  hostlayout::small_setup_fits(c.N, c.C, c.P, c.cam_cnt.data() + 4,
+                                               reinterpret_cast<const int32_t*>(c.h->stage + c.plan.o_pc));
+  plan_from_shape(c);
   c.timer.mark("camera runs (host)");
 }
 
@@ -350,14 +348,14 @@ int alloc_layouts(Setup& c) {
   c.sort_bytes = std::max({setup_sort_bytes(c.N, 64), setup_sort_bytes(nmax, 32), setup_sort_bytes(c.P + 1, 1),
                            setup_sort_bytes(c.N + 1, 2), size_t(256)});
   uint8_t* tb = nullptr;
-  const bool ok = (c.small || c.alloc(d.pt_off, size_t(c.P) + 1)) &&  // (small path: in the camera-run blob)
+  const bool ok = (c.d.plan.small_setup || c.alloc(d.pt_off, size_t(c.P) + 1)) &&  // (small path: in the camera-run blob)
                   c.alloc(d.order, N) && c.alloc(d.uv_pm, 2 * N) && c.alloc(d.cam_pm, N) && c.alloc(d.cam_obs, npad) &&
                   c.alloc(d.cm_p, npad) && c.alloc(d.jchunks, size_t(std::max(1, d.n_jchunks))) &&
                   c.alloc(d.jgrp, size_t(9)) && c.alloc(d.uv_cm, 2 * npad) && c.alloc(d.pos, N) &&
                   c.tmp(c.k64a, N) && c.tmp(c.k64b, N) && c.tmp(c.k32a, size_t(nmax)) && c.tmp(c.k32b, size_t(nmax)) &&
                   c.tmp(c.iota, size_t(nmax)) && c.tmp(c.pt_s, N) && c.tmp(c.cm_order, N) &&
                   c.tmp(c.perm, size_t(std::max<int64_t>(1, nch))) && c.tmp(tb, c.sort_bytes) &&
-                  (!c.wm || (c.alloc(d.woff, wm_waves(c.P) + 1) && c.tmp(c.wm_cnt, wm_waves(c.P) + 1)));
+                  (!c.d.plan.wave_major || (c.alloc(d.woff, wm_waves(c.P) + 1) && c.tmp(c.wm_cnt, wm_waves(c.P) + 1)));
   c.sort_tmp = tb;
   return ok ? 0 : c.rc;
 }
@@ -369,7 +367,7 @@ int upload_runs_blob(Setup& c) {
   DevProblem& d = c.d;
   const hostlayout::SetupPlan& pl = c.plan;
   const hostlayout::Runs& r = c.runs;
-  const bool small = c.small;
+  const bool small = c.d.plan.small_setup;
   StageLayout il;
   const size_t o_rng = il.add(sizeof(int32_t) * r.cam_rng.size()), o_w = il.add(sizeof(int32_t) * r.wcam.size()),
                o_off = il.add(sizeof(int32_t) * r.cam_off.size()),
@@ -471,7 +469,7 @@ int layout_sorted(Setup& c) {
                    c.iota, s);
   if (deferred_uv) launch_pt_off(P, c.k64b, N, C, d.pt_off, s);
   else HIPCHK(exclusive_sum32(c.sort_tmp, c.sort_bytes, c.cnt_p, d.pt_off, int64_t(P) + 1, s));
-  if (c.wm) HIPCHK(launch_wm_off(P, d.pt_off, c.wm_cnt, d.woff, c.sort_tmp, c.sort_bytes, s));
+  if (c.d.plan.wave_major) HIPCHK(launch_wm_off(P, d.pt_off, c.wm_cnt, d.woff, c.sort_tmp, c.sort_bytes, s));
   // camera-major order of the point-major ids: stable sort by camera
   HIPCHK(sort_pairs32(c.sort_tmp, c.sort_bytes, c.k32a, c.k32b, c.iota, c.cm_order, N, uint64_t(std::max(1, C)) - 1,
                       s));
@@ -500,7 +498,7 @@ int enqueue_total_readback(Setup& c) {
   if (!c.plan.deferred_uv) {
     HIPCHK(hipMemcpyAsync(stg, c.poff + c.N, sizeof(int64_t), hipMemcpyDeviceToHost, c.s));
     HIPCHK(hipMemcpyAsync(stg + 8, c.d.jgrp, 9 * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-    if (c.wm)
+    if (c.d.plan.wave_major)
       HIPCHK(hipMemcpyAsync(stg + 48, c.d.woff + wm_waves(c.P), sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
     c.timer.mark("layout launches");
     return 0;
@@ -515,7 +513,7 @@ int enqueue_total_readback(Setup& c) {
   HostCopySet cs;
   cs.add(sd, c.poff + c.N, sizeof(int64_t));
   cs.add(sd + 8, c.d.jgrp, 9 * sizeof(int32_t));
-  if (c.wm) cs.add(sd + 48, c.d.woff + wm_waves(c.P), sizeof(int32_t));
+  if (c.d.plan.wave_major) cs.add(sd + 48, c.d.woff + wm_waves(c.P), sizeof(int32_t));
   launch_copy_to_host(cs, c.s);
   return 0;
 }
@@ -527,12 +525,12 @@ int read_pair_total(Setup& c) {
   std::memcpy(g, stg + 8, sizeof(g));
   c.d.xcd_slice_max = 0;
   for (int i = 0; i < 8; ++i) c.d.xcd_slice_max = std::max(c.d.xcd_slice_max, g[i + 1] - g[i]);
-  if (c.wm) {  // the wave-major copy's slot total, and its cap
+  if (c.d.plan.wave_major) {  // the wave-major copy's slot total, and its cap
     int32_t slots = 0;
     std::memcpy(&slots, stg + 48, sizeof(slots));
-    c.wm_slots = slots;
-    c.wm = hostlayout::wave_major_fits(c.wm_slots, c.N, c.P);
-    if (!c.wm) c.d.woff = nullptr;  // (its buffer goes back with the problem's)
+    c.shape.wm_slots = slots;
+    plan_from_shape(c);
+    if (!c.d.plan.wave_major) c.d.woff = nullptr;  // (its buffer goes back with the problem's)
   }
   c.timer.mark("layouts (device)");
   return 0;
@@ -552,10 +550,8 @@ int alloc_pair_lists(Setup& c) {
   // the lanes per block only -- the pair buffer is sized by twice the
   // estimate, an upper bound of the true count either way.
   d.n_pairs = c.plan.host_counts && !c.cam_slice.empty() ? c.pairs_est : c.n_pairs;
-  const hostlayout::SchurShape sh =
-      hostlayout::schur_shape(d.n_pairs, d.n_blk, std::getenv("SFM_SCHUR_PTS_SUB"), std::getenv("SFM_SCHUR_WG"));
-  d.schur_pts_sub = sh.pts_sub;
-  d.schur_wg_blocks = sh.wg_blocks;
+  c.shape.n_pairs = d.n_pairs;
+  plan_from_shape(c);  // (the shape is complete: the plan is final)
   if (!d.scal_host && hipHostMalloc(&d.scal_host, sizeof(double) * (kNumScalars + 1 + 17)) != hipSuccess) {
     d.scal_host = nullptr;
     return fail(SFM_ENOMEM, "hipHostMalloc failed");
@@ -565,9 +561,9 @@ int alloc_pair_lists(Setup& c) {
   // (and the wave-major stream's, its slot total known by now: filled once
   // uv_pm is, layout_wave_major)
   const bool ok = c.alloc(d.blk, std::max<size_t>(1, size_t(d.n_blk))) &&
-                  (c.small || c.alloc(d.seg, size_t(d.n_blk) + 1)) &&
+                  (c.d.plan.small_setup || c.alloc(d.seg, size_t(d.n_blk) + 1)) &&
                   c.alloc(d.bpts, std::max<size_t>(1, size_t(c.n_pairs))) &&
-                  (!c.wm || (c.alloc(d.uv_wm, 2 * 64 * size_t(c.wm_slots)) && c.alloc(d.cam_wm, 64 * size_t(c.wm_slots))));
+                  (!c.d.plan.wave_major || (c.alloc(d.uv_wm, 2 * 64 * size_t(c.shape.wm_slots)) && c.alloc(d.cam_wm, 64 * size_t(c.shape.wm_slots))));
   return ok ? 0 : c.rc;
 }
 
@@ -616,8 +612,8 @@ int pair_lists_sorted(Setup& c) {
   d.bperm = nullptr;
   d.srec = nullptr;
   d.n_bslots = d.n_blk;
-  if (d.n_blk > kSchurXcdMinBlocks) {
-    const int per = 64 / d.schur_pts_sub * (kThreads / 64);
+  if (d.plan.xcd_block_order) {
+    const int per = 64 / d.plan.schur_pts_sub * (kThreads / 64);
     int32_t *sorted = nullptr, *row_x = nullptr;
     int64_t* grp = nullptr;
     if (!(c.tmp(sorted, size_t(d.n_blk)) && c.tmp(row_x, size_t(c.C)) && c.tmp(grp, 16) &&
@@ -641,50 +637,39 @@ int alloc_solver_arrays(Setup& c) {
   d.n = 6 * c.C;
   d.ld = ((d.n + 1 + kNB - 1) / kNB) * kNB;
   d.nblk = d.ld / kNB;
-  d.max_blocks = std::max({1, c.C, blocks_for(c.N, 256), blocks_for(c.P, 256), d.jac_blocks, d.jac_blocks_rec,
-                           blocks_for(d.N_pad, 256), obs_xcd_blocks(d), pt_xcd_blocks(d)});
+  const ProblemPlan& pp = d.plan;
+  d.max_blocks = max_blocks(c.shape, pp, d.xcd_slice_max);
   if (c.plan.route == ParamRoute::Late || c.plan.route == ParamRoute::None)
     if (int rc = alloc_params(c)) return rc;
-  // the one-pass back substitution, on the large path (the XCD-ordered Schur
-  // blocks) while every camera's record fits the LDS
-  d.pm_backsub = d.n_blk > kSchurXcdMinBlocks && c.C <= kCamPMMax;
-  // pass A stores u at the camera-major position it runs at (coalesced) and
-  // pass B gathers it through pos[]: 85 + 31 -> 60 + 41 us per C3 iteration
-  // against the point-major scatter (SFM_EU_CM=0), S and steps bitwise equal
-  const char* ec = std::getenv("SFM_EU_CM");
-  d.eu_cm = !(ec && ec[0] == '0');
+  // eu (plan.eu_cm): pass A stores u at the camera-major position it runs at
+  // (coalesced) and pass B gathers it through pos[]: 85 + 31 -> 60 + 41 us per
+  // C3 iteration against the point-major scatter (SFM_EU_CM=0), S and steps
+  // bitwise equal
   d.ptG = nullptr;
   d.camS = nullptr;
-  h->force_pack = env_flag("SFM_FORCE_PACK");
+  const size_t tiles = size_t(d.nblk) * d.nblk;
+  bool ok = c.alloc(d.cam_new, 6 * C) && c.alloc(d.X_new, 3 * P) && c.alloc(d.scale_c, 6 * C) &&
+            c.alloc(d.scale_p, 3 * P) && c.alloc(d.diag_c, 6 * C) && c.alloc(d.diag_p, 3 * P) &&
+            c.alloc(d.camR, size_t(kCamR) * C) && c.alloc(d.camRn, 12 * C) &&
+            c.alloc(d.eu, size_t(kEU) * (pp.eu_cm ? npad : N)) && c.alloc(d.ypt, 3 * P) &&
+            c.alloc(d.ptV, size_t(kPtV) * P) && c.alloc(d.ptL, size_t(kPtL) * P) &&
+            c.alloc(d.ptS, size_t(kPtS) * std::max<size_t>(1, P)) &&
+            (!pp.large_system || c.alloc(d.ptG, size_t(kPtG) * std::max<size_t>(1, P))) &&
+            (!pp.large_system || c.alloc(d.camS, size_t(kCamSR) * std::max<size_t>(1, C))) &&
+            c.alloc(d.Ucam, size_t(kUcam) * C) && c.alloc(d.jpart, 27 * std::max<size_t>(1, npad / 64)) &&
+            c.alloc(d.dpart, 27 * std::max<size_t>(1, npad / 64)) && c.alloc(d.S, size_t(d.ld) * d.ld) &&
+            (!(sharded(h) || pp.force_pack) || c.alloc(d.Spack, packed_size(d.n))) &&
+            c.alloc(d.invL, size_t(d.nblk) * kNB * kNB) && c.alloc(d.flags, size_t(d.nblk)) &&
+            c.alloc(d.cflags, 2 * tiles) &&
+            c.alloc(d.cticket, 5);  // task ticket, walker-role ticket, back-substitution role ticket, a panel's two
+  if (!ok) return c.rc;
   // Schur / Cholesky overlap (SFM_OVERLAP=1; unsharded, more than two tiles):
   // per 64x64 tile of S the number of camera blocks (c1 <= c2, stored at
   // rows 6 c2.., columns 6 c1..) whose 6x6 footprint touches it.  (The
   // round-4 mode 2, a full helper grid placed as the Schur pass retires,
   // relied on the dispatcher starting the Schur pass's workgroups first:
   // not guaranteed, and seen to time out the factor, so removed.)
-  const char* ov = std::getenv("SFM_OVERLAP");
-  d.overlap = (ov ? std::atoi(ov) : 0) > 0 && d.nblk > 2 && !sharded(h) ? 1 : 0;
-  const size_t tiles = size_t(d.nblk) * d.nblk;
-  bool ok = c.alloc(d.cam_new, 6 * C) && c.alloc(d.X_new, 3 * P) && c.alloc(d.scale_c, 6 * C) &&
-            c.alloc(d.scale_p, 3 * P) && c.alloc(d.diag_c, 6 * C) && c.alloc(d.diag_p, 3 * P) &&
-            c.alloc(d.camR, size_t(kCamR) * C) && c.alloc(d.camRn, 12 * C) &&
-            c.alloc(d.eu, size_t(kEU) * (d.eu_cm ? npad : N)) && c.alloc(d.ypt, 3 * P) &&
-            c.alloc(d.ptV, size_t(kPtV) * P) && c.alloc(d.ptL, size_t(kPtL) * P) &&
-            c.alloc(d.ptS, size_t(kPtS) * std::max<size_t>(1, P)) &&
-            (d.n_blk <= kSchurXcdMinBlocks || c.alloc(d.ptG, size_t(kPtG) * std::max<size_t>(1, P))) &&
-            (d.n_blk <= kSchurXcdMinBlocks || c.alloc(d.camS, size_t(kCamSR) * std::max<size_t>(1, C))) &&
-            c.alloc(d.Ucam, size_t(kUcam) * C) && c.alloc(d.jpart, 27 * std::max<size_t>(1, npad / 64)) &&
-            c.alloc(d.dpart, 27 * std::max<size_t>(1, npad / 64)) && c.alloc(d.S, size_t(d.ld) * d.ld) &&
-            (!(sharded(h) || h->force_pack) || c.alloc(d.Spack, packed_size(d.n))) &&
-            c.alloc(d.invL, size_t(d.nblk) * kNB * kNB) && c.alloc(d.flags, size_t(d.nblk)) &&
-            c.alloc(d.cflags, 2 * tiles) &&
-            c.alloc(d.cticket, 5);  // task ticket, walker-role ticket, back-substitution role ticket, a panel's two
-  if (!ok) return c.rc;
-  // SFM_SCHUR_WGS (a test knob: few workgroups give each wave of k_schur_pairs_rot_pw
-  // many groups on a small problem), rounded up to the 8 lists; read per problem
-  const char* sw = std::getenv("SFM_SCHUR_WGS");
-  d.schur_wgs = sw ? std::min(1 << 16, std::max(0, std::atoi(sw)) + 7) / 8 * 8 : 0;
-  if (d.overlap) {
+  if (pp.overlap) {
     if (!(c.alloc(d.tile_cnt, tiles) && c.alloc(d.tile_exp, tiles))) return c.rc;
     std::vector<int32_t> te(tiles, 0);
     for (int c1 = 0; c1 < c.C; ++c1)
@@ -703,7 +688,7 @@ int alloc_solver_arrays(Setup& c) {
 // the stream that made uv_pm).
 void layout_wave_major(Setup& c, hipStream_t st) {
   DevProblem& d = c.d;
-  if (c.wm) launch_wm_fill(c.P, d.pt_off, d.woff, d.cam_pm, d.uv_pm, d.cam_wm, d.uv_wm, st);
+  if (c.d.plan.wave_major) launch_wm_fill(c.P, d.pt_off, d.woff, d.cam_pm, d.uv_pm, d.cam_wm, d.uv_wm, st);
 }
 
 // Deferred uv, by now up or nearly (and before it the parameters): its two
@@ -787,7 +772,7 @@ int finish(Setup& c) {
   static const bool sync_setup = env_flag("SFM_SYNC_SETUP");
   const bool deferred_uv = c.plan.deferred_uv;
   if (deferred_uv) HIPCHK(hipStreamWaitEvent(s, h->uev_uv, 0));
-  if (c.small && c.plan.route == ParamRoute::Early && !c.bperm_per && !sync_setup) return 0;
+  if (c.d.plan.small_setup && c.plan.route == ParamRoute::Early && !c.bperm_per && !sync_setup) return 0;
   HIPCHK(hipStreamSynchronize(s));
   if (deferred_uv && *c.uv_err_host != INT32_MAX)
     return fail(SFM_EINVAL, "non-finite observation at " + std::to_string(*c.uv_err_host));
@@ -814,7 +799,7 @@ int run_setup(Setup& c, const double* K9, const double* rot, const double* t) {
   if ((rc = alloc_layouts(c))) return rc;
   if ((rc = upload_runs_blob(c))) return rc;
   if (plan.route == ParamRoute::Early && (rc = upload_params_early(c))) return rc;
-  if (c.small) {
+  if (c.d.plan.small_setup) {
     if ((rc = layout_small(c))) return rc;
   } else {
     if ((rc = layout_sorted(c))) return rc;
@@ -826,13 +811,13 @@ int run_setup(Setup& c, const double* K9, const double* rot, const double* t) {
     if ((rc = read_pair_total(c))) return rc;
   }
   if ((rc = alloc_pair_lists(c))) return rc;
-  if (c.small) pair_lists_small(c);
+  if (c.d.plan.small_setup) pair_lists_small(c);
   else if ((rc = pair_lists_sorted(c))) return rc;
   if ((rc = alloc_solver_arrays(c))) return rc;
   release_pool(c.h);  // earlier problems' buffers this one did not reuse
   if (plan.deferred_uv && (rc = layout_deferred_uv(c))) return rc;
   if (!plan.deferred_uv) layout_wave_major(c, c.s);
-  if (side && c.small && (rc = enqueue_side_params(c))) return rc;  // Side, small path: no layout round trip to hide behind
+  if (side && c.d.plan.small_setup && (rc = enqueue_side_params(c))) return rc;  // Side, small path: no layout round trip to hide behind
   if ((rc = finish_params(c))) return rc;
   return finish(c);
 }
@@ -854,6 +839,7 @@ int sfm_ba_set_problem(sfm_ba_handle* h, int64_t n_obs, const double* obs_uv, co
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
   free_problem(h);
+  read_knobs(&h->knobs, kKnobsProblem);
   c.timer.mark("sync + free");
   h->d.C = n_cams;
   h->d.P = n_pts;

@@ -162,8 +162,6 @@ struct AcceptFold {
   const double* X_src;
   double* X_dst;
 };
-constexpr int kAcceptFoldMaxCams = 256;
-constexpr int64_t kAcceptFoldMaxX = 3 * 8192;
 template <int kTail>
 __global__ __launch_bounds__(1024) void k_reduce_batch_lm(const double* __restrict__ partials, int64_t max_blocks,
                                                           ReduceBatch b, double* __restrict__ scal,
@@ -514,13 +512,13 @@ int fetch_scalars(sfm_ba_handle* h) {
   return 0;
 }
 
-// A phase's closing reduction; in the fused device loop (h->fuse_lm) with
+// A phase's closing reduction; in the fused device loop (LmDriver::DeviceFused*) with
 // the bookkeeping that follows it: k_lm_decide after compute_step
 // (kTailDecide), k_lm_post after an evaluation (kTailPost), k_lm_init after
 // the initial one (kTailInit).
 void reduce_phase(sfm_ba_handle* h, const ReduceBatch& rb, bool copy_fail, int tail) {
   DevProblem& d = h->d;
-  if (h->fuse_lm && rb.n > 0) {
+  if (h->plan.fused_lm() && rb.n > 0) {
 #define SFM_RB_LM(T_)                                                                                      \
   k_reduce_batch_lm<T_><<<rb.n, 1024, 0, h->stream>>>(d.partials, d.max_blocks, rb, d.scal,                 \
                                                       copy_fail ? d.fail : nullptr, d.gate, h->lm_ctl,      \
@@ -529,9 +527,9 @@ void reduce_phase(sfm_ba_handle* h, const ReduceBatch& rb, bool copy_fail, int t
     if (tail == kTailPost) SFM_RB_LM(kTailPost);
     else if (tail == kTailInit) SFM_RB_LM(kTailInit);
     else {
-      if (h->accept_fold)
+      if (h->plan.accept_fold())
         af = AcceptFold{d.C, 3 * int64_t(d.P), d.cam, d.camR,
-                        h->mode != SFM_BA_STRUCT_ONLY ? d.partials + size_t(kPXNormCam) * d.max_blocks : nullptr,
+                        h->plan.cams_var ? d.partials + size_t(kPXNormCam) * d.max_blocks : nullptr,
                         d.cam_new, d.X_new, d.X};
       SFM_RB_LM(kTailDecide);
     }
@@ -541,114 +539,89 @@ void reduce_phase(sfm_ba_handle* h, const ReduceBatch& rb, bool copy_fail, int t
   launch_reduce_batch(d, rb, copy_fail, h->stream);
 }
 
-// Whether an evaluation also prepares the coming step (unsharded
-// STRUCT_AND_POSE beyond the small systems whose camera sums ride in the
-// point pass): the point factor inside the point pass, then k_obs_prep_rc,
-// then the camera sums and the diagonal blocks in one launch.  A sharded
-// solve has a collective between the sums and their use and keeps the
-// stand-alone sequence, as do POSE_ONLY and STRUCT_ONLY.
-bool step_prep_folds(const sfm_ba_handle* h) {
-  const DevProblem& d = h->d;
-  return h->mode == SFM_BA_STRUCT_AND_POSE && !sharded(h) && d.P > 0 && d.C > 64 && d.N_pad > 0 &&
-         !d.schur_wg_blocks;
+// The evaluation's camera sums and their finalisation on their own (mode 0:
+// the unscaled first pass, for the Jacobi scale; mode 1: diagonal and gradient).
+int cam_sums_enqueue(sfm_ba_handle* h, int mode) {
+  DevProblem& d = h->d;
+  hipStream_t s = h->stream;
+  mark_begin(h, kPhCamRed);
+  if (h->plan.sharded) {
+    launch_cam_reduce(d, s);
+    if (int rc = allreduce(h, d.Ucam, size_t(kUcam) * d.C, ncclSum)) return rc;
+    launch_cam_finalize(d, mode, false, mode == 1, s);
+  } else {  // no all-reduce between the two: one launch
+    launch_cam_sum_finalize(d, mode, mode == 1, s);
+  }
+  mark_end(h);
+  return 0;
 }
 
 // Evaluate cost, Jacobian, Jacobi scale (first call), per-block normal
-// equations, LM diagonal and gradient at the current parameters.
+// equations, LM diagonal and gradient at the current parameters, by the
+// solve's plan (ba_plan.h).
 int evaluate_enqueue(sfm_ba_handle* h, bool first, bool jacobi_scaling) {
   SFM_TRACE("sfm:evaluate");
   DevProblem& d = h->d;
+  const SolvePlan& p = h->plan;
   hipStream_t s = h->stream;
   int rc;
   // constant blocks (STRUCT_ONLY: cameras, POSE_ONLY: points) carry a zero
   // Jacobi scale, so their scaled Jacobian columns vanish; their norms and
   // gradients are left out like Ceres leaves out constant blocks
-  const bool cams_var = h->mode != SFM_BA_STRUCT_ONLY, pts_var = h->mode != SFM_BA_POSE_ONLY;
-  const int nbP = std::max(1, blocks_for(d.P, 256)),
-            nbC = std::max(1, blocks_for(d.C, 256));
-  if (h->accept_grid > 0) launch_cam_prep_accept(d, cams_var, h->accept_grid, s);
-  else if (h->accept_grid == 0) launch_cam_prep(d, d.cam, cams_var, s);
+  if (h->accept_grid > 0) launch_cam_prep_accept(d, p.cams_var, h->accept_grid, s);
+  else if (h->accept_grid == 0) launch_cam_prep(d, d.cam, p.cams_var, s);
   // accept_grid < 0: done by the deciding workgroup (AcceptFold)
-  // the coming step's preparation rides along (its radius is final here);
-  // eval_fused: the scaled Jacobian pass is then k_jac_obs_prep's first half,
-  // after the point pass below (which reads nothing the Jacobian pass writes)
-  const bool fold_prep = step_prep_folds(h);
-  const bool fused = fold_prep && h->eval_fused && pts_var;
-  const bool unscaled_first = first && jacobi_scaling;
-  if (unscaled_first || !fused) {
+  // prep_folded: the coming step's preparation rides along (its radius is
+  // final here); JacObsPrep: the scaled Jacobian pass is then k_jac_obs_prep's
+  // first half, after the point pass below (which reads nothing the Jacobian
+  // pass writes)
+  const bool jac_first = p.cam_pass == CamPass::Jacobian;
+  const bool cams_alone = p.cam_sums == CamSums::SumFinalize || p.cam_sums == CamSums::ReduceAllreduceFinalize;
+  if (first && jacobi_scaling) {  // the unscaled pass: the Jacobi scale
     mark_begin(h, kPhJac);
-    launch_jacobian(d, !unscaled_first, s);
+    launch_jacobian(d, false, s);
     mark_end(h);
-  }
-  // unsharded: the U_c sums and their finalisation in one launch
-  const bool fuse_cam = !sharded(h);
-  // small systems (C <= 64): the camera sums ride in the point pass's launch
-  const bool fold_cams = fuse_cam && cams_var && pts_var && d.P > 0 && d.C > 0 && d.C <= 64;
-  if (first && jacobi_scaling) {
-    if (fold_cams) {
+    if (p.cam_sums == CamSums::InPointPass) {
       mark_begin(h, kPhPtEval);
       launch_point_eval_with_cams(d, 0, false, s);
       mark_end(h);
     } else {
-      if (cams_var) {
-        mark_begin(h, kPhCamRed);
-        if (fuse_cam) {
-          launch_cam_sum_finalize(d, 0, false, s);
-        } else {
-          launch_cam_reduce(d, s);
-          if ((rc = allreduce(h, d.Ucam, size_t(kUcam) * d.C, ncclSum))) return rc;
-          launch_cam_finalize(d, 0, false, false, s);
-        }
-        mark_end(h);
-      }
-      if (pts_var) launch_point_eval(d, 0, false, s);
-    }
-    if (!fused) {
-      mark_begin(h, kPhJac);
-      launch_jacobian(d, true, s);
-      mark_end(h);
+      if ((cams_alone || p.cam_sums == CamSums::SumDiag) && (rc = cam_sums_enqueue(h, 0))) return rc;
+      if (p.pts_var) launch_point_eval(d, p.point_pass, 0, false, s);
     }
   }
-  if (fold_cams) {
+  if (jac_first) {
+    mark_begin(h, kPhJac);
+    launch_jacobian(d, true, s);
+    mark_end(h);
+  }
+  if (cams_alone && (rc = cam_sums_enqueue(h, 1))) return rc;
+  if (p.cam_sums == CamSums::None) {
+    hipMemsetAsync(d.partials + size_t(kPGradCam) * d.max_blocks, 0, sizeof(double) * p.nb_cam, s);
+    hipMemsetAsync(d.partials + size_t(kPXNormCam) * d.max_blocks, 0, sizeof(double) * p.nb_cam, s);
+  }
+  if (p.cam_sums == CamSums::InPointPass) {
     mark_begin(h, kPhPtEval);
     launch_point_eval_with_cams(d, 1, true, s);
     mark_end(h);
-  } else if (fold_prep) {
-    // (the camera sums follow the point pass and k_obs_prep_rc, below)
-  } else if (cams_var) {
-    mark_begin(h, kPhCamRed);
-    if (fuse_cam) {
-      launch_cam_sum_finalize(d, 1, true, s);
-    } else {
-      launch_cam_reduce(d, s);
-      if ((rc = allreduce(h, d.Ucam, size_t(kUcam) * d.C, ncclSum))) return rc;
-      launch_cam_finalize(d, 1, false, true, s);
-    }
-    mark_end(h);
-  } else {
-    hipMemsetAsync(d.partials + size_t(kPGradCam) * d.max_blocks, 0, sizeof(double) * nbC, s);
-    hipMemsetAsync(d.partials + size_t(kPXNormCam) * d.max_blocks, 0, sizeof(double) * nbC, s);
-  }
-  if (fold_cams) {
-    // (done above, with the camera sums)
-  } else if (pts_var) {
+  } else if (p.pts_var) {
     mark_begin(h, kPhPtEval);
-    launch_point_eval(d, 1, false, s, fold_prep, h->eval_radius);
+    launch_point_eval(d, p.point_pass, 1, false, s, p.prep_folded, h->eval_radius);
     mark_end(h);
-    if (fold_prep) {
+    if (p.prep_folded) {  // (CamSums::SumDiag: the camera sums follow the observation prep)
       mark_begin(h, kPhPtPrep);
-      if (fused) launch_jac_obs_prep(d, s);
-      else launch_obs_prep(d, s);
+      if (jac_first) launch_obs_prep(d, s);
+      else launch_jac_obs_prep(d, s);
       mark_end(h);
       mark_begin(h, kPhCamRed);
-      launch_cam_sum_diag(d, h->eval_radius, h->rank == 0, s, fused);
+      launch_cam_sum_diag(d, h->eval_radius, h->rank == 0, s, p.stage_cams);
       mark_end(h);
-      h->cams_staged = fused && cam_records_used(d);
+      h->cams_staged = p.stage_cams;
     }
-    h->prep_fresh = fold_prep;
+    h->prep_fresh = p.prep_folded;
   } else {
-    hipMemsetAsync(d.partials + size_t(kPGradPt) * d.max_blocks, 0, sizeof(double) * nbP, s);
-    hipMemsetAsync(d.partials + size_t(kPXNormPt) * d.max_blocks, 0, sizeof(double) * nbP, s);
+    hipMemsetAsync(d.partials + size_t(kPGradPt) * d.max_blocks, 0, sizeof(double) * p.nb_pt, s);
+    hipMemsetAsync(d.partials + size_t(kPXNormPt) * d.max_blocks, 0, sizeof(double) * p.nb_pt, s);
   }
   if (d.N == 0) hipMemsetAsync(d.partials + size_t(kPCost) * d.max_blocks, 0, sizeof(double), s);
   if (d.P == 0) {
@@ -656,13 +629,13 @@ int evaluate_enqueue(sfm_ba_handle* h, bool first, bool jacobi_scaling) {
     hipMemsetAsync(d.partials + size_t(kPXNormPt) * d.max_blocks, 0, sizeof(double), s);
   }
   ReduceBatch rb;
-  rb.add(kPCost, d.jac_blocks, 0, kCost);
-  rb.add(kPGradCam, cams_var && fuse_cam ? std::max(1, d.C) : nbC, 1, kGradMaxCam);
-  rb.add(kPGradPt, nbP, 1, kGradMaxPt);
-  rb.add(kPXNormCam, nbC, 0, kXNorm2Cam);
-  rb.add(kPXNormPt, nbP, 0, kXNorm2Pt);
+  rb.add(kPCost, p.nb_cost, 0, kCost);
+  rb.add(kPGradCam, p.nb_grad_cam, 1, kGradMaxCam);
+  rb.add(kPGradPt, p.nb_pt, 1, kGradMaxPt);
+  rb.add(kPXNormCam, p.nb_cam, 0, kXNorm2Cam);
+  rb.add(kPXNormPt, p.nb_pt, 0, kXNorm2Pt);
   reduce_phase(h, rb, false, first ? kTailInit : kTailPost);
-  if (sharded(h)) {
+  if (p.sharded) {
     if ((rc = allreduce(h, d.scal + kCost, 1, ncclSum))) return rc;
     if ((rc = allreduce(h, d.scal + kGradMaxCam, 2, ncclMax))) return rc;
     if ((rc = allreduce(h, d.scal + kXNorm2Pt, 1, ncclSum))) return rc;
@@ -679,17 +652,16 @@ int evaluate(sfm_ba_handle* h, bool first, bool jacobi_scaling) {
 int compute_step_enqueue(sfm_ba_handle* h, double radius) {
   SFM_TRACE("sfm:compute_step");
   DevProblem& d = h->d;
+  const SolvePlan& p = h->plan;
   hipStream_t s = h->stream;
   int rc;
-  const int nbP = std::max(1, blocks_for(d.P, 256)), nbC = std::max(1, blocks_for(d.C, 256));
   bool cam_done = false;  // the camera step taken by the small-system factor
-  // The evaluation prepared this step (step_prep_folds) unless an
+  // The evaluation prepared this step (prep_folded) unless an
   // unsuccessful or invalid step changed the radius since: then the
   // stand-alone kernels redo it.  Both loops know on the host (prep_fresh):
   // the device loop pauses at such a step, so no launch is spent on the
   // stand-alone kernels while every step is accepted.
-  const bool fold_prep = step_prep_folds(h);
-  const bool redo_prep = !fold_prep || !h->prep_fresh;
+  const bool redo_prep = !p.prep_folded || !h->prep_fresh;
   // the stand-alone prep: point factor and k_obs_prep_rc, then the diagonal blocks
   auto point_prep = [&] {
     if (!redo_prep) return;
@@ -700,7 +672,7 @@ int compute_step_enqueue(sfm_ba_handle* h, double radius) {
   auto schur_diag = [&] {
     if (redo_prep) launch_schur_diag(d, radius, h->rank == 0, s);
   };
-  if (h->mode == SFM_BA_STRUCT_AND_POSE && d.overlap && d.C && !sharded(h) && !h->force_pack) {
+  if (p.overlapped) {
     // Schur / Cholesky overlap: the diagonal blocks and rhs first, then the
     // factorisation on its own stream with half the CUs while k_schur_pts
     // fills the off-diagonal blocks on the other half, in camera-major order
@@ -718,34 +690,34 @@ int compute_step_enqueue(sfm_ba_handle* h, double radius) {
     HIPCHK(hipEventRecord(h->ov_ev[0], s));
     HIPCHK(hipStreamWaitEvent(h->stream2, h->ov_ev[0], 0));
     mark_begin(h, kPhChol, h->stream2);
-    launch_cholesky(d, ++h->chol_epoch, h->stream2, false, -1, d.overlap);
+    launch_cholesky(d, ++h->chol_epoch, h->stream2, false, -1, d.plan.overlap);
     mark_end(h, h->stream2);
-    launch_schur_offdiag(d, d.tile_cnt, s);
+    launch_schur_offdiag(d, p.pair_pass, true, s);
     HIPCHK(hipEventRecord(h->ov_ev[1], h->stream2));
     HIPCHK(hipStreamWaitEvent(s, h->ov_ev[1], 0));
     mark_end(h, nullptr, m_schur);  // (after the join: the Schur phase spans the overlapped factor)
     mark_begin(h, kPhBack);
     launch_backsolve(d, ++h->bs_epoch, s, true);
     mark_end(h);
-  } else if (h->mode == SFM_BA_STRUCT_AND_POSE) {
+  } else if (p.mode == SFM_BA_STRUCT_AND_POSE) {
     point_prep();
     mark_begin(h, kPhSchur);
-    if (fold_prep) {  // (never a block-per-workgroup system: launch_schur's two parts)
+    if (p.prep_folded) {  // (never a block-per-workgroup system: launch_schur's two parts)
       schur_diag();
-      launch_schur_offdiag(d, nullptr, s, h->cams_staged);
+      launch_schur_offdiag(d, p.pair_pass, false, s, h->cams_staged);
     } else {
-      launch_schur(d, radius, h->rank == 0, s);
+      launch_schur(d, p.pair_pass, radius, h->rank == 0, s);
     }
     mark_end(h);
     // (k_schur_diag_sum also wrote the identity padding, y's sentinel and
     // the cleared failure flag; without cameras the separate launch does)
     if (!d.C) launch_pad_init(d, s);
-    if (sharded(h) && h->dist_pt > 0) {
+    if (p.dist_factor) {
       mark_begin(h, kPhChol);
       if ((rc = dist_factor_enqueue(h))) return rc;
       mark_end(h);
     } else {
-      if (sharded(h) || h->force_pack) {
+      if (p.pack_allreduce) {
         // all-reduce only the packed upper triangle + rhs (half the ld^2 image)
         launch_pack_upper(d, false, s);
         if ((rc = allreduce(h, d.Spack, packed_size(d.n), ncclSum))) return rc;
@@ -758,13 +730,13 @@ int compute_step_enqueue(sfm_ba_handle* h, double radius) {
     mark_begin(h, kPhBack);
     launch_backsolve(d, ++h->bs_epoch, s, true);
     mark_end(h);
-  } else if (h->mode == SFM_BA_POSE_ONLY) {
+  } else if (p.mode == SFM_BA_POSE_ONLY) {
     // block-diagonal camera system from the all-reduced U_c (same on every rank)
     launch_cam_solve(d, radius, s);
     // the back substitution reads X from the point records (their factor
     // is unused here: y_p = 0); its bad flags are cleared below
     if (d.P) launch_point_factor(d, radius, s);
-    hipMemsetAsync(d.partials + size_t(kPBad) * d.max_blocks, 0, sizeof(double) * nbP, s);
+    hipMemsetAsync(d.partials + size_t(kPBad) * d.max_blocks, 0, sizeof(double) * p.nb_pt, s);
   } else {
     // STRUCT_ONLY: per-point 3x3 systems only; y_c = 0
     hipMemsetAsync(d.fail, 0, sizeof(int), s);
@@ -775,38 +747,35 @@ int compute_step_enqueue(sfm_ba_handle* h, double radius) {
     }
     hipMemsetAsync(d.ysol, 0, sizeof(double) * 6 * size_t(d.C), s);
   }
-  // large reduced systems: the back substitution as one point-major pass
-  // (k_backsub_pm), which builds its camera records from y itself and takes
-  // the camera step in its first workgroup: no k_cam_update launch there
+  // OnePass (large reduced systems): the back substitution as one point-major
+  // pass (k_backsub_pm), which builds its camera records from y itself and
+  // takes the camera step in its first workgroup: no k_cam_update launch there
   // (cam_done: a one-workgroup factor, never such a system)
-  const bool cams_var = h->mode != SFM_BA_STRUCT_ONLY, pts_var = h->mode != SFM_BA_POSE_ONLY;
-  const bool pm = backsub_pm(d, cams_var, pts_var);
-  if (!cam_done && !pm) launch_cam_update(d, h->rank == 0 && cams_var, s);
+  if (!cam_done && p.backsub != Backsub::OnePass) launch_cam_update(d, h->rank == 0 && p.cams_var, s);
   mark_begin(h, kPhBacksub);
-  launch_point_backsub(d, s, cams_var, pts_var, h->rank == 0 && cams_var);
+  launch_point_backsub(d, p.backsub, s, p.cams_var, p.pts_var, h->rank == 0 && p.cams_var);
   mark_end(h);
   if (d.P == 0) {
     const int slots[] = {kPModel, kPModelPt, kPNewCost, kPStepPt, kPBadBack, kPBad};
     for (int sl : slots) hipMemsetAsync(d.partials + size_t(sl) * d.max_blocks, 0, sizeof(double), s);
   }
-  if (h->rank != 0 || h->mode == SFM_BA_STRUCT_ONLY)
-    hipMemsetAsync(d.partials + size_t(kPStepCam) * d.max_blocks, 0, sizeof(double) * nbC, s);
-  // (k_backsub_pm: every partial per 256-point block)
-  const int nbI = pm ? nbP : d.N_pad ? obs_xcd_blocks(d) : 1;  // k_backsub_a_rc / k_backsub_c grid
-  const int nbB = pm ? nbP : d.P ? pt_xcd_blocks(d) : 1;       // k_backsub_b grid
+  if (h->rank != 0 || !p.cams_var)
+    hipMemsetAsync(d.partials + size_t(kPStepCam) * d.max_blocks, 0, sizeof(double) * p.nb_cam, s);
+  // (nb_obs: the grid of k_backsub_a_rc / k_backsub_c, nb_back: of k_backsub_b;
+  // k_backsub_pm: every partial per 256-point block)
   ReduceBatch rb;
-  rb.add(kPModel, nbI, 0, kModelChange);
-  rb.add(kPNewCost, nbI, 0, kNewCost);
-  rb.add(kPStepPt, nbB, 0, kStep2Pt);
-  rb.add(kPStepCam, nbC, 0, kStep2Cam);
+  rb.add(kPModel, p.nb_obs, 0, kModelChange);
+  rb.add(kPNewCost, p.nb_obs, 0, kNewCost);
+  rb.add(kPStepPt, p.nb_back, 0, kStep2Pt);
+  rb.add(kPStepCam, p.nb_cam, 0, kStep2Cam);
   // bad-step flags: max over point_prep, cam_update and backsub partials
-  rb.add(kPBad, nbP, 1, kBadStep);
-  rb.add(kPBadCam, nbC, 1, kBadCam);
-  rb.add(kPBadBack, nbB, 1, kBadBack);
-  rb.add(kPModelPt, nbB, 0, kModelChangePt);
+  rb.add(kPBad, p.nb_pt, 1, kBadStep);
+  rb.add(kPBadCam, p.nb_cam, 1, kBadCam);
+  rb.add(kPBadBack, p.nb_back, 1, kBadBack);
+  rb.add(kPModelPt, p.nb_back, 0, kModelChangePt);
   // ... and the Cholesky failure flag (an int) into the slot after the scalars
   reduce_phase(h, rb, true, kTailDecide);
-  if (sharded(h)) {
+  if (p.sharded) {
     if ((rc = allreduce(h, d.scal + kModelChange, 4, ncclSum))) return rc;  // model, new cost, step pt, step cam
     if ((rc = allreduce(h, d.scal + kBadStep, 4, ncclMax))) return rc;
     if ((rc = allreduce(h, d.scal + kModelChangePt, 1, ncclSum))) return rc;
@@ -858,7 +827,7 @@ LmCtl lm_start(const sfm_ba_handle* h, const sfm_ba_options& opts) {
   c.max_radius = opts.max_trust_region_radius;
   c.min_radius = opts.min_trust_region_radius;
   c.min_rel_dec = opts.min_relative_decrease;
-  c.prep_fold = step_prep_folds(h) ? 1 : 0;
+  c.prep_fold = h->plan.prep_folded ? 1 : 0;
   return c;
 }
 
@@ -994,37 +963,35 @@ int run_device_lm(sfm_ba_handle* h, const sfm_ba_options& opts, sfm_ba_summary* 
   // at a time: each gated iteration past the end still costs its launches
   // (measured per C1 solve: batch 3 0.49 ms, 4 0.52, 6 0.62; host loop 0.54)
   int batch = 3, batch_next = 2;
-  if (const char* b = std::getenv("SFM_LM_BATCH")) batch = batch_next = std::max(1, std::min(64, std::atoi(b)));
+  if (h->plan.lm_batch) batch = batch_next = h->plan.lm_batch;
   if (opts.max_num_iterations <= 0) batch = 0;  // k_lm_init ends the solve (NO_CONVERGENCE unless converged)
   const bool jac_scaling = opts.jacobi_scaling != 0;
   const int acc_blocks = std::max(1, std::min(1024, blocks_for(6 * int64_t(d.C) + 3 * int64_t(d.P), 256)));
   d.radius_dev = &h->lm_ctl->radius;
-  // without a collective between a phase's reduction and the bookkeeping,
-  // the two are one launch (k_reduce_batch_lm)
-  h->fuse_lm = !sharded(h) && !env_flag("SFM_LM_UNFUSED");
-  h->accept_fold = h->fuse_lm && d.C > 0 && d.C <= kAcceptFoldMaxCams && 3 * int64_t(d.P) <= kAcceptFoldMaxX &&
-                   !env_flag("SFM_NO_ACCEPT_FOLD");
+  // (LmDriver::DeviceFused*: a phase's reduction and the bookkeeping are one
+  // launch, k_reduce_batch_lm)
+  const bool unfused = !h->plan.fused_lm();
   // the initial evaluation (Jacobi scaling on first use); its scalars
   // initialise the loop state on the device
   d.gate = nullptr;
   h->eval_radius = c.radius;  // (the kernels read LmCtl::radius)
   int rc = evaluate_enqueue(h, true, jac_scaling);
-  if (rc == 0 && !h->fuse_lm) k_lm_init<<<1, 1, 0, s>>>(h->lm_ctl, d.scal);
+  if (rc == 0 && unfused) k_lm_init<<<1, 1, 0, s>>>(h->lm_ctl, d.scal);
   while (rc == 0) {
     for (int b = 0; b < batch && rc == 0; ++b) {
       d.gate = &h->lm_ctl->run_step;
       if ((rc = compute_step_enqueue(h, c.radius))) break;
       d.gate = nullptr;
-      if (!h->fuse_lm) k_lm_decide<<<1, 1, 0, s>>>(h->lm_ctl, d.scal, h->lm_trace, h->lm_trace_cap);
+      if (unfused) k_lm_decide<<<1, 1, 0, s>>>(h->lm_ctl, d.scal, h->lm_trace, h->lm_trace_cap);
       d.gate = &h->lm_ctl->run_eval;
       // k_lm_accept's copy inside the evaluation's k_cam_prep, or already
       // done in the deciding workgroup
-      h->accept_grid = h->accept_fold ? -1 : acc_blocks;
+      h->accept_grid = h->plan.accept_fold() ? -1 : acc_blocks;
       rc = evaluate_enqueue(h, false, jac_scaling);
       h->accept_grid = 0;
       if (rc) break;
       d.gate = nullptr;
-      if (!h->fuse_lm) k_lm_post<<<1, 1, 0, s>>>(h->lm_ctl, d.scal, h->lm_trace, h->lm_trace_cap);
+      if (unfused) k_lm_post<<<1, 1, 0, s>>>(h->lm_ctl, d.scal, h->lm_trace, h->lm_trace_cap);
     }
     if (rc) break;
     timer.mark("batch enqueued");
@@ -1053,8 +1020,6 @@ int run_device_lm(sfm_ba_handle* h, const sfm_ba_options& opts, sfm_ba_summary* 
   }
   d.gate = nullptr;
   d.radius_dev = nullptr;
-  h->fuse_lm = false;
-  h->accept_fold = false;
   if (rc) return rc;
   // (the trace is in pinned host memory, complete at the last batch's synchronisation)
   rc = lm_report(opts, c, h->lm_trace, h->lm_trace_cap, sm, push, nonfinite);
@@ -1298,7 +1263,6 @@ int sfm_ba_solve_resident(sfm_ba_handle* h, const sfm_ba_options* opts_in, int32
   }
   HIPCHK(hipSetDevice(h->device));
   DevProblem& d = h->d;
-  h->mode = mode;
   d.min_diag = opts.min_lm_diagonal;
   d.max_diag = opts.max_lm_diagonal;
   if (!opts.jacobi_scaling) {
@@ -1310,15 +1274,14 @@ int sfm_ba_solve_resident(sfm_ba_handle* h, const sfm_ba_options* opts_in, int32
   // Jacobian columns of the constant side vanish and its step is zero
   if (mode == SFM_BA_STRUCT_ONLY && d.C) HIPCHK(hipMemsetAsync(d.scale_c, 0, sizeof(double) * 6 * d.C, h->stream));
   if (mode == SFM_BA_POSE_ONLY && d.P) HIPCHK(hipMemsetAsync(d.scale_p, 0, sizeof(double) * 3 * d.P, h->stream));
-  // the loop's decisions on the device unless a collective needs the host
-  // between the phases (the host-callback hook; the distributed factor's
-  // panel loop: at the sizes it is for, a host round trip per phase is noise)
-  const bool host_lm = h->host_fn || h->coll_fn || (sharded(h) && h->dist_pt > 0) || env_flag("SFM_HOST_LM");
-  // (after h->mode: step_prep_folds reads it)
-  h->eval_fused = step_prep_folds(h) && !env_flag("SFM_EVAL_SPLIT");
+  // which kernels this solve's passes run, and who drives the loop (ba_plan.h)
+  read_knobs(&h->knobs, kKnobsSolve);
+  h->plan = plan_solve(d.plan, SolveShape{d.C, d.P, d.N_pad, d.xcd_slice_max}, mode, sharded(h),
+                       h->host_fn || h->coll_fn, h->dist_pt, h->knobs);
   h->cams_staged = false;
   bool nonfinite = false;
-  const int rc = host_lm ? run_host_lm(h, opts, &sm, push, &nonfinite) : run_device_lm(h, opts, &sm, push, &nonfinite);
+  const int rc = h->plan.lm == LmDriver::Host ? run_host_lm(h, opts, &sm, push, &nonfinite)
+                                              : run_device_lm(h, opts, &sm, push, &nonfinite);
   if (rc && !nonfinite) return rc;
   if (!rc) sm.wall_time_s = now_s();
   if (summary) *summary = sm;
@@ -1415,7 +1378,7 @@ int sfm_ba_evaluate(sfm_ba_handle* h, double* cost, double* res, double* jac) {
   if (d.N == 0) HIPCHK(hipMemsetAsync(d.partials, 0, sizeof(double), h->stream));
   // the record-writing grid (jac_blocks_rec) wrote the cost partials: the
   // solve's larger grid's extra slots still hold the last solve's partials
-  launch_reduce(d, kPCost, d.jac_blocks_rec, 0, kCost, h->stream);
+  launch_reduce(d, kPCost, d.plan.jac_blocks_rec, 0, kCost, h->stream);
   std::vector<double> rec(size_t(kJRec) * d.N_pad);
   std::vector<int32_t> order(size_t(d.N)), pos(size_t(d.N));
   if (d.N) {

@@ -40,6 +40,7 @@
 #include "../../include/sfm_ctracker_compat.hpp"
 #include "../../sfm_amd/csrc/ba_host_layout.h"
 #include "../../sfm_amd/csrc/ba_lm.h"
+#include "../../sfm_amd/csrc/ba_plan.h"
 
 // ---- the oracle's C entry points (oracle/*.cpp, linked in) ----
 extern "C" {
@@ -92,6 +93,13 @@ static int g_checks = 0;
       std::exit(1);                                                              \
     }                                                                            \
   } while (0)
+
+// the environment read_knobs sees in here
+static std::map<std::string, std::string> g_env;
+static const char* fake_env(const char* name) {
+  auto it = g_env.find(name);
+  return it == g_env.end() ? nullptr : it->second.c_str();
+}
 
 struct Scene {
   int C = 0, P = 0;
@@ -372,6 +380,22 @@ static void check_plan() {
   sh = sfm::hostlayout::schur_shape(460 * 210, 210, "7", "0");
   CHECK(sh.pts_sub == 16 && !sh.wg_blocks);
   CHECK(sfm::hostlayout::schur_shape(0, 0, nullptr, nullptr).pts_sub == 8);
+  // the same overrides by way of read_knobs, as the library takes them
+  auto shape_with = [](int64_t n_pairs, int64_t n_blk, const char* sub, const char* wg) {
+    g_env.clear();
+    if (sub) g_env["SFM_SCHUR_PTS_SUB"] = sub;
+    if (wg) g_env["SFM_SCHUR_WG"] = wg;
+    sfm::SolveKnobs k;
+    sfm::read_knobs(&k, sfm::kKnobsProblem, fake_env);
+    g_env.clear();
+    return sfm::hostlayout::schur_shape(n_pairs, n_blk, k.schur_pts_sub, k.schur_wg);
+  };
+  sh = shape_with(460 * 210, 210, nullptr, nullptr);
+  CHECK(sh.pts_sub == 64 && sh.wg_blocks);
+  sh = shape_with(460 * 210, 210, "32", "1");
+  CHECK(sh.pts_sub == 32 && !sh.wg_blocks);
+  sh = shape_with(460 * 210, 210, "7", "0");
+  CHECK(sh.pts_sub == 16 && !sh.wg_blocks);
   // the small path's predicate at its bounds (counts made up: one camera, one point)
   {
     const int32_t one_cam[1] = {65536}, pt64[1] = {64}, pt65[1] = {65};
@@ -430,6 +454,497 @@ static Scal step_scal(double model_change, double new_cost, double step2) {
   return Scal().set(sfm::kModelChange, model_change).set(sfm::kNewCost, new_cost).set(sfm::kStep2Pt, step2);
 }
 static bool same_bits(double a, double b) { return std::memcmp(&a, &b, sizeof(double)) == 0; }
+
+// ---- ba_plan.h: which kernel variant each pass runs ----
+// Expected values are written out as the drivers and launchers decided them
+// before the plan existed (the predicates of sfm_ba_set_problem,
+// evaluate_enqueue, compute_step_enqueue and the launchers), not computed by
+// the functions under test.
+using sfm::Backsub;
+using sfm::CamPass;
+using sfm::CamSums;
+using sfm::LmDriver;
+using sfm::PairPass;
+using sfm::PointPass;
+using sfm::ProblemPlan;
+using sfm::ProblemShape;
+using sfm::SolveKnobs;
+using sfm::SolvePlan;
+
+// A regular scene's shape: every point in 4 views (fewer cameras: in all),
+// ~72 pairs per camera block unless said otherwise, the wave-major stream unpadded.
+static ProblemShape plan_shape(int C, int P, bool small_fits = false, int64_t pairs_per_blk = 72) {
+  ProblemShape sh;
+  const int v = std::min(C, 4);
+  sh.C = C;
+  sh.P = P;
+  sh.N = int64_t(P) * v;
+  const int64_t per_cam = C ? (sh.N + C - 1) / C : 0;
+  sh.n_jchunks = int(C * ((per_cam + 63) / 64));
+  sh.N_pad = 64 * int64_t(sh.n_jchunks);
+  sh.host_counts = sh.small_fits = small_fits;
+  sh.n_pairs = pairs_per_blk * sh.n_blk();
+  sh.wm_slots = int64_t((P + 63) / 64) * v;
+  return sh;
+}
+static bool same_plan(const ProblemPlan& a, const ProblemPlan& b) {
+  return a.small_setup == b.small_setup && a.wave_major == b.wave_major && a.schur_pts_sub == b.schur_pts_sub &&
+         a.schur_wg_blocks == b.schur_wg_blocks && a.large_system == b.large_system &&
+         a.xcd_block_order == b.xcd_block_order && a.pm_backsub == b.pm_backsub && a.eu_cm == b.eu_cm &&
+         a.overlap == b.overlap && a.force_pack == b.force_pack && a.schur_wgs == b.schur_wgs &&
+         a.jac_blocks == b.jac_blocks && a.jac_blocks_rec == b.jac_blocks_rec;
+}
+static bool same_plan(const SolvePlan& a, const SolvePlan& b) {
+  return a.mode == b.mode && a.cams_var == b.cams_var && a.pts_var == b.pts_var && a.sharded == b.sharded &&
+         a.lm == b.lm && a.lm_batch == b.lm_batch && a.prep_folded == b.prep_folded && a.cam_sums == b.cam_sums &&
+         a.cam_pass == b.cam_pass && a.point_pass == b.point_pass && a.stage_cams == b.stage_cams &&
+         a.overlapped == b.overlapped && a.pair_pass == b.pair_pass && a.cam_records_used == b.cam_records_used &&
+         a.dist_factor == b.dist_factor && a.pack_allreduce == b.pack_allreduce && a.backsub == b.backsub &&
+         a.nb_cost == b.nb_cost && a.nb_grad_cam == b.nb_grad_cam && a.nb_cam == b.nb_cam && a.nb_pt == b.nb_pt &&
+         a.nb_obs == b.nb_obs && a.nb_back == b.nb_back;
+}
+// how a solve's collectives are set up
+enum Comm { kNoComm, kRccl, kHostCb };
+static SolvePlan solve_plan(const ProblemShape& sh, const ProblemPlan& pp, int mode, Comm comm = kNoComm,
+                            int dist_pt = 0, const SolveKnobs& k = SolveKnobs(), int32_t xcd_slice_max = 0) {
+  return sfm::plan_solve(pp, sfm::SolveShape{sh.C, sh.P, sh.N_pad, xcd_slice_max}, mode, comm != kNoComm,
+                         comm == kHostCb, dist_pt, k);
+}
+
+static void check_solve_plan() {
+  const SolveKnobs k0;
+  const int SP = SFM_BA_STRUCT_AND_POSE;
+  // ---- the switches: each accepts what its site always did ----
+  {
+    SolveKnobs k;
+    g_env.clear();
+    sfm::read_knobs(&k, sfm::kKnobsProblem | sfm::kKnobsSolve, fake_env);
+    CHECK(k.small_setup && k.pm_wave_major && k.schur_pts_sub == 0 && k.schur_wg == -1 && k.schur_wgs == 0 &&
+          k.eu_cm && !k.overlap && !k.force_pack && k.jac_wg_per_xcd == 0 && !k.eval_split && !k.pe_groups1 &&
+          !k.host_lm && !k.lm_unfused && !k.no_accept_fold && k.lm_batch == 0);
+    g_env = {{"SFM_SMALL_SETUP", "0"},  {"SFM_PM_WAVE_MAJOR", "00"},  {"SFM_SCHUR_PTS_SUB", "7"},
+             {"SFM_SCHUR_WG", "0"},     {"SFM_SCHUR_WGS", "9"},       {"SFM_EU_CM", "0"},
+             {"SFM_OVERLAP", "2"},      {"SFM_FORCE_PACK", "1"},      {"SFM_JAC_WG_PER_XCD", "64"},
+             {"SFM_EVAL_SPLIT", "1"},   {"SFM_PE_GROUPS1", "1"},      {"SFM_HOST_LM", "1"},
+             {"SFM_LM_UNFUSED", "1"},   {"SFM_NO_ACCEPT_FOLD", "1x"}, {"SFM_LM_BATCH", "100"}};
+    sfm::read_knobs(&k, sfm::kKnobsProblem | sfm::kKnobsSolve, fake_env);
+    CHECK(!k.small_setup && !k.pm_wave_major && k.schur_pts_sub == 16 && k.schur_wg == 0 && k.schur_wgs == 16 &&
+          !k.eu_cm && k.overlap && k.force_pack && k.jac_wg_per_xcd == 64 && k.eval_split && k.pe_groups1 &&
+          k.host_lm && k.lm_unfused && k.no_accept_fold && k.lm_batch == 64);
+    // "off unless 0" against "on only at 1"; numbers that do not count; the clamps
+    g_env = {{"SFM_SMALL_SETUP", "no"}, {"SFM_PM_WAVE_MAJOR", ""},   {"SFM_SCHUR_PTS_SUB", "64"},
+             {"SFM_SCHUR_WG", "1"},     {"SFM_SCHUR_WGS", "-5"},     {"SFM_EU_CM", "1"},
+             {"SFM_OVERLAP", "0"},      {"SFM_FORCE_PACK", "2"},     {"SFM_JAC_WG_PER_XCD", "-3"},
+             {"SFM_EVAL_SPLIT", "0"},   {"SFM_PE_GROUPS1", "yes"},   {"SFM_HOST_LM", ""},
+             {"SFM_LM_UNFUSED", "01"},  {"SFM_NO_ACCEPT_FOLD", "0"}, {"SFM_LM_BATCH", "0"}};
+    sfm::read_knobs(&k, sfm::kKnobsProblem | sfm::kKnobsSolve, fake_env);
+    CHECK(k.small_setup && k.pm_wave_major && k.schur_pts_sub == 64 && k.schur_wg == 1 && k.schur_wgs == 0 &&
+          k.eu_cm && !k.overlap && !k.force_pack && k.jac_wg_per_xcd == 0 && !k.eval_split && !k.pe_groups1 &&
+          !k.host_lm && !k.lm_unfused && !k.no_accept_fold && k.lm_batch == 1);
+    g_env = {{"SFM_SCHUR_WGS", "1000000"}, {"SFM_HOST_LM", "1"}};
+    sfm::read_knobs(&k, sfm::kKnobsProblem, fake_env);  // the problem's half alone
+    CHECK(k.schur_wgs == 65536 / 8 * 8 && !k.host_lm && k.schur_pts_sub == 0);
+    g_env.clear();
+  }
+  // ---- literal rows ----
+  // empty sides: nothing divides by zero, the launchers' size guards do the rest
+  {
+    ProblemShape sh = plan_shape(0, 10);  // no cameras (so no observations)
+    ProblemPlan pp = sfm::plan_problem(sh, false, k0);
+    ProblemPlan e;
+    CHECK(same_plan(pp, e));  // all defaults: grids of 8, 8 lanes, nothing large, eu_cm
+    SolvePlan s = solve_plan(sh, pp, SP), es;
+    es.lm = LmDriver::DeviceFused;  // (AcceptFold needs a camera)
+    es.cam_sums = CamSums::SumFinalize;
+    es.nb_cost = 8;
+    es.nb_back = 8;
+    CHECK(same_plan(s, es));
+    sh = plan_shape(10, 0);  // no points
+    pp = sfm::plan_problem(sh, false, k0);
+    CHECK(same_plan(pp, e));
+    s = solve_plan(sh, pp, SP);
+    es = SolvePlan();
+    es.lm = LmDriver::DeviceFusedAcceptFold;
+    es.cam_sums = CamSums::SumFinalize;
+    es.nb_cost = 8;
+    es.nb_grad_cam = 10;
+    CHECK(same_plan(s, es));
+    sh = ProblemShape();  // nothing at all, the counts never made
+    pp = sfm::plan_problem(sh, false, k0);
+    CHECK(same_plan(pp, e));
+    CHECK(sfm::max_blocks(sh, pp, 0) == 8);
+  }
+  // C = 64 / 65: the camera sums leave the point pass, the step's prep folds
+  {
+    ProblemShape sh = plan_shape(64, 1025);
+    ProblemPlan pp = sfm::plan_problem(sh, false, k0);
+    ProblemPlan e;
+    e.wave_major = true;
+    e.jac_blocks = e.jac_blocks_rec = 32;  // 128 chunks: (128 / 8 + 3) / 4 = 4 workgroups per XCD
+    CHECK(same_plan(pp, e));
+    SolvePlan s = solve_plan(sh, pp, SP), es;
+    es.lm = LmDriver::DeviceFusedAcceptFold;
+    es.cam_sums = CamSums::InPointPass;
+    es.point_pass = PointPass::Lds64;
+    es.nb_cost = 32;
+    es.nb_grad_cam = 64;
+    es.nb_pt = 5;
+    es.nb_obs = 32;  // 128 chunks, no slice sizes: ((128 + 3) / 4 + 7) / 8 = 4 per XCD
+    es.nb_back = 8;
+    CHECK(same_plan(s, es));
+    sh = plan_shape(65, 1025);
+    pp = sfm::plan_problem(sh, false, k0);
+    e.jac_blocks = e.jac_blocks_rec = 16;  // 65 chunks: (65 / 8 + 3) / 4 = 2
+    CHECK(same_plan(pp, e));
+    s = solve_plan(sh, pp, SP);
+    es.prep_folded = true;
+    es.cam_sums = CamSums::SumDiag;
+    es.cam_pass = CamPass::JacObsPrep;
+    es.point_pass = PointPass::Lds512x2;
+    es.nb_cost = 16;
+    es.nb_grad_cam = 65;
+    es.nb_obs = 24;  // ((65 + 3) / 4 + 7) / 8 = 3
+    CHECK(same_plan(s, es));
+    CHECK(es.pair_pass == PairPass::Pts && !es.stage_cams && es.backsub == Backsub::ThreePass);
+  }
+  // C = 127 / 128: 8128 / 8256 camera blocks against kSchurXcdMinBlocks = 8192
+  {
+    ProblemShape sh = plan_shape(127, 1025);
+    ProblemPlan pp = sfm::plan_problem(sh, false, k0);
+    ProblemPlan e;
+    e.wave_major = true;
+    e.jac_blocks = e.jac_blocks_rec = 32;  // 127 chunks: (127 / 8 + 3) / 4 = 4
+    CHECK(same_plan(pp, e));               // not large: no ptG / camS, no bperm / srec, three-pass backsub
+    SolvePlan s = solve_plan(sh, pp, SP), es;
+    es.lm = LmDriver::DeviceFusedAcceptFold;
+    es.prep_folded = true;
+    es.cam_sums = CamSums::SumDiag;
+    es.cam_pass = CamPass::JacObsPrep;
+    es.point_pass = PointPass::Lds512x2;
+    es.pair_pass = PairPass::Pts;
+    es.backsub = Backsub::ThreePass;
+    es.nb_cost = 32;
+    es.nb_grad_cam = 127;
+    es.nb_pt = 5;
+    es.nb_obs = 32;  // ((127 + 3) / 4 + 7) / 8 = 4
+    es.nb_back = 8;
+    CHECK(same_plan(s, es));
+    sh = plan_shape(128, 1025);
+    pp = sfm::plan_problem(sh, false, k0);
+    e.large_system = e.xcd_block_order = e.pm_backsub = true;  // ptG, camS, bperm, srec wanted
+    CHECK(same_plan(pp, e));                                   // (128 chunks: 4 workgroups per XCD again)
+    s = solve_plan(sh, pp, SP);
+    es.stage_cams = es.cam_records_used = true;
+    es.pair_pass = PairPass::RotPersistent;
+    es.backsub = Backsub::OnePass;
+    es.nb_grad_cam = 128;
+    es.nb_obs = es.nb_back = 5;  // the one pass: per 256 points
+    CHECK(same_plan(s, es));
+    // ... on the small setup path: no XCD slot order, so no slot records, so not persistent
+    sh = plan_shape(128, 1025, true);
+    pp = sfm::plan_problem(sh, false, k0);
+    e.small_setup = true;
+    e.wave_major = e.xcd_block_order = false;
+    CHECK(same_plan(pp, e));
+    s = solve_plan(sh, pp, SP);
+    es.stage_cams = es.cam_records_used = false;
+    es.pair_pass = PairPass::Rot;
+    CHECK(same_plan(s, es));
+  }
+  // the accept fold's edge: C <= 256 and 3 P <= 24576
+  {
+    ProblemPlan e;
+    e.wave_major = e.large_system = e.xcd_block_order = e.pm_backsub = true;
+    SolvePlan es;
+    es.prep_folded = es.stage_cams = es.cam_records_used = true;
+    es.cam_sums = CamSums::SumDiag;
+    es.cam_pass = CamPass::JacObsPrep;
+    es.point_pass = PointPass::Lds512x2;
+    es.pair_pass = PairPass::RotPersistent;
+    es.backsub = Backsub::OnePass;
+    struct Row {
+      int C, P, jac, nb_cam, nb_pt;  // jac: 8 (n_jchunks / 8 + 3) / 4 with n_jchunks = 512, 514, 768, 514
+      LmDriver lm;
+    };
+    const Row rows[] = {{256, 8192, 128, 1, 32, LmDriver::DeviceFusedAcceptFold},
+                        {257, 8192, 128, 2, 32, LmDriver::DeviceFused},
+                        {256, 8193, 192, 1, 33, LmDriver::DeviceFused},
+                        {257, 8193, 128, 2, 33, LmDriver::DeviceFused}};
+    for (const Row& r : rows) {
+      const ProblemShape sh = plan_shape(r.C, r.P);
+      const ProblemPlan pp = sfm::plan_problem(sh, false, k0);
+      e.jac_blocks = e.jac_blocks_rec = r.jac;  // (the record-writing grid's cap is 128 per XCD: not reached)
+      CHECK(same_plan(pp, e));
+      es.lm = r.lm;
+      es.nb_cost = r.jac;
+      es.nb_grad_cam = r.C;
+      es.nb_cam = r.nb_cam;
+      es.nb_pt = es.nb_obs = es.nb_back = r.nb_pt;
+      CHECK(same_plan(solve_plan(sh, pp, SP), es));
+    }
+  }
+  // C = 512 / 513: the cameras leave the LDS of the point pass and of k_backsub_pm
+  {
+    ProblemShape sh = plan_shape(512, 8193);
+    ProblemPlan pp = sfm::plan_problem(sh, false, k0);
+    ProblemPlan e;
+    e.wave_major = e.large_system = e.xcd_block_order = e.pm_backsub = true;
+    e.jac_blocks = e.jac_blocks_rec = 256;  // 1024 chunks: (1024 / 8 + 3) / 4 = 32
+    CHECK(same_plan(pp, e));
+    SolvePlan s = solve_plan(sh, pp, SP), es;
+    es.lm = LmDriver::DeviceFused;
+    es.prep_folded = es.stage_cams = es.cam_records_used = true;
+    es.cam_sums = CamSums::SumDiag;
+    es.cam_pass = CamPass::JacObsPrep;
+    es.point_pass = PointPass::Lds512x2;
+    es.pair_pass = PairPass::RotPersistent;
+    es.backsub = Backsub::OnePass;
+    es.nb_cost = 256;
+    es.nb_grad_cam = 512;
+    es.nb_cam = 2;
+    es.nb_pt = es.nb_obs = es.nb_back = 33;
+    CHECK(same_plan(s, es));
+    sh = plan_shape(513, 8193);
+    pp = sfm::plan_problem(sh, false, k0);
+    e.pm_backsub = false;
+    e.jac_blocks = e.jac_blocks_rec = 128;  // 513 chunks: (513 / 8 + 3) / 4 = 16
+    CHECK(same_plan(pp, e));
+    s = solve_plan(sh, pp, SP);
+    es.point_pass = PointPass::Rc;
+    es.backsub = Backsub::ThreePass;
+    es.nb_cost = 128;
+    es.nb_grad_cam = 513;
+    es.nb_cam = 3;
+    es.nb_obs = 136;  // no slice sizes: ((513 + 3) / 4 + 7) / 8 = 17 per XCD
+    es.nb_back = 40;  // 1025 points per slice: 5 blocks of 256
+    CHECK(same_plan(s, es));
+    // the observation passes' grid from the largest point slice's chunks, as
+    // every problem with observations has them: (70 + 3) / 4 = 18 per XCD
+    s = solve_plan(sh, pp, SP, kNoComm, 0, k0, 70);
+    es.nb_obs = 144;
+    CHECK(same_plan(s, es));
+    CHECK(sfm::max_blocks(sh, pp, 0) == 513 && sfm::max_blocks(sh, pp, 70) == 513);  // cameras
+    CHECK(sfm::max_blocks(sh, pp, 2100) == 4200);                                    // one slice with most chunks
+  }
+  // a workgroup per block beyond 64 cameras: the prep does not fold (the pass
+  // takes the diagonal blocks itself)
+  {
+    const ProblemShape sh = plan_shape(70, 1025, false, 460);
+    const ProblemPlan pp = sfm::plan_problem(sh, false, k0);
+    ProblemPlan e;
+    e.wave_major = true;
+    e.schur_pts_sub = 64;                   // 8 -> 64 while below 460 / 10
+    e.jac_blocks = e.jac_blocks_rec = 16;   // 70 chunks: (70 / 8 + 3) / 4 = 2
+    CHECK(same_plan(pp, e));                // 2485 blocks: above the 1024 of the shape's own choice
+    SolveKnobs k;
+    k.schur_wg = 1;
+    const ProblemPlan pw = sfm::plan_problem(sh, false, k);
+    e.schur_wg_blocks = true;
+    CHECK(same_plan(pw, e));
+    SolvePlan es;
+    es.lm = LmDriver::DeviceFusedAcceptFold;
+    es.cam_sums = CamSums::SumFinalize;
+    es.cam_pass = CamPass::Jacobian;
+    es.point_pass = PointPass::Lds512x2;
+    es.pair_pass = PairPass::WgBlocks;
+    es.backsub = Backsub::ThreePass;
+    es.nb_cost = 16;
+    es.nb_grad_cam = 70;
+    es.nb_pt = 5;
+    es.nb_obs = 24;  // ((70 + 3) / 4 + 7) / 8 = 3
+    es.nb_back = 8;
+    CHECK(same_plan(solve_plan(sh, pw, SP), es));
+  }
+  // the three modes, the collectives and every switch alone at C = 130, P = 1025
+  const ProblemShape sh130 = plan_shape(130, 1025);
+  const ProblemPlan pp130 = sfm::plan_problem(sh130, false, k0);
+  ProblemPlan ep;
+  ep.wave_major = ep.large_system = ep.xcd_block_order = ep.pm_backsub = true;
+  ep.jac_blocks = ep.jac_blocks_rec = 32;  // 130 chunks: (130 / 8 + 3) / 4 = 4
+  CHECK(same_plan(pp130, ep));
+  CHECK(sfm::max_blocks(sh130, pp130, 0) == 130);  // cameras; the observation passes' 40 and N_pad / 256 = 33 below
+  SolvePlan e130;
+  e130.lm = LmDriver::DeviceFusedAcceptFold;
+  e130.prep_folded = true;
+  e130.cam_sums = CamSums::SumDiag;
+  e130.cam_pass = CamPass::JacObsPrep;
+  e130.point_pass = PointPass::Lds512x2;
+  e130.stage_cams = true;
+  e130.pair_pass = PairPass::RotPersistent;
+  e130.cam_records_used = true;
+  e130.backsub = Backsub::OnePass;
+  e130.nb_cost = 32;
+  e130.nb_grad_cam = 130;
+  e130.nb_pt = e130.nb_obs = e130.nb_back = 5;
+  CHECK(same_plan(solve_plan(sh130, pp130, SP), e130));
+  {
+    SolvePlan e = e130;  // POSE_ONLY: points constant; nothing folds or fuses, three passes
+    e.mode = SFM_BA_POSE_ONLY;
+    e.pts_var = false;
+    e.prep_folded = e.stage_cams = false;
+    e.cam_sums = CamSums::SumFinalize;
+    e.cam_pass = CamPass::Jacobian;
+    e.backsub = Backsub::ThreePass;
+    e.nb_obs = 40;  // ((130 + 3) / 4 + 7) / 8 = 5 per XCD
+    e.nb_back = 8;
+    CHECK(same_plan(solve_plan(sh130, pp130, SFM_BA_POSE_ONLY), e));
+    e.mode = SFM_BA_STRUCT_ONLY;  // cameras constant
+    e.pts_var = true;
+    e.cams_var = false;
+    e.cam_sums = CamSums::None;
+    e.nb_grad_cam = 1;
+    CHECK(same_plan(solve_plan(sh130, pp130, SFM_BA_STRUCT_ONLY), e));
+  }
+  {
+    // sharded: a collective between the camera sums and their use, and between
+    // a phase's reduction and the bookkeeping; no overlap even when asked for
+    SolveKnobs ko;
+    ko.overlap = true;
+    const ProblemPlan ps = sfm::plan_problem(sh130, true, ko);
+    CHECK(same_plan(ps, ep));
+    SolvePlan e = e130;
+    e.sharded = e.pack_allreduce = true;
+    e.lm = LmDriver::Device;
+    e.prep_folded = e.stage_cams = false;
+    e.cam_sums = CamSums::ReduceAllreduceFinalize;
+    e.cam_pass = CamPass::Jacobian;
+    e.nb_grad_cam = 1;
+    CHECK(same_plan(solve_plan(sh130, ps, SP, kRccl, 0, ko), e));
+    e.lm = LmDriver::Host;
+    CHECK(same_plan(solve_plan(sh130, ps, SP, kHostCb, 0, ko), e));
+    e.dist_factor = true;
+    CHECK(same_plan(solve_plan(sh130, ps, SP, kHostCb, 2, ko), e));
+    CHECK(same_plan(solve_plan(sh130, ps, SP, kRccl, 2, ko), e));
+    e = e130;  // a panel width without a communicator changes nothing
+    CHECK(same_plan(solve_plan(sh130, pp130, SP, kNoComm, 2), e));
+  }
+  {
+    // the problem's switches, one at a time
+    SolveKnobs k = k0;
+    k.small_setup = false;  // (not a small-path problem)
+    CHECK(same_plan(sfm::plan_problem(sh130, false, k), ep));
+    const ProblemShape sm = plan_shape(20, 1025, true, 460);  // ... and one that is
+    CHECK(sfm::plan_problem(sm, false, k0).small_setup && !sfm::plan_problem(sm, false, k0).wave_major);
+    CHECK(!sfm::plan_problem(sm, false, k).small_setup && sfm::plan_problem(sm, false, k).wave_major);
+    CHECK(sfm::plan_problem(sm, false, k0).schur_wg_blocks);  // 210 blocks of 460 pairs
+    ProblemPlan e = ep;
+    k = k0, k.pm_wave_major = false, e.wave_major = false;
+    CHECK(same_plan(sfm::plan_problem(sh130, false, k), e));
+    e = ep, k = k0, k.schur_pts_sub = 32, e.schur_pts_sub = 32;
+    CHECK(same_plan(sfm::plan_problem(sh130, false, k), e));
+    e = ep, k = k0, k.schur_wg = 1;  // (only 64 lanes take workgroup blocks)
+    CHECK(same_plan(sfm::plan_problem(sh130, false, k), e));
+    e = ep, k = k0, k.schur_wgs = 16, e.schur_wgs = 16;
+    CHECK(same_plan(sfm::plan_problem(sh130, false, k), e));
+    e = ep, k = k0, k.eu_cm = false, e.eu_cm = false;
+    CHECK(same_plan(sfm::plan_problem(sh130, false, k), e));
+    e = ep, k = k0, k.jac_wg_per_xcd = 2, e.jac_blocks = 16;
+    CHECK(same_plan(sfm::plan_problem(sh130, false, k), e));
+    SolvePlan es = e130;
+    es.nb_cost = 16;
+    CHECK(same_plan(solve_plan(sh130, sfm::plan_problem(sh130, false, k), SP), es));
+    e = ep, k = k0, k.overlap = true, e.overlap = 1;  // 13 tile rows
+    CHECK(same_plan(sfm::plan_problem(sh130, false, k), e));
+    es = e130, es.overlapped = true, es.pair_pass = PairPass::Rot;  // (the records are still staged, as before)
+    CHECK(same_plan(solve_plan(sh130, e, SP), es));
+    CHECK(!sfm::plan_problem(plan_shape(21, 1025), false, k).overlap);  // 126 unknowns + rhs: two tile rows
+    CHECK(sfm::plan_problem(plan_shape(22, 1025), false, k).overlap == 1);
+    k.force_pack = true, e.force_pack = true;  // both: the packed path wins
+    es = e130, es.pack_allreduce = true;
+    CHECK(same_plan(solve_plan(sh130, sfm::plan_problem(sh130, false, k), SP), es));
+    e = ep, k = k0, k.force_pack = true, e.force_pack = true;
+    CHECK(same_plan(sfm::plan_problem(sh130, false, k), e));
+    CHECK(same_plan(solve_plan(sh130, e, SP), es));
+    // the wave-major stream's cap, once its slots are counted
+    ProblemShape pad = sh130;
+    pad.wm_slots = -1;
+    CHECK(sfm::plan_problem(pad, false, k0).wave_major);  // wanted until then
+    pad.wm_slots = (3 * pad.N + 128 * 17) / 128;
+    CHECK(sfm::plan_problem(pad, false, k0).wave_major);
+    pad.wm_slots += 1;
+    CHECK(!sfm::plan_problem(pad, false, k0).wave_major);
+  }
+  {
+    // the solve's switches, one at a time
+    SolveKnobs k = k0;
+    SolvePlan e = e130;
+    k.eval_split = true, e.cam_pass = CamPass::Jacobian, e.stage_cams = false;
+    CHECK(same_plan(solve_plan(sh130, pp130, SP, kNoComm, 0, k), e));
+    e = e130, k = k0, k.pe_groups1 = true, e.point_pass = PointPass::Lds512;
+    CHECK(same_plan(solve_plan(sh130, pp130, SP, kNoComm, 0, k), e));
+    e = e130, k = k0, k.host_lm = true, e.lm = LmDriver::Host;
+    CHECK(same_plan(solve_plan(sh130, pp130, SP, kNoComm, 0, k), e));
+    e = e130, k = k0, k.lm_unfused = true, e.lm = LmDriver::Device;
+    CHECK(same_plan(solve_plan(sh130, pp130, SP, kNoComm, 0, k), e));
+    e = e130, k = k0, k.no_accept_fold = true, e.lm = LmDriver::DeviceFused;
+    CHECK(same_plan(solve_plan(sh130, pp130, SP, kNoComm, 0, k), e));
+    e = e130, k = k0, k.lm_batch = 5, e.lm_batch = 5;
+    CHECK(same_plan(solve_plan(sh130, pp130, SP, kNoComm, 0, k), e));
+  }
+  // ---- invariants over a grid ----
+  std::vector<SolveKnobs> knobs(1, k0);
+  auto with = [&](auto set) { knobs.push_back(k0); set(knobs.back()); };
+  with([](SolveKnobs& k) { k.small_setup = false; });
+  with([](SolveKnobs& k) { k.pm_wave_major = false; });
+  for (int sub : {8, 16, 32, 64}) with([sub](SolveKnobs& k) { k.schur_pts_sub = sub; });
+  for (int wg : {0, 1}) with([wg](SolveKnobs& k) { k.schur_wg = wg; });
+  with([](SolveKnobs& k) { k.schur_pts_sub = 64, k.schur_wg = 1; });  // (the pair that forces workgroup blocks)
+  with([](SolveKnobs& k) { k.schur_wgs = 16; });
+  with([](SolveKnobs& k) { k.eu_cm = false; });
+  with([](SolveKnobs& k) { k.overlap = true; });
+  with([](SolveKnobs& k) { k.force_pack = true; });
+  with([](SolveKnobs& k) { k.jac_wg_per_xcd = 1; });
+  with([](SolveKnobs& k) { k.jac_wg_per_xcd = 1000; });
+  with([](SolveKnobs& k) { k.eval_split = true; });
+  with([](SolveKnobs& k) { k.pe_groups1 = true; });
+  with([](SolveKnobs& k) { k.host_lm = true; });
+  with([](SolveKnobs& k) { k.lm_unfused = true; });
+  with([](SolveKnobs& k) { k.no_accept_fold = true; });
+  with([](SolveKnobs& k) { k.lm_batch = 64; });
+  int n_plans = 0;
+  for (int C : {0, 1, 64, 65, 127, 128, 256, 257, 512, 513, 2000})
+    for (int P : {0, 1, 255, 8192, 8193})
+      for (int small = 0; small < 2; ++small)
+        for (const SolveKnobs& k : knobs) {
+          const ProblemShape sh = plan_shape(C, P, small != 0, C <= 64 ? 460 : 72);
+          for (Comm comm : {kNoComm, kRccl, kHostCb}) {
+            const ProblemPlan pp = sfm::plan_problem(sh, comm != kNoComm, k);
+            CHECK(pp.schur_pts_sub == 8 || pp.schur_pts_sub == 16 || pp.schur_pts_sub == 32 || pp.schur_pts_sub == 64);
+            CHECK(!pp.schur_wg_blocks || pp.schur_pts_sub == 64);
+            CHECK(!pp.xcd_block_order || pp.large_system);
+            CHECK(!pp.pm_backsub || pp.large_system);
+            CHECK(!(pp.wave_major && pp.small_setup));
+            CHECK(pp.jac_blocks >= 8 && pp.jac_blocks % 8 == 0 && pp.jac_blocks_rec >= 8 && pp.jac_blocks_rec % 8 == 0);
+            // the largest point slice's chunks: not counted (0), or an eighth of them and ~5% (what
+            // sfm_ba_set_problem hands to both)
+            const int32_t n_chunks = int32_t(sh.N_pad / 64);
+            for (int v = 0; v < 6; ++v) {
+              const int mode = v % 3;
+              const int32_t slice_max = v < 3 ? 0 : n_chunks / 8 + n_chunks / 128 + 1;
+              const int cap = sfm::max_blocks(sh, pp, slice_max);
+              const SolvePlan s = solve_plan(sh, pp, mode, comm, 0, k, slice_max);
+              ++n_plans;
+              const bool fused = s.cam_pass == CamPass::JacObsPrep;
+              CHECK(!fused || s.prep_folded);
+              CHECK(!s.prep_folded || s.cam_sums == CamSums::SumDiag);
+              CHECK((s.cam_sums == CamSums::SumDiag) == s.prep_folded);
+              CHECK(!s.prep_folded || (mode == SFM_BA_STRUCT_AND_POSE && !s.sharded));
+              CHECK(s.pair_pass != PairPass::RotPersistent || s.cam_records_used);
+              CHECK(!s.cam_records_used || pp.large_system);
+              CHECK(!s.stage_cams || fused);
+              CHECK(s.backsub != Backsub::OnePass || pp.pm_backsub);
+              CHECK(s.backsub != Backsub::OnePass || mode == SFM_BA_STRUCT_AND_POSE);
+              CHECK(!s.fused_lm() || !s.sharded);
+              CHECK(comm != kHostCb || s.lm == LmDriver::Host);
+              CHECK(!s.overlapped || (!s.sharded && !s.pack_allreduce && s.pair_pass != PairPass::RotPersistent));
+              CHECK((s.cam_sums == CamSums::None) == !s.cams_var);
+              for (int nb : {s.nb_cost, s.nb_grad_cam, s.nb_cam, s.nb_pt, s.nb_obs, s.nb_back})
+                CHECK(nb >= 1 && nb <= cap);
+            }
+          }
+        }
+  std::printf("  solve plan: switches, literal rows, %d plans on the grid ok\n", n_plans);
+}
 
 // The oracle's traces of every branch case (tests/golden/lm_replay.txt, from
 // lm_branches.json by make_lm_replay.py) replayed through lm_init / lm_decide
@@ -774,6 +1289,7 @@ int main() {
 
   std::printf("asan: set_problem's host plan (ba_host_layout.h)\n");
   check_plan();
+  check_solve_plan();
 
   std::printf("asan: LM trust-region state machine (ba_lm.h)\n");
   check_lm_replay();

@@ -23,7 +23,7 @@ import lm_cases as L
 
 SEED = L.SEED
 
-# restated from sfm_amd/csrc/ba_host_layout.h
+# restated from sfm_amd/csrc/ba_host_layout.h (the constants ba_plan.h's plans are made from)
 K_HOST_CHECK_MAX_OBS = 65536
 K_STAGE_MAX_BYTES = 1 << 20
 K_SMALL_SETUP_MAX_C = 256

@@ -87,7 +87,7 @@ def test_scene_is_what_it_claims_to_be(name):
 
 @pytest.mark.parametrize("name", NAMES)
 def test_regime_predicates(name):
-    """Restated from ba_host_layout.h / ba_problem.hip: which kernels a scene runs."""
+    """Restated from ba_plan.h (plan_problem, plan_solve): which kernels a scene runs."""
     _, st, _, _, _ = _solved(name)
     C = st["n_cams"]
     assert st["n_blk"] == C * (C + 1) // 2
