@@ -691,6 +691,70 @@ int sfm_frame_detect(sfm_matcher* mt, sfm_klt_handle* klt, const uint8_t* img, i
                      const sfm_camera* cam, int32_t threshold, int32_t octaves, int32_t capacity, float* kps,
                      int32_t* octave, uint8_t* desc, double* pts, int32_t* n_out);
 
+/* ---- Scan guidance: object mask, centroid and oriented bounding box -----------
+ * CScanGuidance::calculateMask(frame, pts3d, K, P) (CScanGuidance.cpp:39-105),
+ * which CSfM::addFrame calls after tracking() / mapping() on every RUNNING
+ * frame (CSfM.cpp:80-81), with getCentroid / getBoundingBox.  Per call: the
+ * mean of the map points; their projection to integer pixels of the frame,
+ * scaled by 0.25; the convex hull of those filled as a mask; the quarter-size
+ * frame (resize, INTER_LINEAR) converted to HSV (float, BGR order); the masked
+ * H-S histogram; its back-projection; the pixels whose value / hull area
+ * exceeds the threshold; cv::minAreaRect of them, scaled back by 4.  The
+ * OpenCV calls are restated from OpenCV 3.0 (tests/guidance_ref.py) and held
+ * bit for bit against that restatement -- parity with OpenCV unpinned; the
+ * fill is the closed hull, without the rasteriser's Bresenham edge pixels.
+ * One upload of the frame, one small download and one host synchronisation
+ * per call; no floating-point atomics, so equal input gives equal bits. */
+typedef struct sfm_guidance sfm_guidance;
+typedef struct sfm_guidance_options {
+  int32_t h_bins, s_bins;   /* 60, 50 (over [0,360) x [0,1)) */
+  double threshold, alpha;  /* 0.01, 0.9 */
+  int32_t ema;              /* 0: the reference as written (histogram replaced every frame;
+                               its _frameCount is never incremented); 1: the blend at
+                               CScanGuidance.cpp:81, the first update replacing */
+  int32_t reserved;
+} sfm_guidance_options;
+typedef struct sfm_guidance_result {
+  double centroid[3];                            /* NaN for an empty map */
+  float box_center[2], box_size[2], box_angle;   /* full-frame pixels, degrees */
+  int32_t n_points, n_projected, n_hull, n_accepted;
+  double area;                                   /* of the hull, quarter-size pixels */
+} sfm_guidance_result;
+/* Host only. */
+void sfm_guidance_default_options(sfm_guidance_options*);
+/* SFM_EINVAL: width or height below 8 (or above 8192), a bin count outside
+ * 1..256 (or both 256: the packed bin index keeps one value for "outside"),
+ * a non-finite threshold or alpha.  options NULL = the defaults. */
+int sfm_guidance_create(int32_t device, int32_t width, int32_t height,
+                        const sfm_guidance_options*, sfm_guidance** out);
+int sfm_guidance_destroy(sfm_guidance*);
+/* The live points of the device map store, read where they are (ascending
+ * index = _pts3DIdx order).  img: 8-bit, 3 channels, width x height, row
+ * stride in bytes; memory channel 0 is taken as B, as the reference passes
+ * its frame.  R9 row-major, t3, K9 (fx, fy, cx, cy used): P = [R|t].
+ * SFM_EINVAL, before any device work: a NULL argument, a non-finite K, R or
+ * t, stride < 3 * width, the map on another device than the handle.  An
+ * empty map succeeds: NaN centroid, the zero box. */
+int sfm_guidance_update(sfm_guidance*, sfm_map*, const uint8_t* img, int32_t stride,
+                        const double* R9, const double* t3, const double* K9,
+                        sfm_guidance_result* out);
+/* caller-held points [n][3] (a CMap kept on the host); pts3d may be NULL for n = 0 */
+int sfm_guidance_update_points(sfm_guidance*, int32_t n, const double* pts3d,
+                               const uint8_t* img, int32_t stride,
+                               const double* R9, const double* t3, const double* K9,
+                               sfm_guidance_result* out);
+/* planes of the last update, any pointer NULL (hs = height/4, ws = width/4):
+ * mask [hs][ws] u8, bins [hs][ws][2] i16 (-1 = outside),
+ * hist [h_bins][s_bins] float (the state the back-projection read),
+ * bproj [hs][ws] float,
+ * extents [hs][2] i32 (accepted pixels; ws, -1 = empty row) */
+int sfm_guidance_read_planes(sfm_guidance*, uint8_t* mask, int16_t* bins,
+                             float* hist, float* bproj, int32_t* extents);
+/* Device time of the last update in ms: upload, kernels, download. */
+int sfm_guidance_last_time(sfm_guidance*, double* ms3);
+/* host only: cv::minAreaRect of integer points [n][2]; box5 = cx cy w h angle */
+int sfm_min_area_rect(int32_t n, const int32_t* pts_xy, float* box5);
+
 /* Synthetic scenes, host-only.  Points [p_begin, p_end) of a
  * scene with n_pts_total points; every camera is returned.  Observations are
  * sorted by (point, camera); pt_idx is relative to p_begin.

@@ -15,7 +15,8 @@ from .cmap import CMap, DeviceMap, representative_descriptors
 from .pnp import solvePnPRansac
 from .init import TwoViewResult, two_view_init
 from .camera import Camera, FrameFrontEnd, rgb_to_grey
+from .guidance import GuidanceFrame, ScanGuidance, min_area_rect
 
-__all__ = ["Camera", "FrameFrontEnd", "rgb_to_grey", "BundleAdjuster", "CTracker", "CMap", "DeviceMap", "solvePnPRansac", "two_view_init", "TwoViewResult", "representative_descriptors", "KLTTracker", "calc_optical_flow_pyr_lk", "video", "BAOptions", "BASummary", "BAIteration", "SfmError", "make_options",
+__all__ = ["ScanGuidance", "GuidanceFrame", "min_area_rect", "Camera", "FrameFrontEnd", "rgb_to_grey", "BundleAdjuster", "CTracker", "CMap", "DeviceMap", "solvePnPRansac", "two_view_init", "TwoViewResult", "representative_descriptors", "KLTTracker", "calc_optical_flow_pyr_lk", "video", "BAOptions", "BASummary", "BAIteration", "SfmError", "make_options",
            "solve", "default_options", "device_count", "exported_symbols", "lib", "scene", "LIB_PATH",
            "STRUCT_ONLY", "POSE_ONLY", "STRUCT_AND_POSE"]

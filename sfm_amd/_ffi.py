@@ -139,6 +139,33 @@ class CameraStruct(ctypes.Structure):
     ]
 
 
+class GuidanceOptions(ctypes.Structure):
+    """sfm_guidance_options."""
+    _fields_ = [
+        ("h_bins", c_int32),
+        ("s_bins", c_int32),
+        ("threshold", c_double),
+        ("alpha", c_double),
+        ("ema", c_int32),
+        ("reserved", c_int32),
+    ]
+
+
+class GuidanceResult(ctypes.Structure):
+    """sfm_guidance_result."""
+    _fields_ = [
+        ("centroid", c_double * 3),
+        ("box_center", c_float * 2),
+        ("box_size", c_float * 2),
+        ("box_angle", c_float),
+        ("n_points", c_int32),
+        ("n_projected", c_int32),
+        ("n_hull", c_int32),
+        ("n_accepted", c_int32),
+        ("area", c_double),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGNATURES = {
     "sfm_abi_version": (c_int32, []),
@@ -261,6 +288,16 @@ _SIGNATURES = {
     "sfm_klt_push_frame_rgb": (c_int, [c_void_p, c_void_p, c_int32]),
     "sfm_frame_detect": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(CameraStruct), c_int32,
                                  c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int32)]),
+    "sfm_guidance_default_options": (None, [POINTER(GuidanceOptions)]),
+    "sfm_guidance_create": (c_int, [c_int32, c_int32, c_int32, POINTER(GuidanceOptions), POINTER(c_void_p)]),
+    "sfm_guidance_destroy": (c_int, [c_void_p]),
+    "sfm_guidance_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                    POINTER(GuidanceResult)]),
+    "sfm_guidance_update_points": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                                           c_void_p, POINTER(GuidanceResult)]),
+    "sfm_guidance_read_planes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sfm_guidance_last_time": (c_int, [c_void_p, c_void_p]),
+    "sfm_min_area_rect": (c_int, [c_int32, c_void_p, c_void_p]),
     "sfm_scene_default_intrinsics": (None, [c_void_p]),
     "sfm_scene_generate": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_uint64, c_double, c_double,
                                    c_double, c_double] + [c_void_p] * 10),
@@ -340,10 +377,17 @@ def default_two_view_options() -> TwoViewOptions:
     return o
 
 
+def default_guidance_options() -> GuidanceOptions:
+    o = GuidanceOptions()
+    lib().sfm_guidance_default_options(ctypes.byref(o))
+    return o
+
+
 def device_count() -> int:
     return int(lib().sfm_device_count())
 
 
-__all__ = ["lib", "check", "ptr", "BAOptions", "BASummary", "BAIteration", "KLTParams", "GFTTParams", "TwoViewOptions", "CameraStruct", "SfmError",
+__all__ = ["lib", "check", "ptr", "BAOptions", "BASummary", "BAIteration", "KLTParams", "GFTTParams", "TwoViewOptions", "CameraStruct", "GuidanceOptions", "GuidanceResult",
+           "default_guidance_options", "SfmError",
            "default_options", "default_klt_params", "default_gftt_params", "default_two_view_options",
            "device_count", "exported_symbols", "LIB_PATH", "c_uint8"]

@@ -51,6 +51,7 @@
 #include <string>
 #include <vector>
 #include "sfm_trace.h"
+#include "map_internal.h"
 #include "../../include/sfm_amd.h"
 
 void sfm_internal_set_error(const std::string& msg);  // ba_solver.hip
@@ -1542,5 +1543,11 @@ const double* map_points_dev(sfm_map* h, int32_t* n_pts, int* device) {
   *n_pts = h->n_pts;
   *device = h->device;
   return h->X.p;
+}
+
+// The points and live flags where they are (map_internal.h): no copy and no
+// synchronisation; the reader orders its stream after `stream` with an event.
+MapPointsView map_points_view(sfm_map* h) {
+  return MapPointsView{h->X.p, h->pt_live.p, h->n_pts, h->n_live, h->device, h->s};
 }
 }  // namespace sfm

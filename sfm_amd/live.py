@@ -266,9 +266,12 @@ def _filter_matches(K, f0, f1, uv0, uv1, X, max_err):
 class LiveSfM:
     def __init__(self, stream: KeypointStream | None = None, device: int = 0, init_gap: int = 5,
                  init: str = "known", init_options: dict | None = None, cull: bool = False,
-                 cull_kf_rate: float = 0.9, min_visibility: int = 3, camera=None):
+                 cull_kf_rate: float = 0.9, min_visibility: int = 3, camera=None, guidance: bool = False,
+                 guidance_options: dict | None = None):
         if init not in ("known", "estimate"):
             raise ValueError(f"init must be 'known' or 'estimate', not {init!r}")
+        if guidance and camera is None:
+            raise ValueError("guidance needs a camera (it reads the colour frame: process_image)")
         self.init = init
         self.init_options = dict(init_options or {})
         self.init_log: list[dict] = []   # init="estimate": one entry per attempt
@@ -301,6 +304,16 @@ class LiveSfM:
             self.stats.update({"culled_points": 0, "culled_keyframes": 0})
         self.times = {"stream": 0.0, "track": 0.0, "map_match": 0.0, "mapping": 0.0, "ba": 0.0}
         self._pending: _Frame | None = None
+        # CScanGuidance (CSfM.cpp:80-81): after every RUNNING frame's tracking
+        # and mapping, on the map's live points, read on the device
+        self._guidance = None
+        self.guidance = None                 # the latest GuidanceFrame
+        self.guidance_log: list = []         # one per call
+        self._prev_img = None                # _prevFrame.getFrame() (kept by reference, as a cv::Mat would be)
+        if guidance:
+            from .guidance import ScanGuidance
+            self._guidance = ScanGuidance(camera.width, camera.height, device=device, **(guidance_options or {}))
+            self.times["guidance"] = 0.0
         # the fused device calls (SFM_LIVE_COMPOSED=1: the composed calls,
         # for A/B timing; the tests compare both forms)
         composed = os.environ.get("SFM_LIVE_COMPOSED") == "1"
@@ -336,12 +349,32 @@ class LiveSfM:
             th = getattr(self.stream, "threshold", 60)
             oc = getattr(self.stream, "octaves", 6)
             self._front = FrameFrontEnd(self.camera, matcher=self.matcher, threshold=th, octaves=oc)
+        if self._guidance is not None and np.ndim(img) != 3:
+            raise ValueError("guidance needs the colour frame: img must be [h][w][3]")
+        running = len(self.kfs) >= 2            # CSfM's RUNNING state at entry
         kps, _, desc, pts = self._front.detect(img)
         self._installed = True
         try:
             self._process(k, pts, desc, kps[:, :2].astype(np.float64))
         finally:
             self._installed = False
+        if self._guidance is not None:
+            self._guide(k, img, running)
+
+    def _guide(self, k: int, img, running: bool) -> None:
+        """_guidance.calculateMask(_prevFrame.getFrame(), mapPts, Kopt, P of
+        _prevFrame) (CSfM.cpp:80-81): on a lost frame _prevFrame, and so the
+        image, is the earlier frame's."""
+        if self.prev is not None and self.prev.no == k:
+            self._prev_img = img
+        if not running:
+            return
+        if self._prev_img is None:
+            raise ValueError("guidance needs every frame through process_image (the previous frame has no image)")
+        t0 = time.perf_counter()
+        self.guidance = self._guidance.update(self._prev_img, _R(self.prev.rot), self.prev.t, self.K, map=self.map)
+        self.guidance_log.append(self.guidance)
+        self.times["guidance"] += time.perf_counter() - t0
 
     def _push_current(self, pts, desc, ptsd) -> None:
         """sfm_matcher_push_frame of the frame being processed, unless
@@ -645,5 +678,7 @@ class LiveSfM:
         self.map.setPointsAtIdx(order, X)
 
     def close(self) -> None:
+        if self._guidance is not None:
+            self._guidance.close()
         self.matcher.close()
         self.map.close()
