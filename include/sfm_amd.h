@@ -266,6 +266,38 @@ int sfm_matcher_match_keyframes(sfm_matcher* h, int32_t q_slot, const int32_t* q
                                 int32_t t_slot, const int32_t* t_idx, int32_t n_t, double ratio_test,
                                 double min_distance, double max_distance, int32_t* idx0, int32_t* idx1,
                                 int32_t* n_matches);
+/* CSfM::mapping's point creation for one keyframe pair (CSfM.cpp:138-176) in
+ * one call on the stored keyframe rows: matchFeatures of the older keyframe's
+ * unmatched rows idx0[n0] (slot0) against the new keyframe's idx1[n1] (slot1)
+ * as sfm_matcher_match_keyframes does it (CSfM.cpp:141-147),
+ * GeometryUtils::triangulatePoints on P_i = K_i [R_i|t_i] (CSfM.cpp:156, the
+ * arithmetic of sfm_triangulate_points) and GeometryUtils::
+ * calculateFundamentalMatrix + filterMatches (CSfM.cpp:164-165, as
+ * sfm_filter_matches below states it).  K9 / R9 row-major, t3; K upper
+ * triangular with K[8] = 1.  Out: the kept matches in the matcher's order,
+ * m0 / m1 [capacity] subset-local (into idx0 / idx1) and X [capacity][3],
+ * *n_kept of them; *n_matched = the matches before the filter.  One staged
+ * upload, one download, one host synchronisation.  n0 == 0 or n1 < 2: no
+ * matches.  When the kept count exceeds capacity, *n_kept is set, nothing
+ * else is written and SFM_EINVAL is returned (capacity min(n0, n1) always
+ * fits).  Every argument is checked before the first device call. */
+int sfm_matcher_pair_points(sfm_matcher* h, int32_t slot0, const int32_t* idx0, int32_t n0, int32_t slot1,
+                            const int32_t* idx1, int32_t n1, double ratio_test, double min_distance,
+                            double max_distance, const double* K9_0, const double* R9_0, const double* t3_0,
+                            const double* K9_1, const double* R9_1, const double* t3_1, double max_err,
+                            int32_t capacity, int32_t* m0, int32_t* m1, double* X, int32_t* n_kept,
+                            int32_t* n_matched);
+/* The re-finding of new map points in one keyframe in between
+ * (CSfM.cpp:191-221): sfm_matcher_match_keyframes(q_slot, q_idx, n_q, q_pts,
+ * t_slot, ...) with q_pts = the projections of X [n_q][3] through (K9, R9,
+ * t3) (GeometryUtils::projectPoints with zero distortion, CSfM.cpp:199-206),
+ * projected on the device: uv = ((R X + t)_xy / (R X + t)_z) (fx, fy) + (cx,
+ * cy).  q_idx must not repeat.  Subset-local indices out, capacity >=
+ * min(n_q, n_t).  One upload, one host synchronisation. */
+int sfm_matcher_refind_points(sfm_matcher* h, int32_t q_slot, const int32_t* q_idx, int32_t n_q, const double* X,
+                              const double* K9, const double* R9, const double* t3, int32_t t_slot,
+                              const int32_t* t_idx, int32_t n_t, double ratio_test, double min_distance,
+                              double max_distance, int32_t* idx0, int32_t* idx1, int32_t* n_matches);
 /* bool CTracker::matchFeatures() (CTracker.cpp:419-477): the two whole
  * frames, DISTORTED positions when distorted != 0 (CTracker.cpp:429-430);
  * fills _prevIdx/_currIdx; the reference's bool is n >= _minFeatures. */
@@ -312,6 +344,15 @@ int sfm_map_add_point_matches(sfm_map* h, int32_t n, const int32_t* pts3d_idx, c
                               int32_t frame_no);
 /* CMap::addDescriptors (CMap.cpp:308-315): one row [desc_bytes] per point. */
 int sfm_map_add_descriptors(sfm_map* h, int32_t n, const int32_t* pts3d_idx, const uint8_t* desc);
+/* A keyframe's matched rows into the map (CSfM.cpp:174-176, 214-221, 595-619):
+ * addPointMatches(pts3d_idx, rows, frame_no) when with_observations != 0,
+ * then addDescriptors(pts3d_idx, the descriptor rows rows[n] of keyframe
+ * `slot` of the matcher's keyframe store), the words copied device to device.
+ * The store ends up exactly as after those two calls; one host
+ * synchronisation.  The map and the matcher must share device and descriptor
+ * width; the points must be live and the rows stored. */
+int sfm_map_add_keyframe_rows(sfm_map* h, sfm_matcher* mt, int32_t slot, int32_t frame_no, int32_t n,
+                              const int32_t* pts3d_idx, const int32_t* rows, int32_t with_observations);
 /* CMap::getPointsAtIdx (CMap.cpp:134-143) and its inverse (BA write-back). */
 int sfm_map_get_points(sfm_map* h, int32_t n, const int32_t* pts3d_idx, double* pts3d);
 int sfm_map_set_points(sfm_map* h, int32_t n, const int32_t* pts3d_idx, const double* pts3d);
@@ -475,6 +516,21 @@ int sfm_pnp_ransac(int32_t device, int32_t n, const double* obj, const double* i
  * [n_cams][12] row-major 3x4 projection matrices; X [n][3] out. */
 int sfm_triangulate_points(int32_t device, int32_t n, const int32_t* cam0, const int32_t* cam1, const double* uv0,
                            const double* uv1, int32_t n_cams, const double* P, double* X);
+/* GeometryUtils::calculateFundamentalMatrix + filterMatches as CSfM::mapping
+ * calls them (CSfM.cpp:164-165) on host arrays: match i seen at uv0[i] in
+ * keyframe 0 and uv1[i] in keyframe 1, triangulated to X[i].  status[i] = 1
+ * iff X[i] is finite, its depth (R_i X + t_i)_z is positive in both
+ * keyframes, and the point-to-epipolar-line distances d1 = |l1.h1| /
+ * sqrt(l1x^2 + l1y^2), l1 = F h0, and d0 likewise with l0 = F^T h1, are both
+ * <= max_err, where F = K1^-T [t]x R K0^-1, R = R1 R0^T, t = t1 - R t0 (K
+ * upper triangular with K[8] = 1; F9 (optional) receives F row-major).  Two
+ * equal poses give F = 0 and keep nothing.  GeometryUtils is absent from the
+ * reference tree: this is the build's reading of the call site, PARITY
+ * UNPINNED; pinned bit for bit to tests/map_points_ref.py.  The same kernel
+ * body and host composition as sfm_matcher_pair_points. */
+int sfm_filter_matches(int32_t device, int32_t n, const double* uv0, const double* uv1, const double* X,
+                       const double* K9_0, const double* R9_0, const double* t3_0, const double* K9_1,
+                       const double* R9_1, const double* t3_1, double max_err, uint8_t* status, double* F9);
 
 /* Two-view map initialisation: steps 2-5 of CSfM::init (CSfM.cpp:842-946)
  * on the matches of the first keyframe and a later frame, in one synchronous

@@ -248,6 +248,17 @@ _SIGNATURES = {
     "sfm_matcher_match_keyframes": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
                                             c_int32, c_double, c_double, c_double, c_void_p, c_void_p,
                                             POINTER(c_int32)]),
+    "sfm_matcher_pair_points": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_double,
+                                        c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_double, c_int32, c_void_p, c_void_p, c_void_p, POINTER(c_int32),
+                                        POINTER(c_int32)]),
+    "sfm_matcher_refind_points": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_int32, c_void_p, c_int32, c_double, c_double, c_double,
+                                          c_void_p, c_void_p, POINTER(c_int32)]),
+    "sfm_filter_matches": (c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
+    "sfm_map_add_keyframe_rows": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                          c_int32]),
     "sfm_track_pnp": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_double, c_double, c_double, c_int32,
                               c_void_p, c_int32, c_double, c_double, c_void_p, c_void_p, POINTER(c_int32),
                               POINTER(c_int32), c_int32, c_void_p, c_void_p, POINTER(c_int32)]),

@@ -111,6 +111,18 @@ class DeviceMap:
         d = np.ascontiguousarray(np.asarray(descriptors, np.uint8).reshape(len(a), self.desc_bytes))
         check(lib().sfm_map_add_descriptors(self._h, len(a), ptr(a), ptr(d)), "sfm_map_add_descriptors")
 
+    def addKeyframeRows(self, matcher, slot: int, frameNo: int, pts3DIdx, rows, with_observations: bool = True) -> None:
+        """addPointMatches(pts3DIdx, rows, frameNo) (with_observations) then
+        addDescriptors(pts3DIdx, the descriptor rows `rows` of keyframe `slot`
+        of `matcher`'s keyframe store), the descriptors copied on the device
+        (sfm_map_add_keyframe_rows)."""
+        a = np.ascontiguousarray(np.asarray(pts3DIdx, np.int32).reshape(-1))
+        b = np.ascontiguousarray(np.asarray(rows, np.int32).reshape(-1))
+        if len(a) != len(b):
+            raise ValueError("one keyframe row per point")
+        check(lib().sfm_map_add_keyframe_rows(self._h, matcher._h, int(slot), int(frameNo), len(a), ptr(a), ptr(b),
+                                              1 if with_observations else 0), "sfm_map_add_keyframe_rows")
+
     def getPointsAtIdx(self, pts3DIdx) -> np.ndarray:
         a = np.ascontiguousarray(np.asarray(pts3DIdx, np.int32).reshape(-1))
         X = np.zeros((max(1, len(a)), 3))

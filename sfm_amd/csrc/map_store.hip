@@ -52,6 +52,7 @@
 #include <vector>
 #include "sfm_trace.h"
 #include "map_internal.h"
+#include "mappoint_internal.h"
 #include "../../include/sfm_amd.h"
 
 void sfm_internal_set_error(const std::string& msg);  // ba_solver.hip
@@ -521,6 +522,7 @@ int matcher_match_current_dev(sfm_matcher* h, hipEvent_t after, const uint64_t* 
 int matcher_current_n(const sfm_matcher* h);
 int matcher_words(const sfm_matcher* h);
 int matcher_device(const sfm_matcher* h);
+int matcher_keyframe_rows(sfm_matcher* h, int32_t slot, const uint64_t** desc, int* n, hipEvent_t* ready);
 }  // namespace sfm
 
 using namespace sfm;
@@ -985,6 +987,64 @@ int sfm_map_add_descriptors(sfm_map* h, int32_t n, const int32_t* pts3d_idx, con
   std::memcpy(words.data(), desc, size_t(n) * h->desc_bytes);
   if (int rc = append(h, h->desc, words.data(), int64_t(n) * h->W)) return rc;
   if (int rc = append(h, h->desc_pt, pts3d_idx, n)) return rc;
+  h->dcsr = false;
+  return sync(h);
+}
+
+// addPointMatches(pts3d_idx, rows, frame_no) (with_observations != 0) then
+// addDescriptors(pts3d_idx, descriptor rows `rows` of the matcher's keyframe
+// `slot`): the two lists go up once, the descriptor words are copied from the
+// matcher's keyframe store on the device, one synchronisation.
+int sfm_map_add_keyframe_rows(sfm_map* h, sfm_matcher* mt, int32_t slot, int32_t frame_no, int32_t n,
+                              const int32_t* pts3d_idx, const int32_t* rows, int32_t with_observations) {
+  SFM_TRACE("sfm_map_add_keyframe_rows");
+  if (!h || !mt) return mapfail(SFM_EINVAL, "NULL handle");
+  if (n < 0) return mapfail(SFM_EINVAL, "negative size");
+  if (n && (!pts3d_idx || !rows)) return mapfail(SFM_EINVAL, "NULL argument");
+  if (matcher_words(mt) != h->W || matcher_device(mt) != h->device)
+    return mapfail(SFM_EINVAL, "the map and the matcher differ in descriptor width or device");
+  if (int rc = check_live(h, n, pts3d_idx)) return rc;
+  if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
+  const uint64_t* kdesc = nullptr;
+  int kn = 0;
+  hipEvent_t ready = nullptr;
+  if (int rc = matcher_keyframe_rows(mt, slot, &kdesc, &kn, &ready)) return rc;
+  for (int32_t i = 0; i < n; ++i)
+    if (rows[i] < 0 || rows[i] >= kn)
+      return mapfail(SFM_EINVAL, "keyframe row " + std::to_string(rows[i]) + " out of range at " + std::to_string(i));
+  if (n == 0) return 0;
+  int rc = 0;
+  auto* up = static_cast<int32_t*>(scratch(h, "kfrows", sizeof(int32_t) * 2 * size_t(n), &rc));
+  int32_t* pin = pin_reserve(h, 2 * size_t(n), &rc);
+  if (rc) return rc;
+  const int64_t no = with_observations ? n : 0;
+  if ((rc = grow(h, h->ob_pt, h->ob_pt.n + no)) || (rc = grow(h, h->ob_frame, h->ob_frame.n + no)) ||
+      (rc = grow(h, h->ob_idx, h->ob_idx.n + no)) || (rc = grow(h, h->ob_mm, h->ob_mm.n + no)) ||
+      (rc = grow(h, h->desc, h->desc.n + int64_t(n) * h->W)) || (rc = grow(h, h->desc_pt, h->desc_pt.n + n)))
+    return rc;
+  // the keyframe's rows are the matcher's upload: ordered after its stream
+  if (hipStreamWaitEvent(h->s, ready, 0) != hipSuccess) return mapfail(SFM_EIO, "stream wait failed");
+  (void)hipStreamSynchronize(h->s);  // (the pinned block may feed an earlier copy)
+  std::memcpy(pin, pts3d_idx, sizeof(int32_t) * size_t(n));
+  std::memcpy(pin + n, rows, sizeof(int32_t) * size_t(n));
+  (void)hipMemcpyAsync(up, pin, sizeof(int32_t) * 2 * size_t(n), hipMemcpyHostToDevice, h->s);
+  const size_t nb = sizeof(int32_t) * size_t(n);
+  if (with_observations) {
+    (void)hipMemcpyAsync(h->ob_pt.p + h->ob_pt.n, up, nb, hipMemcpyDeviceToDevice, h->s);
+    (void)hipMemcpyAsync(h->ob_idx.p + h->ob_idx.n, up + n, nb, hipMemcpyDeviceToDevice, h->s);
+    k_fill_i32<<<grid(n), 256, 0, h->s>>>(n, h->ob_frame.p + h->ob_frame.n, frame_no);
+    (void)hipMemsetAsync(h->ob_mm.p + h->ob_mm.n, 1, size_t(n), h->s);
+    k_add_views<<<grid(n), 256, 0, h->s>>>(n, up, h->pt_views.p);  // _ptsViews[idx]++
+    h->ob_pt.n += n;
+    h->ob_frame.n += n;
+    h->ob_idx.n += n;
+    h->ob_mm.n += n;
+    h->ocsr = false;
+  }
+  launch_copy_desc_rows(h->s, n, up + n, kdesc, h->W, h->desc.p + h->desc.n);
+  (void)hipMemcpyAsync(h->desc_pt.p + h->desc_pt.n, up, nb, hipMemcpyDeviceToDevice, h->s);
+  h->desc.n += int64_t(n) * h->W;
+  h->desc_pt.n += n;
   h->dcsr = false;
   return sync(h);
 }

@@ -39,6 +39,7 @@
 #include "../../include/sfm_amd.h"
 #include "ordered_compact.h"
 #include "frame_internal.h"
+#include "mappoint_internal.h"
 
 void sfm_internal_set_error(const std::string& msg);  // ba_solver.hip
 
@@ -252,6 +253,7 @@ struct sfm_matcher {
   int n_cu = 256;
   hipStream_t stream = nullptr;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  hipEvent_t ev_rows = nullptr;  // matcher_keyframe_rows: the keyframe store's uploads are done
   MatchFrame frame[2];        // [prev, curr] after the swap
   int cur = 1;                // index of the current frame in frame[]
   int frames_pushed = 0;
@@ -434,6 +436,20 @@ int matcher_words(const sfm_matcher* h) { return h->W; }
 int matcher_device(const sfm_matcher* h) { return h->device; }
 int matcher_desc_bytes(const sfm_matcher* h) { return h->desc_bytes; }
 
+// For sfm_map_add_keyframe_rows (map_store.hip): the descriptor words of
+// keyframe `slot` ([*n][matcher_words]) and an event after which they are
+// complete (the store's upload runs on the matcher's stream).
+int matcher_keyframe_rows(sfm_matcher* h, int32_t slot, const uint64_t** desc, int* n, hipEvent_t* ready) {
+  if (slot < 0 || size_t(slot) >= h->kf.size()) return mfail(SFM_EINVAL, "keyframe slot not stored");
+  if (!h->ev_rows && hipEventCreateWithFlags(&h->ev_rows, hipEventDisableTiming) != hipSuccess)
+    return mfail(SFM_EIO, "hipEventCreate failed");
+  if (hipEventRecord(h->ev_rows, h->stream) != hipSuccess) return mfail(SFM_EIO, "hipEventRecord failed");
+  *desc = h->kf[size_t(slot)].desc;
+  *n = h->kf[size_t(slot)].n;
+  *ready = h->ev_rows;
+  return 0;
+}
+
 // For sfm_frame_detect (frame_kernels.hip): sfm_matcher_push_frame in two
 // halves around a device-side fill.  begin sizes the slot push_frame would
 // overwrite (the previous frame's: call it only once the new frame is known
@@ -508,6 +524,7 @@ int sfm_matcher_destroy(sfm_matcher* h) {
   for (auto& kv : h->dev) hipFree(kv.second.first);
   for (auto& kv : h->pin) hipHostFree(kv.second.first);
   for (auto e : h->ev) hipEventDestroy(e);
+  if (h->ev_rows) hipEventDestroy(h->ev_rows);
   hipStreamDestroy(h->stream);
   delete h;
   return 0;
@@ -745,6 +762,129 @@ int sfm_matcher_match_keyframes(sfm_matcher* h, int32_t q_slot, const int32_t* q
   return 0;
 }
 
+// CSfM::mapping's point creation for one keyframe pair (CSfM.cpp:138-176):
+// the member-window match of the two keyframes' unmatched rows, the
+// triangulation and the filter (mappoint_kernels.hip) as one stream of
+// launches on the resident rows -- one staged upload (the index lists; the
+// matrices go as kernel arguments), one download, one synchronisation.
+int sfm_matcher_pair_points(sfm_matcher* h, int32_t slot0, const int32_t* idx0, int32_t n0, int32_t slot1,
+                            const int32_t* idx1, int32_t n1, double ratio_test, double min_distance,
+                            double max_distance, const double* K9_0, const double* R9_0, const double* t3_0,
+                            const double* K9_1, const double* R9_1, const double* t3_1, double max_err,
+                            int32_t capacity, int32_t* m0, int32_t* m1, double* X, int32_t* n_kept,
+                            int32_t* n_matched) {
+  SFM_TRACE("sfm_matcher_pair_points");
+  if (!h || !n_kept || !n_matched || !m0 || !m1 || !X) return mfail(SFM_EINVAL, "NULL argument");
+  *n_kept = 0;
+  *n_matched = 0;
+  if (!K9_0 || !R9_0 || !t3_0 || !K9_1 || !R9_1 || !t3_1) return mfail(SFM_EINVAL, "NULL matrix");
+  if (slot0 < 0 || slot1 < 0 || size_t(slot0) >= h->kf.size() || size_t(slot1) >= h->kf.size())
+    return mfail(SFM_EINVAL, "keyframe slot not stored");
+  if (n0 < 0 || n1 < 0 || capacity < 0 || (n0 && !idx0) || (n1 && !idx1)) return mfail(SFM_EINVAL, "bad index lists");
+  if (!ok_ratio_window(ratio_test, min_distance, max_distance) || !std::isfinite(max_err))
+    return mfail(SFM_EINVAL, "non-finite threshold");
+  sfm::PairArgs pa;
+  if (!sfm::compose_pair(K9_0, R9_0, t3_0, K9_1, R9_1, t3_1, max_err, &pa))
+    return mfail(SFM_EINVAL, "K must be finite and upper triangular with K[8] = 1, R and t finite");
+  const MatchFrame& f0 = h->kf[size_t(slot0)];
+  const MatchFrame& f1 = h->kf[size_t(slot1)];
+  for (int32_t i = 0; i < n0; ++i)
+    if (idx0[i] < 0 || idx0[i] >= f0.n) return mfail(SFM_EINVAL, "row index out of range (older keyframe)");
+  for (int32_t i = 0; i < n1; ++i)
+    if (idx1[i] < 0 || idx1[i] >= f1.n) return mfail(SFM_EINVAL, "row index out of range (new keyframe)");
+  if (n0 == 0 || n1 < 2) return 0;  // reference UB with < 2 train rows: no matches
+  if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
+  int rc = 0;
+  // result block: head (kept, matched, pad x2) | m0 [n0] | m1 [n0] | X [n0][3]
+  const size_t ni = 4 + 2 * size_t(n0);
+  const size_t blk = ni / 2 + 3 * size_t(n0);  // in doubles
+  int* ix = pbuf<int>(h, "ppidx", size_t(n0) + n1, &rc);
+  int* dix = dbuf<int>(h, "dppidx", size_t(n0) + n1, &rc);
+  double* dXall = dbuf<double>(h, "ppX", 3 * size_t(n0), &rc);
+  int* dks = dbuf<int>(h, "ppks", 2 * size_t(n0), &rc);
+  double* dblk = dbuf<double>(h, "ppblk", blk, &rc);
+  double* hblk = pbuf<double>(h, "ppblkh", blk, &rc);
+  if (rc) return rc;
+  hipStreamSynchronize(h->stream);  // (the pinned stage may feed an earlier copy)
+  std::memcpy(ix, idx0, sizeof(int) * size_t(n0));
+  std::memcpy(ix + n0, idx1, sizeof(int) * size_t(n1));
+  hipMemcpyAsync(dix, ix, sizeof(int) * (size_t(n0) + n1), hipMemcpyHostToDevice, h->stream);
+  int* out = nullptr;
+  if ((rc = run_match_async(h, f0.desc, dix, f0.pts, n0, f1.desc, dix + n0, f1.pts, n1, ratio_test, min_distance,
+                            max_distance, &out)))
+    return rc;
+  int* dhead = reinterpret_cast<int*>(dblk);
+  sfm::launch_pair_points(h->stream, out, n0, dix, dix + n0, f0.pts, f1.pts, pa, dXall, dks, dks + n0, dhead,
+                          dhead + 4, dhead + 4 + n0, dblk + ni / 2);
+  hipMemcpyAsync(hblk, dblk, sizeof(double) * blk, hipMemcpyDeviceToHost, h->stream);
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return mfail(SFM_EIO, "point-creation kernels failed");
+  const int* hh = reinterpret_cast<const int*>(hblk);
+  const int kept = hh[0];
+  *n_kept = kept;
+  if (kept > capacity)
+    return mfail(SFM_EINVAL, "capacity " + std::to_string(capacity) + " < " + std::to_string(kept) + " kept matches");
+  *n_matched = hh[1];
+  std::memcpy(m0, hh + 4, sizeof(int) * size_t(kept));
+  std::memcpy(m1, hh + 4 + n0, sizeof(int) * size_t(kept));
+  std::memcpy(X, hblk + ni / 2, sizeof(double) * 3 * size_t(kept));
+  return 0;
+}
+
+// The re-finding of new points in one keyframe in between (CSfM.cpp:191-221):
+// sfm_matcher_match_keyframes with q_pts = the projections of X, projected on
+// the device (k_project_rows) -- one upload, one synchronisation.
+int sfm_matcher_refind_points(sfm_matcher* h, int32_t q_slot, const int32_t* q_idx, int32_t n_q, const double* X,
+                              const double* K9, const double* R9, const double* t3, int32_t t_slot,
+                              const int32_t* t_idx, int32_t n_t, double ratio_test, double min_distance,
+                              double max_distance, int32_t* idx0, int32_t* idx1, int32_t* n_matches) {
+  SFM_TRACE("sfm_matcher_refind_points");
+  if (!h || !n_matches || !idx0 || !idx1) return mfail(SFM_EINVAL, "NULL argument");
+  *n_matches = 0;
+  if (!K9 || !R9 || !t3) return mfail(SFM_EINVAL, "NULL matrix");
+  if (q_slot < 0 || t_slot < 0 || size_t(q_slot) >= h->kf.size() || size_t(t_slot) >= h->kf.size())
+    return mfail(SFM_EINVAL, "keyframe slot not stored");
+  if (n_q < 0 || n_t < 0 || (n_q && (!q_idx || !X)) || (n_t && !t_idx)) return mfail(SFM_EINVAL, "bad index lists");
+  if (!ok_ratio_window(ratio_test, min_distance, max_distance)) return mfail(SFM_EINVAL, "non-finite threshold");
+  for (int i = 0; i < 9; ++i)
+    if (!std::isfinite(K9[i]) || !std::isfinite(R9[i])) return mfail(SFM_EINVAL, "non-finite matrix");
+  for (int i = 0; i < 3; ++i)
+    if (!std::isfinite(t3[i])) return mfail(SFM_EINVAL, "non-finite matrix");
+  const MatchFrame& fq = h->kf[size_t(q_slot)];
+  const MatchFrame& ft = h->kf[size_t(t_slot)];
+  std::vector<char> seen(size_t(fq.n), 0);
+  for (int32_t i = 0; i < n_q; ++i) {
+    if (q_idx[i] < 0 || q_idx[i] >= fq.n) return mfail(SFM_EINVAL, "query index out of range");
+    if (seen[size_t(q_idx[i])]) return mfail(SFM_EINVAL, "query index repeated");
+    seen[size_t(q_idx[i])] = 1;
+  }
+  for (int32_t i = 0; i < n_t; ++i)
+    if (t_idx[i] < 0 || t_idx[i] >= ft.n) return mfail(SFM_EINVAL, "train index out of range");
+  if (n_q == 0 || n_t < 2) return 0;  // reference UB with < 2 train rows: no matches
+  if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
+  int rc = 0;
+  // stage: q_idx | t_idx | (8-B aligned) X
+  const size_t ni = (size_t(n_q) + n_t + 1) & ~size_t(1);
+  auto* st = pbuf<int>(h, "rfidx", ni + 6 * size_t(n_q), &rc);
+  auto* d = dbuf<int>(h, "drfidx", ni + 6 * size_t(n_q), &rc);
+  double* duv = dbuf<double>(h, "rfuv", 2 * size_t(fq.n), &rc);
+  if (rc) return rc;
+  hipStreamSynchronize(h->stream);
+  std::memcpy(st, q_idx, sizeof(int) * size_t(n_q));
+  std::memcpy(st + n_q, t_idx, sizeof(int) * size_t(n_t));
+  std::memcpy(st + ni, X, sizeof(double) * 3 * size_t(n_q));
+  hipMemcpyAsync(d, st, sizeof(int) * (ni + 6 * size_t(n_q)), hipMemcpyHostToDevice, h->stream);
+  sfm::launch_project_rows(h->stream, n_q, d, reinterpret_cast<const double*>(d + ni), R9, t3, K9, duv);
+  int* res = nullptr;
+  if ((rc = run_match(h, fq.desc, d, duv, n_q, ft.desc, d + n_q, ft.pts, n_t, ratio_test, min_distance, max_distance,
+                      &res)))
+    return rc;
+  const int m = res[2 * n_q];
+  std::memcpy(idx0, res, sizeof(int) * size_t(m));
+  std::memcpy(idx1, res + n_q, sizeof(int) * size_t(m));
+  *n_matches = m;
+  return 0;
+}
+
 int sfm_matcher_knn2(sfm_matcher* h, const uint8_t* desc0, int32_t n0, const uint8_t* desc1, int32_t n1,
                      int32_t* best_idx, int32_t* best_dist, int32_t* second_idx, int32_t* second_dist) {
   if (!h) return mfail(SFM_EINVAL, "handle is NULL");
@@ -820,6 +960,43 @@ int sfm_match_features(int32_t device, const double* pts0, const uint8_t* desc0,
   if (!h) return rc;
   return sfm_matcher_match(h, pts0, desc0, n0, pts1, desc1, n1, ratio_test, min_distance, max_distance, idx0, idx1,
                            n_matches);
+}
+
+// GeometryUtils::calculateFundamentalMatrix + filterMatches (CSfM.cpp:164-165)
+// on host arrays: the kernel body and the host composition of
+// sfm_matcher_pair_points (mappoint_kernels.hip), through the cached handle's
+// stream and pools.
+int sfm_filter_matches(int32_t device, int32_t n, const double* uv0, const double* uv1, const double* X,
+                       const double* K9_0, const double* R9_0, const double* t3_0, const double* K9_1,
+                       const double* R9_1, const double* t3_1, double max_err, uint8_t* status, double* F9) {
+  if (n < 0) return mfail(SFM_EINVAL, "negative size");
+  if (!K9_0 || !R9_0 || !t3_0 || !K9_1 || !R9_1 || !t3_1) return mfail(SFM_EINVAL, "NULL matrix");
+  if (n && (!uv0 || !uv1 || !X || !status)) return mfail(SFM_EINVAL, "NULL argument");
+  if (!std::isfinite(max_err)) return mfail(SFM_EINVAL, "non-finite threshold");
+  sfm::PairArgs pa;
+  if (!sfm::compose_pair(K9_0, R9_0, t3_0, K9_1, R9_1, t3_1, max_err, &pa))
+    return mfail(SFM_EINVAL, "K must be finite and upper triangular with K[8] = 1, R and t finite");
+  if (F9) std::memcpy(F9, pa.F, sizeof(pa.F));
+  if (n == 0) return 0;
+  int rc = 0;
+  sfm_matcher* h = cached_matcher(device, 64, &rc);
+  if (!h) return rc;
+  if (hipSetDevice(device) != hipSuccess) return mfail(SFM_ENODEV, "hipSetDevice failed");
+  double* st = pbuf<double>(h, "fin", 7 * size_t(n), &rc);
+  double* d = dbuf<double>(h, "dfin", 7 * size_t(n), &rc);
+  uint8_t* ds = dbuf<uint8_t>(h, "fst", size_t(n), &rc);
+  uint8_t* hs = pbuf<uint8_t>(h, "fsth", size_t(n), &rc);
+  if (rc) return rc;
+  hipStreamSynchronize(h->stream);
+  std::memcpy(st, uv0, sizeof(double) * 2 * size_t(n));
+  std::memcpy(st + 2 * size_t(n), uv1, sizeof(double) * 2 * size_t(n));
+  std::memcpy(st + 4 * size_t(n), X, sizeof(double) * 3 * size_t(n));
+  hipMemcpyAsync(d, st, sizeof(double) * 7 * size_t(n), hipMemcpyHostToDevice, h->stream);
+  sfm::launch_filter(h->stream, n, d, d + 2 * size_t(n), d + 4 * size_t(n), pa, ds);
+  hipMemcpyAsync(hs, ds, size_t(n), hipMemcpyDeviceToHost, h->stream);
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return mfail(SFM_EIO, "filter kernel failed");
+  std::memcpy(status, hs, size_t(n));
+  return 0;
 }
 
 int sfm_representative_descriptors(int32_t device, const uint8_t* desc, const int32_t* row_off, int32_t n_pts,

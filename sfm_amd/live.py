@@ -40,6 +40,17 @@ in the reference tree, so filterMatches is restated from its call site
 (CSfM.cpp:164-165) as positive depth in both keyframes and the point-to-
 epipolar-line distance <= _maxReprErr both ways.
 
+Point creation on the device (device_mapping=True, off by default): the pair
+loop of CSfM::mapping (CSfM.cpp:138-227) as device calls on the matcher's
+keyframe store -- per older keyframe one sfm_matcher_pair_points (match,
+triangulate, filter; self.map_log keeps every call), per keyframe in between
+one sfm_matcher_refind_points, and the descriptor rows go into the map from
+the keyframe store (sfm_map_add_keyframe_rows; the keyframe insert of
+tracking too).  The same map calls in the same order as the host loop; the
+filter and the projection round in the fixed association of
+tests/map_points_ref.py, the host loop's as numpy's BLAS does, so borderline
+matches may differ between the two.
+
 Culling (cull=True; CSfM.cpp:232-252, 692-752, off by default): between the
 pair loop and the BA, CSfM::cullMapPoints (CMap::removePointsThreshold on
 the device map store, then CFrame::cullPoints on every keyframe, the
@@ -267,7 +278,7 @@ class LiveSfM:
     def __init__(self, stream: KeypointStream | None = None, device: int = 0, init_gap: int = 5,
                  init: str = "known", init_options: dict | None = None, cull: bool = False,
                  cull_kf_rate: float = 0.9, min_visibility: int = 3, camera=None, guidance: bool = False,
-                 guidance_options: dict | None = None):
+                 guidance_options: dict | None = None, device_mapping: bool = False):
         if init not in ("known", "estimate"):
             raise ValueError(f"init must be 'known' or 'estimate', not {init!r}")
         if guidance and camera is None:
@@ -304,6 +315,13 @@ class LiveSfM:
             self.stats.update({"culled_points": 0, "culled_keyframes": 0})
         self.times = {"stream": 0.0, "track": 0.0, "map_match": 0.0, "mapping": 0.0, "ba": 0.0}
         self._pending: _Frame | None = None
+        # CSfM::mapping's point creation as device calls on the resident
+        # keyframe rows (sfm_matcher_pair_points / sfm_matcher_refind_points /
+        # sfm_map_add_keyframe_rows), off by default: the default path's filter
+        # and projection round as numpy's BLAS does, the device's in the fixed
+        # association of tests/map_points_ref.py
+        self.device_mapping = bool(device_mapping)
+        self.map_log: list[dict] = []    # device_mapping: one entry per keyframe-pair call
         # CScanGuidance (CSfM.cpp:80-81): after every RUNNING frame's tracking
         # and mapping, on the map's live points, read on the device
         self._guidance = None
@@ -480,8 +498,11 @@ class LiveSfM:
             self.kfs.append(kf)
             self._store_keyframe(kf)
             m = np.flatnonzero(kf.pt3d >= 0)
-            self.map.addPointMatches(kf.pt3d[m], m, kf.no)
-            self.map.addDescriptors(kf.pt3d[m], kf.desc[m])
+            if self.device_mapping:     # the descriptors are in the keyframe store already
+                self.map.addKeyframeRows(self.matcher, kf.slot, kf.no, kf.pt3d[m], m)
+            else:
+                self.map.addPointMatches(kf.pt3d[m], m, kf.no)
+                self.map.addDescriptors(kf.pt3d[m], kf.desc[m])
             t2 = time.perf_counter()
             self._cur = cur
             self._mapping()
@@ -575,7 +596,9 @@ class LiveSfM:
         if self.cull:
             self._flush_counters()
         new_kf = self.kfs[-1]
-        for i in range(len(self.kfs) - 1):
+        if self.device_mapping:
+            self._create_points_device(new_kf)
+        for i in range(0 if self.device_mapping else len(self.kfs) - 1):
             kf = self.kfs[i]
             cu = np.flatnonzero(new_kf.pt3d < 0)
             pu = np.flatnonzero(kf.pt3d < 0)
@@ -627,6 +650,48 @@ class LiveSfM:
         self.times["ba"] += time.perf_counter() - t0
         if self.cull:
             self.map.incrementMapAge(0, 1)      # CSfM.cpp:304
+
+    def _create_points_device(self, new_kf: _Frame) -> None:
+        """The pair loop of _mapping (CSfM.cpp:138-227) on the device calls:
+        per older keyframe one sfm_matcher_pair_points (match, triangulate,
+        filter), the new points' descriptor rows from the keyframe store
+        (sfm_map_add_keyframe_rows), per keyframe in between one
+        sfm_matcher_refind_points.  The same map calls in the same order as
+        the host loop."""
+        K, R1 = self.K, _R(new_kf.rot)
+        for i in range(len(self.kfs) - 1):
+            kf = self.kfs[i]
+            cu = np.flatnonzero(new_kf.pt3d < 0).astype(np.int32)
+            pu = np.flatnonzero(kf.pt3d < 0).astype(np.int32)
+            if len(cu) < 2 or len(pu) < 2:
+                continue
+            R0 = _R(kf.rot)
+            m0, m1, Xf, n_matched = self.matcher.pair_points(kf.slot, pu, new_kf.slot, cu, K, R0, kf.t, K, R1,
+                                                             new_kf.t, MAX_REPR_ERR)
+            self.map_log.append({"frame": new_kf.no, "slot0": kf.slot, "slot1": new_kf.slot, "idx0": pu, "idx1": cu,
+                                 "K": np.array(K, np.float64), "R0": R0.copy(), "t0": kf.t.copy(), "R1": R1.copy(),
+                                 "t1": new_kf.t.copy(), "m0": m0, "m1": m1, "X": Xf, "n_matched": n_matched})
+            if not len(m0):
+                continue
+            p2, c2 = pu[m0], cu[m1]
+            idx = self.map.addNewPoints(Xf, p2.reshape(1, -1), [kf.no])
+            kf.pt3d[p2] = idx
+            self.map.addKeyframeRows(self.matcher, kf.slot, kf.no, idx, p2, with_observations=False)
+            # re-find the new points in the keyframes in between (CSfM.cpp:189-221)
+            for j in range(i + 1, len(self.kfs) - 1):
+                kj = self.kfs[j]
+                uj = np.flatnonzero(kj.pt3d < 0).astype(np.int32)
+                if len(uj) < 2:
+                    continue
+                near_kf = abs(kj.no - kf.no) < abs(kj.no - new_kf.no)
+                q0, q1 = self.matcher.refind_points(kf.slot if near_kf else new_kf.slot, p2 if near_kf else c2, Xf, K,
+                                                    _R(kj.rot), kj.t, kj.slot, uj, 0.8, 0.0, MAX_REPR_ERR)
+                if len(q0):
+                    self.map.addKeyframeRows(self.matcher, kj.slot, kj.no, idx[q0], uj[q1])
+                    kj.pt3d[uj[q1]] = idx[q0]
+            self.map.addKeyframeRows(self.matcher, new_kf.slot, new_kf.no, idx, c2)
+            new_kf.pt3d[c2] = idx
+            self.stats["new_points"] += len(idx)
 
     def _bundle_adjust(self) -> None:
         """CSfM::bundleAdjustment over all keyframes (CSfM.cpp:300-348): per

@@ -66,6 +66,29 @@ def triangulate_points(cam0, cam1, uv0, uv1, P, device: int = 0) -> np.ndarray:
     return X[:n].copy()
 
 
+def filter_matches(uv0, uv1, X, K0, R0, t0, K1, R1, t1, max_err: float = 7.0, device: int = 0, return_F: bool = False):
+    """GeometryUtils::calculateFundamentalMatrix + filterMatches as
+    CSfM::mapping calls them (CSfM.cpp:164-165) on the device
+    (sfm_filter_matches): bool [n], True = X finite, positive depth in both
+    keyframes, point-to-epipolar-line distance <= max_err both ways; with
+    return_F also F = K1^-T [t]x R K0^-1."""
+    uv0 = np.ascontiguousarray(np.asarray(uv0, np.float64).reshape(-1, 2))
+    uv1 = np.ascontiguousarray(np.asarray(uv1, np.float64).reshape(-1, 2))
+    X = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1, 3))
+    n = int(uv0.shape[0])
+    if uv1.shape[0] != n or X.shape[0] != n:
+        raise ValueError("uv0, uv1 and X must have one row per match")
+    m9 = [np.ascontiguousarray(np.asarray(m, np.float64).reshape(9)) for m in (K0, R0, K1, R1)]
+    t3 = [np.ascontiguousarray(np.asarray(t, np.float64).reshape(3)) for t in (t0, t1)]
+    status = np.zeros(max(1, n), np.uint8)
+    F = np.zeros(9)
+    check(lib().sfm_filter_matches(device, n, ptr(uv0), ptr(uv1), ptr(X), ptr(m9[0]), ptr(m9[1]), ptr(t3[0]),
+                                   ptr(m9[2]), ptr(m9[3]), ptr(t3[1]), float(max_err), ptr(status), ptr(F)),
+          "sfm_filter_matches")
+    keep = status[:n].astype(bool)
+    return (keep, F.reshape(3, 3)) if return_F else keep
+
+
 def video_gt_pose(video, k: int, depth: float = 10.0):
     """(rvec, t) of frame k of sfm_amd.video.SyntheticVideo relative to frame 0:
     a pinhole camera rolling about its optical axis and translating over the

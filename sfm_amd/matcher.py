@@ -109,6 +109,53 @@ class FeatureMatcher:
                                                 ctypes.byref(nm)), "sfm_matcher_match_keyframes")
         return o0[:nm.value].copy(), o1[:nm.value].copy()
 
+    def pair_points(self, slot0: int, idx0, slot1: int, idx1, K0, R0, t0, K1, R1, t1, max_err: float = 7.0,
+                    ratio=RATIO_TEST, min_distance=MIN_MATCH_DISTANCE, max_distance=MAX_MATCH_DISTANCE,
+                    capacity: int | None = None):
+        """CSfM::mapping's point creation for one keyframe pair in one device
+        call (sfm_matcher_pair_points): match the rows idx0 of slot0 against
+        idx1 of slot1, triangulate on K [R|t], filter (positive depth, epipolar
+        distance <= max_err both ways).  -> (m0, m1, X, n_matched): the kept
+        matches subset-local, in the matcher's order, their points, and the
+        match count before the filter."""
+        a = np.ascontiguousarray(np.asarray(idx0).reshape(-1), dtype=np.int32)
+        b = np.ascontiguousarray(np.asarray(idx1).reshape(-1), dtype=np.int32)
+        m9 = [np.ascontiguousarray(np.asarray(m, np.float64).reshape(9)) for m in (K0, R0, K1, R1)]
+        t3 = [np.ascontiguousarray(np.asarray(t, np.float64).reshape(3)) for t in (t0, t1)]
+        cap = max(1, min(a.size, b.size)) if capacity is None else int(capacity)
+        o0, o1, X = np.zeros(max(1, cap), np.int32), np.zeros(max(1, cap), np.int32), np.zeros((max(1, cap), 3))
+        nk, nm = c_int32(0), c_int32(0)
+        rc = lib().sfm_matcher_pair_points(self._h, int(slot0), ptr(a), a.size, int(slot1), ptr(b), b.size, ratio,
+                                           min_distance, max_distance, ptr(m9[0]), ptr(m9[1]), ptr(t3[0]), ptr(m9[2]),
+                                           ptr(m9[3]), ptr(t3[1]), float(max_err), cap, ptr(o0), ptr(o1), ptr(X),
+                                           ctypes.byref(nk), ctypes.byref(nm))
+        try:
+            check(rc, "sfm_matcher_pair_points")
+        except Exception as e:
+            e.n_kept = nk.value      # (reported when the capacity was too small)
+            raise
+        return o0[:nk.value].copy(), o1[:nk.value].copy(), X[:nk.value].copy(), nm.value
+
+    def refind_points(self, q_slot: int, q_idx, X, K, R, t, t_slot: int, t_idx, ratio=RATIO_TEST,
+                      min_distance=MIN_MATCH_DISTANCE, max_distance=MAX_MATCH_DISTANCE):
+        """match_keyframes(q_slot, q_idx, t_slot, t_idx, q_pts = the
+        projections of X through (K, R, t)), projected on the device
+        (sfm_matcher_refind_points) -> subset-local (query, train) indices."""
+        a = np.ascontiguousarray(np.asarray(q_idx).reshape(-1), dtype=np.int32)
+        b = np.ascontiguousarray(np.asarray(t_idx).reshape(-1), dtype=np.int32)
+        Xc = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1, 3))
+        if Xc.shape[0] != a.size:
+            raise ValueError("one point per query row")
+        K9 = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+        R9 = np.ascontiguousarray(np.asarray(R, np.float64).reshape(9))
+        t3 = np.ascontiguousarray(np.asarray(t, np.float64).reshape(3))
+        cap = max(1, min(a.size, b.size))
+        o0, o1, nm = np.zeros(cap, np.int32), np.zeros(cap, np.int32), c_int32(0)
+        check(lib().sfm_matcher_refind_points(self._h, int(q_slot), ptr(a), a.size, ptr(Xc), ptr(K9), ptr(R9), ptr(t3),
+                                              int(t_slot), ptr(b), b.size, ratio, min_distance, max_distance, ptr(o0),
+                                              ptr(o1), ctypes.byref(nm)), "sfm_matcher_refind_points")
+        return o0[:nm.value].copy(), o1[:nm.value].copy()
+
     def track_pnp(self, device_map, prev_pt3d, K, min_matches: int, iterations: int = 20, reproj_err: float = 7.0,
                   confidence: float = 0.99, ratio=RATIO_TEST, min_distance=MIN_MATCH_DISTANCE,
                   max_distance=MAX_MATCH_DISTANCE):
