@@ -597,6 +597,13 @@ int sfm_two_view_init(int32_t device, int32_t n, const float* pts0, const float*
  * factor+solve; *chol_fail = 1 if a pivot was not positive. */
 int sfm_dense_spd_solve(int32_t device, int32_t n, const double* A, const double* b, double* y, int32_t reps,
                         double* ms, int32_t* chol_fail);
+/* Testing hook: the same solve with the factor taken by column panels of
+ * panel_tiles 64-column tiles, as one rank of the distributed factor
+ * (sfm_ba_set_distributed_factor) runs it: per panel the panel factor, then
+ * its update of every later panel; then the same back substitution.
+ * n >= 128 (at least three tiles with the right-hand side's row). */
+int sfm_dense_spd_solve_panels(int32_t device, int32_t n, const double* A, const double* b, double* y,
+                               int32_t panel_tiles, int32_t* chol_fail);
 /* Measurement plumbing (bench.py, not a reference interface): the best
  * STREAM-copy bandwidth (read + write bytes / s, 16-B accesses) over a few
  * launch shapes, `bytes` per buffer, `reps` timed launches each. */

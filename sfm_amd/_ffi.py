@@ -272,6 +272,7 @@ _SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int32)]),
     "sfm_dense_spd_solve": (c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, POINTER(c_double),
                                     POINTER(c_int32)]),
+    "sfm_dense_spd_solve_panels": (c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, POINTER(c_int32)]),
     "sfm_bench_stream_copy": (c_int, [c_int32, c_int64, c_int32, POINTER(c_double)]),
     "sfm_dist_factor_profile": (c_int, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p]),

@@ -219,3 +219,17 @@ def dense_spd_solve(A, b, device: int = 0, reps: int = 1):
     check(lib().sfm_dense_spd_solve(device, n, ptr(A), ptr(b), ptr(y), reps, ctypes.byref(ms), ctypes.byref(fl)),
           "sfm_dense_spd_solve")
     return y, ms.value, fl.value
+
+
+def dense_spd_solve_panels(A, b, panel_tiles: int, device: int = 0):
+    """Testing hook: dense_spd_solve with the factor taken by column panels of
+    `panel_tiles` tiles (one rank of the distributed factor).  Returns
+    (y, chol_fail)."""
+    A = _f64(A)
+    b = _f64(b)
+    n = int(A.shape[0])
+    y = np.zeros(n)
+    fl = c_int32(0)
+    check(lib().sfm_dense_spd_solve_panels(device, n, ptr(A), ptr(b), ptr(y), int(panel_tiles), ctypes.byref(fl)),
+          "sfm_dense_spd_solve_panels")
+    return y, fl.value

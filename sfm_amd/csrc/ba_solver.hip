@@ -1517,9 +1517,16 @@ int sfm_dist_factor_profile(int32_t device, int32_t n, int32_t nranks, int32_t p
   return 0;
 }
 
-int sfm_dense_spd_solve(int32_t device, int32_t n, const double* A, const double* b, double* y, int32_t reps,
-                        double* ms, int32_t* chol_fail) {
-  if (n <= 0 || !A || !b || !y || reps < 1) return fail(SFM_EINVAL, "bad arguments");
+// sfm_dense_spd_solve (panel_tiles == 0: launch_cholesky) and
+// sfm_dense_spd_solve_panels (panel_tiles >= 1: the distributed factor's
+// device work on one rank, panel by panel: launch_cholesky_panel, then
+// launch_panel_update of every later panel, as dist_factor_enqueue and
+// sfm_dist_factor_profile chain them); launch_backsolve after either.
+static int dense_solve(int32_t device, int32_t n, const double* A, const double* b, double* y, int32_t reps,
+                       int32_t panel_tiles, double* ms, int32_t* chol_fail) {
+  if (n <= 0 || !A || !b || !y || reps < 1 || panel_tiles < 0) return fail(SFM_EINVAL, "bad arguments");
+  // (up to two tiles launch_backsolve leaves the solve to k_chol_small, which the panel factor does not run)
+  if (panel_tiles > 0 && (n + 1 + kNB - 1) / kNB <= 2) return fail(SFM_EINVAL, "panel factor: n < 128");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(SFM_ENODEV, "no device");
   HIPCHK(hipSetDevice(device));
@@ -1556,10 +1563,20 @@ int sfm_dense_spd_solve(int32_t device, int32_t n, const double* A, const double
   HIPCHK(hipEventCreate(&e0));
   HIPCHK(hipEventCreate(&e1));
   float total = 0.f;
+  int pepoch = 0;  // the panels' flag epoch: one per panel launch
   for (int r = 0; r < reps; ++r) {
     HIPCHK(hipMemcpyAsync(S, S0, bytes, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipEventRecord(e0, s));
-    launch_cholesky(d, r + 1, s);
+    if (panel_tiles > 0) {
+      HIPCHK(hipMemsetAsync(fl, 0, sizeof(int), s));
+      const int np = (d.nblk + panel_tiles - 1) / panel_tiles;
+      for (int k = 0; k < np; ++k) {
+        launch_cholesky_panel(d, k, panel_tiles, ++pepoch, s);
+        launch_panel_update(d, k, k + 1, INT32_MAX / 2, panel_tiles, 1, 0, s);
+      }
+    } else {
+      launch_cholesky(d, r + 1, s);
+    }
     launch_backsolve(d, r + 1, s);
     HIPCHK(hipEventRecord(e1, s));
     HIPCHK(hipEventSynchronize(e1));
@@ -1576,6 +1593,17 @@ int sfm_dense_spd_solve(int32_t device, int32_t n, const double* A, const double
   hipFree(S); hipFree(S0); hipFree(invd); hipFree(flags); hipFree(ys); hipFree(fl);
   hipStreamDestroy(s);
   return 0;
+}
+
+int sfm_dense_spd_solve(int32_t device, int32_t n, const double* A, const double* b, double* y, int32_t reps,
+                        double* ms, int32_t* chol_fail) {
+  return dense_solve(device, n, A, b, y, reps, 0, ms, chol_fail);
+}
+
+int sfm_dense_spd_solve_panels(int32_t device, int32_t n, const double* A, const double* b, double* y,
+                               int32_t panel_tiles, int32_t* chol_fail) {
+  if (panel_tiles < 1) return fail(SFM_EINVAL, "bad arguments");
+  return dense_solve(device, n, A, b, y, 1, panel_tiles, nullptr, chol_fail);
 }
 
 int sfm_ba_bench_jacobian(sfm_ba_handle* h, int32_t reps, double* avg_ms) {

@@ -59,6 +59,12 @@ __device__ unsigned long long g_bstamp[256 * 8];  // k_backsolve per block row (
 #define PSTAMP(j, w) do { } while (0)
 #define BSTAMP(b, k) do { } while (0)
 #endif
+// Test instantiations of the walker (SFM_CHOL_TEST_SKEW, tests/test_gpu_chol.py):
+// g_skew_steps[0] counts the steps that took the fast path (prefetched
+// subdiagonal tile and the next diagonal tile's flag both seen: no flag wait
+// between the Tn writes and the TRSM), [1] all steps with a tile below the
+// diagonal.  Read and reset by sfm_debug_chol_skew_steps.
+__device__ unsigned long long g_skew_steps[2];
 namespace {
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
@@ -1119,7 +1125,15 @@ __device__ __forceinline__ void w_st_row3(double* dst, const double* Wl) {
   }
 }
 
-template <bool kPanel>  // a column panel (ncols < nb possible) or the whole factor (ncols == nb)
+// the hold: kSkewSleeps x s_sleep 127; one s_sleep 127 is about 127 x 64 = 8128
+// clocks (3.4 us at 2.4 GHz), so ~7 us in all: a fixed count, no spin on memory
+constexpr int kSkewSleeps = 2;
+
+// kPanel: a column panel (ncols < nb possible) or the whole factor (ncols == nb).
+// kSkew (tests only; 0 in production, whose code it leaves as it is): 1 holds
+// waves 1-3 back right before their Tn writes, 2 holds wave 0 back instead, so
+// the hand-off of Tn to the TRSM is exercised with either side late.
+template <bool kPanel, int kSkew = 0>
 __device__ __forceinline__ void fused_walker(double* __restrict__ A, int ld, int n, int nb, int ncols,
                              double* __restrict__ Winv,
                              int* __restrict__ F, const int* __restrict__ Pf, int epoch, double* T, double* Wl,
@@ -1162,6 +1176,19 @@ __device__ __forceinline__ void fused_walker(double* __restrict__ A, int ld, int
     if (bad) atomicOr(fail, 1);
     const bool early = more && (__builtin_amdgcn_readfirstlane(rdy[0]) != 0 || __builtin_amdgcn_readfirstlane(rdy[3]) == 14);
     const bool diag_out = next && __builtin_amdgcn_readfirstlane(rdy[1]) != 0;
+    if constexpr (kSkew != 0) {
+      if (more && t == 0) {
+        atomicAdd(&g_skew_steps[0], early && diag_out ? 1ULL : 0ULL);
+        atomicAdd(&g_skew_steps[1], 1ULL);
+      }
+      if ((kSkew == 1) == (w >= 1)) {
+#pragma unroll
+        for (int q = 0; q < kSkewSleeps; ++q) asm volatile("s_sleep 127" ::: "memory");
+        // (asm with a memory clobber, not __builtin_amdgcn_s_sleep: the builtin is
+        // declared to touch no memory, and with it the Tn writes below were
+        // free to move ahead of the hold -- the skew then delayed nothing)
+      }
+    }
     // the prefetched subdiagonal tile into Tn (waves 1-3)
     if (early && w >= 1) pre.store();
     WSTAMPV(j, 15, early ? 1ull : 0ull);
@@ -1193,13 +1220,16 @@ __device__ __forceinline__ void fused_walker(double* __restrict__ A, int ld, int
       tile_ld2_sc1(sv, A + size_t(j0) * ld + i0, ld);
       tile_put2(Tn, sv);
     }
-    if (next) {
-      // the next diagonal partial tile (out long before; wave 3 saw its flag
-      // in panel 3): its loads run under the TRSM and the L_j+1,j stores
-      if (!diag_out) block_wait_sc1(fdiag, epoch, fail);
-      tile_ld2_sc1(nx, A + size_t(i0) * ld + i0, ld);
-    }
-    if (!early || !diag_out) __syncthreads();  // (the Tn writes above: before the TRSM reads them)
+    // the next diagonal partial tile (out long before; wave 3 saw its flag
+    // in panel 3): its loads run under the TRSM and the L_j+1,j stores.  A
+    // flag not seen yet is awaited only after W_j's flag is out (below): the
+    // tile's ticket comes after those of column j's tiles, which await W_j --
+    // waiting for it here stalled a grid with fewer running helpers than
+    // column j has such tiles until the bounded waits gave up (fail bit 4).
+    if (diag_out) tile_ld2_sc1(nx, A + size_t(i0) * ld + i0, ld);
+    // the Tn writes above (waves 1-3's pre.store(), or the reload) before the
+    // TRSM reads them (wave w reads rows 16 w .. 16 w + 15 of every column)
+    __syncthreads();
     WSTAMP(j, 12);
     // subdiagonal tile: L_j+1,j = Tn W^T, kept in Ls for the next update
     f64x4 x[4];
@@ -1210,6 +1240,10 @@ __device__ __forceinline__ void fused_walker(double* __restrict__ A, int ld, int
     // P(j+1,j) lands ~4.5 us before the walker needs it)
     block_publish_wt(F + j * nb + j, epoch);
     WSTAMP(j, 13);
+    if (next && !diag_out) {
+      block_wait_sc1(fdiag, epoch, fail);
+      tile_ld2_sc1(nx, A + size_t(i0) * ld + i0, ld);
+    }
     if (next) {
       // the next step's column-block-0 update products (its MFMAs run while
       // the stores below drain)
@@ -1230,7 +1264,7 @@ __device__ __forceinline__ void fused_walker(double* __restrict__ A, int ld, int
 // tepoch: the ticket epoch (the flag epoch `epoch` for a whole factor; 1 for
 // a panel, whose tickets are zeroed before its launch -- its task count
 // differs from panel to panel)
-template <bool kPanel>
+template <bool kPanel, int kSkew = 0>
 __global__ __launch_bounds__(256) void k_chol_fused(double* __restrict__ A, int ld, int n, int nb, int ncols,
                                                     double* __restrict__ Winv, int* __restrict__ F,
                                                     int* __restrict__ Pf, unsigned long long* __restrict__ ticket,
@@ -1268,7 +1302,7 @@ __global__ __launch_bounds__(256) void k_chol_fused(double* __restrict__ A, int 
   const int role = __builtin_amdgcn_readfirstlane(sh[1]);
   __syncthreads();
   if (role == 0) {
-    fused_walker<kPanel>(A, ld, n, nb, ncols, Winv, F, Pf, epoch, T, Wl, Ls, Tn, scr, sh, fail);
+    fused_walker<kPanel, kSkew>(A, ld, n, nb, ncols, Winv, F, Pf, epoch, T, Wl, Ls, Tn, scr, sh, fail);
     return;
   }
   const int ntask = chol_tasks(nb, kPanel ? ncols : nb);
@@ -1680,8 +1714,17 @@ bool launch_cholesky(const DevProblem& d, int epoch, hipStream_t s, bool clear_f
   const int cap = helpers_env > 0 ? std::min(helpers_env, full) : full;
   const int nhelp = std::max(1, std::min(ntask, cap));
   const int* tc = overlap ? d.tile_cnt : nullptr;
-  k_chol_fused<false><<<1 + nhelp, 256, 0, s>>>(d.S, d.ld, d.n, nb, nb, d.invL, d.cflags, d.cflags + size_t(nb) * nb,
-                                         d.cticket, epoch, epoch, nhelp, d.fail, d.gate, tc, d.tile_exp);
+  // (SFM_CHOL_TEST_SKEW=1|2, tests only: the walker's skewed instantiations,
+  // on the one-stream schedule)
+  static const int skew_env = [] {
+    const char* e = std::getenv("SFM_CHOL_TEST_SKEW");
+    return e ? std::atoi(e) : 0;
+  }();
+  auto* kern = k_chol_fused<false>;
+  if (!overlap && skew_env == 1) kern = k_chol_fused<false, 1>;
+  if (!overlap && skew_env == 2) kern = k_chol_fused<false, 2>;
+  kern<<<1 + nhelp, 256, 0, s>>>(d.S, d.ld, d.n, nb, nb, d.invL, d.cflags, d.cflags + size_t(nb) * nb, d.cticket, epoch,
+                                 epoch, nhelp, d.fail, d.gate, tc, d.tile_exp);
   return false;
 }
 
@@ -1748,6 +1791,14 @@ void launch_spd_fill(double* A, int ld, int n, unsigned seed, hipStream_t s) {
 }
 
 }  // namespace sfm
+
+// Unlisted (tests/test_gpu_chol.py): the skewed walkers' step counts since
+// the last call, {fast path, all}; then zeroed.
+extern "C" int sfm_debug_chol_skew_steps(unsigned long long* out) {
+  const unsigned long long zero[2] = {0, 0};
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(sfm::g_skew_steps), sizeof(zero)) != hipSuccess) return -5;
+  return hipMemcpyToSymbol(HIP_SYMBOL(sfm::g_skew_steps), zero, sizeof(zero)) == hipSuccess ? 0 : -5;
+}
 
 #ifdef SFM_CHOL_STAMPS
 extern "C" int sfm_debug_bstamps(unsigned long long* out, int n) {

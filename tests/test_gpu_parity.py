@@ -94,34 +94,49 @@ def test_matcher_bit_exact():
             assert np.array_equal(a, b)
 
 
-@pytest.mark.parametrize("path", ["fused", "stepwise"])
+_persistent_dense = None
+
+
+def _dense_persistent():
+    """The dense cases on the persistent pair at every size (SFM_CHOL_NO_SMALL=1
+    is read once per process: one child runs the whole list, tests/chol_child.py)."""
+    global _persistent_dense
+    if _persistent_dense is None:
+        from tests import chol_child
+        _persistent_dense = chol_child.in_child("parity", SFM_CHOL_NO_SMALL="1")
+    return _persistent_dense
+
+
+@pytest.mark.parametrize("path", ["fused", "persistent"])
 @pytest.mark.parametrize("n", [6, 63, 64, 65, 130, 600, 3000])
-def test_dense_cholesky_solve(n, path, monkeypatch):
-    """Both factorisations: the persistent single-launch one (default) and
-    the three-launches-per-column one (SFM_CHOL_STEPWISE=1)."""
+def test_dense_cholesky_solve(n, path):
+    """Both paths: the default (k_chol_small up to two tiles, the persistent
+    single-launch factor + k_backsolve above) and the persistent pair at every
+    size."""
     from sfm_amd.ba import dense_spd_solve
-    if path == "stepwise":
-        monkeypatch.setenv("SFM_CHOL_STEPWISE", "1")
-    rng = np.random.default_rng(n)
-    M = rng.standard_normal((n, n))
-    A = M @ M.T + n * np.eye(n)
-    b = rng.standard_normal(n)
-    y, ms, fl = dense_spd_solve(A, b, reps=3 if n >= 600 else 1)
+    from tests import chol_child
+    A, b = chol_child.well(n)
+    if path == "persistent":
+        hexy, fl = _dense_persistent()[f"solve-{n}"]
+        y = chol_child.unhex(hexy)
+    else:
+        y, ms, fl = dense_spd_solve(A, b, reps=3 if n >= 600 else 1)
+        print(f"n={n}: {ms:.3f} ms per factor+solve")
     assert fl == 0
     ref = np.linalg.solve(A, b)
     assert np.max(np.abs(y - ref)) <= 1e-10 * np.max(np.abs(ref))
-    print(f"n={n}: {ms:.3f} ms per factor+solve")
 
 
-@pytest.mark.parametrize("path", ["fused", "stepwise"])
+@pytest.mark.parametrize("path", ["fused", "persistent"])
 @pytest.mark.parametrize("n", [100, 700])
-def test_dense_cholesky_reports_indefinite(n, path, monkeypatch):
+def test_dense_cholesky_reports_indefinite(n, path):
     from sfm_amd.ba import dense_spd_solve
-    if path == "stepwise":
-        monkeypatch.setenv("SFM_CHOL_STEPWISE", "1")
-    A = np.eye(n)
-    A[n // 2, n // 2] = -1.0
-    _, _, fl = dense_spd_solve(A, np.ones(n))
+    if path == "persistent":
+        fl = _dense_persistent()[f"indefinite-{n}"]
+    else:
+        A = np.eye(n)
+        A[n // 2, n // 2] = -1.0
+        _, _, fl = dense_spd_solve(A, np.ones(n))
     assert fl == 1
 
 
