@@ -34,9 +34,9 @@ constexpr int kPtV = 10;
 constexpr int kPtL = 10;
 // Per-point Schur record (k_schur_pts): X (3), Jacobi scale (3), L (6), 1/l_ii (3), pad: 128 B.
 constexpr int kPtS = 16;
-// Per-point record of k_schur_pairs_rot: X (3), G_p = diag(s_p) L_p^-T (G00 G01 G02 G11 G12 G22), pad: 128 B.
+// Per-point record of k_schur_pairs_rot_pw: X (3), G_p = diag(s_p) L_p^-T (G00 G01 G02 G11 G12 G22), pad: 128 B.
 constexpr int kPtG = 16;
-// Per-camera record of k_schur_pairs_rot's staging (one side of a block in LDS; camS):
+// Per-camera record of k_schur_pairs_rot_pw's staging (one side of a block in LDS; camS):
 // R 9 | t 3 | fx sk fy | first-order flag | J 9 (row-major) | Jacobi scale 6 | pad.
 constexpr int kCamSR = 32;
 // Cholesky tile size.
@@ -74,11 +74,6 @@ struct DevProblem {
   int4* jchunks = nullptr;     // [n_jchunks] (camera, first position, count, 0): k_jacobian work units
   int32_t n_jchunks = 0;
   int32_t xcd_slice_max = 0;   // chunks of the largest of the 8 point slices (host copy)
-  // Schur / Cholesky overlap (compute_step_enqueue): per 64x64 tile of S the
-  // camera blocks landed so far and the count that completes it
-  int32_t* tile_cnt = nullptr;  // [nblk * nblk], zeroed before each Schur pass
-  int32_t* tile_exp = nullptr;  // [nblk * nblk], from set_problem (both with plan.overlap: k_chol_fused
-                                // waits on tile_cnt and leaves CUs to k_schur_pts)
   int32_t* jgrp = nullptr;     // [9] chunk-table offsets of the 8 point slices (one per XCD)
   double* uv_cm = nullptr;     // [N_pad][2] uv in camera-major order
   int32_t* pos = nullptr;      // [N] camera-major position of point-major observation q
@@ -100,8 +95,7 @@ struct DevProblem {
   double* camRn = nullptr;    // [C][12] candidate R (9) + t (3)
   double* jrec = nullptr;     // [N_pad][20] at camera-major position (J_X 6 | r 2 | J_c 12): evaluate API only,
                               // allocated on first use (the solve writes no records)
-  double* eu = nullptr;       // [N][kEU] back substitution pass A output (point-major), or
-                              // [N_pad][kEU] at camera-major positions (plan.eu_cm)
+  double* eu = nullptr;       // [N_pad][kEU] back substitution pass A output, at camera-major positions
   double* ypt = nullptr;      // [P][3] point steps y_p (scaled space)
   int32_t* wcam = nullptr;    // [N_pad / 64] camera of each camera-major wavefront (runs padded to 64)
   double* ptV = nullptr;      // [P][10]
@@ -140,7 +134,7 @@ struct DevProblem {
                               // empty slot (k_schur_pairs_rot_pw reads these in place of bperm -> blk -> seg)
   double* camS = nullptr;     // [C][kCamSR] with ptG: each camera's staged record (k_cam_stage_rot, once per pass)
   double* ptS = nullptr;      // [P][kPtS] X 3, scale 3, l10 l20 l21, 1/l_ii 3, z 3, pad
-  double* ptG = nullptr;      // [P][16] X 3, G_p = diag(s_p) L_p^-T (6, upper), pad: k_schur_pairs_rot's record
+  double* ptG = nullptr;      // [P][16] X 3, G_p = diag(s_p) L_p^-T (6, upper), pad: k_schur_pairs_rot_pw's record
                               // (plan.large_system; nullptr: k_schur_pts and ptS alone)
   // per-wave diagonal-block / rhs partials from k_obs_prep_rc ([N_pad/64][27])
   double* dpart = nullptr;
@@ -201,14 +195,13 @@ void launch_point_prep(const DevProblem& d, double radius, hipStream_t s);
 // the per-wave diagonal-block / rhs partials (k_obs_prep_rc; reads the point records)
 void launch_obs_prep(const DevProblem& d, hipStream_t s);
 void launch_point_factor(const DevProblem& d, double radius, hipStream_t s);
-// the diagonal blocks + rhs and the pair pass, not overlapped (WgBlocks: in one launch)
+// the diagonal blocks + rhs and the pair pass (WgBlocks: in one launch)
 void launch_schur(const DevProblem& d, PairPass v, double radius, bool add_diag, hipStream_t s);
 // its two parts: the diagonal blocks + rhs (k_schur_diag_sum) and the
-// off-diagonal blocks (overlapped: beside the factorisation, the blocks in
-// their plain order and counted per 64x64 tile in tile_cnt as they land)
+// off-diagonal blocks
 void launch_schur_diag(const DevProblem& d, double radius, bool add_diag, hipStream_t s);
 // cams_staged: camS already holds the cameras' records (launch_cam_sum_diag)
-void launch_schur_offdiag(const DevProblem& d, PairPass v, bool overlapped, hipStream_t s, bool cams_staged = false);
+void launch_schur_offdiag(const DevProblem& d, PairPass v, hipStream_t s, bool cams_staged = false);
 // launch_cam_sum_finalize (mode 1, with the gradient partials) and
 // launch_schur_diag in one launch (after launch_obs_prep, in the evaluation);
 // stage_cams: and k_cam_stage_rot's records (SolvePlan::stage_cams)
@@ -240,11 +233,8 @@ void launch_reduce_batch(const DevProblem& d, const ReduceBatch& b, bool copy_fa
 // ---- dense Cholesky (chol_kernels.hip) ----
 // cam_step >= 0: a small system's one-workgroup factor also takes the
 // camera step (k_cam_update; cam_step > 0: with its step-length partial);
-// returns whether it did.  overlap: plan.overlap when the factor runs beside
-// k_schur_pts (its helpers then await tile_cnt and take the overlap's grid),
-// 0 otherwise -- only the overlapped branch zeroes and fills tile_cnt
-bool launch_cholesky(const DevProblem& d, int epoch, hipStream_t s, bool clear_fail = true, int cam_step = -1,
-                     int overlap = 0);
+// returns whether it did
+bool launch_cholesky(const DevProblem& d, int epoch, hipStream_t s, bool clear_fail = true, int cam_step = -1);
 // W_k granules back to the sentinel (k_schur_diag_sum does this in the solve)
 // sentinel_set: y already holds kYSentinel (k_pad_init wrote it)
 void launch_backsolve(const DevProblem& d, int epoch, hipStream_t s, bool sentinel_set = false);

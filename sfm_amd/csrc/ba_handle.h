@@ -132,10 +132,6 @@ struct sfm_ba_handle {
   // they are.
   bool cams_staged = false;
   int n_cu = 0;  // compute units of the device (queried once)
-  // Schur / Cholesky overlap (DevProblem::plan.overlap): the factorisation's
-  // stream and the two events that fork and join it
-  hipStream_t stream2 = nullptr;
-  hipEvent_t ov_ev[2] = {nullptr, nullptr};
   // set_problem's uploads beside the layout kernels (large problems): the
   // parameters (uev), and uv from a worker thread (uev_uv)
   hipStream_t ustream = nullptr;

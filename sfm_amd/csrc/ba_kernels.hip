@@ -431,7 +431,7 @@ __device__ __forceinline__ double point_factor_body(int p, const double v[9], co
     st2(o + 12, z0, z1); st2(o + 14, z2, 0.0);
   }
   if (ptG) {
-    // k_schur_pairs_rot's record: X and G_p = diag(s_p) L^-T (upper triangular)
+    // k_schur_pairs_rot_pw's record: X and G_p = diag(s_p) L^-T (upper triangular)
     const double i00 = 1.0 / l00, i11 = 1.0 / l11, i22 = 1.0 / l22;
     const double li10 = -l10 * i00 * i11, li21 = -l21 * i11 * i22, li20 = -(l20 * i00 + l21 * li10) * i22;
     double* o = ptG + size_t(kPtG) * p;
@@ -658,7 +658,7 @@ __global__ __launch_bounds__(kThreads * kGroups) void k_point_eval_lds(int P, in
 // With ptS != nullptr it also writes the point's 128-B record for the
 // camera-side passes (X 3 | Jacobi scale 3 | l10 l20 l21 | 1/l_ii 3 | z 3 |
 // pad): everything obs_recompute and k_schur_pts read of a point, one line.
-// With ptG != nullptr (large reduced systems) also k_schur_pairs_rot's
+// With ptG != nullptr (large reduced systems) also k_schur_pairs_rot_pw's
 // record: X and G_p = diag(s_p) L^-T.
 __global__ __launch_bounds__(kThreads) void k_point_factor(int P, const double* __restrict__ ptV,
                                                            const double* __restrict__ diag_p, double radius,
@@ -1100,7 +1100,7 @@ __global__ __launch_bounds__(kThreads) void k_backsub_a_rc(const int32_t* __rest
                                                            const double* __restrict__ scale_c,
                                                            const double* __restrict__ ptS,
                                                            const double* __restrict__ ysol, double* __restrict__ eu,
-                                                           int eu_cm, double* __restrict__ part_model, const int* __restrict__ gate) {
+                                                           double* __restrict__ part_model, const int* __restrict__ gate) {
   if (gate && *gate == 0) return;  // device LM loop: phase skipped
   __shared__ double sh[4];
   const int l = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -1120,10 +1120,10 @@ __global__ __launch_bounds__(kThreads) void k_backsub_a_rc(const int32_t* __rest
     const int qo = cam_obs[i];
     if (qo >= 0) {
       model += e0 * o.rec[kRes] + e1 * o.rec[kRes + 1] - 0.5 * (e0 * e0 + e1 * e1);
-      // u goes to the observation's POINT-major slot (32 B): pass B then
-      // streams a point's u contiguously instead of gathering 48-B records
+      // u goes to this camera-major position's 32-B slot (coalesced); pass B
+      // gathers a point's u through pos[]
       const double* M = o.M;
-      double* dst = eu + 4 * (eu_cm ? size_t(i) : size_t(qo));
+      double* dst = eu + 4 * size_t(i);
       // (the whole 32-B slot, padding included: full-line writes, 59 -> 51 us at C3)
       st2(dst, M[0] * e0 + M[3] * e1, M[1] * e0 + M[4] * e1);
       st2(dst + 2, M[2] * e0 + M[5] * e1, 0.0);
@@ -1300,7 +1300,7 @@ __global__ __launch_bounds__(kThreads, 3) void k_schur_pts(int64_t n_slots, cons
                                                         const double* __restrict__ scale_c, double* __restrict__ S,
                                                         int ld,
                                                         const int32_t* __restrict__ bperm, const int* __restrict__ gate,
-                                                        int* __restrict__ tile_cnt, int nbt, const DiagFold df) {
+                                                        const DiagFold df) {
   if (gate && *gate == 0) return;  // device LM loop: phase skipped
   static_assert(kWpb == 1 || (kWpb == kThreads / 64 && kSub == 64), "4 waves per block take 64 lanes each");
   constexpr int kPer = 64 / kSub;  // blocks per wave
@@ -1461,10 +1461,7 @@ __global__ __launch_bounds__(kThreads, 3) void k_schur_pts(int64_t n_slots, cons
     auto put = [&](int e, double v) {
       double* q = Sb + size_t(e / 6) * ld + e % 6;
       v = v * sc1[e / 6] * sc2[e % 6];
-      v = add ? *q - v : -v;
-      // overlapped with the factorisation: write-through, counted per tile
-      if (tile_cnt) __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else *q = v;
+      *q = add ? *q - v : -v;
     };
     constexpr int kR = kSub >= 32 ? 1 : 32 / kSub;
     if (kSub == 64) {
@@ -1475,22 +1472,9 @@ __global__ __launch_bounds__(kThreads, 3) void k_schur_pts(int64_t n_slots, cons
     }
     if (sl < 4) put(32 + sl, sl == 0 ? t32 : sl == 1 ? t33 : sl == 2 ? t34 : t35);
   }
-  if (tile_cnt) {
-    // Schur/Cholesky overlap: the block's entries are out (write-through,
-    // drained by this wave), then one lane per block counts it into every
-    // 64x64 tile its 6x6 footprint touches; a helper of k_chol_fused reads a
-    // tile once its count is complete (set_problem's tile_exp)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (own && sl == 0) {
-      const int r0 = 6 * cc.y, c0 = 6 * cc.x;
-      for (int I = r0 / 64; I <= (r0 + 5) / 64; ++I)
-        for (int J = c0 / 64; J <= (c0 + 5) / 64; ++J)
-          __hip_atomic_fetch_add(tile_cnt + I * nbt + J, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
 }
 
-// k_schur_pairs_rot: k_schur_pts<kSub, 1> for large reduced systems, with the
+// k_schur_pairs_rot_pw: k_schur_pts<kSub, 1> for large reduced systems, with the
 // rotation columns taken from the ROTATED point.  With [j_k]x = dR_k R^T,
 // dR_k X = j_k x y (y = R X), i.e. Q = [dR_0 X | dR_1 X | dR_2 X] = -[y]x J
 // with J = [j_0 j_1 j_2], and a pair's [Q_1 | I]^T H [Q_2 | I] becomes
@@ -1508,7 +1492,7 @@ __global__ __launch_bounds__(kThreads, 3) void k_schur_pts(int64_t n_slots, cons
 // Entry i (row-major, 0..8) of [e_k]x = d([w]x)/dw_k: +1 at (k+2, k+1), -1 at
 // (k+1, k+2), indices mod 3 -- what rotation()'s first-order branch stores as
 // dR/dw_k.  A camera whose 27 dR/dw entries equal these is a first-order
-// camera, for k_schur_pairs_rot's staging and for cam_pm_pack alike.
+// camera, for stage_cams_rot and for cam_pm_pack alike.
 __device__ __forceinline__ double skew_basis_entry(int k, int i) {
   const int r = i / 3, q = i % 3;
   return (r == (k + 2) % 3 && q == (k + 1) % 3) ? 1.0 : (r == (k + 1) % 3 && q == (k + 2) % 3) ? -1.0 : 0.0;
@@ -1653,7 +1637,7 @@ __device__ __forceinline__ void pairs_rot_step(const double* cs1, const double* 
 template <int kSub>
 __device__ __forceinline__ void pairs_rot_finish(const double* cs1, const double* cs2, double (&acc)[36],
                                                  const bool own, const int2 cc, double* __restrict__ S, int ld,
-                                                 const int* tile_cnt, int l, int sl) {
+                                                 int l, int sl) {
   // once per block: rows 0..2 <- J_1^T rows, then columns 0..2 <- columns J_2
   {
     const double* J1 = cs1 + 16;
@@ -1686,10 +1670,7 @@ __device__ __forceinline__ void pairs_rot_finish(const double* cs1, const double
     auto put = [&](int e, double v) {
       double* q = Sb + size_t(e / 6) * ld + e % 6;
       v = v * sc1[e / 6] * sc2[e % 6];
-      v = add ? *q - v : -v;
-      // overlapped with the factorisation: write-through, counted per tile
-      if (tile_cnt) __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else *q = v;
+      *q = add ? *q - v : -v;
     };
     constexpr int kR = kSub >= 32 ? 1 : 32 / kSub;
     if (kSub == 64) {
@@ -1699,84 +1680,6 @@ __device__ __forceinline__ void pairs_rot_finish(const double* cs1, const double
       for (int r = 0; r < kR; ++r) put(kR * sl + r, v32[r]);
     }
     if (sl < 4) put(32 + sl, sl == 0 ? t32 : sl == 1 ? t33 : sl == 2 ? t34 : t35);
-  }
-}
-
-// One group of 64 / kSub slots per wave, a workgroup's four groups once: the
-// form of the Schur / Cholesky overlap (tile_cnt, the blocks in plain order).
-template <int kSub>
-__global__ __launch_bounds__(kThreads, 2) void k_schur_pairs_rot(int64_t n_slots, const int2* __restrict__ blk,
-                                                              const int32_t* __restrict__ seg,
-                                                              const int32_t* __restrict__ bpts,
-                                                              const double* __restrict__ ptG,
-                                                              const double* __restrict__ camR,
-                                                              const double* __restrict__ cam,
-                                                              const double* __restrict__ Kc,
-                                                              const double* __restrict__ scale_c,
-                                                              double* __restrict__ S, int ld,
-                                                              const int32_t* __restrict__ bperm,
-                                                              const int* __restrict__ gate, int* __restrict__ tile_cnt,
-                                                              int nbt) {
-  if (gate && *gate == 0) return;  // device LM loop: phase skipped
-  constexpr int kPer = 64 / kSub;  // blocks per wave
-  __shared__ __attribute__((aligned(16))) double cst[kThreads / 64][kPer][2 * kCamSR];
-  const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, g = l / kSub, sl = l % kSub;
-  const int64_t wb = (int64_t(blockIdx.x) * (kThreads / 64) + wv) * kPer;
-  // (block order, empty slots and the clamped, one-step-ahead index loads: as k_schur_pts)
-  auto slot_blk = [&](int64_t k) -> int32_t { return k < n_slots ? (bperm ? bperm[k] : int32_t(k)) : -1; };
-  const int32_t bs = slot_blk(wb + g);
-  const bool own = bs >= 0;
-  const int64_t b = own ? bs : 0;
-  const int2 cc = blk[b];
-  const double* cs1 = cst[wv][g];
-  const double* cs2 = cs1 + kCamSR;
-  {
-    const int32_t bq = slot_blk(wb + l % kPer);
-    const int2 cq = blk[bq >= 0 ? bq : 0];
-    stage_cams_rot<kSub>(&cst[wv][0][0], cq.x, cq.y, camR, cam, Kc, scale_c, l);
-  }
-  wave_lds_sync();
-  const int kb = seg[b], ke = own ? seg[b + 1] : kb;
-  double acc[36];  // row-major 6x6: [y1]x H [y2]x^T | [y1]x H ; H [y2]x^T | H
-#pragma unroll
-  for (int e = 0; e < 36; ++e) acc[e] = 0.0;
-  int len = ke - kb;
-#pragma unroll
-  for (int off = kSub; off < 64; off <<= 1) len = max(len, __shfl_xor(len, off));
-  // The record gather runs one step ahead, its index two steps ahead: a
-  // step's five 16-B loads are issued together at the top of the step before
-  // and waited for once (the empty asm below materialises all ten values).
-  int p_nx = bpts[kb + sl + kSub < ke ? kb + sl + kSub : 0];
-  double2 n0, n1, n2, n3, n4;
-  {
-    const double* r = ptG + size_t(kPtG) * bpts[kb + sl < ke ? kb + sl : 0];
-    n0 = ld2(r); n1 = ld2(r + 2); n2 = ld2(r + 4); n3 = ld2(r + 6); n4 = ld2(r + 8);
-  }
-  for (int k0 = 0; k0 < len; k0 += kSub) {
-    double2 x0 = n0, x1 = n1, x2 = n2, x3 = n3, x4 = n4;
-    asm volatile("" : "+v"(x0.x), "+v"(x0.y), "+v"(x1.x), "+v"(x1.y), "+v"(x2.x), "+v"(x2.y), "+v"(x3.x), "+v"(x3.y),
-                 "+v"(x4.x), "+v"(p_nx));
-    const int k = kb + k0 + sl;
-    const bool valid = k < ke;
-    {
-      const double* r = ptG + size_t(kPtG) * p_nx;
-      n0 = ld2(r); n1 = ld2(r + 2); n2 = ld2(r + 4); n3 = ld2(r + 6); n4 = ld2(r + 8);
-    }
-    p_nx = bpts[k + 2 * kSub < ke ? k + 2 * kSub : 0];
-    // (fences: the loads above stay here, and each camera's constants are
-    // read from LDS where they are used, not hoisted into live registers)
-    asm volatile("" ::: "memory");
-    pairs_rot_step(cs1, cs2, x0, x1, x2, x3, x4, valid, acc);
-  }
-  pairs_rot_finish<kSub>(cs1, cs2, acc, own, cc, S, ld, tile_cnt, l, sl);
-  if (tile_cnt) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (as k_schur_pts: the block is out, then counted)
-    if (own && sl == 0) {
-      const int r0 = 6 * cc.y, c0 = 6 * cc.x;
-      for (int I = r0 / 64; I <= (r0 + 5) / 64; ++I)
-        for (int J = c0 / 64; J <= (c0 + 5) / 64; ++J)
-          __hip_atomic_fetch_add(tile_cnt + I * nbt + J, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
   }
 }
 
@@ -1804,7 +1707,7 @@ __global__ __launch_bounds__(kThreads) void k_cam_stage_rot(int C, const double*
   }
 }
 
-// The pass outside the overlap: waves that walk several groups.  The grid is
+// The pair pass of a large system: waves that walk several groups.  The grid is
 // a few resident generations (launch_schur_offdiag); workgroup w serves list
 // w % 8 of the slot order (set_problem's XCD-aware groups: the workgroups one XCD gets under
 // round-robin placement, a speed assumption only).  A list is dealt out in
@@ -1888,7 +1791,9 @@ __global__ __launch_bounds__(kThreads, 2) void k_schur_pairs_rot_pw(const int4* 
     int len = ke - kb;
 #pragma unroll
     for (int off = kSub; off < 64; off <<= 1) len = max(len, __shfl_xor(len, off));
-    // (the loop of k_schur_pairs_rot: the record gather one step ahead, its index two)
+    // The record gather runs one step ahead, its index two steps ahead: a
+    // step's five 16-B loads are issued together at the top of the step before
+    // and waited for once (the empty asm below materialises all ten values).
     for (int k0 = 0; k0 < len; k0 += kSub) {
       double2 x0 = n0, x1 = n1, x2 = n2, x3 = n3, x4 = n4;
       asm volatile("" : "+v"(x0.x), "+v"(x0.y), "+v"(x1.x), "+v"(x1.y), "+v"(x2.x), "+v"(x2.y), "+v"(x3.x), "+v"(x3.y),
@@ -1900,6 +1805,8 @@ __global__ __launch_bounds__(kThreads, 2) void k_schur_pairs_rot_pw(const int4* 
         n0 = ld2(r); n1 = ld2(r + 2); n2 = ld2(r + 4); n3 = ld2(r + 6); n4 = ld2(r + 8);
       }
       p_nx = bpts[k + 2 * kSub < ke ? k + 2 * kSub : 0];
+      // (fences: the loads above stay here, and each camera's constants are
+      // read from LDS where they are used, not hoisted into live registers)
       asm volatile("" ::: "memory");
       pairs_rot_step(cs1, cs2, x0, x1, x2, x3, x4, valid, acc);
     }
@@ -1910,7 +1817,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_schur_pairs_rot_pw(const int4* 
     }
     p_nx = iB1;
     asm volatile("" ::: "memory");
-    pairs_rot_finish<kSub>(cs1, cs2, acc, own, cc, S, ld, nullptr, l, sl);
+    pairs_rot_finish<kSub>(cs1, cs2, acc, own, cc, S, ld, l, sl);
     wave_lds_sync();
     tA = tB; tB = tC; tC += W;
     rA = rB; rB = rC;
@@ -2127,7 +2034,7 @@ __global__ __launch_bounds__(kThreads) void k_cam_solve(int C, const double* __r
 // passes so that only per-point quantities are gathered:
 //   A (k_backsub_a_rc, camera-major, one wavefront = 64 positions of one
 //       camera): e_o = J_c,o y_c,  u_o = M_o^T e_o  -> eu at the
-//       observation's point-major slot (J and M recomputed)
+//       observation's camera-major position (J and M recomputed)
 //   B (one lane per point):  y_p = L^-T (z_p - sum_o u_o),  delta_p = -y_p,
 //       X_new = X + s_p delta_p, |dX|^2, finite check  -> ypt[p], X_new
 //   C (camera-major): candidate residual at (cam_new, X_new).
@@ -2136,9 +2043,11 @@ __global__ __launch_bounds__(kThreads) void k_cam_solve(int C, const double* __r
 // Camera runs are padded to whole wavefronts, so a wavefront never spans two
 // cameras (its camera comes from wcam) and padding lanes are masked.
 
-__global__ __launch_bounds__(kThreads) void k_backsub_b(int P, const int32_t* __restrict__ pt_off,
+// (8 waves per SIMD: the gather is latency-bound, and 64 VGPRs are what it had
+// before the four positions of a round became one 16-B load -- 66 without the bound)
+__global__ __launch_bounds__(kThreads, 8) void k_backsub_b(int P, const int32_t* __restrict__ pt_off,
                                                         const double* __restrict__ eu,
-                                                        const int32_t* __restrict__ eu_pos,
+                                                        const int32_t* __restrict__ pos,
                                                         const double* __restrict__ ptL,
                                                         const double* __restrict__ ptV,
                                                         const double* __restrict__ scale_p,
@@ -2162,8 +2071,8 @@ __global__ __launch_bounds__(kThreads) void k_backsub_b(int P, const int32_t* __
     double w0 = L[6], w1 = L[7], w2 = L[8];
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;  // sum of u = L^-1 J_X^T e
     const int q0 = pt_off[p], q1 = pt_off[p + 1];
-    // pass A's u: at the point-major slot, or (eu_pos) at the camera-major
-    // position.  Four observations' positions, then their u, are loaded
+    // pass A's u: at the observation's camera-major position (pos).  Four
+    // observations' positions, then their u, are loaded
     // before any is summed (two memory round trips per four instead of two
     // per observation: what bounds keyframe-sized problems); the sums still
     // run in observation order.
@@ -2171,7 +2080,7 @@ __global__ __launch_bounds__(kThreads) void k_backsub_b(int P, const int32_t* __
     for (; q + 4 <= q1; q += 4) {
       int ps[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) ps[j] = eu_pos ? eu_pos[q + j] : q + j;
+      for (int j = 0; j < 4; ++j) ps[j] = pos[q + j];
       double2 a[4];
       double b[4];
 #pragma unroll
@@ -2189,7 +2098,7 @@ __global__ __launch_bounds__(kThreads) void k_backsub_b(int P, const int32_t* __
       }
     }
     for (; q < q1; ++q) {
-      const double* u = eu + 4 * (eu_pos ? size_t(eu_pos[q]) : size_t(q));
+      const double* u = eu + 4 * size_t(pos[q]);
       const double2 u01 = ld2(u);
       const double u2 = u[2];
       w0 -= u01.x;
@@ -2599,11 +2508,11 @@ void launch_schur(const DevProblem& d, PairPass v, double radius, bool add_diag,
                      (d.n + kNB - 1) / kNB * kNB, d.fail, reinterpret_cast<unsigned long long*>(d.ysol)};
     k_schur_pts<64, kThreads / 64><<<int(d.n_bslots), kThreads, 0, s>>>(d.n_bslots, d.blk, d.seg, d.bpts, d.ptS,
                                                                        d.camR, d.cam, d.Kc, d.scale_c, d.S, d.ld,
-                                                                       d.bperm, d.gate, nullptr, d.nblk, f);
+                                                                       d.bperm, d.gate, f);
     return;
   }
   launch_schur_diag(d, radius, add_diag, s);
-  launch_schur_offdiag(d, v, false, s);
+  launch_schur_offdiag(d, v, s);
 }
 void launch_cam_sum_diag(const DevProblem& d, double radius, bool add_diag, hipStream_t s, bool stage_cams) {
   if (!d.C) return;
@@ -2626,37 +2535,26 @@ static void with_sub(int sub, F&& f) {
   else if (sub == 32) f(std::integral_constant<int, 32>{});
   else f(std::integral_constant<int, 64>{});
 }
-// overlapped with k_chol_fused (compute_step_enqueue): the blocks in their
-// plain order (camera-major: the factor's tile columns complete left to
-// right) and counted per tile
-void launch_schur_offdiag(const DevProblem& d, PairPass v, bool overlapped, hipStream_t s, bool cams_staged) {
+void launch_schur_offdiag(const DevProblem& d, PairPass v, hipStream_t s, bool cams_staged) {
   if (!d.n_blk) return;
-  int* tile_cnt = overlapped ? d.tile_cnt : nullptr;
-  const int64_t n_slots = overlapped ? d.n_blk : d.n_bslots;
-  const int32_t* bperm = overlapped ? nullptr : d.bperm;
+  const int64_t n_slots = d.n_bslots;
   const int sub = d.plan.schur_pts_sub, per = 64 / sub * (kThreads / 64);
   const int nb = int((n_slots + per - 1) / per);
   switch (v) {
     case PairPass::WgBlocks:  // small systems: one block per workgroup
       k_schur_pts<64, kThreads / 64><<<int(n_slots), kThreads, 0, s>>>(n_slots, d.blk, d.seg, d.bpts, d.ptS,
                                                                       d.camR, d.cam, d.Kc, d.scale_c, d.S, d.ld,
-                                                                      bperm, d.gate, tile_cnt, d.nblk, DiagFold{});
+                                                                      d.bperm, d.gate, DiagFold{});
       break;
     case PairPass::Pts:
       with_sub(sub, [&](auto S) {
         k_schur_pts<decltype(S)::value><<<nb, kThreads, 0, s>>>(n_slots, d.blk, d.seg, d.bpts, d.ptS, d.camR, d.cam,
-                                                                d.Kc, d.scale_c, d.S, d.ld, bperm, d.gate, tile_cnt,
-                                                                d.nblk, DiagFold{});
+                                                                d.Kc, d.scale_c, d.S, d.ld, d.bperm, d.gate,
+                                                                DiagFold{});
       });
       break;
-    case PairPass::Rot:  // large reduced systems: the rotated-point form (k_point_factor wrote ptG)
-      with_sub(sub, [&](auto S) {
-        k_schur_pairs_rot<decltype(S)::value><<<nb, kThreads, 0, s>>>(n_slots, d.blk, d.seg, d.bpts, d.ptG, d.camR,
-                                                                      d.cam, d.Kc, d.scale_c, d.S, d.ld, bperm, d.gate,
-                                                                      tile_cnt, d.nblk);
-      });
-      break;
-    case PairPass::RotPersistent: {  // ... with persistent waves over the slot and camera records
+    case PairPass::RotPersistent: {  // large reduced systems: the rotated-point form (k_point_factor wrote
+                                     // ptG), with persistent waves over the slot and camera records
       // 2 workgroups per CU are resident (2 waves per SIMD); the grid is four
       // times that (C3: a wave walks 2 groups, the dispatcher evens out the
       // lists' unequal groups; one resident generation of longer walks measured
@@ -2705,7 +2603,6 @@ void launch_cam_solve(const DevProblem& d, double radius, hipStream_t s) {
 }
 void launch_point_backsub(const DevProblem& d, Backsub v, hipStream_t s, bool cams_var, bool pts_var,
                           bool count_norm) {
-  const bool eu_cm = d.plan.eu_cm;
   if (v == Backsub::OnePass) {  // one point-major pass, the camera step included
     constexpr int kG = 4;  // one 1024-thread workgroup per CU (its LDS copy is up to 148 KB)
     k_backsub_pm<kG><<<blocks_for(d.P, kG * kThreads), kG * kThreads, 0, s>>>(
@@ -2718,17 +2615,16 @@ void launch_point_backsub(const DevProblem& d, Backsub v, hipStream_t s, bool ca
   // cameras constant (STRUCT_ONLY): e = J_c y_c = 0 and u = 0
   if (d.N_pad && cams_var)
     k_backsub_a_rc<<<obs_xcd_blocks(d), kThreads, 0, s>>>(d.jgrp, d.jchunks, d.cm_p, d.uv_cm, d.cam_obs, d.camR,
-                                                          d.cam, d.Kc, d.scale_c, d.ptS, d.ysol, d.eu, eu_cm ? 1 : 0,
+                                                          d.cam, d.Kc, d.scale_c, d.ptS, d.ysol, d.eu,
                                                           slot(d, kPModel), d.gate);
   else if (d.N_pad) {
-    (void)hipMemsetAsync(d.eu, 0, sizeof(double) * 4 * size_t(eu_cm ? d.N_pad : d.N), s);
+    (void)hipMemsetAsync(d.eu, 0, sizeof(double) * 4 * size_t(d.N_pad), s);
     (void)hipMemsetAsync(slot(d, kPModel), 0, sizeof(double) * size_t(obs_xcd_blocks(d)), s);
   }
   if (d.P && pts_var) {
-    k_backsub_b<<<pt_xcd_blocks(d), kThreads, 0, s>>>(d.P, d.pt_off, d.eu, eu_cm ? d.pos : nullptr,
-                                                               d.ptL, d.ptV, d.scale_p,
-                                                               d.X, d.X_new, d.ypt, slot(d, kPStepPt),
-                                                               slot(d, kPBadBack), slot(d, kPModelPt), d.gate);
+    k_backsub_b<<<pt_xcd_blocks(d), kThreads, 0, s>>>(d.P, d.pt_off, d.eu, d.pos, d.ptL, d.ptV, d.scale_p, d.X,
+                                                      d.X_new, d.ypt, slot(d, kPStepPt), slot(d, kPBadBack),
+                                                      slot(d, kPModelPt), d.gate);
   } else if (d.P) {
     // points constant (POSE_ONLY): y_p = 0, X_new = X, no step, no bad flag
     const size_t nbP = size_t(pt_xcd_blocks(d));

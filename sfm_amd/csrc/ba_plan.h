@@ -5,10 +5,10 @@
 //                 one function (read_knobs) at the two times they always were:
 //                 the problem's half in sfm_ba_set_problem, the solve's half at
 //                 the start of each sfm_ba_solve_resident
-//   ProblemPlan   what set_problem decides from the problem's shape, whether a
-//                 communicator is set, and the knobs (plan_problem); stored
-//                 with the problem (DevProblem::plan).  set_problem allocates
-//                 what the plan asks for
+//   ProblemPlan   what set_problem decides from the problem's shape and the
+//                 knobs (plan_problem); stored with the problem
+//                 (DevProblem::plan).  set_problem allocates what the plan
+//                 asks for
 //   SolvePlan     what one solve adds from its mode, its collectives and the
 //                 knobs (plan_solve): per pass an enum naming the kernels it
 //                 stands for, and the reduction batches' block counts.  The
@@ -51,8 +51,6 @@ struct SolveKnobs {
   int schur_pts_sub = 0;      // SFM_SCHUR_PTS_SUB  8 / 32 / 64 (anything else: 16) lanes per block; 0: by pair count
   int schur_wg = -1;          // SFM_SCHUR_WG       1 / other: a workgroup per block forced on / off; -1: by shape
   int schur_wgs = 0;          // SFM_SCHUR_WGS      the persistent pair pass's grid, up to a multiple of 8; 0: by CUs
-  bool eu_cm = true;          // SFM_EU_CM          0: back substitution pass A scatters u point-major
-  bool overlap = false;       // SFM_OVERLAP        > 0: the factor beside the Schur pair pass
   bool force_pack = false;    // SFM_FORCE_PACK     1: the packed all-reduce path on one rank
   int jac_wg_per_xcd = 0;     // SFM_JAC_WG_PER_XCD > 0: workgroups per XCD of the solve's Jacobian pass
   // the solve's (sfm_ba_solve_resident)
@@ -79,9 +77,6 @@ inline void read_knobs(SolveKnobs* k, int when, EnvGet get = env_get) {
     k->schur_wg = hostlayout::schur_wg_forced(get("SFM_SCHUR_WG"));
     const char* v = get("SFM_SCHUR_WGS");
     k->schur_wgs = v ? std::min(1 << 16, std::max(0, std::atoi(v)) + 7) / 8 * 8 : 0;
-    k->eu_cm = not0("SFM_EU_CM");
-    v = get("SFM_OVERLAP");
-    k->overlap = (v ? std::atoi(v) : 0) > 0;
     k->force_pack = is1("SFM_FORCE_PACK");
     v = get("SFM_JAC_WG_PER_XCD");
     k->jac_wg_per_xcd = v ? std::max(0, std::atoi(v)) : 0;
@@ -130,7 +125,6 @@ struct ProblemShape {
   int64_t wm_slots = -1;  // 64-lane slots of the wave-major stream
 
   int64_t n_blk() const { return int64_t(C) * (C + 1) / 2; }        // upper-triangle camera blocks
-  int chol_tiles() const { return ((6 * C + 1 + 63) / 64 * 64) / 64; }  // 64x64 tile rows of the augmented system
 };
 
 struct ProblemPlan {
@@ -141,15 +135,13 @@ struct ProblemPlan {
   bool large_system = false;     // n_blk > kSchurXcdMinBlocks: the rotated-point pair pass (ptG, camS exist)
   bool xcd_block_order = false;  // ... and the XCD-aware slot order on the sorted path (bperm, srec exist)
   bool pm_backsub = false;       // large, C <= kCamPMMax: the back substitution may run as k_backsub_pm's one pass
-  bool eu_cm = true;             // back substitution pass A stores u at camera-major positions
-  int overlap = 0;               // the factor may run beside the pair pass (tile_cnt, tile_exp exist)
   bool force_pack = false;       // the packed all-reduce path on one rank (Spack exists)
   int schur_wgs = 0;             // the persistent pair pass's grid; 0: eight workgroups per CU
   int jac_blocks = 8;            // persistent grid of the solve's Jacobian pass (the cost partials' count)
   int jac_blocks_rec = 8;        // ... of the record-writing variant (evaluate API, bench roofline)
 };
 
-inline ProblemPlan plan_problem(const ProblemShape& sh, bool sharded, const SolveKnobs& k) {
+inline ProblemPlan plan_problem(const ProblemShape& sh, const SolveKnobs& k) {
   ProblemPlan p;
   // multiples of 8 (one point slice per XCD); the record-free pass of the
   // solve (no 160-B stores) prefers the larger grid: 256 workgroups per XCD,
@@ -171,8 +163,6 @@ inline ProblemPlan plan_problem(const ProblemShape& sh, bool sharded, const Solv
   p.large_system = sh.n_blk() > kSchurXcdMinBlocks;
   p.xcd_block_order = p.large_system && !p.small_setup;
   p.pm_backsub = p.large_system && sh.C <= kCamPMMax;
-  p.eu_cm = k.eu_cm;
-  p.overlap = k.overlap && sh.chol_tiles() > 2 && !sharded ? 1 : 0;
   p.force_pack = k.force_pack;
   p.schur_wgs = k.schur_wgs;
   return p;
@@ -215,9 +205,8 @@ enum class PointPass {
 };
 // the Schur pair pass (the off-diagonal blocks)
 enum class PairPass {
-  WgBlocks,       // k_schur_pts<64, 4>: a workgroup per block (not overlapped: with the diagonal blocks, DiagFold)
+  WgBlocks,       // k_schur_pts<64, 4>: a workgroup per block, with the diagonal blocks (DiagFold)
   Pts,            // k_schur_pts<sub>
-  Rot,            // k_schur_pairs_rot<sub>
   RotPersistent,  // k_cam_stage_rot<sub> unless the evaluation staged the cameras, then k_schur_pairs_rot_pw<sub>
 };
 enum class Backsub {
@@ -244,7 +233,6 @@ struct SolvePlan {
   PointPass point_pass = PointPass::Lds64;  // (run while pts_var; its point factor folded in: prep_folded)
   bool stage_cams = false;                  // k_cam_sum_diag also leaves the cameras' staged records (camS)
   // step
-  bool overlapped = false;  // the factor on its own stream beside the pair pass
   PairPass pair_pass = PairPass::Pts;
   bool cam_records_used = false;  // the pair pass reads camS
   bool dist_factor = false;       // the distributed factor's panel loop
@@ -299,10 +287,7 @@ inline SolvePlan plan_solve(const ProblemPlan& pp, const SolveShape& sh, int32_t
   s.point_pass = C <= 64 ? PointPass::Lds64
                  : C <= 512 && !k.pe_groups1 ? PointPass::Lds512x2
                  : C <= 512 ? PointPass::Lds512 : PointPass::Rc;
-  s.overlapped = both && pp.overlap && C > 0 && !sharded && !pp.force_pack;
-  s.pair_pass = pp.schur_wg_blocks ? PairPass::WgBlocks
-                : pp.large_system && pp.xcd_block_order && !s.overlapped ? PairPass::RotPersistent
-                : pp.large_system ? PairPass::Rot : PairPass::Pts;
+  s.pair_pass = pp.schur_wg_blocks ? PairPass::WgBlocks : pp.large_system ? PairPass::RotPersistent : PairPass::Pts;
   s.cam_records_used = C > 0 && pp.large_system && pp.xcd_block_order && !pp.schur_wg_blocks;
   s.stage_cams = s.cam_pass == CamPass::JacObsPrep && s.cam_records_used;
   s.pack_allreduce = sharded || pp.force_pack;

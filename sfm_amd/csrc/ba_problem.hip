@@ -113,7 +113,7 @@ size_t wm_waves(int P) { return (size_t(P) + 63) / 64; }
 // The problem's plan from what the setup knows so far: after the camera runs
 // (the counts that come back from the layouts still open), and again once
 // the pair count and the wave-major slot total are in.
-void plan_from_shape(Setup& c) { c.d.plan = plan_problem(c.shape, sharded(c.h), c.h->knobs); }
+void plan_from_shape(Setup& c) { c.d.plan = plan_problem(c.shape, c.h->knobs); }
 
 // Any failure returns through here: the buffers go back to the pool.
 struct ProblemGuard {
@@ -633,7 +633,7 @@ int pair_lists_sorted(Setup& c) {
 int alloc_solver_arrays(Setup& c) {
   sfm_ba_handle* h = c.h;
   DevProblem& d = c.d;
-  const size_t C = size_t(c.C), P = size_t(c.P), N = size_t(c.N), npad = size_t(d.N_pad);
+  const size_t C = size_t(c.C), P = size_t(c.P), npad = size_t(d.N_pad);
   d.n = 6 * c.C;
   d.ld = ((d.n + 1 + kNB - 1) / kNB) * kNB;
   d.nblk = d.ld / kNB;
@@ -641,17 +641,16 @@ int alloc_solver_arrays(Setup& c) {
   d.max_blocks = max_blocks(c.shape, pp, d.xcd_slice_max);
   if (c.plan.route == ParamRoute::Late || c.plan.route == ParamRoute::None)
     if (int rc = alloc_params(c)) return rc;
-  // eu (plan.eu_cm): pass A stores u at the camera-major position it runs at
-  // (coalesced) and pass B gathers it through pos[]: 85 + 31 -> 60 + 41 us per
-  // C3 iteration against the point-major scatter (SFM_EU_CM=0), S and steps
-  // bitwise equal
+  // eu: pass A stores u at the camera-major position it runs at (coalesced)
+  // and pass B gathers it through pos[]: 85 + 31 -> 60 + 41 us per C3
+  // iteration against a point-major scatter, S and steps bitwise equal
   d.ptG = nullptr;
   d.camS = nullptr;
   const size_t tiles = size_t(d.nblk) * d.nblk;
   bool ok = c.alloc(d.cam_new, 6 * C) && c.alloc(d.X_new, 3 * P) && c.alloc(d.scale_c, 6 * C) &&
             c.alloc(d.scale_p, 3 * P) && c.alloc(d.diag_c, 6 * C) && c.alloc(d.diag_p, 3 * P) &&
             c.alloc(d.camR, size_t(kCamR) * C) && c.alloc(d.camRn, 12 * C) &&
-            c.alloc(d.eu, size_t(kEU) * (pp.eu_cm ? npad : N)) && c.alloc(d.ypt, 3 * P) &&
+            c.alloc(d.eu, size_t(kEU) * npad) && c.alloc(d.ypt, 3 * P) &&
             c.alloc(d.ptV, size_t(kPtV) * P) && c.alloc(d.ptL, size_t(kPtL) * P) &&
             c.alloc(d.ptS, size_t(kPtS) * std::max<size_t>(1, P)) &&
             (!pp.large_system || c.alloc(d.ptG, size_t(kPtG) * std::max<size_t>(1, P))) &&
@@ -663,21 +662,6 @@ int alloc_solver_arrays(Setup& c) {
             c.alloc(d.cflags, 2 * tiles) &&
             c.alloc(d.cticket, 5);  // task ticket, walker-role ticket, back-substitution role ticket, a panel's two
   if (!ok) return c.rc;
-  // Schur / Cholesky overlap (SFM_OVERLAP=1; unsharded, more than two tiles):
-  // per 64x64 tile of S the number of camera blocks (c1 <= c2, stored at
-  // rows 6 c2.., columns 6 c1..) whose 6x6 footprint touches it.  (The
-  // round-4 mode 2, a full helper grid placed as the Schur pass retires,
-  // relied on the dispatcher starting the Schur pass's workgroups first:
-  // not guaranteed, and seen to time out the factor, so removed.)
-  if (pp.overlap) {
-    if (!(c.alloc(d.tile_cnt, tiles) && c.alloc(d.tile_exp, tiles))) return c.rc;
-    std::vector<int32_t> te(tiles, 0);
-    for (int c1 = 0; c1 < c.C; ++c1)
-      for (int c2 = c1; c2 < c.C; ++c2)
-        for (int I = 6 * c2 / kNB; I <= (6 * c2 + 5) / kNB; ++I)
-          for (int J = 6 * c1 / kNB; J <= (6 * c1 + 5) / kNB; ++J) ++te[size_t(I) * d.nblk + J];
-    HIPCHK(hipMemcpy(d.tile_exp, te.data(), sizeof(int32_t) * te.size(), hipMemcpyHostToDevice));
-  }
   ok = c.alloc(d.ysol, size_t(d.ld)) && c.alloc(d.fail, size_t(1)) &&
        c.alloc(d.partials, size_t(kNumPartialSlots) * d.max_blocks) &&
        c.alloc(d.scal, size_t(kNumScalars) + 1);  // + the Cholesky failure int (k_reduce_batch)

@@ -73,23 +73,21 @@ namespace {
 constexpr size_t kParamPrefetchMaxBytes = size_t(1) << 20;  // one-shot solves that prefetch their parameters
 
 // ---- phase timing (HIP events on the solver stream; read at the per-iteration sync)
-int mark_begin(sfm_ba_handle* h, int ph, hipStream_t on = nullptr) {
-  if (!h->profiling) return -1;
+void mark_begin(sfm_ba_handle* h, int ph) {
+  if (!h->profiling) return;
   if (h->ev_used + 2 > int(h->ev.size())) {
     const size_t old = h->ev.size();
     h->ev.resize(old + 256);
     for (size_t i = old; i < h->ev.size(); ++i) hipEventCreate(&h->ev[i]);
   }
   h->ev_marks.push_back({ph, h->ev_used});
-  hipEventRecord(h->ev[h->ev_used], on ? on : h->stream);
+  hipEventRecord(h->ev[h->ev_used], h->stream);
   h->ev_used += 2;
-  return int(h->ev_marks.size()) - 1;
 }
-// ends mark `m` (default: the last one begun)
-void mark_end(sfm_ba_handle* h, hipStream_t on = nullptr, int m = -1) {
+// ends the last mark begun
+void mark_end(sfm_ba_handle* h) {
   if (!h->profiling) return;
-  const auto& mk = m < 0 ? h->ev_marks.back() : h->ev_marks[size_t(m)];
-  hipEventRecord(h->ev[mk.second + 1], on ? on : h->stream);
+  hipEventRecord(h->ev[h->ev_marks.back().second + 1], h->stream);
 }
 void collect_marks(sfm_ba_handle* h) {
   if (!h->profiling) return;
@@ -672,39 +670,12 @@ int compute_step_enqueue(sfm_ba_handle* h, double radius) {
   auto schur_diag = [&] {
     if (redo_prep) launch_schur_diag(d, radius, h->rank == 0, s);
   };
-  if (p.overlapped) {
-    // Schur / Cholesky overlap: the diagonal blocks and rhs first, then the
-    // factorisation on its own stream with half the CUs while k_schur_pts
-    // fills the off-diagonal blocks on the other half, in camera-major order
-    // (the factor's tile columns complete left to right); a helper reads an
-    // S tile once k_schur_pts has counted all its camera blocks in
-    point_prep();
-    if (!h->stream2) {
-      HIPCHK(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&h->ov_ev[0], hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&h->ov_ev[1], hipEventDisableTiming));
-    }
-    const int m_schur = mark_begin(h, kPhSchur);
-    HIPCHK(hipMemsetAsync(d.tile_cnt, 0, sizeof(int32_t) * size_t(d.nblk) * d.nblk, s));
-    schur_diag();
-    HIPCHK(hipEventRecord(h->ov_ev[0], s));
-    HIPCHK(hipStreamWaitEvent(h->stream2, h->ov_ev[0], 0));
-    mark_begin(h, kPhChol, h->stream2);
-    launch_cholesky(d, ++h->chol_epoch, h->stream2, false, -1, d.plan.overlap);
-    mark_end(h, h->stream2);
-    launch_schur_offdiag(d, p.pair_pass, true, s);
-    HIPCHK(hipEventRecord(h->ov_ev[1], h->stream2));
-    HIPCHK(hipStreamWaitEvent(s, h->ov_ev[1], 0));
-    mark_end(h, nullptr, m_schur);  // (after the join: the Schur phase spans the overlapped factor)
-    mark_begin(h, kPhBack);
-    launch_backsolve(d, ++h->bs_epoch, s, true);
-    mark_end(h);
-  } else if (p.mode == SFM_BA_STRUCT_AND_POSE) {
+  if (p.mode == SFM_BA_STRUCT_AND_POSE) {
     point_prep();
     mark_begin(h, kPhSchur);
     if (p.prep_folded) {  // (never a block-per-workgroup system: launch_schur's two parts)
       schur_diag();
-      launch_schur_offdiag(d, p.pair_pass, false, s, h->cams_staged);
+      launch_schur_offdiag(d, p.pair_pass, s, h->cams_staged);
     } else {
       launch_schur(d, p.pair_pass, radius, h->rank == 0, s);
     }
@@ -1099,12 +1070,6 @@ int sfm_ba_destroy(sfm_ba_handle* h) {
   }
   for (hipEvent_t e : h->dist.ev_red) hipEventDestroy(e);
   if (h->dist.ev_sent) hipEventDestroy(h->dist.ev_sent);
-  if (h->stream2) {
-    hipStreamSynchronize(h->stream2);
-    hipStreamDestroy(h->stream2);
-    hipEventDestroy(h->ov_ev[0]);
-    hipEventDestroy(h->ov_ev[1]);
-  }
   if (h->ustream) {
     hipStreamSynchronize(h->ustream);
     hipStreamDestroy(h->ustream);

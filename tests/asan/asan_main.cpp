@@ -482,7 +482,8 @@ static ProblemShape plan_shape(int C, int P, bool small_fits = false, int64_t pa
   const int64_t per_cam = C ? (sh.N + C - 1) / C : 0;
   sh.n_jchunks = int(C * ((per_cam + 63) / 64));
   sh.N_pad = 64 * int64_t(sh.n_jchunks);
-  sh.host_counts = sh.small_fits = small_fits;
+  sh.host_counts = small_fits;
+  sh.small_fits = small_fits && sh.n_blk() <= sfm::kSchurXcdMinBlocks;  // (hostlayout::small_setup_fits' bound)
   sh.n_pairs = pairs_per_blk * sh.n_blk();
   sh.wm_slots = int64_t((P + 63) / 64) * v;
   return sh;
@@ -490,15 +491,15 @@ static ProblemShape plan_shape(int C, int P, bool small_fits = false, int64_t pa
 static bool same_plan(const ProblemPlan& a, const ProblemPlan& b) {
   return a.small_setup == b.small_setup && a.wave_major == b.wave_major && a.schur_pts_sub == b.schur_pts_sub &&
          a.schur_wg_blocks == b.schur_wg_blocks && a.large_system == b.large_system &&
-         a.xcd_block_order == b.xcd_block_order && a.pm_backsub == b.pm_backsub && a.eu_cm == b.eu_cm &&
-         a.overlap == b.overlap && a.force_pack == b.force_pack && a.schur_wgs == b.schur_wgs &&
+         a.xcd_block_order == b.xcd_block_order && a.pm_backsub == b.pm_backsub &&
+         a.force_pack == b.force_pack && a.schur_wgs == b.schur_wgs &&
          a.jac_blocks == b.jac_blocks && a.jac_blocks_rec == b.jac_blocks_rec;
 }
 static bool same_plan(const SolvePlan& a, const SolvePlan& b) {
   return a.mode == b.mode && a.cams_var == b.cams_var && a.pts_var == b.pts_var && a.sharded == b.sharded &&
          a.lm == b.lm && a.lm_batch == b.lm_batch && a.prep_folded == b.prep_folded && a.cam_sums == b.cam_sums &&
          a.cam_pass == b.cam_pass && a.point_pass == b.point_pass && a.stage_cams == b.stage_cams &&
-         a.overlapped == b.overlapped && a.pair_pass == b.pair_pass && a.cam_records_used == b.cam_records_used &&
+         a.pair_pass == b.pair_pass && a.cam_records_used == b.cam_records_used &&
          a.dist_factor == b.dist_factor && a.pack_allreduce == b.pack_allreduce && a.backsub == b.backsub &&
          a.nb_cost == b.nb_cost && a.nb_grad_cam == b.nb_grad_cam && a.nb_cam == b.nb_cam && a.nb_pt == b.nb_pt &&
          a.nb_obs == b.nb_obs && a.nb_back == b.nb_back;
@@ -520,39 +521,49 @@ static void check_solve_plan() {
     g_env.clear();
     sfm::read_knobs(&k, sfm::kKnobsProblem | sfm::kKnobsSolve, fake_env);
     CHECK(k.small_setup && k.pm_wave_major && k.schur_pts_sub == 0 && k.schur_wg == -1 && k.schur_wgs == 0 &&
-          k.eu_cm && !k.overlap && !k.force_pack && k.jac_wg_per_xcd == 0 && !k.eval_split && !k.pe_groups1 &&
+          !k.force_pack && k.jac_wg_per_xcd == 0 && !k.eval_split && !k.pe_groups1 &&
           !k.host_lm && !k.lm_unfused && !k.no_accept_fold && k.lm_batch == 0);
     g_env = {{"SFM_SMALL_SETUP", "0"},  {"SFM_PM_WAVE_MAJOR", "00"},  {"SFM_SCHUR_PTS_SUB", "7"},
-             {"SFM_SCHUR_WG", "0"},     {"SFM_SCHUR_WGS", "9"},       {"SFM_EU_CM", "0"},
-             {"SFM_OVERLAP", "2"},      {"SFM_FORCE_PACK", "1"},      {"SFM_JAC_WG_PER_XCD", "64"},
+             {"SFM_SCHUR_WG", "0"},     {"SFM_SCHUR_WGS", "9"},
+             {"SFM_FORCE_PACK", "1"},   {"SFM_JAC_WG_PER_XCD", "64"},
              {"SFM_EVAL_SPLIT", "1"},   {"SFM_PE_GROUPS1", "1"},      {"SFM_HOST_LM", "1"},
              {"SFM_LM_UNFUSED", "1"},   {"SFM_NO_ACCEPT_FOLD", "1x"}, {"SFM_LM_BATCH", "100"}};
     sfm::read_knobs(&k, sfm::kKnobsProblem | sfm::kKnobsSolve, fake_env);
     CHECK(!k.small_setup && !k.pm_wave_major && k.schur_pts_sub == 16 && k.schur_wg == 0 && k.schur_wgs == 16 &&
-          !k.eu_cm && k.overlap && k.force_pack && k.jac_wg_per_xcd == 64 && k.eval_split && k.pe_groups1 &&
+          k.force_pack && k.jac_wg_per_xcd == 64 && k.eval_split && k.pe_groups1 &&
           k.host_lm && k.lm_unfused && k.no_accept_fold && k.lm_batch == 64);
     // "off unless 0" against "on only at 1"; numbers that do not count; the clamps
     g_env = {{"SFM_SMALL_SETUP", "no"}, {"SFM_PM_WAVE_MAJOR", ""},   {"SFM_SCHUR_PTS_SUB", "64"},
-             {"SFM_SCHUR_WG", "1"},     {"SFM_SCHUR_WGS", "-5"},     {"SFM_EU_CM", "1"},
-             {"SFM_OVERLAP", "0"},      {"SFM_FORCE_PACK", "2"},     {"SFM_JAC_WG_PER_XCD", "-3"},
+             {"SFM_SCHUR_WG", "1"},     {"SFM_SCHUR_WGS", "-5"},
+             {"SFM_FORCE_PACK", "2"},   {"SFM_JAC_WG_PER_XCD", "-3"},
              {"SFM_EVAL_SPLIT", "0"},   {"SFM_PE_GROUPS1", "yes"},   {"SFM_HOST_LM", ""},
              {"SFM_LM_UNFUSED", "01"},  {"SFM_NO_ACCEPT_FOLD", "0"}, {"SFM_LM_BATCH", "0"}};
     sfm::read_knobs(&k, sfm::kKnobsProblem | sfm::kKnobsSolve, fake_env);
     CHECK(k.small_setup && k.pm_wave_major && k.schur_pts_sub == 64 && k.schur_wg == 1 && k.schur_wgs == 0 &&
-          k.eu_cm && !k.overlap && !k.force_pack && k.jac_wg_per_xcd == 0 && !k.eval_split && !k.pe_groups1 &&
+          !k.force_pack && k.jac_wg_per_xcd == 0 && !k.eval_split && !k.pe_groups1 &&
           !k.host_lm && !k.lm_unfused && !k.no_accept_fold && k.lm_batch == 1);
     g_env = {{"SFM_SCHUR_WGS", "1000000"}, {"SFM_HOST_LM", "1"}};
     sfm::read_knobs(&k, sfm::kKnobsProblem, fake_env);  // the problem's half alone
     CHECK(k.schur_wgs == 65536 / 8 * 8 && !k.host_lm && k.schur_pts_sub == 0);
+    // the retired switches (the Schur / Cholesky overlap, the point-major u
+    // scatter) select nothing any more: the plans of the empty environment
+    for (const ProblemShape& sh : {plan_shape(130, 1025), plan_shape(60, 1025)}) {
+      SolveKnobs kr;
+      g_env = {{"SFM_OVERLAP", "1"}, {"SFM_EU_CM", "0"}};
+      sfm::read_knobs(&kr, sfm::kKnobsProblem | sfm::kKnobsSolve, fake_env);
+      const ProblemPlan pr = sfm::plan_problem(sh, kr), p0 = sfm::plan_problem(sh, k0);
+      CHECK(same_plan(pr, p0));
+      CHECK(same_plan(solve_plan(sh, pr, SP, kNoComm, 0, kr), solve_plan(sh, p0, SP)));
+    }
     g_env.clear();
   }
   // ---- literal rows ----
   // empty sides: nothing divides by zero, the launchers' size guards do the rest
   {
     ProblemShape sh = plan_shape(0, 10);  // no cameras (so no observations)
-    ProblemPlan pp = sfm::plan_problem(sh, false, k0);
+    ProblemPlan pp = sfm::plan_problem(sh, k0);
     ProblemPlan e;
-    CHECK(same_plan(pp, e));  // all defaults: grids of 8, 8 lanes, nothing large, eu_cm
+    CHECK(same_plan(pp, e));  // all defaults: grids of 8, 8 lanes, nothing large
     SolvePlan s = solve_plan(sh, pp, SP), es;
     es.lm = LmDriver::DeviceFused;  // (AcceptFold needs a camera)
     es.cam_sums = CamSums::SumFinalize;
@@ -560,7 +571,7 @@ static void check_solve_plan() {
     es.nb_back = 8;
     CHECK(same_plan(s, es));
     sh = plan_shape(10, 0);  // no points
-    pp = sfm::plan_problem(sh, false, k0);
+    pp = sfm::plan_problem(sh, k0);
     CHECK(same_plan(pp, e));
     s = solve_plan(sh, pp, SP);
     es = SolvePlan();
@@ -570,14 +581,14 @@ static void check_solve_plan() {
     es.nb_grad_cam = 10;
     CHECK(same_plan(s, es));
     sh = ProblemShape();  // nothing at all, the counts never made
-    pp = sfm::plan_problem(sh, false, k0);
+    pp = sfm::plan_problem(sh, k0);
     CHECK(same_plan(pp, e));
     CHECK(sfm::max_blocks(sh, pp, 0) == 8);
   }
   // C = 64 / 65: the camera sums leave the point pass, the step's prep folds
   {
     ProblemShape sh = plan_shape(64, 1025);
-    ProblemPlan pp = sfm::plan_problem(sh, false, k0);
+    ProblemPlan pp = sfm::plan_problem(sh, k0);
     ProblemPlan e;
     e.wave_major = true;
     e.jac_blocks = e.jac_blocks_rec = 32;  // 128 chunks: (128 / 8 + 3) / 4 = 4 workgroups per XCD
@@ -593,7 +604,7 @@ static void check_solve_plan() {
     es.nb_back = 8;
     CHECK(same_plan(s, es));
     sh = plan_shape(65, 1025);
-    pp = sfm::plan_problem(sh, false, k0);
+    pp = sfm::plan_problem(sh, k0);
     e.jac_blocks = e.jac_blocks_rec = 16;  // 65 chunks: (65 / 8 + 3) / 4 = 2
     CHECK(same_plan(pp, e));
     s = solve_plan(sh, pp, SP);
@@ -610,7 +621,7 @@ static void check_solve_plan() {
   // C = 127 / 128: 8128 / 8256 camera blocks against kSchurXcdMinBlocks = 8192
   {
     ProblemShape sh = plan_shape(127, 1025);
-    ProblemPlan pp = sfm::plan_problem(sh, false, k0);
+    ProblemPlan pp = sfm::plan_problem(sh, k0);
     ProblemPlan e;
     e.wave_major = true;
     e.jac_blocks = e.jac_blocks_rec = 32;  // 127 chunks: (127 / 8 + 3) / 4 = 4
@@ -630,7 +641,7 @@ static void check_solve_plan() {
     es.nb_back = 8;
     CHECK(same_plan(s, es));
     sh = plan_shape(128, 1025);
-    pp = sfm::plan_problem(sh, false, k0);
+    pp = sfm::plan_problem(sh, k0);
     e.large_system = e.xcd_block_order = e.pm_backsub = true;  // ptG, camS, bperm, srec wanted
     CHECK(same_plan(pp, e));                                   // (128 chunks: 4 workgroups per XCD again)
     s = solve_plan(sh, pp, SP);
@@ -640,16 +651,12 @@ static void check_solve_plan() {
     es.nb_grad_cam = 128;
     es.nb_obs = es.nb_back = 5;  // the one pass: per 256 points
     CHECK(same_plan(s, es));
-    // ... on the small setup path: no XCD slot order, so no slot records, so not persistent
+    // ... which the small setup path never takes (hostlayout::small_setup_fits):
+    // the same plans where the host counted the observations
     sh = plan_shape(128, 1025, true);
-    pp = sfm::plan_problem(sh, false, k0);
-    e.small_setup = true;
-    e.wave_major = e.xcd_block_order = false;
+    pp = sfm::plan_problem(sh, k0);
     CHECK(same_plan(pp, e));
-    s = solve_plan(sh, pp, SP);
-    es.stage_cams = es.cam_records_used = false;
-    es.pair_pass = PairPass::Rot;
-    CHECK(same_plan(s, es));
+    CHECK(same_plan(solve_plan(sh, pp, SP), es));
   }
   // the accept fold's edge: C <= 256 and 3 P <= 24576
   {
@@ -672,7 +679,7 @@ static void check_solve_plan() {
                         {257, 8193, 128, 2, 33, LmDriver::DeviceFused}};
     for (const Row& r : rows) {
       const ProblemShape sh = plan_shape(r.C, r.P);
-      const ProblemPlan pp = sfm::plan_problem(sh, false, k0);
+      const ProblemPlan pp = sfm::plan_problem(sh, k0);
       e.jac_blocks = e.jac_blocks_rec = r.jac;  // (the record-writing grid's cap is 128 per XCD: not reached)
       CHECK(same_plan(pp, e));
       es.lm = r.lm;
@@ -686,7 +693,7 @@ static void check_solve_plan() {
   // C = 512 / 513: the cameras leave the LDS of the point pass and of k_backsub_pm
   {
     ProblemShape sh = plan_shape(512, 8193);
-    ProblemPlan pp = sfm::plan_problem(sh, false, k0);
+    ProblemPlan pp = sfm::plan_problem(sh, k0);
     ProblemPlan e;
     e.wave_major = e.large_system = e.xcd_block_order = e.pm_backsub = true;
     e.jac_blocks = e.jac_blocks_rec = 256;  // 1024 chunks: (1024 / 8 + 3) / 4 = 32
@@ -705,7 +712,7 @@ static void check_solve_plan() {
     es.nb_pt = es.nb_obs = es.nb_back = 33;
     CHECK(same_plan(s, es));
     sh = plan_shape(513, 8193);
-    pp = sfm::plan_problem(sh, false, k0);
+    pp = sfm::plan_problem(sh, k0);
     e.pm_backsub = false;
     e.jac_blocks = e.jac_blocks_rec = 128;  // 513 chunks: (513 / 8 + 3) / 4 = 16
     CHECK(same_plan(pp, e));
@@ -730,7 +737,7 @@ static void check_solve_plan() {
   // takes the diagonal blocks itself)
   {
     const ProblemShape sh = plan_shape(70, 1025, false, 460);
-    const ProblemPlan pp = sfm::plan_problem(sh, false, k0);
+    const ProblemPlan pp = sfm::plan_problem(sh, k0);
     ProblemPlan e;
     e.wave_major = true;
     e.schur_pts_sub = 64;                   // 8 -> 64 while below 460 / 10
@@ -738,7 +745,7 @@ static void check_solve_plan() {
     CHECK(same_plan(pp, e));                // 2485 blocks: above the 1024 of the shape's own choice
     SolveKnobs k;
     k.schur_wg = 1;
-    const ProblemPlan pw = sfm::plan_problem(sh, false, k);
+    const ProblemPlan pw = sfm::plan_problem(sh, k);
     e.schur_wg_blocks = true;
     CHECK(same_plan(pw, e));
     SolvePlan es;
@@ -757,7 +764,7 @@ static void check_solve_plan() {
   }
   // the three modes, the collectives and every switch alone at C = 130, P = 1025
   const ProblemShape sh130 = plan_shape(130, 1025);
-  const ProblemPlan pp130 = sfm::plan_problem(sh130, false, k0);
+  const ProblemPlan pp130 = sfm::plan_problem(sh130, k0);
   ProblemPlan ep;
   ep.wave_major = ep.large_system = ep.xcd_block_order = ep.pm_backsub = true;
   ep.jac_blocks = ep.jac_blocks_rec = 32;  // 130 chunks: (130 / 8 + 3) / 4 = 4
@@ -797,10 +804,9 @@ static void check_solve_plan() {
   }
   {
     // sharded: a collective between the camera sums and their use, and between
-    // a phase's reduction and the bookkeeping; no overlap even when asked for
+    // a phase's reduction and the bookkeeping
     SolveKnobs ko;
-    ko.overlap = true;
-    const ProblemPlan ps = sfm::plan_problem(sh130, true, ko);
+    const ProblemPlan ps = sfm::plan_problem(sh130, ko);
     CHECK(same_plan(ps, ep));
     SolvePlan e = e130;
     e.sharded = e.pack_allreduce = true;
@@ -822,47 +828,37 @@ static void check_solve_plan() {
     // the problem's switches, one at a time
     SolveKnobs k = k0;
     k.small_setup = false;  // (not a small-path problem)
-    CHECK(same_plan(sfm::plan_problem(sh130, false, k), ep));
+    CHECK(same_plan(sfm::plan_problem(sh130, k), ep));
     const ProblemShape sm = plan_shape(20, 1025, true, 460);  // ... and one that is
-    CHECK(sfm::plan_problem(sm, false, k0).small_setup && !sfm::plan_problem(sm, false, k0).wave_major);
-    CHECK(!sfm::plan_problem(sm, false, k).small_setup && sfm::plan_problem(sm, false, k).wave_major);
-    CHECK(sfm::plan_problem(sm, false, k0).schur_wg_blocks);  // 210 blocks of 460 pairs
+    CHECK(sfm::plan_problem(sm, k0).small_setup && !sfm::plan_problem(sm, k0).wave_major);
+    CHECK(!sfm::plan_problem(sm, k).small_setup && sfm::plan_problem(sm, k).wave_major);
+    CHECK(sfm::plan_problem(sm, k0).schur_wg_blocks);  // 210 blocks of 460 pairs
     ProblemPlan e = ep;
     k = k0, k.pm_wave_major = false, e.wave_major = false;
-    CHECK(same_plan(sfm::plan_problem(sh130, false, k), e));
+    CHECK(same_plan(sfm::plan_problem(sh130, k), e));
     e = ep, k = k0, k.schur_pts_sub = 32, e.schur_pts_sub = 32;
-    CHECK(same_plan(sfm::plan_problem(sh130, false, k), e));
+    CHECK(same_plan(sfm::plan_problem(sh130, k), e));
     e = ep, k = k0, k.schur_wg = 1;  // (only 64 lanes take workgroup blocks)
-    CHECK(same_plan(sfm::plan_problem(sh130, false, k), e));
+    CHECK(same_plan(sfm::plan_problem(sh130, k), e));
     e = ep, k = k0, k.schur_wgs = 16, e.schur_wgs = 16;
-    CHECK(same_plan(sfm::plan_problem(sh130, false, k), e));
-    e = ep, k = k0, k.eu_cm = false, e.eu_cm = false;
-    CHECK(same_plan(sfm::plan_problem(sh130, false, k), e));
+    CHECK(same_plan(sfm::plan_problem(sh130, k), e));
     e = ep, k = k0, k.jac_wg_per_xcd = 2, e.jac_blocks = 16;
-    CHECK(same_plan(sfm::plan_problem(sh130, false, k), e));
+    CHECK(same_plan(sfm::plan_problem(sh130, k), e));
     SolvePlan es = e130;
     es.nb_cost = 16;
-    CHECK(same_plan(solve_plan(sh130, sfm::plan_problem(sh130, false, k), SP), es));
-    e = ep, k = k0, k.overlap = true, e.overlap = 1;  // 13 tile rows
-    CHECK(same_plan(sfm::plan_problem(sh130, false, k), e));
-    es = e130, es.overlapped = true, es.pair_pass = PairPass::Rot;  // (the records are still staged, as before)
-    CHECK(same_plan(solve_plan(sh130, e, SP), es));
-    CHECK(!sfm::plan_problem(plan_shape(21, 1025), false, k).overlap);  // 126 unknowns + rhs: two tile rows
-    CHECK(sfm::plan_problem(plan_shape(22, 1025), false, k).overlap == 1);
-    k.force_pack = true, e.force_pack = true;  // both: the packed path wins
-    es = e130, es.pack_allreduce = true;
-    CHECK(same_plan(solve_plan(sh130, sfm::plan_problem(sh130, false, k), SP), es));
+    CHECK(same_plan(solve_plan(sh130, sfm::plan_problem(sh130, k), SP), es));
     e = ep, k = k0, k.force_pack = true, e.force_pack = true;
-    CHECK(same_plan(sfm::plan_problem(sh130, false, k), e));
+    es = e130, es.pack_allreduce = true;
+    CHECK(same_plan(sfm::plan_problem(sh130, k), e));
     CHECK(same_plan(solve_plan(sh130, e, SP), es));
     // the wave-major stream's cap, once its slots are counted
     ProblemShape pad = sh130;
     pad.wm_slots = -1;
-    CHECK(sfm::plan_problem(pad, false, k0).wave_major);  // wanted until then
+    CHECK(sfm::plan_problem(pad, k0).wave_major);  // wanted until then
     pad.wm_slots = (3 * pad.N + 128 * 17) / 128;
-    CHECK(sfm::plan_problem(pad, false, k0).wave_major);
+    CHECK(sfm::plan_problem(pad, k0).wave_major);
     pad.wm_slots += 1;
-    CHECK(!sfm::plan_problem(pad, false, k0).wave_major);
+    CHECK(!sfm::plan_problem(pad, k0).wave_major);
   }
   {
     // the solve's switches, one at a time
@@ -890,8 +886,6 @@ static void check_solve_plan() {
   for (int wg : {0, 1}) with([wg](SolveKnobs& k) { k.schur_wg = wg; });
   with([](SolveKnobs& k) { k.schur_pts_sub = 64, k.schur_wg = 1; });  // (the pair that forces workgroup blocks)
   with([](SolveKnobs& k) { k.schur_wgs = 16; });
-  with([](SolveKnobs& k) { k.eu_cm = false; });
-  with([](SolveKnobs& k) { k.overlap = true; });
   with([](SolveKnobs& k) { k.force_pack = true; });
   with([](SolveKnobs& k) { k.jac_wg_per_xcd = 1; });
   with([](SolveKnobs& k) { k.jac_wg_per_xcd = 1000; });
@@ -908,7 +902,7 @@ static void check_solve_plan() {
         for (const SolveKnobs& k : knobs) {
           const ProblemShape sh = plan_shape(C, P, small != 0, C <= 64 ? 460 : 72);
           for (Comm comm : {kNoComm, kRccl, kHostCb}) {
-            const ProblemPlan pp = sfm::plan_problem(sh, comm != kNoComm, k);
+            const ProblemPlan pp = sfm::plan_problem(sh, k);
             CHECK(pp.schur_pts_sub == 8 || pp.schur_pts_sub == 16 || pp.schur_pts_sub == 32 || pp.schur_pts_sub == 64);
             CHECK(!pp.schur_wg_blocks || pp.schur_pts_sub == 64);
             CHECK(!pp.xcd_block_order || pp.large_system);
@@ -936,7 +930,6 @@ static void check_solve_plan() {
               CHECK(s.backsub != Backsub::OnePass || mode == SFM_BA_STRUCT_AND_POSE);
               CHECK(!s.fused_lm() || !s.sharded);
               CHECK(comm != kHostCb || s.lm == LmDriver::Host);
-              CHECK(!s.overlapped || (!s.sharded && !s.pack_allreduce && s.pair_pass != PairPass::RotPersistent));
               CHECK((s.cam_sums == CamSums::None) == !s.cams_var);
               for (int nb : {s.nb_cost, s.nb_grad_cam, s.nb_cam, s.nb_pt, s.nb_obs, s.nb_back})
                 CHECK(nb >= 1 && nb <= cap);

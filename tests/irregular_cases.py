@@ -1,6 +1,6 @@
 """Seeded scenes with the visibility a tracker produces, at the camera counts
 whose kernels the regular scenes alone reach (more than 64 cameras: the step
-preparation folded into the evaluation; from 128 on: k_schur_pairs_rot and
+preparation folded into the evaluation; from 128 on: k_schur_pairs_rot_pw and
 k_backsub_pm): points of every degree from 0 to nearly C, cameras without
 observations (the last block row of S among them), (camera, point) keys
 observed twice, observations in shuffled caller order.

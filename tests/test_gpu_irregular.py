@@ -4,7 +4,7 @@ observations (the last block row of S among them), 40 doubled (camera, point)
 keys, shuffled caller order -- where every other test of these paths has ten
 views per point, in generator order, and no camera twice.
 
-* 128+ cameras (irr_136, irr_136_big, rej_130_irr): k_schur_pairs_rot with
+* 128+ cameras (irr_136, irr_136_big, rej_130_irr): k_schur_pairs_rot_pw with
   empty, one-pair and 130-pair lists and same-camera pairs in its diagonal
   blocks, which k_cam_sum_diag (folded evaluation) or k_schur_diag_sum (the
   prep redone after a rejected step) write first; k_backsub_pm with points of
@@ -115,7 +115,7 @@ def test_evaluate_keeps_the_callers_order(name):
 
 @pytest.mark.parametrize("sub", [16, 32, 64])
 def test_other_lanes_per_block_match_oracle(sub, monkeypatch):
-    # k_schur_pairs_rot<16 / 32 / 64>: most lists (a mean of 9 pairs) shorter
+    # k_schur_pairs_rot_pw<16 / 32 / 64>: most lists (a mean of 9 pairs) shorter
     # than the lanes of a block, empty ones, the diagonal ones
     monkeypatch.setenv("SFM_SCHUR_PTS_SUB", str(sub))
     o, g = _oracle("irr_136"), _solve_device("irr_136")
@@ -166,7 +166,7 @@ def _branch_oracle(name):
 def test_rejected_steps_redo_the_prep(name, monkeypatch):
     """Five rejected steps in a row, then accepted ones: the stand-alone prep
     kernels rewrite the diagonal blocks that hold same-camera pairs (130
-    cameras: before k_schur_pairs_rot adds to them) for five stale radii."""
+    cameras: before k_schur_pairs_rot_pw adds to them) for five stale radii."""
     c = FIX[name]
     oracle = _branch_oracle(name)
     dev, host = H.solve_device_and_host(c, oracle[0], monkeypatch)

@@ -3,7 +3,7 @@
 against the point-major arrays it copies (SFM_PM_WAVE_MAJOR=0): bitwise the
 same solve, on both LM loops.
 
-Scenes: 130 cameras (the smallest count on the k_schur_pairs_rot / k_backsub_pm
+Scenes: 130 cameras (the smallest count on the k_schur_pairs_rot_pw / k_backsub_pm
 path), 1 / 63 / 65 / 257 / 1025 points -- one lane, one wave short of full, a
 second wave of one lane, a second 256-point block, a second workgroup of
 k_backsub_pm<4> -- with 2..12 views per point: 2 + ((p + 189) // 23) % 11, so a

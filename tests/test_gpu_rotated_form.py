@@ -1,7 +1,7 @@
 """The two kernels of large reduced systems against the oracle, and the small
 path's bits against fixtures recorded before they existed:
 
-* k_schur_pairs_rot, the off-diagonal Schur pass with the rotation columns
+* k_schur_pairs_rot_pw, the off-diagonal Schur pass with the rotation columns
   taken from the rotated point (j_k x (R X)), and
 * k_backsub_pm, the one-pass point-major back substitution (at most 512
   cameras, STRUCT_AND_POSE).
@@ -152,7 +152,7 @@ def test_gate_boundary(cams):
     # k_schur_pts and the three-pass back substitution -- that they do is
     # shown by test_127_cameras_are_bitwise_the_recorded_solve,
     # whose fixture the commit before these kernels recorded --, 128 (8256)
-    # and 129 cameras take k_schur_pairs_rot and k_backsub_pm
+    # and 129 cameras take k_schur_pairs_rot_pw and k_backsub_pm
     assert (cams * (cams + 1) // 2 > 8192) == (cams >= 128)
     s = _scene(cams, 10)
     o, g = _solve_both(s)
@@ -161,7 +161,7 @@ def test_gate_boundary(cams):
 
 @pytest.mark.parametrize("sub", [16, 32, 64])
 def test_other_lanes_per_block_match_oracle(sub, monkeypatch):
-    # k_schur_pairs_rot<16 / 32 / 64>: the camera staging's lane mapping and
+    # k_schur_pairs_rot_pw<16 / 32 / 64>: the camera staging's lane mapping and
     # ballot masks depend on the lanes per block (set_problem reads the override)
     monkeypatch.setenv("SFM_SCHUR_PTS_SUB", str(sub))
     o, g = _solve_both(_scene(136, 10), oracle=_oracle_136())

@@ -91,7 +91,7 @@ def test_regime_predicates(name):
     _, st, _, _, _ = _solved(name)
     C = st["n_cams"]
     assert st["n_blk"] == C * (C + 1) // 2
-    large = st["n_blk"] > IC.K_SCHUR_XCD_MIN_BLOCKS  # k_schur_pairs_rot, and k_backsub_pm while C <= kCamPMMax
+    large = st["n_blk"] > IC.K_SCHUR_XCD_MIN_BLOCKS  # k_schur_pairs_rot_pw, and k_backsub_pm while C <= kCamPMMax
     assert large == (name in ("irr_136", "irr_136_big", "rej_130_irr")) == (C >= 128)
     assert 64 < C <= IC.K_CAM_PM_MAX  # the evaluation prepares the step; every camera record fits the LDS
     assert (st["n_obs"] <= IC.K_HOST_CHECK_MAX_OBS) == (name != "irr_136_big")

@@ -1,12 +1,13 @@
-"""A/B workload: C3 set_problem + 3 resident solves; prints the final cost
-bits so ablation builds (SFM_AMD_LIB) can be checked bitwise against base."""
+"""A/B workload: set_problem + 3 resident solves of a bench configuration
+(the first argument; default C3); prints the final cost bits so ablation builds
+(SFM_AMD_LIB) can be checked bitwise against base."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sfm_amd
 from sfm_amd import scene as S
 
-sc = S.config("C3")
+sc = S.config(sys.argv[1] if len(sys.argv) > 1 else "C3")
 ba = sfm_amd.BundleAdjuster(0)
 ba.set_problem(sc.uv, sc.cam_idx, sc.pt_idx, sc.K, sc.rot, sc.t, sc.X)
 for _ in range(3):
