@@ -32,9 +32,11 @@ __device__ unsigned long long g_wstamp[256 * 16];
 __device__ unsigned long long g_hstamp[128 * 128 * 2];
 __device__ unsigned long long g_pstamp[256 * 4];  // per wave: the end of its panel-3 work
 __device__ unsigned long long g_bstamp[256 * 8];  // k_backsolve per block row (sfm_debug_bstamps)
-#define BSTAMP(b, k)                                                                          \
+// (by the first thread of the row's slot of its row group; BSTAMPV: a value)
+#define BSTAMP(b, k) BSTAMPV(b, k, __builtin_amdgcn_s_memrealtime())
+#define BSTAMPV(b, k, val)                                                                    \
   do {                                                                                        \
-    if (threadIdx.x == 0 && (b) < 256) g_bstamp[(b) * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); \
+    if ((threadIdx.x & 255) == 0 && (b) >= 0 && (b) < 256) g_bstamp[(b) * 8 + (k)] = (val);  \
   } while (0)
 #define WSTAMP(j, k)                                                                          \
   do {                                                                                        \
@@ -58,6 +60,7 @@ __device__ unsigned long long g_bstamp[256 * 8];  // k_backsolve per block row (
 #define HSTAMP(i, j, k) do { } while (0)
 #define PSTAMP(j, w) do { } while (0)
 #define BSTAMP(b, k) do { } while (0)
+#define BSTAMPV(b, k, val) do { } while (0)
 #endif
 // Test instantiations of the walker (SFM_CHOL_TEST_SKEW, tests/test_gpu_chol.py):
 // g_skew_steps[0] counts the steps that took the fast path (prefetched
@@ -88,6 +91,25 @@ __device__ __forceinline__ double bcast(double v, int src) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
   const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
   return __hiloint2double(hi, lo);
+}
+
+// v + its xor-1 partner's, then + the xor-2 partner's, within each quad of
+// lanes, by DPP quad_perm moves of the two halves of the double.  Both lanes
+// of a pair add the same two values, so the sums are bitwise those of
+// `v += __shfl_xor(v, 1); v += __shfl_xor(v, 2)` (ds_bpermute: an LDS
+// crossbar round trip per half and level) at a few cycles per level.  Every
+// lane of the wave must be active.
+template <int kCtrl>
+__device__ __forceinline__ double dpp_f64(double v) {
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), kCtrl, 0xF, 0xF, false);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), kCtrl, 0xF, 0xF, false);
+  return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double quad_sum(double v) {
+  constexpr int kQuadXor1 = 0xB1, kQuadXor2 = 0x4E;  // quad_perm:[1,0,3,2], [2,3,0,1]
+  v += dpp_f64<kQuadXor1>(v);
+  v += dpp_f64<kQuadXor2>(v);
+  return v;
 }
 
 // POTRF of one 64x64 tile plus its inverse W = L^-1, four wavefronts,
@@ -1283,7 +1305,7 @@ __global__ __launch_bounds__(256) void k_chol_fused(double* __restrict__ A, int 
 }
 
 // Back substitution L^T y = z (z = row n of the augmented factor, i.e.
-// L^-1 rhs), ONE launch: workgroup b owns block row b (64 unknowns),
+// L^-1 rhs), ONE launch: four waves own block row b (64 unknowns),
 //   y_b = W_b^T (z_b - sum_{k>b} L_kb^T y_k),
 // and every L_kb tile is prefetched before y_k is awaited.  The entries of
 // y are their own flags: y is filled with a signalling-NaN sentinel before
@@ -1293,39 +1315,123 @@ __global__ __launch_bounds__(256) void k_chol_fused(double* __restrict__ A, int 
 // LDS.  Against a flag after the data this drops the producer's drain and
 // the consumer's invalidate + reload: one memory round trip per hand-off
 // instead of three (127 -> 98 us at n = 3000 for LDS staging alone, see
-// DESIGN.md).  Chunked consumption or several blocks per workgroup measured
-// slower: whatever runs after the awaited block arrives is on the chain.
-// Rows go by start order (the chain's first row to the first workgroup to
-// run), so every awaited row belongs to a running workgroup whatever the
-// residency; every wait is bounded and a timeout sets bit 1 of *fail (an
-// error, never a hang).
+// DESIGN.md).  Chunked consumption measured slower: whatever runs after the
+// awaited block arrives is on the chain.
+//
+// Row groups: a workgroup of 256 R threads owns R consecutive block rows
+// (group g: rows nb - 1 - g R .. nb - R - g R), each with its own four
+// waves, W segment, accumulator and tile prefetch, exactly the single-row
+// kernel's (R = 1, the one the library launches: R = 2 measured slower, see
+// launch_backsolve).  Only the cross-CU hand-off is shared: the awaited y
+// arrives a group at a time (wave 0 of slot i polls row i of the awaited
+// group, the R polls in parallel, one barrier), every row applies the R
+// blocks in descending k (one FMA chain, the single-row order), and inside the
+// group a finished row reaches the row below through LDS, not memory.  Every
+// entry of y is the same operation sequence for every R.
+// Groups go by start order (the chain's first rows to the first workgroup
+// to run), so every awaited group belongs to a running workgroup whatever
+// the residency; every wait is bounded and a timeout sets bit 1 of *fail (an
+// error, never a hang); every barrier is reached by every wave on every path.
 
-__global__ __launch_bounds__(256) void k_backsolve(const double* __restrict__ A, int ld, int n, int nb,
-                                                   const double* __restrict__ Winv, double* __restrict__ y,
-                                                   int* __restrict__ fail, const int* __restrict__ gate,
-                                                   unsigned long long* __restrict__ rticket, int epoch) {
-  if (gate && *gate == 0) {  // device LM loop: phase skipped (its row tickets still taken)
-    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(rticket, (unsigned long long)nb);
+// acc + sum_i l[i] ys[i], i = 0 .. 15, one chain in that order.  The LDS
+// operands are read ahead of the first FMA (one wait, as mfma16's).
+__device__ __forceinline__ double chain16(const double (&l)[16], const double* ys, double acc) {
+  double yv[16];
+#pragma unroll
+  for (int i = 0; i < 16; i += 2) {
+    const double2 q = *reinterpret_cast<const double2*>(ys + i);
+    yv[i] = q.x;
+    yv[i + 1] = q.y;
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(yv[i]));
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc = fma(l[i], yv[i], acc);
+  return acc;
+}
+
+// A thread's 16 tile entries (column c, rows 16 seg .. +16 of a tile: 128
+// contiguous bytes) are loaded a quad to 64 contiguous bytes per
+// instruction: piece 4 i + seg (16 bytes) of the column's 512, i = 0 .. 7.
+// A wave's load then touches 16 lines, each by two neighbouring
+// instructions, where a load of the thread's own 128 bytes touches 64 lines
+// with every one of its eight instructions (with two rows' waves on a CU
+// those lines no longer stay in the L1 between the instructions).  The
+// pieces reach their threads through a wave-private LDS image, half a
+// column (segments 0, 1, then 2, 3) at a time; a wave's LDS operations run
+// in order, so this takes no barrier.  Data movement only.
+constexpr int kStageCol = 32 + 2;             // doubles per column of the image: half a column + one piece of padding
+constexpr int kStageWave = 16 * kStageCol;    // a wave holds 16 columns
+__device__ __forceinline__ void tile_issue(double (&g)[16], const double* colq, int seg) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const double2 q = *reinterpret_cast<const double2*>(colq + 8 * i + 2 * seg);
+    g[2 * i] = q.x;
+    g[2 * i + 1] = q.y;
+  }
+}
+__device__ __forceinline__ void tile_turn(double (&l)[16], const double (&g)[16], double* stage, int seg) {
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      *reinterpret_cast<double2*>(stage + 8 * i + 2 * seg) = make_double2(g[8 * half + 2 * i], g[8 * half + 2 * i + 1]);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if ((seg >> 1) == half) {
+#pragma unroll
+      for (int i = 0; i < 16; i += 2) {
+        const double2 q = *reinterpret_cast<const double2*>(stage + 16 * (seg & 1) + i);
+        l[i] = q.x;
+        l[i + 1] = q.y;
+      }
+    }
+  }
+}
+
+template <int R>
+__global__ __launch_bounds__(256 * R) void k_backsolve(const double* __restrict__ A, int ld, int n, int nb,
+                                                       const double* __restrict__ Winv, double* __restrict__ y,
+                                                       int* __restrict__ fail, const int* __restrict__ gate,
+                                                       unsigned long long* __restrict__ rticket, int epoch) {
+  const int ng = (nb + R - 1) / R;  // row groups = workgroups = tickets per launch
+  if (gate && *gate == 0) {  // device LM loop: phase skipped (its group tickets still taken)
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(rticket, (unsigned long long)ng);
     return;
   }
-  __shared__ double v[NB];
-  __shared__ double yl[2][NB];
+  __shared__ __attribute__((aligned(16))) double v[R][NB];
+  __shared__ __attribute__((aligned(16))) double yl[2][R][NB];  // the awaited group's y, double-buffered
+  __shared__ __attribute__((aligned(16))) double yg[R][NB];     // this group's finished rows, for the rows below
+  __shared__ __attribute__((aligned(16))) double stg[4 * R][kStageWave];  // tile_turn's image, per wave
   __shared__ int timed_out;
-  __shared__ int row;
-  // block row by start order: the chain's first row goes to the first
-  // workgroup to run, so every row a workgroup awaits belongs to one that
+  __shared__ int grp;
+  // row group by start order: the chain's first rows go to the first
+  // workgroup to run, so every group a workgroup awaits belongs to one that
   // is already running (any residency, any dispatch order)
-  if (threadIdx.x == 0) row = int(atomicAdd(rticket, 1ULL) - (unsigned long long)(epoch - 1) * (unsigned long long)nb);
+  if (threadIdx.x == 0) grp = int(atomicAdd(rticket, 1ULL) - (unsigned long long)(epoch - 1) * (unsigned long long)ng);
   __syncthreads();
-  const int b = nb - 1 - __builtin_amdgcn_readfirstlane(row);
+  const int g = __builtin_amdgcn_readfirstlane(grp);
+  // slot i = waves 4 i .. 4 i + 3 owns block row nb - 1 - g R - i; a slot
+  // past row 0 (the last group when R does not divide nb) only polls and
+  // keeps the barriers
+  const int slot = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 8);
+  const int b = nb - 1 - g * R - slot;
+  const bool live = b >= 0;
+  const bool poller = (__builtin_amdgcn_readfirstlane(threadIdx.x) & 255) < 64;  // scalar (see block_wait)
   const int k0 = b * NB;
   const int nreal = (n - k0) < NB ? (n - k0) : NB;
-  const int t = threadIdx.x, col = t >> 2, seg = t & 3;
-  if (t == 0) timed_out = 0;
+  const int t = threadIdx.x & 255, col = t >> 2, seg = t & 3;
+  if (threadIdx.x == 0) timed_out = 0;
+  BSTAMPV(b, 6, (unsigned long long)R);
+  BSTAMPV(b, 7, (unsigned long long)slot);
   // off the chain: z entry and the W_b column segment W(16 seg + i, col)
-  const double zc = (seg == 0 && col < nreal) ? A[size_t(k0 + col) * ld + n] : 0.0;
+  const double zc = (live && seg == 0 && col < nreal) ? A[size_t(k0 + col) * ld + n] : 0.0;
+  const double* colq = live ? A + size_t(k0 + col) * ld : A;  // column k0 + col: tile (k, b) at rows 64 k
+  double* stage = &stg[threadIdx.x >> 6][(col & 15) * kStageCol];
   double wr[16];
-  {
+  if (live) {
     const double* Wr = Winv + size_t(b) * NB * NB + size_t(col) * NB + 16 * seg;
 #pragma unroll
     for (int i = 0; i < 16; i += 2) {
@@ -1334,22 +1440,40 @@ __global__ __launch_bounds__(256) void k_backsolve(const double* __restrict__ A,
       wr[i + 1] = q.y;
     }
   }
+  // The tiles under this group's higher rows (lg[j]: tile (b + slot - j, b),
+  // j < slot) are fetched here, off the chain; the tiles under group h's rows
+  // are in flight (gq) from the top of iteration h - 1 on, a whole arrival
+  // ahead of their use.
+  double gq[R][16];
+  double lv[R][16];
+  double lg[R > 1 ? R - 1 : 1][16];
+  if (live) {
+#pragma unroll
+    for (int j = 0; j + 1 < R; ++j)
+      if (j < slot) tile_issue(gq[j], colq + size_t(nb - 1 - g * R - j) * NB, seg);
+#pragma unroll
+    for (int j = 0; j + 1 < R; ++j)
+      if (j < slot) tile_turn(lg[j], gq[j], stage, seg);
+    if (0 < g) {
+#pragma unroll
+      for (int j = 0; j < R; ++j) tile_issue(gq[j], colq + size_t(nb - 1 - j) * NB, seg);
+    }
+  }
   __syncthreads();
   double acc = 0.0;
-  // column k0 + col, rows 64 k + 16 seg .. +16 of tile (k, b)
-  const double* colp = A + size_t(k0 + col) * ld + 16 * seg;
-  for (int k = nb - 1; k > b; --k) {
-    double lv[16];
+  for (int h = 0; h < g; ++h) {
+    const int kt = nb - 1 - h * R;  // the awaited group's rows kt .. kt - R + 1 (all real: h < g)
+    if (live) {
 #pragma unroll
-    for (int i = 0; i < 16; i += 2) {
-      const double2 q = *reinterpret_cast<const double2*>(colp + size_t(k) * NB + i);
-      lv[i] = q.x;
-      lv[i + 1] = q.y;
+      for (int j = 0; j < R; ++j) tile_turn(lv[j], gq[j], stage, seg);
+#pragma unroll
+      for (int j = 0; j < R; ++j)
+        if (h + 1 < g) tile_issue(gq[j], colq + size_t(nb - 1 - (h + 1) * R - j) * NB, seg);
     }
-    double* yb = yl[k & 1];  // double-buffered: one barrier per block
-    if (wave0()) {  // scalar branch (see block_wait)
+    double* yb = &yl[h & 1][0][0];  // double-buffered: one barrier per group
+    if (poller) {                   // wave 0 of slot i: the awaited group's row i
       const int lane = threadIdx.x & 63;
-      const double* p = y + size_t(k) * NB + lane;
+      const double* p = y + size_t(kt - slot) * NB + lane;
       double yv = 0.0;
       for (long spins = 0;; ++spins) {
         yv = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1360,35 +1484,63 @@ __global__ __launch_bounds__(256) void k_backsolve(const double* __restrict__ A,
         }
         __builtin_amdgcn_s_sleep(1);
       }
-      yb[lane] = yv;
-      if (k == b + 1) BSTAMP(b, 0);
+      yb[slot * NB + lane] = yv;
+      if (h == g - 1) BSTAMP(b, 0);
     }
     __syncthreads();
-    if (k == b + 1) BSTAMP(b, 1);
+    if (h == g - 1) BSTAMP(b, 1);
     if (__builtin_amdgcn_readfirstlane(timed_out)) break;
+    if (live) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) acc = fma(lv[i], yb[16 * seg + i], acc);
+      for (int j = 0; j < R; ++j) acc = chain16(lv[j], yb + j * NB + 16 * seg, acc);  // descending k
+    }
   }
-  // the four row segments of a column sit in adjacent lanes
-  acc += __shfl_xor(acc, 1);
-  acc += __shfl_xor(acc, 2);
-  if (seg == 0) v[col] = (col < nreal) ? zc - acc : 0.0;
-  BSTAMP(b, 2);
-  __syncthreads();
-  BSTAMP(b, 3);
-  // y_b[col] = sum_c W(c, col) v[c]: 16 terms per lane in four chains, then
-  // the four segments
-  double p4[4] = {0.0, 0.0, 0.0, 0.0};
+  // the group's rows finish from the highest to the lowest; a finished row
+  // reaches the rows below through LDS (and the other groups through y)
 #pragma unroll
-  for (int i = 0; i < 16; ++i) p4[i & 3] = fma(wr[i], v[16 * seg + i], p4[i & 3]);
-  double sum = (p4[0] + p4[1]) + (p4[2] + p4[3]);
-  sum += __shfl_xor(sum, 1);
-  sum += __shfl_xor(sum, 2);
-  // write-through (sc1) relaxed store of the final value: the consumers'
-  // polls see it when it lands, with nothing to order after it
-  if (seg == 0) __hip_atomic_store(y + size_t(k0) + col, col < nreal ? sum : 0.0, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-  BSTAMP(b, 4);
+  for (int s = 0; s < R; ++s) {
+    const bool mine = live && slot == s;
+    if (mine) {
+      // the four row segments of a column sit in adjacent lanes
+      acc = quad_sum(acc);
+      if (seg == 0) v[s][col] = (col < nreal) ? zc - acc : 0.0;
+      BSTAMP(b, 2);
+    }
+    __syncthreads();
+    if (mine) {
+      BSTAMP(b, 3);
+      // y_b[col] = sum_c W(c, col) v[c]: 16 terms per lane in four chains,
+      // then the four segments
+      double vv[16];
+#pragma unroll
+      for (int i = 0; i < 16; i += 2) {
+        const double2 q = *reinterpret_cast<const double2*>(&v[s][16 * seg + i]);
+        vv[i] = q.x;
+        vv[i + 1] = q.y;
+      }
+#pragma unroll
+      for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(vv[i]));
+      double p4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int i = 0; i < 16; ++i) p4[i & 3] = fma(wr[i], vv[i], p4[i & 3]);
+      const double sum = quad_sum((p4[0] + p4[1]) + (p4[2] + p4[3]));
+      if (seg == 0) {
+        const double yv = col < nreal ? sum : 0.0;
+        if (s + 1 < R) yg[s][col] = yv;
+        // write-through (sc1) relaxed store of the final value: the
+        // consumers' polls see it when it lands, with nothing to order after it
+        __hip_atomic_store(y + size_t(k0) + col, yv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      BSTAMP(b, 4);
+    }
+    if (s + 1 < R) {
+      __syncthreads();
+      if (live && slot > s) {  // the last link of row s + 1's chain (k = b + 1); an earlier one of the rows below it
+        if (slot == s + 1) BSTAMP(b, 5);
+        acc = chain16(lg[s], &yg[s][16 * seg], acc);
+      }
+    }
+  }
   if (wave0() && timed_out) atomicOr(fail, 2);
 }
 
@@ -1679,7 +1831,18 @@ void launch_backsolve(const DevProblem& d, int epoch, hipStream_t s, bool sentin
   // the solve's k_pad_init writes it, saving a launch)
   if (!sentinel_set)
     (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d.ysol), int(kYSentinelWord), size_t(nb_real) * NB * 2, s);
-  k_backsolve<<<nb_real, 256, 0, s>>>(d.S, d.ld, d.n, nb_real, d.invL, d.ysol, d.fail, d.gate, d.cticket + 2, epoch);
+  // block rows per workgroup: one value for every nb, picked by measurement
+  // (profiles/backsolve_rows_ab.txt: R = 1 57 us at C3, R = 2 69 us -- two
+  // rows' tile loads and polls share one CU's memory queue, and the hand-off
+  // into such a CU costs what the group saves; R = 3 spills.
+  // -DSFM_BACKSOLVE_ROWS builds the others for such a measurement only)
+#ifndef SFM_BACKSOLVE_ROWS
+#define SFM_BACKSOLVE_ROWS 1
+#endif
+  constexpr int R = SFM_BACKSOLVE_ROWS;
+  static_assert(R >= 1 && R <= 3, "1024 threads leave no registers for four prefetched tiles");
+  k_backsolve<R><<<(nb_real + R - 1) / R, 256 * R, 0, s>>>(d.S, d.ld, d.n, nb_real, d.invL, d.ysol, d.fail, d.gate,
+                                                           d.cticket + 2, epoch);
 }
 
 int launch_cholesky_panel(const DevProblem& d, int k, int pt, int epoch, hipStream_t s) {
