@@ -604,6 +604,41 @@ int sfm_dense_spd_solve(int32_t device, int32_t n, const double* A, const double
  * n >= 128 (at least three tiles with the right-hand side's row). */
 int sfm_dense_spd_solve_panels(int32_t device, int32_t n, const double* A, const double* b, double* y,
                                int32_t panel_tiles, int32_t* chol_fail);
+/* Testing hook: the geometry kernels' small dense linear algebra (cv::SVD as
+ * JacobiSVDImpl_, cv::solve(DECOMP_SVD), epnp's qr_solve) run on the device
+ * on `batch` problems, as the product kernels run it, every output returned.
+ * `in` / `out` are flat, problem after problem, matrices row-major:
+ *   SVD_MxN     in A [M][N]             out w [N] | U [N][M] | Vt [N][N]
+ *               (row i of U = i-th left singular vector, w descending)
+ *   SVD_AT_9x7  in A [9][7]             out w [7] | U [7][9]  (no V: the
+ *               7-point null space of sfm_two_view_init)
+ *   LSTSQ_6xN   in A [6][N] | b [6]     out x [N]
+ *   QR_6x4      in A [6][4] | b [6] | x0 [4]
+ *                                       out x [4] | flag (1.0 solved; 0.0
+ *               singular: x = x0 untouched)
+ *   SVD12       in symmetric A [12][12] out ut [4][12]: the left singular
+ *               vectors of the four smallest singular values, smallest first
+ * variant 0: one problem per lane, the sequential sweeps, 256-thread
+ * workgroups.  variant 1: one problem per wave through the lane-parallel
+ * sweeps (SVD_6x4, SVD_6x5, LSTSQ_6x4, LSTSQ_6x5; SVD12 runs only so), in
+ * 192-thread workgroups of three waves, each on its own LDS slice, as the
+ * EPnP kernel is launched.  1 <= batch <= 2^20. */
+enum {
+  SFM_LINALG_SVD_3x3 = 0,
+  SFM_LINALG_SVD_4x4 = 1,
+  SFM_LINALG_SVD_9x9 = 2,
+  SFM_LINALG_SVD_6x3 = 3,
+  SFM_LINALG_SVD_6x4 = 4,
+  SFM_LINALG_SVD_6x5 = 5,
+  SFM_LINALG_SVD_AT_9x7 = 6,
+  SFM_LINALG_LSTSQ_6x3 = 7,
+  SFM_LINALG_LSTSQ_6x4 = 8,
+  SFM_LINALG_LSTSQ_6x5 = 9,
+  SFM_LINALG_QR_6x4 = 10,
+  SFM_LINALG_SVD12 = 11,
+  SFM_LINALG_NUM_OPS = 12
+};
+int sfm_linalg_probe(int32_t device, int32_t op, int32_t variant, int32_t batch, const double* in, double* out);
 /* Measurement plumbing (bench.py, not a reference interface): the best
  * STREAM-copy bandwidth (read + write bytes / s, 16-B accesses) over a few
  * launch shapes, `bytes` per buffer, `reps` timed launches each. */

@@ -273,6 +273,7 @@ _SIGNATURES = {
     "sfm_dense_spd_solve": (c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, POINTER(c_double),
                                     POINTER(c_int32)]),
     "sfm_dense_spd_solve_panels": (c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, POINTER(c_int32)]),
+    "sfm_linalg_probe": (c_int, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "sfm_bench_stream_copy": (c_int, [c_int32, c_int64, c_int32, POINTER(c_double)]),
     "sfm_dist_factor_profile": (c_int, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p]),
@@ -399,7 +400,29 @@ def device_count() -> int:
     return int(lib().sfm_device_count())
 
 
-__all__ = ["lib", "check", "ptr", "BAOptions", "BASummary", "BAIteration", "KLTParams", "GFTTParams", "TwoViewOptions", "CameraStruct", "GuidanceOptions", "GuidanceResult",
+# Testing hook sfm_linalg_probe: op -> (code, doubles in, doubles out per
+# problem, has a per-wave variant); include/sfm_amd.h SFM_LINALG_*.
+LINALG_OPS = {
+    "svd3x3": (0, 9, 3 + 9 + 9, False), "svd4x4": (1, 16, 4 + 16 + 16, False), "svd9x9": (2, 81, 9 + 81 + 81, False),
+    "svd6x3": (3, 18, 3 + 18 + 9, False), "svd6x4": (4, 24, 4 + 24 + 16, True), "svd6x5": (5, 30, 5 + 30 + 25, True),
+    "svd_at9x7": (6, 63, 7 + 63, False), "lstsq6x3": (7, 24, 3, False), "lstsq6x4": (8, 30, 4, True),
+    "lstsq6x5": (9, 36, 5, True), "qr6x4": (10, 34, 5, False), "svd12": (11, 144, 48, True),
+}
+
+
+def linalg_probe(op: str, variant: int, data: np.ndarray, device: int = 0) -> np.ndarray:
+    """Testing hook: run `op` (a LINALG_OPS name) on the device on the batch
+    data [batch][doubles in], one problem per lane (variant 0) or per wave
+    (variant 1) -> [batch][doubles out] (layouts: include/sfm_amd.h)."""
+    code, n_in, n_out, _ = LINALG_OPS[op]
+    data = np.ascontiguousarray(data, np.float64)
+    assert data.ndim == 2 and data.shape[1] == n_in, (op, data.shape)
+    out = np.empty((data.shape[0], n_out), np.float64)
+    check(lib().sfm_linalg_probe(device, code, int(variant), data.shape[0], ptr(data), ptr(out)), "sfm_linalg_probe")
+    return out
+
+
+__all__ = ["lib", "check", "ptr", "LINALG_OPS", "linalg_probe", "BAOptions", "BASummary", "BAIteration", "KLTParams", "GFTTParams", "TwoViewOptions", "CameraStruct", "GuidanceOptions", "GuidanceResult",
            "default_guidance_options", "SfmError",
            "default_options", "default_klt_params", "default_gftt_params", "default_two_view_options",
            "device_count", "exported_symbols", "LIB_PATH", "c_uint8"]

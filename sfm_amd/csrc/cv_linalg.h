@@ -16,6 +16,11 @@ namespace sfm {
 namespace {
 
 constexpr double kDblEps = DBL_EPSILON, kDblMin = DBL_MIN;
+// One wave's LDS slice, in doubles, where the `lds` path below runs
+// (k_pnp_epnp of pnp_kernels.hip and the probe kernels of linalg_probe.hip,
+// one slice per wave of a workgroup): >= 5 (6 + 5) for the rows of the 6x5
+// SVD; 6 * 10 + 6 also holds L and rho for the Gauss-Newton rows.
+constexpr int kSvdLds = 6 * 10 + 6;
 
 __host__ __device__ __forceinline__ unsigned cv_rng_next(uint64_t& state) {
   state = uint64_t(unsigned(state)) * 4164903690ull + (state >> 32);

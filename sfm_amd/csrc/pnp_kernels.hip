@@ -208,8 +208,8 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 // lds: this wave's kSvdLds doubles (ut at the end of the 12x12; the rows of
-// the beta cases' 6x5 / 6x4 SVDs, cv_linalg.h cv_svd_sweeps_lanes)
-constexpr int kSvdLds = 6 * 10 + 6;  // (>= 5 (6 + 5): also L and rho for the Gauss-Newton rows)
+// the beta cases' 6x5 / 6x4 SVDs, cv_linalg.h cv_svd_sweeps_lanes; the size
+// is cv_linalg.h's, shared with the probe kernels)
 // One pass of schedule S; ch[t] |= a rotation of tag t turned.
 // JacobiSVDImpl_ keeps W_i = |row i|^2, set from the row itself after every
 // rotation of row i (and at the start), so W_i is always tree16(u_i * u_i)
@@ -388,6 +388,32 @@ __device__ void cv_svd12_lanes(double (&u)[12], double* lds, double (&ut)[4][12]
   for (int q = 0; q < 4; ++q)
 #pragma unroll
     for (int m = 0; m < 12; ++m) ut[q][m] = lds[q * 12 + m];
+}
+
+// Testing hook (sfm_linalg_probe, linalg_probe.hip): cv_svd12_lanes on a
+// batch of symmetric 12x12 matrices (in [batch][12][12]), one per wave,
+// launched as k_pnp_epnp is -- 192 threads, wave w on lds[w] -- and loaded as
+// epnp5_common loads M^T M (lane k mod 16 holds entry k of every row, lanes
+// 12..15 zeros).  out [batch][4][12] = the four ut rows.
+__global__ __launch_bounds__(192) void k_probe_svd12(int batch, const double* __restrict__ in,
+                                                     double* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) double lds[3][kSvdLds];
+  const int w = threadIdx.x >> 6;
+  const int i = blockIdx.x * 3 + w;
+  if (i >= batch) return;  // (a whole wave; the SVD synchronises waves only)
+  const int col = threadIdx.x & 15;
+  const double* a = in + size_t(i) * 144;
+  double u[12], ut[4][12];
+#pragma unroll
+  for (int r = 0; r < 12; ++r) u[r] = col < 12 ? a[r * 12 + col] : 0.0;
+  // (inlined here before the inliner weighs the product's call: with a
+  // second live caller k_pnp_epnp would stop inlining the SVD and spill)
+  [[clang::always_inline]] cv_svd12_lanes(u, lds[w], ut);
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int m = 0; m < 12; ++m) out[size_t(i) * 48 + q * 12 + m] = ut[q][m];
 }
 
 // Host build of the same 12x12 SVD (tools/pnp_host_check): the butterfly
@@ -1092,6 +1118,11 @@ int pnp_ransac_dev(hipStream_t s, const int* d_n, int gate, const double* d_obj,
   return hipGetLastError() == hipSuccess ? 0 : pfail(SFM_EIO, "PnP launch failed");
 }
 int pnp_max_iters() { return kMaxIters; }
+// sfm_linalg_probe's 12x12 op (device buffers, stream s; no synchronisation)
+int probe_svd12(int batch, const double* d_in, double* d_out, hipStream_t s) {
+  k_probe_svd12<<<(batch + 2) / 3, 192, 0, s>>>(batch, d_in, d_out);
+  return hipGetLastError() == hipSuccess ? 0 : SFM_EIO;
+}
 int pnp_model_size() { return kModel; }
 }  // namespace sfm
 

@@ -1,9 +1,10 @@
 """GPU: the device solvePnPRansac (sfm_pnp_ransac, pnp_kernels.hip) against
 the oracle (oracle/pnp_oracle.py) on seeded scenes: the same found flag,
-the SAME inlier index list (integer parity), and the pose within 1e-6 (the
-device's Jacobi SVDs and the oracle's LAPACK agree to rounding; the pose
-is invariant to the eigenvector signs).  Covers n = 5 (no sampling), n = 6,
-planar points, 90 % outliers (adaptive bound never shrinks) and n < 5."""
+the SAME inlier index list (integer parity), and the pose within 1e-6.  The
+oracle restates OpenCV's Jacobi SVD, back substitution and qr_solve in the
+kernels' operation order (no LAPACK), and tests/test_gpu_linalg.py pins those
+primitives to it bit for bit; the 1e-6 covers what lies outside them.
+Covers n = 5 (no sampling), n = 6, planar points, 90 % outliers (adaptive bound never shrinks) and n < 5."""
 import numpy as np
 import pytest
 
