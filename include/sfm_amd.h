@@ -287,6 +287,36 @@ int sfm_matcher_pair_points(sfm_matcher* h, int32_t slot0, const int32_t* idx0, 
                             const double* K9_1, const double* R9_1, const double* t3_1, double max_err,
                             int32_t capacity, int32_t* m0, int32_t* m1, double* X, int32_t* n_kept,
                             int32_t* n_matched);
+/* sfm_matcher_pair_points for n_pairs older keyframes against the same rows
+ * idx1[n1] of the new keyframe (slot1), up to the first pair that keeps a
+ * point.  CSfM::mapping's pair loop (CSfM.cpp:138-227) shrinks the new
+ * keyframe's unmatched set only after a pair that kept a point, so until then
+ * every pair sees the same idx1: the first productive pair of this call, in
+ * the caller's order, is the one the pair-by-pair loop reaches, with the same
+ * bits.  The caller applies it, recomputes idx1 and calls again for the
+ * keyframes after it.
+ *   Pair b: slot0[b], rows idx0[idx0_off[b] .. idx0_off[b + 1]) (idx0_off
+ * [n_pairs + 1], idx0_off[0] = 0, non-decreasing), matrices K9_0 / R9_0 /
+ * t3_0 + b * 9 / 9 / 3.  slot0 entries may repeat; none may equal slot1;
+ * n_pairs <= 65535.
+ *   Out: n_kept[b] and n_matched[b] for every pair, as sfm_matcher_pair_points
+ * returns them for that pair; *first = the lowest b with n_kept[b] > 0, or -1;
+ * m0 / m1 [capacity] and X [capacity][3] = pair *first's kept matches,
+ * subset-local, in the matcher's order (untouched when *first == -1).  The
+ * pairs after *first are computed against the same idx1 and only counted.
+ *   n_pairs == 0: *first = -1.  A pair without rows, or n1 < 2: no matches.
+ * When n_kept[*first] exceeds capacity, first, n_kept and n_matched are set,
+ * m0 / m1 / X are not written and SFM_EINVAL is returned; capacity
+ * min(max_b n0_b, n1) always fits.  Every argument (NULLs, slots, row indices,
+ * offsets, every pair's matrices) is checked before the first device call; an
+ * error leaves the handle usable.  One staged upload, a number of launches
+ * that does not depend on n_pairs, one download, one host synchronisation. */
+int sfm_matcher_pair_points_first(sfm_matcher* h, int32_t n_pairs, const int32_t* slot0, const int32_t* idx0,
+                                  const int32_t* idx0_off, int32_t slot1, const int32_t* idx1, int32_t n1,
+                                  double ratio_test, double min_distance, double max_distance, const double* K9_0,
+                                  const double* R9_0, const double* t3_0, const double* K9_1, const double* R9_1,
+                                  const double* t3_1, double max_err, int32_t capacity, int32_t* first, int32_t* m0,
+                                  int32_t* m1, double* X, int32_t* n_kept, int32_t* n_matched);
 /* The re-finding of new map points in one keyframe in between
  * (CSfM.cpp:191-221): sfm_matcher_match_keyframes(q_slot, q_idx, n_q, q_pts,
  * t_slot, ...) with q_pts = the projections of X [n_q][3] through (K9, R9,

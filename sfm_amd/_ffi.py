@@ -252,6 +252,10 @@ _SIGNATURES = {
                                         c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_double, c_int32, c_void_p, c_void_p, c_void_p, POINTER(c_int32),
                                         POINTER(c_int32)]),
+    "sfm_matcher_pair_points_first": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                              c_int32, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_double, c_int32, POINTER(c_int32),
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sfm_matcher_refind_points": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_int32, c_void_p, c_int32, c_double, c_double, c_double,
                                           c_void_p, c_void_p, POINTER(c_int32)]),

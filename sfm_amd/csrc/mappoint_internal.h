@@ -17,6 +17,22 @@ struct PairArgs {
   double max_err;
 };
 
+// One keyframe pair of a batch (sfm_matcher_pair_points_first): the older
+// keyframe's rows and where this pair's pieces lie in the call's buffers.  The
+// table is device-resident, staged with the index lists; the new keyframe's
+// side (its rows, idx1, n1) is common to all items.
+struct PairItem {
+  const uint64_t* desc;  // the older keyframe's descriptor words [.][W]
+  const double* pts;     // ... and positions [.][2]
+  int n0;                // rows of this item
+  int idx_off;           // idx0 list in the staged index lists; also slot / keep / src (one int per row)
+  int out_off;           // the matcher's block out [2 n0 + 1]
+  int pad;
+  long long part_off;    // partial 2-NN keys [nslice][n0][2]
+  long long key_off;     // key / first [n1]
+  long long x_off;       // Xall [n0][3]
+};
+
 // Host, plain C++, unfused.  false: K is not upper triangular with K[8] = 1
 // and non-zero fx, fy (the closed-form inverse needs that), or an input is not
 // finite.
@@ -33,6 +49,15 @@ bool compose_pair(const double* K0, const double* R0, const double* t0, const do
 void launch_pair_points(hipStream_t s, const int* out, int n0, const int* qidx, const int* tidx, const double* pts0,
                         const double* pts1, const PairArgs& a, double* Xall, int* keep, int* src, int* head, int* m0,
                         int* m1, double* X);
+// The same for the B items of a batch, then the pick: per item b the points
+// and keep flags of its matches (out + out_off, the arithmetic of
+// launch_pair_points through pa[b]) and their ordered compaction (src +
+// idx_off; head[1 + b] = kept); then head[1 + B + b] = matched, head[0] = the
+// lowest b with kept > 0 (-1: none) and that item's kept matches in m0 / m1 /
+// X.  Three launches whatever B; max_n0 = the longest item.
+void launch_pair_points_first(hipStream_t s, const PairItem* items, const PairArgs* pa, int B, int max_n0,
+                              const int* out, const int* idx, const int* tidx, const double* pts1, double* Xall,
+                              int* keep, int* src, int* head, int* m0, int* m1, double* X);
 // The filter alone on n given matches: status[i] = 1 kept.
 void launch_filter(hipStream_t s, int n, const double* uv0, const double* uv1, const double* X, const PairArgs& a,
                    uint8_t* status);

@@ -55,11 +55,10 @@ __device__ __forceinline__ bool pair_keep(const PairArgs& a, double u0, double v
 
 // One lane per match k < count (the count where the matcher left it): both
 // keypoints through the subset lists, the point, the flag.
-__global__ __launch_bounds__(256) void k_pair_points(const int* __restrict__ out, int n0, const int* __restrict__ qidx,
-                                                     const int* __restrict__ tidx, const double* __restrict__ pts0,
-                                                     const double* __restrict__ pts1, const PairArgs a,
-                                                     double* __restrict__ Xall, int* __restrict__ keep) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void pair_point(const int* __restrict__ out, int n0, const int* __restrict__ qidx,
+                                           const int* __restrict__ tidx, const double* __restrict__ pts0,
+                                           const double* __restrict__ pts1, const PairArgs& a,
+                                           double* __restrict__ Xall, int* __restrict__ keep, int k) {
   if (k >= n0) return;
   if (k >= out[2 * n0]) {
     keep[k] = 0;
@@ -75,8 +74,49 @@ __global__ __launch_bounds__(256) void k_pair_points(const int* __restrict__ out
   keep[k] = pair_keep(a, u0, v0, u1, v1, X) ? 1 : 0;
 }
 
-// The kept matches (src[pos] = the pos-th kept k; head[0] = their count, as
-// k_compact_keep wrote it) into the result block.
+__global__ __launch_bounds__(256) void k_pair_points(const int* __restrict__ out, int n0, const int* __restrict__ qidx,
+                                                     const int* __restrict__ tidx, const double* __restrict__ pts0,
+                                                     const double* __restrict__ pts1, const PairArgs a,
+                                                     double* __restrict__ Xall, int* __restrict__ keep) {
+  pair_point(out, n0, qidx, tidx, pts0, pts1, a, Xall, keep, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// item blockIdx.y of a batch; its matrices are wave-uniform loads from pa
+__global__ __launch_bounds__(256) void k_pair_points_items(const PairItem* __restrict__ items,
+                                                           const PairArgs* __restrict__ pa,
+                                                           const int* __restrict__ out, const int* __restrict__ idx,
+                                                           const int* __restrict__ tidx,
+                                                           const double* __restrict__ pts1, double* __restrict__ Xall,
+                                                           int* __restrict__ keep) {
+  const PairItem& it = items[blockIdx.y];
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= it.n0) return;
+  pair_point(out + it.out_off, it.n0, idx + it.idx_off, tidx, it.pts, pts1, pa[blockIdx.y], Xall + it.x_off,
+             keep + it.idx_off, k);
+}
+
+// one workgroup per item: head[1 + item] = its kept count
+__global__ __launch_bounds__(1024) void k_compact_keep_items(const PairItem* __restrict__ items,
+                                                             const int* __restrict__ keep, int* __restrict__ src,
+                                                             int* __restrict__ head) {
+  const PairItem& it = items[blockIdx.x];
+  compact_keep(it.n0, keep + it.idx_off, src + it.idx_off, head + 1 + blockIdx.x);
+}
+
+// the pos-th kept match (src[pos] = the pos-th kept k) into the result block
+__device__ __forceinline__ void gather_kept(const int* __restrict__ out, int n0, const int* __restrict__ src,
+                                            const double* __restrict__ Xall, int pos, int* __restrict__ m0,
+                                            int* __restrict__ m1, double* __restrict__ X) {
+  const int k = src[pos];
+  m0[pos] = out[k];
+  m1[pos] = out[n0 + k];
+  X[3 * size_t(pos)] = Xall[3 * size_t(k)];
+  X[3 * size_t(pos) + 1] = Xall[3 * size_t(k) + 1];
+  X[3 * size_t(pos) + 2] = Xall[3 * size_t(k) + 2];
+}
+
+// The kept matches (head[0] = their count, as k_compact_keep wrote it) into
+// the result block.
 __global__ __launch_bounds__(256) void k_pair_gather(const int* __restrict__ out, int n0, const int* __restrict__ src,
                                                      const double* __restrict__ Xall, int* __restrict__ head,
                                                      int* __restrict__ m0, int* __restrict__ m1,
@@ -84,12 +124,35 @@ __global__ __launch_bounds__(256) void k_pair_gather(const int* __restrict__ out
   const int pos = blockIdx.x * blockDim.x + threadIdx.x;
   if (pos == 0) head[1] = out[2 * n0];
   if (pos >= n0 || pos >= head[0]) return;
-  const int k = src[pos];
-  m0[pos] = out[k];
-  m1[pos] = out[n0 + k];
-  X[3 * size_t(pos)] = Xall[3 * size_t(k)];
-  X[3 * size_t(pos) + 1] = Xall[3 * size_t(k) + 1];
-  X[3 * size_t(pos) + 2] = Xall[3 * size_t(k) + 2];
+  gather_kept(out, n0, src, Xall, pos, m0, m1, X);
+}
+
+// The pick of a batch, one workgroup: every item's match count beside its
+// kept count (head: first | kept [B] | matched [B]), the lowest item with a
+// kept match -- a min over the lanes' strided items, across the wave by
+// shuffles and across the four waves through LDS, so B may exceed a wave --
+// and that item's kept matches into the one result block.
+__global__ __launch_bounds__(256) void k_pick_first(const PairItem* __restrict__ items, int B,
+                                                    const int* __restrict__ out, const int* __restrict__ src,
+                                                    const double* __restrict__ Xall, int* __restrict__ head,
+                                                    int* __restrict__ m0, int* __restrict__ m1,
+                                                    double* __restrict__ X) {
+  __shared__ int wave_min[4];
+  int best = 0x7fffffff;
+  for (int b = threadIdx.x; b < B; b += 256) {
+    head[1 + B + b] = out[items[b].out_off + 2 * items[b].n0];
+    if (head[1 + b] > 0) best = min(best, b);
+  }
+  for (int o = 32; o >= 1; o >>= 1) best = min(best, __shfl_xor(best, o));
+  if ((threadIdx.x & 63) == 0) wave_min[threadIdx.x >> 6] = best;
+  __syncthreads();
+  best = min(min(wave_min[0], wave_min[1]), min(wave_min[2], wave_min[3]));
+  if (threadIdx.x == 0) head[0] = best == 0x7fffffff ? -1 : best;
+  if (best == 0x7fffffff) return;
+  const PairItem& it = items[best];
+  const int kept = head[1 + best];
+  for (int pos = threadIdx.x; pos < kept; pos += 256)
+    gather_kept(out + it.out_off, it.n0, src + it.idx_off, Xall + it.x_off, pos, m0, m1, X);
 }
 
 __global__ __launch_bounds__(256) void k_filter(int n, const double* __restrict__ uv0, const double* __restrict__ uv1,
@@ -200,6 +263,14 @@ void launch_pair_points(hipStream_t s, const int* out, int n0, const int* qidx, 
   k_pair_points<<<blocks(n0), 256, 0, s>>>(out, n0, qidx, tidx, pts0, pts1, a, Xall, keep);
   k_compact_keep<<<1, 1024, 0, s>>>(n0, keep, src, head);
   k_pair_gather<<<blocks(n0), 256, 0, s>>>(out, n0, src, Xall, head, m0, m1, X);
+}
+
+void launch_pair_points_first(hipStream_t s, const PairItem* items, const PairArgs* pa, int B, int max_n0,
+                              const int* out, const int* idx, const int* tidx, const double* pts1, double* Xall,
+                              int* keep, int* src, int* head, int* m0, int* m1, double* X) {
+  k_pair_points_items<<<dim3(blocks(max_n0), B), 256, 0, s>>>(items, pa, out, idx, tidx, pts1, Xall, keep);
+  k_compact_keep_items<<<B, 1024, 0, s>>>(items, keep, src, head);
+  k_pick_first<<<1, 256, 0, s>>>(items, B, out, src, Xall, head, m0, m1, X);
 }
 
 void launch_filter(hipStream_t s, int n, const double* uv0, const double* uv1, const double* X, const PairArgs& a,

@@ -61,18 +61,17 @@ __device__ __forceinline__ void top2_insert(unsigned long long k, unsigned long 
   k0 = lt0 ? k : k0;
 }
 
-// Partial 2-NN of query block blockIdx.x against train slice blockIdx.y.
+// Partial 2-NN of query block qb against train slice sl (one workgroup).
 // Query i is row qidx[i] of q (qidx == nullptr: row i), train t is row
-// tidx[t] of tr; part[(y * n0 + i) * 2 + {0,1}] = the two smallest keys.
+// tidx[t] of tr; part[(sl * n0 + i) * 2 + {0,1}] = the two smallest keys.
 template <int W, bool kIdx>
-__global__ __launch_bounds__(kQ * kWaves) void k_knn2_part(const uint64_t* __restrict__ q, const int* __restrict__ qidx,
-                                                           int n0, const uint64_t* __restrict__ tr,
-                                                           const int* __restrict__ tidx, int n1, int slice,
-                                                           unsigned long long* __restrict__ part) {
+__device__ __forceinline__ void knn2_block(const uint64_t* __restrict__ q, const int* __restrict__ qidx, int n0,
+                                           const uint64_t* __restrict__ tr, const int* __restrict__ tidx, int n1,
+                                           int slice, unsigned long long* __restrict__ part, int qb, int sl) {
   __shared__ unsigned long long red[kWaves][kQ][2];
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: the train loop is scalar
-  const int i = blockIdx.x * kQ + lane;
+  const int i = qb * kQ + lane;
   uint64_t x[W];
   if (i < n0) {
     const size_t row = qidx ? size_t(qidx[i]) : size_t(i);
@@ -83,7 +82,7 @@ __global__ __launch_bounds__(kQ * kWaves) void k_knn2_part(const uint64_t* __res
     for (int k = 0; k < W; ++k) x[k] = 0ull;
   }
   unsigned long long k0 = kNoKey, k1 = kNoKey;
-  const int t0 = blockIdx.y * slice, t1 = min(n1, t0 + slice);
+  const int t0 = sl * slice, t1 = min(n1, t0 + slice);
   const int per = (t1 - t0 + kWaves - 1) / kWaves;
   const int a = t0 + w * per, b = min(t1, a + per);
   // four rows in flight per step (four 64-B scalar loads, then the
@@ -123,10 +122,35 @@ __global__ __launch_bounds__(kQ * kWaves) void k_knn2_part(const uint64_t* __res
       top2_insert(red[v][lane][1], k0, k1);
     }
     if (i < n0) {
-      part[(size_t(blockIdx.y) * n0 + i) * 2] = k0;
-      part[(size_t(blockIdx.y) * n0 + i) * 2 + 1] = k1;
+      part[(size_t(sl) * n0 + i) * 2] = k0;
+      part[(size_t(sl) * n0 + i) * 2 + 1] = k1;
     }
   }
+}
+
+// query block blockIdx.x against train slice blockIdx.y
+template <int W, bool kIdx>
+__global__ __launch_bounds__(kQ * kWaves) void k_knn2_part(const uint64_t* __restrict__ q, const int* __restrict__ qidx,
+                                                           int n0, const uint64_t* __restrict__ tr,
+                                                           const int* __restrict__ tidx, int n1, int slice,
+                                                           unsigned long long* __restrict__ part) {
+  knn2_block<W, kIdx>(q, qidx, n0, tr, tidx, n1, slice, part, blockIdx.x, blockIdx.y);
+}
+
+// The same for every item of a batch (sfm_matcher_pair_points_first): item
+// blockIdx.z's query rows against the common train rows.  The grid's x is
+// sized for the longest item; a workgroup past its own item's rows leaves as
+// a whole, before the LDS and the barrier.
+template <int W>
+__global__ __launch_bounds__(kQ * kWaves) void k_knn2_part_items(const sfm::PairItem* __restrict__ items,
+                                                                 const int* __restrict__ idx,
+                                                                 const uint64_t* __restrict__ tr,
+                                                                 const int* __restrict__ tidx, int n1, int slice,
+                                                                 unsigned long long* __restrict__ part) {
+  const sfm::PairItem& it = items[blockIdx.z];
+  const int n0 = it.n0;
+  if (int(blockIdx.x) * kQ >= n0) return;
+  knn2_block<W, true>(it.desc, idx + it.idx_off, n0, tr, tidx, n1, slice, part + it.part_off, blockIdx.x, blockIdx.y);
 }
 
 __device__ __forceinline__ void merge_parts(const unsigned long long* __restrict__ part, int n0, int nslice, int i,
@@ -156,13 +180,12 @@ __global__ void k_knn2_merge(const unsigned long long* __restrict__ part, int n0
 //   first[j] = min over accepted queries of i               -> slot order
 // Positions are those of rows qidx[i] / tidx[j] (nullptr: i / j).
 // (n0_dev: the query count on the device, n0 its bound -- sfm_map_match_frame)
-__global__ void k_accept(const unsigned long long* __restrict__ part, int n0, const int* __restrict__ n0_dev, int nslice,
-                         const double* __restrict__ p0, const int* __restrict__ qidx, const double* __restrict__ p1,
-                         const int* __restrict__ tidx, double ratio_test, double minSq, double maxSq,
-                         unsigned long long* __restrict__ key, int* __restrict__ first) {
+__device__ __forceinline__ void accept_query(const unsigned long long* __restrict__ part, int n0, int nslice, int i,
+                                             const double* __restrict__ p0, const int* __restrict__ qidx,
+                                             const double* __restrict__ p1, const int* __restrict__ tidx,
+                                             double ratio_test, double minSq, double maxSq,
+                                             unsigned long long* __restrict__ key, int* __restrict__ first) {
 #pragma clang fp contract(off)
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (n0_dev ? *n0_dev : n0)) return;
   unsigned long long k0, k1;
   merge_parts(part, n0, nslice, i, k0, k1);
   if (k0 == kNoKey || k1 == kNoKey) return;  // < 2 train rows: the reference reads past matches[i] (UB)
@@ -178,6 +201,51 @@ __global__ void k_accept(const unsigned long long* __restrict__ part, int n0, co
     atomicMin(&key[j], (static_cast<unsigned long long>(d0) << 32) | unsigned(i));
     atomicMin(&first[j], i);
   }
+}
+
+__global__ void k_accept(const unsigned long long* __restrict__ part, int n0, const int* __restrict__ n0_dev, int nslice,
+                         const double* __restrict__ p0, const int* __restrict__ qidx, const double* __restrict__ p1,
+                         const int* __restrict__ tidx, double ratio_test, double minSq, double maxSq,
+                         unsigned long long* __restrict__ key, int* __restrict__ first) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (n0_dev ? *n0_dev : n0)) return;
+  accept_query(part, n0, nslice, i, p0, qidx, p1, tidx, ratio_test, minSq, maxSq, key, first);
+}
+
+// item blockIdx.y of a batch: its queries, its own key / first block
+__global__ void k_accept_items(const sfm::PairItem* __restrict__ items, const int* __restrict__ idx, int nslice,
+                               const unsigned long long* __restrict__ part, const double* __restrict__ p1,
+                               const int* __restrict__ tidx, double ratio_test, double minSq, double maxSq,
+                               unsigned long long* __restrict__ key, int* __restrict__ first) {
+  const sfm::PairItem& it = items[blockIdx.y];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= it.n0) return;
+  accept_query(part + it.part_off, it.n0, nslice, i, it.pts, idx + it.idx_off, p1, tidx, ratio_test, minSq, maxSq,
+               key + it.key_off, first + it.key_off);
+}
+
+__global__ void k_reset_items(const sfm::PairItem* __restrict__ items, int n1, unsigned long long* __restrict__ key,
+                              int* __restrict__ first, int* __restrict__ slot) {
+  const sfm::PairItem& it = items[blockIdx.y];
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n1) { key[it.key_off + t] = kNoKey; first[it.key_off + t] = 0x7fffffff; }
+  if (t < it.n0) slot[it.idx_off + t] = 0;
+}
+
+__global__ void k_mark_first_items(const sfm::PairItem* __restrict__ items, int n1, const int* __restrict__ first,
+                                   int* __restrict__ slot) {
+  const sfm::PairItem& it = items[blockIdx.y];
+  sfm::mark_first(n1, first + it.key_off, slot + it.idx_off, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// one workgroup per item
+__global__ __launch_bounds__(1024) void k_compact_slots_items(const sfm::PairItem* __restrict__ items,
+                                                              const int* __restrict__ slot,
+                                                              const unsigned long long* __restrict__ key,
+                                                              int* __restrict__ out) {
+  const sfm::PairItem& it = items[blockIdx.x];
+  int* o = out + it.out_off;
+  sfm::compact_slots<false>(it.n0, slot + it.idx_off, key + it.key_off, o, o + it.n0, o + 2 * it.n0);
 }
 
 __global__ void k_reset(int n1, unsigned long long* __restrict__ key, int* __restrict__ first, int n0,
@@ -827,6 +895,150 @@ int sfm_matcher_pair_points(sfm_matcher* h, int32_t slot0, const int32_t* idx0, 
   std::memcpy(m0, hh + 4, sizeof(int) * size_t(kept));
   std::memcpy(m1, hh + 4 + n0, sizeof(int) * size_t(kept));
   std::memcpy(X, hblk + ni / 2, sizeof(double) * 3 * size_t(kept));
+  return 0;
+}
+
+// sfm_matcher_pair_points for many older keyframes against one set of the new
+// keyframe's rows, up to the first pair that keeps a point: while no pair has
+// kept one the caller's unmatched set does not change, so the pairs are
+// independent and the first productive one (in the caller's order) is what
+// the pair-by-pair loop would have reached.  One staged upload (item table |
+// per-pair matrices | index lists), eight launches whatever n_pairs, one
+// download (first | kept [B] | matched [B] | the first productive pair's
+// matches), one synchronisation.
+int sfm_matcher_pair_points_first(sfm_matcher* h, int32_t n_pairs, const int32_t* slot0, const int32_t* idx0,
+                                  const int32_t* idx0_off, int32_t slot1, const int32_t* idx1, int32_t n1,
+                                  double ratio_test, double min_distance, double max_distance, const double* K9_0,
+                                  const double* R9_0, const double* t3_0, const double* K9_1, const double* R9_1,
+                                  const double* t3_1, double max_err, int32_t capacity, int32_t* first, int32_t* m0,
+                                  int32_t* m1, double* X, int32_t* n_kept, int32_t* n_matched) {
+  SFM_TRACE("sfm_matcher_pair_points_first");
+  if (!h || !first || !n_kept || !n_matched || !m0 || !m1 || !X) return mfail(SFM_EINVAL, "NULL argument");
+  *first = -1;
+  if (n_pairs < 0 || n_pairs > 65535) return mfail(SFM_EINVAL, "n_pairs must be in 0..65535");
+  for (int32_t b = 0; b < n_pairs; ++b) n_kept[b] = n_matched[b] = 0;
+  if (n_pairs == 0) return 0;
+  if (!slot0 || !idx0_off) return mfail(SFM_EINVAL, "NULL pair list");
+  if (!K9_0 || !R9_0 || !t3_0 || !K9_1 || !R9_1 || !t3_1) return mfail(SFM_EINVAL, "NULL matrix");
+  if (slot1 < 0 || size_t(slot1) >= h->kf.size()) return mfail(SFM_EINVAL, "keyframe slot not stored");
+  if (n1 < 0 || capacity < 0 || (n1 && !idx1)) return mfail(SFM_EINVAL, "bad index lists");
+  if (idx0_off[0] != 0) return mfail(SFM_EINVAL, "idx0_off[0] must be 0");
+  for (int32_t b = 0; b < n_pairs; ++b)
+    if (idx0_off[b + 1] < idx0_off[b]) return mfail(SFM_EINVAL, "idx0_off must not decrease");
+  const int total = idx0_off[n_pairs];
+  if (total && !idx0) return mfail(SFM_EINVAL, "bad index lists");
+  if (!ok_ratio_window(ratio_test, min_distance, max_distance) || !std::isfinite(max_err))
+    return mfail(SFM_EINVAL, "non-finite threshold");
+  const MatchFrame& f1 = h->kf[size_t(slot1)];
+  for (int32_t i = 0; i < n1; ++i)
+    if (idx1[i] < 0 || idx1[i] >= f1.n) return mfail(SFM_EINVAL, "row index out of range (new keyframe)");
+  std::vector<sfm::PairArgs> pa;
+  pa.resize(size_t(n_pairs));
+  int max_n0 = 0;
+  long long qb_total = 0;
+  for (int32_t b = 0; b < n_pairs; ++b) {
+    if (slot0[b] < 0 || size_t(slot0[b]) >= h->kf.size()) return mfail(SFM_EINVAL, "keyframe slot not stored");
+    if (slot0[b] == slot1) return mfail(SFM_EINVAL, "an older keyframe's slot is the new keyframe's");
+    const MatchFrame& f0 = h->kf[size_t(slot0[b])];
+    for (int32_t i = idx0_off[b]; i < idx0_off[b + 1]; ++i)
+      if (idx0[i] < 0 || idx0[i] >= f0.n) return mfail(SFM_EINVAL, "row index out of range (older keyframe)");
+    if (!sfm::compose_pair(K9_0 + 9 * size_t(b), R9_0 + 9 * size_t(b), t3_0 + 3 * size_t(b), K9_1, R9_1, t3_1, max_err,
+                           &pa[size_t(b)]))
+      return mfail(SFM_EINVAL, "K must be finite and upper triangular with K[8] = 1, R and t finite");
+    const int n0 = idx0_off[b + 1] - idx0_off[b];
+    max_n0 = std::max(max_n0, n0);
+    qb_total += (n0 + kQ - 1) / kQ;
+  }
+  if (total == 0 || n1 < 2) return 0;  // reference UB with < 2 train rows: no matches
+  if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
+  int rc = 0;
+  const size_t B = size_t(n_pairs);
+  // train slices as slices_for sizes them, from the batch's query blocks
+  const int nslice = int(std::min<long long>(std::max<long long>(1, (2 * h->n_cu + qb_total - 1) / qb_total),
+                                             std::max(1, n1 / 64)));
+  const int slice = (n1 + nslice - 1) / nslice;
+  // stage (8-B units): item table | matrices | idx0 (all items) | idx1
+  static_assert(sizeof(sfm::PairItem) % 8 == 0 && sizeof(sfm::PairArgs) % 8 == 0, "staged in 8-B units");
+  const size_t w_items = B * sizeof(sfm::PairItem) / 8, w_pa = B * sizeof(sfm::PairArgs) / 8;
+  const size_t w_idx = (size_t(total) + size_t(n1) + 1) / 2;
+  const size_t w_stage = w_items + w_pa + w_idx;
+  // result block: head (first | kept [B] | matched [B], even) | m0 [cap] | m1 [cap] | X [cap][3]
+  const size_t cap = size_t(std::min(max_n0, n1));
+  const size_t hi = (2 * B + 2) & ~size_t(1);
+  const size_t blk = hi / 2 + cap + 3 * cap;  // in doubles
+  auto* st = pbuf<uint64_t>(h, "pfstage", w_stage, &rc);
+  auto* dst = dbuf<uint64_t>(h, "dpfstage", w_stage, &rc);
+  auto* part = dbuf<unsigned long long>(h, "part", 2 * size_t(total) * nslice, &rc);
+  auto* key = dbuf<unsigned long long>(h, "key", B * size_t(n1), &rc);
+  int* dfirst = dbuf<int>(h, "first", B * size_t(n1), &rc);
+  int* slot = dbuf<int>(h, "slot", size_t(total), &rc);
+  int* out = dbuf<int>(h, "out", 2 * size_t(total) + B, &rc);
+  double* dXall = dbuf<double>(h, "ppX", 3 * size_t(total), &rc);
+  int* dks = dbuf<int>(h, "ppks", 2 * size_t(total), &rc);
+  double* dblk = dbuf<double>(h, "pfblk", blk, &rc);
+  double* hblk = pbuf<double>(h, "pfblkh", blk, &rc);
+  if (rc) return rc;
+  hipStream_t s = h->stream;
+  hipStreamSynchronize(s);  // (the pinned stage may feed an earlier copy)
+  auto* items = reinterpret_cast<sfm::PairItem*>(st);
+  for (size_t b = 0; b < B; ++b) {
+    const MatchFrame& f0 = h->kf[size_t(slot0[b])];
+    sfm::PairItem& it = items[b];
+    it.desc = f0.desc;
+    it.pts = f0.pts;
+    it.n0 = idx0_off[b + 1] - idx0_off[b];
+    it.idx_off = idx0_off[b];
+    it.out_off = 2 * idx0_off[b] + int(b);
+    it.pad = 0;
+    it.part_off = 2ll * idx0_off[b] * nslice;
+    it.key_off = (long long)(b) * n1;
+    it.x_off = 3ll * idx0_off[b];
+  }
+  std::memcpy(st + w_items, pa.data(), B * sizeof(sfm::PairArgs));
+  int* ix = reinterpret_cast<int*>(st + w_items + w_pa);
+  std::memcpy(ix, idx0, sizeof(int) * size_t(total));
+  std::memcpy(ix + total, idx1, sizeof(int) * size_t(n1));
+  hipMemcpyAsync(dst, st, w_stage * 8, hipMemcpyHostToDevice, s);
+  const auto* ditems = reinterpret_cast<const sfm::PairItem*>(dst);
+  const auto* dpa = reinterpret_cast<const sfm::PairArgs*>(dst + w_items);
+  const int* dix = reinterpret_cast<const int*>(dst + w_items + w_pa);
+  const int* dtix = dix + total;
+  const unsigned by = unsigned(n_pairs);
+  hipEventRecord(h->ev[0], s);
+  k_reset_items<<<dim3((std::max(max_n0, n1) + 255) / 256, by), 256, 0, s>>>(ditems, n1, key, dfirst, slot);
+  const dim3 grid((max_n0 + kQ - 1) / kQ, nslice, by);
+  switch (h->W) {
+#define CASE(w) \
+  case w: k_knn2_part_items<w><<<grid, kQ * kWaves, 0, s>>>(ditems, dix, f1.desc, dtix, n1, slice, part); break;
+    CASE(1) CASE(2) CASE(4) CASE(8) CASE(16) CASE(32) CASE(64)
+#undef CASE
+    default: return mfail(SFM_EINVAL, "descriptor width must be <= 512 bytes");
+  }
+  hipEventRecord(h->ev[1], s);
+  k_accept_items<<<dim3((max_n0 + 255) / 256, by), 256, 0, s>>>(ditems, dix, nslice, part, f1.pts, dtix, ratio_test,
+                                                                 min_distance * min_distance,
+                                                                 max_distance * max_distance, key, dfirst);
+  k_mark_first_items<<<dim3((n1 + 255) / 256, by), 256, 0, s>>>(ditems, n1, dfirst, slot);
+  k_compact_slots_items<<<by, 1024, 0, s>>>(ditems, slot, key, out);
+  int* dhead = reinterpret_cast<int*>(dblk);
+  sfm::launch_pair_points_first(s, ditems, dpa, n_pairs, max_n0, out, dix, dtix, f1.pts, dXall, dks, dks + total, dhead,
+                                dhead + hi, dhead + hi + cap, dblk + hi / 2 + cap);
+  hipEventRecord(h->ev[2], s);
+  hipMemcpyAsync(hblk, dblk, sizeof(double) * blk, hipMemcpyDeviceToHost, s);
+  if (hipStreamSynchronize(s) != hipSuccess) return mfail(SFM_EIO, "point-creation kernels failed");
+  hipEventElapsedTime(&h->last_knn_ms, h->ev[0], h->ev[1]);
+  hipEventElapsedTime(&h->last_total_ms, h->ev[0], h->ev[2]);
+  const int* hh = reinterpret_cast<const int*>(hblk);
+  *first = hh[0];
+  std::memcpy(n_kept, hh + 1, sizeof(int) * B);
+  std::memcpy(n_matched, hh + 1 + B, sizeof(int) * B);
+  if (hh[0] < 0) return 0;
+  const int kept = n_kept[hh[0]];
+  if (kept > capacity)
+    return mfail(SFM_EINVAL, "capacity " + std::to_string(capacity) + " < " + std::to_string(kept) + " kept matches");
+  std::memcpy(m0, hh + hi, sizeof(int) * size_t(kept));
+  std::memcpy(m1, hh + hi + cap, sizeof(int) * size_t(kept));
+  std::memcpy(X, hblk + hi / 2 + cap, sizeof(double) * 3 * size_t(kept));
   return 0;
 }
 

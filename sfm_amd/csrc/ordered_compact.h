@@ -14,19 +14,22 @@ namespace sfm {
 namespace {  // one copy per translation unit
 
 // slot_train[i] = j + 1 if query i is the first accepted query of train j.
-__global__ void k_mark_first(int n1, const int* __restrict__ first, int* __restrict__ slot_train) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void mark_first(int n1, const int* __restrict__ first, int* __restrict__ slot_train, int j) {
   if (j < n1 && first[j] != 0x7fffffff) slot_train[first[j]] = j + 1;
+}
+__global__ void k_mark_first(int n1, const int* __restrict__ first, int* __restrict__ slot_train) {
+  mark_first(n1, first, slot_train, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // Ordered compaction (single workgroup, prefix sum over the query order).
 // kInvert: the key's low word holds 0xffffffff - query (latest query wins
 // ties under atomicMin) instead of the query itself.
+// (compact_slots: the workgroup's body, for a kernel that picks its pointers
+// per workgroup)
 template <bool kInvert>
-__global__ __launch_bounds__(1024) void k_compact_slots(int n0, const int* __restrict__ slot_train,
-                                                        const unsigned long long* __restrict__ key,
-                                                        int* __restrict__ idx0, int* __restrict__ idx1,
-                                                        int* __restrict__ count) {
+__device__ __forceinline__ void compact_slots(int n0, const int* __restrict__ slot_train,
+                                              const unsigned long long* __restrict__ key, int* __restrict__ idx0,
+                                              int* __restrict__ idx1, int* __restrict__ count) {
   __shared__ int sums[1024];
   __shared__ int base;
   if (threadIdx.x == 0) base = 0;
@@ -55,13 +58,20 @@ __global__ __launch_bounds__(1024) void k_compact_slots(int n0, const int* __res
   }
   if (threadIdx.x == 0) *count = base;
 }
+template <bool kInvert>
+__global__ __launch_bounds__(1024) void k_compact_slots(int n0, const int* __restrict__ slot_train,
+                                                        const unsigned long long* __restrict__ key,
+                                                        int* __restrict__ idx0, int* __restrict__ idx1,
+                                                        int* __restrict__ count) {
+  compact_slots<kInvert>(n0, slot_train, key, idx0, idx1, count);
+}
 
 // Ordered compaction of plain keep flags (the BRISK descriptor's border
 // rule, k_brisk_describe): src[pos] = i for the pos-th kept i, in order;
 // *count = the number kept.  One workgroup of 16 waves, 1024 flags a step: a
 // ballot orders the flags inside a wave, the 16 wave totals order the waves.
-__global__ __launch_bounds__(1024) void k_compact_keep(int n, const int* __restrict__ keep, int* __restrict__ src,
-                                                       int* __restrict__ count) {
+__device__ __forceinline__ void compact_keep(int n, const int* __restrict__ keep, int* __restrict__ src,
+                                             int* __restrict__ count) {
   __shared__ int wave_sum[16];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   int base = 0;  // the same in every thread
@@ -83,6 +93,10 @@ __global__ __launch_bounds__(1024) void k_compact_keep(int n, const int* __restr
     __syncthreads();
   }
   if (threadIdx.x == 0) *count = base;
+}
+__global__ __launch_bounds__(1024) void k_compact_keep(int n, const int* __restrict__ keep, int* __restrict__ src,
+                                                       int* __restrict__ count) {
+  compact_keep(n, keep, src, count);
 }
 
 }  // namespace

@@ -49,7 +49,10 @@ the keyframe store (sfm_map_add_keyframe_rows; the keyframe insert of
 tracking too).  The same map calls in the same order as the host loop; the
 filter and the projection round in the fixed association of
 tests/map_points_ref.py, the host loop's as numpy's BLAS does, so borderline
-matches may differ between the two.
+matches may differ between the two.  batch_pairs=True (with device_mapping)
+runs all older keyframes of a new one in one call, up to the first pair that
+keeps a point (sfm_matcher_pair_points_first): a pair that keeps none changes
+nothing, so the map is the pair-by-pair loop's, bit for bit, in fewer calls.
 
 Culling (cull=True; CSfM.cpp:232-252, 692-752, off by default): between the
 pair loop and the BA, CSfM::cullMapPoints (CMap::removePointsThreshold on
@@ -278,9 +281,11 @@ class LiveSfM:
     def __init__(self, stream: KeypointStream | None = None, device: int = 0, init_gap: int = 5,
                  init: str = "known", init_options: dict | None = None, cull: bool = False,
                  cull_kf_rate: float = 0.9, min_visibility: int = 3, camera=None, guidance: bool = False,
-                 guidance_options: dict | None = None, device_mapping: bool = False):
+                 guidance_options: dict | None = None, device_mapping: bool = False, batch_pairs: bool = False):
         if init not in ("known", "estimate"):
             raise ValueError(f"init must be 'known' or 'estimate', not {init!r}")
+        if batch_pairs and not device_mapping:
+            raise ValueError("batch_pairs batches the device calls of device_mapping=True")
         if guidance and camera is None:
             raise ValueError("guidance needs a camera (it reads the colour frame: process_image)")
         self.init = init
@@ -322,6 +327,10 @@ class LiveSfM:
         # association of tests/map_points_ref.py
         self.device_mapping = bool(device_mapping)
         self.map_log: list[dict] = []    # device_mapping: one entry per keyframe-pair call
+        # all older keyframes of a new one in one call, up to the first pair
+        # that keeps a point (sfm_matcher_pair_points_first): the same map,
+        # bit for bit, in fewer calls; map_log then has one entry per batch
+        self.batch_pairs = bool(batch_pairs)
         # CScanGuidance (CSfM.cpp:80-81): after every RUNNING frame's tracking
         # and mapping, on the map's live points, read on the device
         self._guidance = None
@@ -659,6 +668,9 @@ class LiveSfM:
         sfm_matcher_refind_points.  The same map calls in the same order as
         the host loop."""
         K, R1 = self.K, _R(new_kf.rot)
+        if self.batch_pairs:
+            self._create_points_batched(new_kf, K, R1)
+            return
         for i in range(len(self.kfs) - 1):
             kf = self.kfs[i]
             cu = np.flatnonzero(new_kf.pt3d < 0).astype(np.int32)
@@ -673,25 +685,65 @@ class LiveSfM:
                                  "t1": new_kf.t.copy(), "m0": m0, "m1": m1, "X": Xf, "n_matched": n_matched})
             if not len(m0):
                 continue
-            p2, c2 = pu[m0], cu[m1]
-            idx = self.map.addNewPoints(Xf, p2.reshape(1, -1), [kf.no])
-            kf.pt3d[p2] = idx
-            self.map.addKeyframeRows(self.matcher, kf.slot, kf.no, idx, p2, with_observations=False)
-            # re-find the new points in the keyframes in between (CSfM.cpp:189-221)
-            for j in range(i + 1, len(self.kfs) - 1):
-                kj = self.kfs[j]
-                uj = np.flatnonzero(kj.pt3d < 0).astype(np.int32)
-                if len(uj) < 2:
-                    continue
-                near_kf = abs(kj.no - kf.no) < abs(kj.no - new_kf.no)
-                q0, q1 = self.matcher.refind_points(kf.slot if near_kf else new_kf.slot, p2 if near_kf else c2, Xf, K,
-                                                    _R(kj.rot), kj.t, kj.slot, uj, 0.8, 0.0, MAX_REPR_ERR)
-                if len(q0):
-                    self.map.addKeyframeRows(self.matcher, kj.slot, kj.no, idx[q0], uj[q1])
-                    kj.pt3d[uj[q1]] = idx[q0]
-            self.map.addKeyframeRows(self.matcher, new_kf.slot, new_kf.no, idx, c2)
-            new_kf.pt3d[c2] = idx
-            self.stats["new_points"] += len(idx)
+            self._add_pair_points(i, new_kf, pu[m0], cu[m1], Xf)
+
+    def _create_points_batched(self, new_kf: _Frame, K, R1) -> None:
+        """_create_points_device's loop with one sfm_matcher_pair_points_first
+        per stretch of older keyframes that keep no point: a pair that keeps
+        none changes nothing, so every older keyframe from i on is matched
+        against the same unmatched rows cu in one call; the first pair that
+        keeps a point is applied as the loop applies it, and the next call
+        starts behind it with the new cu."""
+        n_old = len(self.kfs) - 1
+        i = 0
+        while i < n_old:
+            cu = np.flatnonzero(new_kf.pt3d < 0).astype(np.int32)
+            if len(cu) < 2:
+                break
+            js, pus = [], []
+            for j in range(i, n_old):
+                pu = np.flatnonzero(self.kfs[j].pt3d < 0).astype(np.int32)
+                if len(pu) >= 2:
+                    js.append(j)
+                    pus.append(pu)
+            if not js:
+                break
+            R0s = np.stack([_R(self.kfs[j].rot) for j in js])
+            t0s = np.stack([self.kfs[j].t for j in js])
+            slots0 = [self.kfs[j].slot for j in js]
+            first, m0, m1, Xf, n_kept, n_matched = self.matcher.pair_points_first(
+                slots0, pus, new_kf.slot, cu, K, R0s, t0s, K, R1, new_kf.t, MAX_REPR_ERR)
+            self.map_log.append({"frame": new_kf.no, "slots0": slots0, "slot1": new_kf.slot, "idx0": pus, "idx1": cu,
+                                 "K": np.array(K, np.float64), "R0s": R0s, "t0s": t0s, "R1": R1.copy(),
+                                 "t1": new_kf.t.copy(), "first": first, "m0": m0, "m1": m1, "X": Xf,
+                                 "n_kept": n_kept, "n_matched": n_matched})
+            if first < 0:
+                break
+            self._add_pair_points(js[first], new_kf, pus[first][m0], cu[m1], Xf)
+            i = js[first] + 1
+
+    def _add_pair_points(self, i: int, new_kf: _Frame, p2, c2, Xf) -> None:
+        """The new points Xf of older keyframe i's rows p2 and the new
+        keyframe's rows c2 into the map (CSfM.cpp:178-227)."""
+        K, kf = self.K, self.kfs[i]
+        idx = self.map.addNewPoints(Xf, p2.reshape(1, -1), [kf.no])
+        kf.pt3d[p2] = idx
+        self.map.addKeyframeRows(self.matcher, kf.slot, kf.no, idx, p2, with_observations=False)
+        # re-find the new points in the keyframes in between (CSfM.cpp:189-221)
+        for j in range(i + 1, len(self.kfs) - 1):
+            kj = self.kfs[j]
+            uj = np.flatnonzero(kj.pt3d < 0).astype(np.int32)
+            if len(uj) < 2:
+                continue
+            near_kf = abs(kj.no - kf.no) < abs(kj.no - new_kf.no)
+            q0, q1 = self.matcher.refind_points(kf.slot if near_kf else new_kf.slot, p2 if near_kf else c2, Xf, K,
+                                                _R(kj.rot), kj.t, kj.slot, uj, 0.8, 0.0, MAX_REPR_ERR)
+            if len(q0):
+                self.map.addKeyframeRows(self.matcher, kj.slot, kj.no, idx[q0], uj[q1])
+                kj.pt3d[uj[q1]] = idx[q0]
+        self.map.addKeyframeRows(self.matcher, new_kf.slot, new_kf.no, idx, c2)
+        new_kf.pt3d[c2] = idx
+        self.stats["new_points"] += len(idx)
 
     def _bundle_adjust(self) -> None:
         """CSfM::bundleAdjustment over all keyframes (CSfM.cpp:300-348): per

@@ -136,6 +136,49 @@ class FeatureMatcher:
             raise
         return o0[:nk.value].copy(), o1[:nk.value].copy(), X[:nk.value].copy(), nm.value
 
+    def pair_points_first(self, slots0, idx0_list, slot1: int, idx1, K0s, R0s, t0s, K1, R1, t1, max_err: float = 7.0,
+                          ratio=RATIO_TEST, min_distance=MIN_MATCH_DISTANCE, max_distance=MAX_MATCH_DISTANCE,
+                          capacity: int | None = None):
+        """pair_points for many older keyframes against the same rows idx1 of
+        slot1 in one device call (sfm_matcher_pair_points_first), up to the
+        first pair that keeps a point: pair b is the rows idx0_list[b] of
+        slots0[b] with K0s[b], R0s[b], t0s[b] (K0s may be one matrix for
+        all).  -> (first, m0, m1, X, n_kept, n_matched): the lowest b that
+        kept a match (-1: none), that pair's kept matches as pair_points
+        returns them (empty when first == -1), and every pair's kept and
+        matched counts."""
+        B = len(slots0)
+        s0 = np.ascontiguousarray(np.asarray(slots0).reshape(-1), dtype=np.int32)
+        lists = [np.asarray(a).reshape(-1) for a in idx0_list]
+        if len(lists) != B:
+            raise ValueError("one index list per pair")
+        off = np.zeros(B + 1, np.int32)
+        off[1:] = np.cumsum([a.size for a in lists])
+        a = np.ascontiguousarray(np.concatenate(lists) if B else np.zeros(0), dtype=np.int32)
+        b = np.ascontiguousarray(np.asarray(idx1).reshape(-1), dtype=np.int32)
+        K0 = np.asarray(K0s, np.float64)
+        K0 = np.ascontiguousarray(np.broadcast_to(K0.reshape(-1, 9) if K0.size != 9 else K0.reshape(1, 9), (B, 9)))
+        R0 = np.ascontiguousarray(np.asarray(R0s, np.float64).reshape(B, 9))
+        t0 = np.ascontiguousarray(np.asarray(t0s, np.float64).reshape(B, 3))
+        m9 = [np.ascontiguousarray(np.asarray(m, np.float64).reshape(9)) for m in (K1, R1)]
+        t3 = np.ascontiguousarray(np.asarray(t1, np.float64).reshape(3))
+        n0_max = max((x.size for x in lists), default=0)
+        cap = min(n0_max, b.size) if capacity is None else int(capacity)
+        n = max(1, cap)
+        o0, o1, X = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, 3))
+        nk, nm, first = np.zeros(max(1, B), np.int32), np.zeros(max(1, B), np.int32), c_int32(-1)
+        rc = lib().sfm_matcher_pair_points_first(self._h, B, ptr(s0), ptr(a), ptr(off), int(slot1), ptr(b), b.size,
+                                                 ratio, min_distance, max_distance, ptr(K0), ptr(R0), ptr(t0),
+                                                 ptr(m9[0]), ptr(m9[1]), ptr(t3), float(max_err), cap,
+                                                 ctypes.byref(first), ptr(o0), ptr(o1), ptr(X), ptr(nk), ptr(nm))
+        try:
+            check(rc, "sfm_matcher_pair_points_first")
+        except Exception as e:
+            e.first, e.n_kept, e.n_matched = first.value, nk[:B].copy(), nm[:B].copy()   # (capacity too small)
+            raise
+        k = int(nk[first.value]) if first.value >= 0 else 0
+        return first.value, o0[:k].copy(), o1[:k].copy(), X[:k].copy(), nk[:B].copy(), nm[:B].copy()
+
     def refind_points(self, q_slot: int, q_idx, X, K, R, t, t_slot: int, t_idx, ratio=RATIO_TEST,
                       min_distance=MIN_MATCH_DISTANCE, max_distance=MAX_MATCH_DISTANCE):
         """match_keyframes(q_slot, q_idx, t_slot, t_idx, q_pts = the

@@ -1,13 +1,17 @@
-"""Map-point creation in the live loop, host path | device path, timed (writes
+"""Map-point creation in the live loop, host path | device path | device path
+with all older keyframes in one call, timed (writes
 profiles/map_points_timing.txt, or --out PATH):
 
 * the 300-frame live loop (bench.py's live leg: frames generated before the
-  timed region, one warm-up of 25 frames) with device_mapping off | on,
-  alternating, median of three rounds: frames/s, the point-creation loop's
-  wall time (times["mapping"] - times["ba"]), keyframes, map points;
+  timed region, one warm-up of 25 frames) with device_mapping off | on | on
+  with batch_pairs, alternating, median of three rounds: frames/s, the
+  point-creation loop's wall time (times["mapping"] - times["ba"]),
+  keyframes, map points;
 * the device calls the point-creation loop makes per keyframe, counted in one
   untimed run per variant (every counted call blocks on one host
-  synchronisation; the count is deterministic).
+  synchronisation; the count is deterministic); for the batched variant also
+  every call's pair count B, its device time (the handle's HIP events) and
+  the pairs computed behind the first productive one, which are discarded.
 
 Every run is a fresh child process (this file with --child)."""
 import argparse
@@ -20,7 +24,7 @@ import time
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R)
 N = 300
-MATCHER_CALLS = ("match_keyframes", "match", "pair_points", "refind_points")
+MATCHER_CALLS = ("match_keyframes", "match", "pair_points", "pair_points_first", "refind_points")
 MAP_CALLS = ("addNewPoints", "addPointMatches", "addDescriptors", "addKeyframeRows")
 
 
@@ -56,22 +60,38 @@ def count_calls(s) -> dict:
     return counts
 
 
-def child(device: bool, count: bool) -> None:
+def batch_stats(s) -> list:
+    """One record per pair_points_first call: B, rows, first, device ms."""
+    recs = []
+    f = s.matcher.pair_points_first
+
+    def g(slots0, idx0_list, slot1, idx1, *a, **k):
+        out = f(slots0, idx0_list, slot1, idx1, *a, **k)
+        knn_ms, total_ms = s.matcher.last_time_ms()
+        recs.append({"B": len(slots0), "rows0": int(sum(len(x) for x in idx0_list)), "rows1": len(idx1),
+                     "first": int(out[0]), "knn_ms": knn_ms, "total_ms": total_ms})
+        return out
+    s.matcher.pair_points_first = g
+    return recs
+
+
+def child(device: bool, batch: bool, count: bool) -> None:
     from sfm_amd.live import KeypointStream, LiveSfM
     st = KeypointStream()
     frames = [st.frame(k)[:2] for k in range(N)]
-    warm = LiveSfM(st, device_mapping=device)
+    warm = LiveSfM(st, device_mapping=device, batch_pairs=batch)
     for k in range(25):
         warm.process(k, *frames[k])
     warm.close()
-    s = LiveSfM(st, device_mapping=device)
+    s = LiveSfM(st, device_mapping=device, batch_pairs=batch)
+    batches = batch_stats(s) if count and batch else []
     counts = count_calls(s) if count else {}
     t0 = time.perf_counter()
     for k in range(N):
         s.process(k, *frames[k])
     wall = time.perf_counter() - t0
     n_pts, n_obs, _ = s.map.size()
-    out = {"device_mapping": device, "frames_per_s": N / wall, "keyframes": len(s.kfs), "map_points": int(n_pts),
+    out = {"device_mapping": device, "batch_pairs": batch, "batches": batches, "frames_per_s": N / wall, "keyframes": len(s.kfs), "map_points": int(n_pts),
            "observations": int(n_obs), "ba_s": s.times["ba"], "mapping_s": s.times["mapping"],
            "create_s": s.times["mapping"] - s.times["ba"], "lost": s.lost, "tracked": s.stats["tracked"],
            "mappings": len(s.ba_log) - 1, "calls": counts}
@@ -79,9 +99,9 @@ def child(device: bool, count: bool) -> None:
     print("RESULT " + json.dumps(out), flush=True)
 
 
-def run_child(device: bool, count: bool = False) -> dict:
+def run_child(device: bool, batch: bool = False, count: bool = False) -> dict:
     cmd = [sys.executable, os.path.abspath(__file__), "--child"] + (["--device"] if device else []) + \
-        (["--count"] if count else [])
+        (["--batch"] if batch else []) + (["--count"] if count else [])
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     if out.returncode != 0:
         raise RuntimeError(out.stdout + out.stderr)
@@ -97,33 +117,49 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--device", action="store_true")
+    ap.add_argument("--batch", action="store_true")
     ap.add_argument("--count", action="store_true")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(R, "profiles", "map_points_timing.txt"))
     a = ap.parse_args()
     if a.child:
-        child(a.device, a.count)
+        child(a.device, a.batch, a.count)
         return
-    cols = {"host": [], "device": []}
+    cols = {"host": [], "device": [], "batched": []}
     for _ in range(a.rounds):
         cols["host"].append(run_child(False))
         cols["device"].append(run_child(True))
+        cols["batched"].append(run_child(True, True))
     lines = [f"live loop, {N} frames of synthetic detector output, map-point creation on the host (default) | on the "
-             f"device (device_mapping=True); {a.rounds} rounds alternating, medians (every round's value in brackets)"]
+             f"device (device_mapping=True) | on the device, all older keyframes in one call (device_mapping=True, "
+             f"batch_pairs=True); {a.rounds} rounds alternating, medians (every round's value in brackets)"]
     for name, runs in cols.items():
         r = runs[-1]
-        lines.append(f"{name:6s}: {med([x['frames_per_s'] for x in runs]):7.1f} frames/s "
+        lines.append(f"{name:7s}: {med([x['frames_per_s'] for x in runs]):7.1f} frames/s "
                      f"[{', '.join('%.1f' % x['frames_per_s'] for x in runs)}], point creation (mapping - BA) "
                      f"{med([x['create_s'] for x in runs]):.4f} s [{', '.join('%.4f' % x['create_s'] for x in runs)}], "
                      f"mapping {med([x['mapping_s'] for x in runs]):.4f} s, BA {med([x['ba_s'] for x in runs]):.4f} s, "
                      f"{r['keyframes']} keyframes, {r['map_points']} map points, {r['observations']} observations, "
                      f"tracked {r['tracked']}, lost {r['lost']}")
-    for name, device in (("host", False), ("device", True)):
-        r = run_child(device, count=True)
+    for name, device, batch in (("host", False, False), ("device", True, False), ("batched", True, True)):
+        r = run_child(device, batch, count=True)
         total = sum(r["calls"].values())
-        lines.append(f"{name:6s}: {total} device calls in the point-creation loop over {r['mappings']} mappings = "
+        lines.append(f"{name:7s}: {total} device calls in the point-creation loop over {r['mappings']} mappings = "
                      f"{total / max(1, r['mappings']):.1f} per keyframe, one host synchronisation each ("
                      + ", ".join(f"{k} {v}" for k, v in sorted(r["calls"].items())) + ")")
+        if batch:
+            bs = r["batches"]
+            hit = [x for x in bs if x["first"] >= 0]
+            lines.append(f"batched: {len(bs)} pair_points_first calls, {len(hit)} with a productive pair; pairs per call "
+                         f"median {med([x['B'] for x in bs])}, max {max(x['B'] for x in bs)}; older-keyframe rows per "
+                         f"call median {med([x['rows0'] for x in bs])}; device time per call (first launch to the "
+                         f"pick, HIP events) median {med([x['total_ms'] for x in bs]):.3f} ms, max "
+                         f"{max(x['total_ms'] for x in bs):.3f} ms, of which the 2-NN search median "
+                         f"{med([x['knn_ms'] for x in bs]):.3f} ms; pairs computed in all {sum(x['B'] for x in bs)}, of "
+                         f"them behind the first productive pair (discarded, computed again by the next call) "
+                         f"{sum(x['B'] - x['first'] - 1 for x in hit)}")
+            lines.append("batched: (B, rows0, rows1, first, total ms) per call: "
+                         + " ".join(f"({x['B']},{x['rows0']},{x['rows1']},{x['first']},{x['total_ms']:.3f})" for x in bs))
     text = "\n".join(lines) + "\n"
     print(text, end="")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
