@@ -261,7 +261,7 @@ int sfm_matcher_store_keyframe(sfm_matcher* h, int32_t slot, const double* pts, 
  * CSfM.cpp:199-206 passes them; q_idx must not repeat then -- else the
  * keyframe's own), train rows t_idx[n_t] of slot t_slot.  Subset-local
  * indices out (into q_idx / t_idx), bitwise sfm_matcher_match on the same
- * rows; capacity >= min(n_q, n_t). */
+ * rows; idx0 / idx1 not NULL, capacity >= min(n_q, n_t). */
 int sfm_matcher_match_keyframes(sfm_matcher* h, int32_t q_slot, const int32_t* q_idx, int32_t n_q, const double* q_pts,
                                 int32_t t_slot, const int32_t* t_idx, int32_t n_t, double ratio_test,
                                 double min_distance, double max_distance, int32_t* idx0, int32_t* idx1,
@@ -280,7 +280,9 @@ int sfm_matcher_match_keyframes(sfm_matcher* h, int32_t q_slot, const int32_t* q
  * upload, one download, one host synchronisation.  n0 == 0 or n1 < 2: no
  * matches.  When the kept count exceeds capacity, *n_kept is set, nothing
  * else is written and SFM_EINVAL is returned (capacity min(n0, n1) always
- * fits).  Every argument is checked before the first device call. */
+ * fits).  Every argument is checked before the first device call.  This is
+ * the n_pairs = 1 case of sfm_matcher_pair_points_first below: one host path,
+ * one set of kernels (slot0 == slot1 is allowed here only). */
 int sfm_matcher_pair_points(sfm_matcher* h, int32_t slot0, const int32_t* idx0, int32_t n0, int32_t slot1,
                             const int32_t* idx1, int32_t n1, double ratio_test, double min_distance,
                             double max_distance, const double* K9_0, const double* R9_0, const double* t3_0,
@@ -342,7 +344,7 @@ int sfm_matcher_match(sfm_matcher* h, const double* pts0, const uint8_t* desc0, 
 /* The 2-NN search alone on host arrays. */
 int sfm_matcher_knn2(sfm_matcher* h, const uint8_t* desc0, int32_t n0, const uint8_t* desc1, int32_t n1,
                      int32_t* best_idx, int32_t* best_dist, int32_t* second_idx, int32_t* second_dist);
-/* Device time (ms, HIP events) of the last match: [2-NN search, whole call on the device]. */
+/* Device time (ms, HIP events) of the last match or point-creation call (sfm_matcher_pair_points[_first]): [2-NN search, whole call on the device]. */
 int sfm_matcher_last_time(sfm_matcher* h, double* ms2);
 
 /* CMap::getRepresentativeDescriptors (CMap.cpp:345-381),

@@ -1,5 +1,6 @@
 // Seams of the map-point creation (mappoint_kernels.hip): the kernels and
-// the host composition behind sfm_matcher_pair_points,
+// the host composition behind sfm_matcher_pair_points and
+// sfm_matcher_pair_points_first (one path, pair_points_run),
 // sfm_matcher_refind_points, sfm_filter_matches (match_kernels.hip) and
 // sfm_map_add_keyframe_rows (map_store.hip).
 #pragma once
@@ -8,8 +9,9 @@
 
 namespace sfm {
 
-// What one keyframe pair's kernels read, composed once per call on the host
-// (compose_pair) and passed by value as a kernel argument.
+// What one keyframe pair's kernels read, composed once per pair on the host
+// (compose_pair): staged with the item table for the point creation, passed
+// by value as a kernel argument to the filter alone (launch_filter).
 struct PairArgs {
   double P0[12], P1[12];  // K [R|t], row-major 3x4
   double F[9];            // K1^-T [t]x R K0^-1, row-major
@@ -17,10 +19,11 @@ struct PairArgs {
   double max_err;
 };
 
-// One keyframe pair of a batch (sfm_matcher_pair_points_first): the older
-// keyframe's rows and where this pair's pieces lie in the call's buffers.  The
-// table is device-resident, staged with the index lists; the new keyframe's
-// side (its rows, idx1, n1) is common to all items.
+// One keyframe pair of a point-creation call (sfm_matcher_pair_points: one
+// item; sfm_matcher_pair_points_first: n_pairs): the older keyframe's rows and
+// where this pair's pieces lie in the call's buffers.  The table is
+// device-resident, staged with the index lists; the new keyframe's side (its
+// rows, idx1, n1) is common to all items.
 struct PairItem {
   const uint64_t* desc;  // the older keyframe's descriptor words [.][W]
   const double* pts;     // ... and positions [.][2]
@@ -41,20 +44,15 @@ bool compose_pair(const double* K0, const double* R0, const double* t0, const do
 
 // All launches below: on stream s, no synchronisation.
 //
-// The matcher's result block `out` ([2 n0 + 1]: query | train | count,
-// subset-local) -> per match k < count the triangulated point Xall[k] and the
-// keep flag (0 for k >= count); then the kept matches, in match order, into
-// the result block: head[0] = kept, head[1] = count, m0 / m1 [n0] the kept
-// matches' subset-local indices, X [n0][3] their points.
-void launch_pair_points(hipStream_t s, const int* out, int n0, const int* qidx, const int* tidx, const double* pts0,
-                        const double* pts1, const PairArgs& a, double* Xall, int* keep, int* src, int* head, int* m0,
-                        int* m1, double* X);
-// The same for the B items of a batch, then the pick: per item b the points
-// and keep flags of its matches (out + out_off, the arithmetic of
-// launch_pair_points through pa[b]) and their ordered compaction (src +
-// idx_off; head[1 + b] = kept); then head[1 + B + b] = matched, head[0] = the
-// lowest b with kept > 0 (-1: none) and that item's kept matches in m0 / m1 /
-// X.  Three launches whatever B; max_n0 = the longest item.
+// The tail of a point-creation call of B items (B = 1: one keyframe pair).
+// Per item b the matcher's result block out + out_off ([2 n0 + 1]: query |
+// train | count, subset-local) -> per match k < count the triangulated point
+// Xall[x_off + k] through pa[b] and the keep flag (0 for k >= count), then
+// their ordered compaction (src + idx_off; head[1 + b] = kept); then the
+// pick: head[1 + B + b] = matched, head[0] = the lowest b with kept > 0 (-1:
+// none) and that item's kept matches, in match order, in m0 / m1 (subset-local
+// indices) and X (their points).  Three launches whatever B; max_n0 = the
+// longest item.
 void launch_pair_points_first(hipStream_t s, const PairItem* items, const PairArgs* pa, int B, int max_n0,
                               const int* out, const int* idx, const int* tidx, const double* pts1, double* Xall,
                               int* keep, int* src, int* head, int* m0, int* m1, double* X);

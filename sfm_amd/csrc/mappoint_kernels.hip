@@ -14,9 +14,10 @@
 //
 // Fixed association (this file is compiled with -ffp-contract=off, host and
 // device): every 3-term sum is (a b + c d) + e f, a fourth term is added
-// last; the host composes F, P0 = K0 [R0|t0] and P1 once per call in plain
-// C++ (compose_pair) and the kernels take them as arguments.  One lane per
-// match, no atomics: the keep flags are ordered by k_compact_keep
+// last; the host composes F, P0 = K0 [R0|t0] and P1 once per pair in plain
+// C++ (compose_pair); the point-creation kernels read them from the call's
+// staged table, the filter alone (k_filter) takes them as an argument.  One
+// lane per match, no atomics: the keep flags are ordered by compact_keep
 // (ordered_compact.h), so the kept matches stay in the matcher's order.
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -74,14 +75,7 @@ __device__ __forceinline__ void pair_point(const int* __restrict__ out, int n0, 
   keep[k] = pair_keep(a, u0, v0, u1, v1, X) ? 1 : 0;
 }
 
-__global__ __launch_bounds__(256) void k_pair_points(const int* __restrict__ out, int n0, const int* __restrict__ qidx,
-                                                     const int* __restrict__ tidx, const double* __restrict__ pts0,
-                                                     const double* __restrict__ pts1, const PairArgs a,
-                                                     double* __restrict__ Xall, int* __restrict__ keep) {
-  pair_point(out, n0, qidx, tidx, pts0, pts1, a, Xall, keep, blockIdx.x * blockDim.x + threadIdx.x);
-}
-
-// item blockIdx.y of a batch; its matrices are wave-uniform loads from pa
+// item blockIdx.y of a call; its matrices are wave-uniform loads from pa
 __global__ __launch_bounds__(256) void k_pair_points_items(const PairItem* __restrict__ items,
                                                            const PairArgs* __restrict__ pa,
                                                            const int* __restrict__ out, const int* __restrict__ idx,
@@ -115,20 +109,8 @@ __device__ __forceinline__ void gather_kept(const int* __restrict__ out, int n0,
   X[3 * size_t(pos) + 2] = Xall[3 * size_t(k) + 2];
 }
 
-// The kept matches (head[0] = their count, as k_compact_keep wrote it) into
-// the result block.
-__global__ __launch_bounds__(256) void k_pair_gather(const int* __restrict__ out, int n0, const int* __restrict__ src,
-                                                     const double* __restrict__ Xall, int* __restrict__ head,
-                                                     int* __restrict__ m0, int* __restrict__ m1,
-                                                     double* __restrict__ X) {
-  const int pos = blockIdx.x * blockDim.x + threadIdx.x;
-  if (pos == 0) head[1] = out[2 * n0];
-  if (pos >= n0 || pos >= head[0]) return;
-  gather_kept(out, n0, src, Xall, pos, m0, m1, X);
-}
-
-// The pick of a batch, one workgroup: every item's match count beside its
-// kept count (head: first | kept [B] | matched [B]), the lowest item with a
+// The pick among a call's B items, one workgroup: every item's match count
+// beside its kept count (head: first | kept [B] | matched [B]), the lowest item with a
 // kept match -- a min over the lanes' strided items, across the wave by
 // shuffles and across the four waves through LDS, so B may exceed a wave --
 // and that item's kept matches into the one result block.
@@ -255,14 +237,6 @@ bool compose_pair(const double* K0, const double* R0, const double* t0, const do
   out->z1[3] = t1[2];
   out->max_err = max_err;
   return true;
-}
-
-void launch_pair_points(hipStream_t s, const int* out, int n0, const int* qidx, const int* tidx, const double* pts0,
-                        const double* pts1, const PairArgs& a, double* Xall, int* keep, int* src, int* head, int* m0,
-                        int* m1, double* X) {
-  k_pair_points<<<blocks(n0), 256, 0, s>>>(out, n0, qidx, tidx, pts0, pts1, a, Xall, keep);
-  k_compact_keep<<<1, 1024, 0, s>>>(n0, keep, src, head);
-  k_pair_gather<<<blocks(n0), 256, 0, s>>>(out, n0, src, Xall, head, m0, m1, X);
 }
 
 void launch_pair_points_first(hipStream_t s, const PairItem* items, const PairArgs* pa, int B, int max_n0,

@@ -137,7 +137,7 @@ __global__ __launch_bounds__(kQ * kWaves) void k_knn2_part(const uint64_t* __res
   knn2_block<W, kIdx>(q, qidx, n0, tr, tidx, n1, slice, part, blockIdx.x, blockIdx.y);
 }
 
-// The same for every item of a batch (sfm_matcher_pair_points_first): item
+// The same for every item of a point-creation call (pair_points_run): item
 // blockIdx.z's query rows against the common train rows.  The grid's x is
 // sized for the longest item; a workgroup past its own item's rows leaves as
 // a whole, before the LDS and the barrier.
@@ -371,12 +371,14 @@ T* pbuf(sfm_matcher* h, const char* name, size_t count, int* rc) {
 
 // Train slices: enough workgroups to put ~8 waves on every CU, each slice
 // at least 64 rows (one row per lane-step of every wave is not worth less).
-int slices_for(const sfm_matcher* h, int n0, int n1) {
-  const int qb = (n0 + kQ - 1) / kQ;
-  const int want = std::max(1, (2 * h->n_cu + qb - 1) / qb);
+// qb: the call's query blocks (of kQ rows), all items of a batch together.
+int slices_for_blocks(const sfm_matcher* h, long long qb, int n1) {
+  const long long want = std::max<long long>(1, (2 * h->n_cu + qb - 1) / qb);
   const int most = std::max(1, n1 / 64);
-  return std::min(want, most);
+  return int(std::min<long long>(want, most));
 }
+
+int slices_for(const sfm_matcher* h, int n0, int n1) { return slices_for_blocks(h, (n0 + kQ - 1) / kQ, n1); }
 
 int launch_knn(sfm_matcher* h, const uint64_t* q, const int* qidx, int n0, const uint64_t* tr, const int* tidx,
                int n1, unsigned long long* part, int nslice) {
@@ -469,11 +471,133 @@ bool ok_ratio_window(double ratio, double mn, double mx) {
   return std::isfinite(ratio) && std::isfinite(mn) && std::isfinite(mx);
 }
 
+// every idx[i], i < n, is a row of a frame of `rows` rows
+bool rows_in_range(const int32_t* idx, int32_t n, int rows) {
+  for (int32_t i = 0; i < n; ++i)
+    if (idx[i] < 0 || idx[i] >= rows) return false;
+  return true;
+}
+
+// run_match's result block ([2 n0 + 1]: query | train | count) into the caller's arrays
+void copy_matches(const int* res, int n0, int32_t* idx0, int32_t* idx1, int32_t* n_matches) {
+  const int m = res[2 * n0];
+  std::memcpy(idx0, res, sizeof(int) * size_t(m));
+  std::memcpy(idx1, res + n0, sizeof(int) * size_t(m));
+  *n_matches = m;
+}
+
+// CSfM::mapping's point creation (CSfM.cpp:138-176) for B older keyframes
+// against one set of the new keyframe's rows, up to the first pair that keeps
+// a point; sfm_matcher_pair_points is B = 1.  Per pair b: the member-window
+// match of rows idx0[idx0_off[b] .. idx0_off[b + 1]) of keyframe slot0[b]
+// with rows idx1 of f1, the triangulation and the filter through pa[b]
+// (mappoint_kernels.hip), all on the resident rows.  One staged upload (item
+// table | per-pair matrices | index lists), eight launches whatever B, one
+// download (first | kept [B] | matched [B] | the first productive pair's
+// matches), one synchronisation.  The caller has checked slots and index
+// lists, composed pa, found a row in idx0 and two in idx1 and set the device.
+int pair_points_run(sfm_matcher* h, int B_, const int32_t* slot0, const int32_t* idx0, const int32_t* idx0_off,
+                    const MatchFrame& f1, const int32_t* idx1, int n1, double ratio_test, double min_distance,
+                    double max_distance, const sfm::PairArgs* pa, int capacity, int32_t* first, int32_t* m0,
+                    int32_t* m1, double* X, int32_t* n_kept, int32_t* n_matched) {
+  int rc = 0;
+  const size_t B = size_t(B_);
+  const int total = idx0_off[B];
+  int max_n0 = 0;
+  long long qb_total = 0;
+  for (size_t b = 0; b < B; ++b) {
+    const int n0 = idx0_off[b + 1] - idx0_off[b];
+    max_n0 = std::max(max_n0, n0);
+    qb_total += (n0 + kQ - 1) / kQ;
+  }
+  const int nslice = slices_for_blocks(h, qb_total, n1);
+  const int slice = (n1 + nslice - 1) / nslice;
+  // stage (8-B units): item table | matrices | idx0 (all items) | idx1
+  static_assert(sizeof(sfm::PairItem) % 8 == 0 && sizeof(sfm::PairArgs) % 8 == 0, "staged in 8-B units");
+  const size_t w_items = B * sizeof(sfm::PairItem) / 8, w_pa = B * sizeof(sfm::PairArgs) / 8;
+  const size_t w_idx = (size_t(total) + size_t(n1) + 1) / 2;
+  const size_t w_stage = w_items + w_pa + w_idx;
+  // result block: head (first | kept [B] | matched [B], even) | m0 [cap] | m1 [cap] | X [cap][3]
+  const size_t cap = size_t(std::min(max_n0, n1));
+  const size_t hi = (2 * B + 2) & ~size_t(1);
+  const size_t blk = hi / 2 + cap + 3 * cap;  // in doubles
+  auto* st = pbuf<uint64_t>(h, "pfstage", w_stage, &rc);
+  auto* dst = dbuf<uint64_t>(h, "dpfstage", w_stage, &rc);
+  auto* part = dbuf<unsigned long long>(h, "part", 2 * size_t(total) * nslice, &rc);
+  auto* key = dbuf<unsigned long long>(h, "key", B * size_t(n1), &rc);
+  int* dfirst = dbuf<int>(h, "first", B * size_t(n1), &rc);
+  int* slot = dbuf<int>(h, "slot", size_t(total), &rc);
+  int* out = dbuf<int>(h, "out", 2 * size_t(total) + B, &rc);
+  double* dXall = dbuf<double>(h, "ppX", 3 * size_t(total), &rc);
+  int* dks = dbuf<int>(h, "ppks", 2 * size_t(total), &rc);
+  double* dblk = dbuf<double>(h, "pfblk", blk, &rc);
+  double* hblk = pbuf<double>(h, "pfblkh", blk, &rc);
+  if (rc) return rc;
+  hipStream_t s = h->stream;
+  hipStreamSynchronize(s);  // (the pinned stage may feed an earlier copy)
+  auto* items = reinterpret_cast<sfm::PairItem*>(st);
+  for (size_t b = 0; b < B; ++b) {
+    const MatchFrame& f0 = h->kf[size_t(slot0[b])];
+    sfm::PairItem& it = items[b];
+    it.desc = f0.desc;
+    it.pts = f0.pts;
+    it.n0 = idx0_off[b + 1] - idx0_off[b];
+    it.idx_off = idx0_off[b];
+    it.out_off = 2 * idx0_off[b] + int(b);
+    it.pad = 0;
+    it.part_off = 2ll * idx0_off[b] * nslice;
+    it.key_off = (long long)(b) * n1;
+    it.x_off = 3ll * idx0_off[b];
+  }
+  std::memcpy(st + w_items, pa, B * sizeof(sfm::PairArgs));
+  int* ix = reinterpret_cast<int*>(st + w_items + w_pa);
+  std::memcpy(ix, idx0, sizeof(int) * size_t(total));
+  std::memcpy(ix + total, idx1, sizeof(int) * size_t(n1));
+  hipMemcpyAsync(dst, st, w_stage * 8, hipMemcpyHostToDevice, s);
+  const auto* ditems = reinterpret_cast<const sfm::PairItem*>(dst);
+  const auto* dpa = reinterpret_cast<const sfm::PairArgs*>(dst + w_items);
+  const int* dix = reinterpret_cast<const int*>(dst + w_items + w_pa);
+  const int* dtix = dix + total;
+  const unsigned by = unsigned(B_);
+  hipEventRecord(h->ev[0], s);
+  k_reset_items<<<dim3((std::max(max_n0, n1) + 255) / 256, by), 256, 0, s>>>(ditems, n1, key, dfirst, slot);
+  const dim3 grid((max_n0 + kQ - 1) / kQ, nslice, by);
+  switch (h->W) {
+#define CASE(w) \
+  case w: k_knn2_part_items<w><<<grid, kQ * kWaves, 0, s>>>(ditems, dix, f1.desc, dtix, n1, slice, part); break;
+    CASE(1) CASE(2) CASE(4) CASE(8) CASE(16) CASE(32) CASE(64)
+#undef CASE
+    default: return mfail(SFM_EINVAL, "descriptor width must be <= 512 bytes");
+  }
+  hipEventRecord(h->ev[1], s);
+  k_accept_items<<<dim3((max_n0 + 255) / 256, by), 256, 0, s>>>(ditems, dix, nslice, part, f1.pts, dtix, ratio_test,
+                                                                 min_distance * min_distance,
+                                                                 max_distance * max_distance, key, dfirst);
+  k_mark_first_items<<<dim3((n1 + 255) / 256, by), 256, 0, s>>>(ditems, n1, dfirst, slot);
+  k_compact_slots_items<<<by, 1024, 0, s>>>(ditems, slot, key, out);
+  int* dhead = reinterpret_cast<int*>(dblk);
+  sfm::launch_pair_points_first(s, ditems, dpa, B_, max_n0, out, dix, dtix, f1.pts, dXall, dks, dks + total, dhead,
+                                dhead + hi, dhead + hi + cap, dblk + hi / 2 + cap);
+  hipEventRecord(h->ev[2], s);
+  hipMemcpyAsync(hblk, dblk, sizeof(double) * blk, hipMemcpyDeviceToHost, s);
+  if (hipStreamSynchronize(s) != hipSuccess) return mfail(SFM_EIO, "point-creation kernels failed");
+  hipEventElapsedTime(&h->last_knn_ms, h->ev[0], h->ev[1]);
+  hipEventElapsedTime(&h->last_total_ms, h->ev[0], h->ev[2]);
+  const int* hh = reinterpret_cast<const int*>(hblk);
+  *first = hh[0];
+  std::memcpy(n_kept, hh + 1, sizeof(int) * B);
+  std::memcpy(n_matched, hh + 1 + B, sizeof(int) * B);
+  if (hh[0] < 0) return 0;
+  const int kept = n_kept[hh[0]];
+  if (kept > capacity)
+    return mfail(SFM_EINVAL, "capacity " + std::to_string(capacity) + " < " + std::to_string(kept) + " kept matches");
+  std::memcpy(m0, hh + hi, sizeof(int) * size_t(kept));
+  std::memcpy(m1, hh + hi + cap, sizeof(int) * size_t(kept));
+  std::memcpy(X, hblk + hi / 2 + cap, sizeof(double) * 3 * size_t(kept));
+  return 0;
+}
+
 }  // namespace
-
-extern "C" {
-
-}  // extern "C"
 
 namespace sfm {
 // pnp_kernels.hip / map_store.hip (sfm_track_pnp)
@@ -652,10 +776,8 @@ int sfm_matcher_match_subset(sfm_matcher* h, const int32_t* prev_idx, int32_t n_
   if (!ok_ratio_window(ratio_test, min_distance, max_distance)) return mfail(SFM_EINVAL, "non-finite threshold");
   const MatchFrame& fp = h->frame[h->cur ^ 1];
   const MatchFrame& fc = h->frame[h->cur];
-  for (int32_t i = 0; i < n_prev; ++i)
-    if (prev_idx[i] < 0 || prev_idx[i] >= fp.n) return mfail(SFM_EINVAL, "prev index out of range");
-  for (int32_t i = 0; i < n_curr; ++i)
-    if (curr_idx[i] < 0 || curr_idx[i] >= fc.n) return mfail(SFM_EINVAL, "curr index out of range");
+  if (!rows_in_range(prev_idx, n_prev, fp.n)) return mfail(SFM_EINVAL, "prev index out of range");
+  if (!rows_in_range(curr_idx, n_curr, fc.n)) return mfail(SFM_EINVAL, "curr index out of range");
   if (n_prev == 0 || n_curr < 2) return 0;  // reference UB with < 2 train rows: no matches
   if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
   int rc = 0;
@@ -671,13 +793,12 @@ int sfm_matcher_match_subset(sfm_matcher* h, const int32_t* prev_idx, int32_t n_
   if ((rc = run_match(h, fp.desc, dix, fp.pts, n_prev, fc.desc, dix + n_prev, fc.pts, n_curr, ratio_test,
                       min_distance, max_distance, &res)))
     return rc;
-  const int m = res[2 * n_prev];
+  copy_matches(res, n_prev, prev_match, curr_match, n_matches);
   // frame-global indices (CTracker.cpp:406-407, 412)
-  for (int k = 0; k < m; ++k) {
-    prev_match[k] = prev_idx[res[k]];
-    curr_match[k] = curr_idx[res[n_prev + k]];
+  for (int k = 0; k < *n_matches; ++k) {
+    prev_match[k] = prev_idx[prev_match[k]];
+    curr_match[k] = curr_idx[curr_match[k]];
   }
-  *n_matches = m;
   return 0;
 }
 
@@ -695,10 +816,7 @@ int sfm_matcher_match_frames(sfm_matcher* h, int32_t distorted, double ratio_tes
   int rc = run_match(h, fp.desc, nullptr, distorted ? fp.ptsd : fp.pts, fp.n, fc.desc, nullptr,
                      distorted ? fc.ptsd : fc.pts, fc.n, ratio_test, min_distance, max_distance, &res);
   if (rc) return rc;
-  const int m = res[2 * fp.n];
-  std::memcpy(prev_idx, res, sizeof(int) * size_t(m));
-  std::memcpy(curr_idx, res + fp.n, sizeof(int) * size_t(m));
-  *n_matches = m;
+  copy_matches(res, fp.n, prev_idx, curr_idx, n_matches);
   return 0;
 }
 
@@ -730,10 +848,7 @@ int sfm_matcher_match(sfm_matcher* h, const double* pts0, const uint8_t* desc0, 
   if ((rc = run_match(h, d, nullptr, dp, n0, d + w0, nullptr, dp + 2 * size_t(n0), n1, ratio_test, min_distance,
                       max_distance, &res)))
     return rc;
-  const int m = res[2 * n0];
-  std::memcpy(idx0, res, sizeof(int) * size_t(m));
-  std::memcpy(idx1, res + n0, sizeof(int) * size_t(m));
-  *n_matches = m;
+  copy_matches(res, n0, idx0, idx1, n_matches);
   return 0;
 }
 
@@ -781,7 +896,7 @@ int sfm_matcher_match_keyframes(sfm_matcher* h, int32_t q_slot, const int32_t* q
                                 double min_distance, double max_distance, int32_t* idx0, int32_t* idx1,
                                 int32_t* n_matches) {
   SFM_TRACE("sfm_matcher_match_keyframes");
-  if (!h || !n_matches) return mfail(SFM_EINVAL, "NULL argument");
+  if (!h || !n_matches || !idx0 || !idx1) return mfail(SFM_EINVAL, "NULL argument");
   *n_matches = 0;
   if (q_slot < 0 || t_slot < 0 || size_t(q_slot) >= h->kf.size() || size_t(t_slot) >= h->kf.size())
     return mfail(SFM_EINVAL, "keyframe slot not stored");
@@ -789,16 +904,15 @@ int sfm_matcher_match_keyframes(sfm_matcher* h, int32_t q_slot, const int32_t* q
   if (!ok_ratio_window(ratio_test, min_distance, max_distance)) return mfail(SFM_EINVAL, "non-finite threshold");
   const MatchFrame& fq = h->kf[size_t(q_slot)];
   const MatchFrame& ft = h->kf[size_t(t_slot)];
-  std::vector<char> seen(q_pts ? size_t(fq.n) : 0, 0);
-  for (int32_t i = 0; i < n_q; ++i) {
-    if (q_idx[i] < 0 || q_idx[i] >= fq.n) return mfail(SFM_EINVAL, "query index out of range");
-    if (q_pts) {
+  if (!rows_in_range(q_idx, n_q, fq.n)) return mfail(SFM_EINVAL, "query index out of range");
+  if (q_pts) {
+    std::vector<char> seen(size_t(fq.n), 0);
+    for (int32_t i = 0; i < n_q; ++i) {
       if (seen[size_t(q_idx[i])]) return mfail(SFM_EINVAL, "query index repeated with given positions");
       seen[size_t(q_idx[i])] = 1;
     }
   }
-  for (int32_t i = 0; i < n_t; ++i)
-    if (t_idx[i] < 0 || t_idx[i] >= ft.n) return mfail(SFM_EINVAL, "train index out of range");
+  if (!rows_in_range(t_idx, n_t, ft.n)) return mfail(SFM_EINVAL, "train index out of range");
   if (n_q == 0 || n_t < 2) return 0;  // reference UB with < 2 train rows: no matches
   if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
   int rc = 0;
@@ -823,18 +937,12 @@ int sfm_matcher_match_keyframes(sfm_matcher* h, int32_t q_slot, const int32_t* q
   if ((rc = run_match(h, fq.desc, d, p0, n_q, ft.desc, d + n_q, ft.pts, n_t, ratio_test, min_distance, max_distance,
                       &res)))
     return rc;
-  const int m = res[2 * n_q];
-  std::memcpy(idx0, res, sizeof(int) * size_t(m));
-  std::memcpy(idx1, res + n_q, sizeof(int) * size_t(m));
-  *n_matches = m;
+  copy_matches(res, n_q, idx0, idx1, n_matches);
   return 0;
 }
 
 // CSfM::mapping's point creation for one keyframe pair (CSfM.cpp:138-176):
-// the member-window match of the two keyframes' unmatched rows, the
-// triangulation and the filter (mappoint_kernels.hip) as one stream of
-// launches on the resident rows -- one staged upload (the index lists; the
-// matrices go as kernel arguments), one download, one synchronisation.
+// pair_points_run with one pair.  (slot0 == slot1 is allowed here.)
 int sfm_matcher_pair_points(sfm_matcher* h, int32_t slot0, const int32_t* idx0, int32_t n0, int32_t slot1,
                             const int32_t* idx1, int32_t n1, double ratio_test, double min_distance,
                             double max_distance, const double* K9_0, const double* R9_0, const double* t3_0,
@@ -854,47 +962,19 @@ int sfm_matcher_pair_points(sfm_matcher* h, int32_t slot0, const int32_t* idx0, 
   sfm::PairArgs pa;
   if (!sfm::compose_pair(K9_0, R9_0, t3_0, K9_1, R9_1, t3_1, max_err, &pa))
     return mfail(SFM_EINVAL, "K must be finite and upper triangular with K[8] = 1, R and t finite");
-  const MatchFrame& f0 = h->kf[size_t(slot0)];
   const MatchFrame& f1 = h->kf[size_t(slot1)];
-  for (int32_t i = 0; i < n0; ++i)
-    if (idx0[i] < 0 || idx0[i] >= f0.n) return mfail(SFM_EINVAL, "row index out of range (older keyframe)");
-  for (int32_t i = 0; i < n1; ++i)
-    if (idx1[i] < 0 || idx1[i] >= f1.n) return mfail(SFM_EINVAL, "row index out of range (new keyframe)");
+  if (!rows_in_range(idx0, n0, h->kf[size_t(slot0)].n))
+    return mfail(SFM_EINVAL, "row index out of range (older keyframe)");
+  if (!rows_in_range(idx1, n1, f1.n)) return mfail(SFM_EINVAL, "row index out of range (new keyframe)");
   if (n0 == 0 || n1 < 2) return 0;  // reference UB with < 2 train rows: no matches
   if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
-  int rc = 0;
-  // result block: head (kept, matched, pad x2) | m0 [n0] | m1 [n0] | X [n0][3]
-  const size_t ni = 4 + 2 * size_t(n0);
-  const size_t blk = ni / 2 + 3 * size_t(n0);  // in doubles
-  int* ix = pbuf<int>(h, "ppidx", size_t(n0) + n1, &rc);
-  int* dix = dbuf<int>(h, "dppidx", size_t(n0) + n1, &rc);
-  double* dXall = dbuf<double>(h, "ppX", 3 * size_t(n0), &rc);
-  int* dks = dbuf<int>(h, "ppks", 2 * size_t(n0), &rc);
-  double* dblk = dbuf<double>(h, "ppblk", blk, &rc);
-  double* hblk = pbuf<double>(h, "ppblkh", blk, &rc);
+  const int32_t off[2] = {0, n0};
+  int32_t first = -1, kept = 0, matched = 0;
+  const int rc = pair_points_run(h, 1, &slot0, idx0, off, f1, idx1, n1, ratio_test, min_distance, max_distance, &pa,
+                                 capacity, &first, m0, m1, X, &kept, &matched);
+  *n_kept = kept;  // (also when the capacity was too small; *n_matched stays 0 then)
   if (rc) return rc;
-  hipStreamSynchronize(h->stream);  // (the pinned stage may feed an earlier copy)
-  std::memcpy(ix, idx0, sizeof(int) * size_t(n0));
-  std::memcpy(ix + n0, idx1, sizeof(int) * size_t(n1));
-  hipMemcpyAsync(dix, ix, sizeof(int) * (size_t(n0) + n1), hipMemcpyHostToDevice, h->stream);
-  int* out = nullptr;
-  if ((rc = run_match_async(h, f0.desc, dix, f0.pts, n0, f1.desc, dix + n0, f1.pts, n1, ratio_test, min_distance,
-                            max_distance, &out)))
-    return rc;
-  int* dhead = reinterpret_cast<int*>(dblk);
-  sfm::launch_pair_points(h->stream, out, n0, dix, dix + n0, f0.pts, f1.pts, pa, dXall, dks, dks + n0, dhead,
-                          dhead + 4, dhead + 4 + n0, dblk + ni / 2);
-  hipMemcpyAsync(hblk, dblk, sizeof(double) * blk, hipMemcpyDeviceToHost, h->stream);
-  if (hipStreamSynchronize(h->stream) != hipSuccess) return mfail(SFM_EIO, "point-creation kernels failed");
-  const int* hh = reinterpret_cast<const int*>(hblk);
-  const int kept = hh[0];
-  *n_kept = kept;
-  if (kept > capacity)
-    return mfail(SFM_EINVAL, "capacity " + std::to_string(capacity) + " < " + std::to_string(kept) + " kept matches");
-  *n_matched = hh[1];
-  std::memcpy(m0, hh + 4, sizeof(int) * size_t(kept));
-  std::memcpy(m1, hh + 4 + n0, sizeof(int) * size_t(kept));
-  std::memcpy(X, hblk + ni / 2, sizeof(double) * 3 * size_t(kept));
+  *n_matched = matched;
   return 0;
 }
 
@@ -902,10 +982,7 @@ int sfm_matcher_pair_points(sfm_matcher* h, int32_t slot0, const int32_t* idx0, 
 // keyframe's rows, up to the first pair that keeps a point: while no pair has
 // kept one the caller's unmatched set does not change, so the pairs are
 // independent and the first productive one (in the caller's order) is what
-// the pair-by-pair loop would have reached.  One staged upload (item table |
-// per-pair matrices | index lists), eight launches whatever n_pairs, one
-// download (first | kept [B] | matched [B] | the first productive pair's
-// matches), one synchronisation.
+// the pair-by-pair loop would have reached.
 int sfm_matcher_pair_points_first(sfm_matcher* h, int32_t n_pairs, const int32_t* slot0, const int32_t* idx0,
                                   const int32_t* idx0_off, int32_t slot1, const int32_t* idx1, int32_t n1,
                                   double ratio_test, double min_distance, double max_distance, const double* K9_0,
@@ -930,116 +1007,22 @@ int sfm_matcher_pair_points_first(sfm_matcher* h, int32_t n_pairs, const int32_t
   if (!ok_ratio_window(ratio_test, min_distance, max_distance) || !std::isfinite(max_err))
     return mfail(SFM_EINVAL, "non-finite threshold");
   const MatchFrame& f1 = h->kf[size_t(slot1)];
-  for (int32_t i = 0; i < n1; ++i)
-    if (idx1[i] < 0 || idx1[i] >= f1.n) return mfail(SFM_EINVAL, "row index out of range (new keyframe)");
+  if (!rows_in_range(idx1, n1, f1.n)) return mfail(SFM_EINVAL, "row index out of range (new keyframe)");
   std::vector<sfm::PairArgs> pa;
   pa.resize(size_t(n_pairs));
-  int max_n0 = 0;
-  long long qb_total = 0;
   for (int32_t b = 0; b < n_pairs; ++b) {
     if (slot0[b] < 0 || size_t(slot0[b]) >= h->kf.size()) return mfail(SFM_EINVAL, "keyframe slot not stored");
     if (slot0[b] == slot1) return mfail(SFM_EINVAL, "an older keyframe's slot is the new keyframe's");
-    const MatchFrame& f0 = h->kf[size_t(slot0[b])];
-    for (int32_t i = idx0_off[b]; i < idx0_off[b + 1]; ++i)
-      if (idx0[i] < 0 || idx0[i] >= f0.n) return mfail(SFM_EINVAL, "row index out of range (older keyframe)");
+    if (!rows_in_range(idx0 + idx0_off[b], idx0_off[b + 1] - idx0_off[b], h->kf[size_t(slot0[b])].n))
+      return mfail(SFM_EINVAL, "row index out of range (older keyframe)");
     if (!sfm::compose_pair(K9_0 + 9 * size_t(b), R9_0 + 9 * size_t(b), t3_0 + 3 * size_t(b), K9_1, R9_1, t3_1, max_err,
                            &pa[size_t(b)]))
       return mfail(SFM_EINVAL, "K must be finite and upper triangular with K[8] = 1, R and t finite");
-    const int n0 = idx0_off[b + 1] - idx0_off[b];
-    max_n0 = std::max(max_n0, n0);
-    qb_total += (n0 + kQ - 1) / kQ;
   }
   if (total == 0 || n1 < 2) return 0;  // reference UB with < 2 train rows: no matches
   if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
-  int rc = 0;
-  const size_t B = size_t(n_pairs);
-  // train slices as slices_for sizes them, from the batch's query blocks
-  const int nslice = int(std::min<long long>(std::max<long long>(1, (2 * h->n_cu + qb_total - 1) / qb_total),
-                                             std::max(1, n1 / 64)));
-  const int slice = (n1 + nslice - 1) / nslice;
-  // stage (8-B units): item table | matrices | idx0 (all items) | idx1
-  static_assert(sizeof(sfm::PairItem) % 8 == 0 && sizeof(sfm::PairArgs) % 8 == 0, "staged in 8-B units");
-  const size_t w_items = B * sizeof(sfm::PairItem) / 8, w_pa = B * sizeof(sfm::PairArgs) / 8;
-  const size_t w_idx = (size_t(total) + size_t(n1) + 1) / 2;
-  const size_t w_stage = w_items + w_pa + w_idx;
-  // result block: head (first | kept [B] | matched [B], even) | m0 [cap] | m1 [cap] | X [cap][3]
-  const size_t cap = size_t(std::min(max_n0, n1));
-  const size_t hi = (2 * B + 2) & ~size_t(1);
-  const size_t blk = hi / 2 + cap + 3 * cap;  // in doubles
-  auto* st = pbuf<uint64_t>(h, "pfstage", w_stage, &rc);
-  auto* dst = dbuf<uint64_t>(h, "dpfstage", w_stage, &rc);
-  auto* part = dbuf<unsigned long long>(h, "part", 2 * size_t(total) * nslice, &rc);
-  auto* key = dbuf<unsigned long long>(h, "key", B * size_t(n1), &rc);
-  int* dfirst = dbuf<int>(h, "first", B * size_t(n1), &rc);
-  int* slot = dbuf<int>(h, "slot", size_t(total), &rc);
-  int* out = dbuf<int>(h, "out", 2 * size_t(total) + B, &rc);
-  double* dXall = dbuf<double>(h, "ppX", 3 * size_t(total), &rc);
-  int* dks = dbuf<int>(h, "ppks", 2 * size_t(total), &rc);
-  double* dblk = dbuf<double>(h, "pfblk", blk, &rc);
-  double* hblk = pbuf<double>(h, "pfblkh", blk, &rc);
-  if (rc) return rc;
-  hipStream_t s = h->stream;
-  hipStreamSynchronize(s);  // (the pinned stage may feed an earlier copy)
-  auto* items = reinterpret_cast<sfm::PairItem*>(st);
-  for (size_t b = 0; b < B; ++b) {
-    const MatchFrame& f0 = h->kf[size_t(slot0[b])];
-    sfm::PairItem& it = items[b];
-    it.desc = f0.desc;
-    it.pts = f0.pts;
-    it.n0 = idx0_off[b + 1] - idx0_off[b];
-    it.idx_off = idx0_off[b];
-    it.out_off = 2 * idx0_off[b] + int(b);
-    it.pad = 0;
-    it.part_off = 2ll * idx0_off[b] * nslice;
-    it.key_off = (long long)(b) * n1;
-    it.x_off = 3ll * idx0_off[b];
-  }
-  std::memcpy(st + w_items, pa.data(), B * sizeof(sfm::PairArgs));
-  int* ix = reinterpret_cast<int*>(st + w_items + w_pa);
-  std::memcpy(ix, idx0, sizeof(int) * size_t(total));
-  std::memcpy(ix + total, idx1, sizeof(int) * size_t(n1));
-  hipMemcpyAsync(dst, st, w_stage * 8, hipMemcpyHostToDevice, s);
-  const auto* ditems = reinterpret_cast<const sfm::PairItem*>(dst);
-  const auto* dpa = reinterpret_cast<const sfm::PairArgs*>(dst + w_items);
-  const int* dix = reinterpret_cast<const int*>(dst + w_items + w_pa);
-  const int* dtix = dix + total;
-  const unsigned by = unsigned(n_pairs);
-  hipEventRecord(h->ev[0], s);
-  k_reset_items<<<dim3((std::max(max_n0, n1) + 255) / 256, by), 256, 0, s>>>(ditems, n1, key, dfirst, slot);
-  const dim3 grid((max_n0 + kQ - 1) / kQ, nslice, by);
-  switch (h->W) {
-#define CASE(w) \
-  case w: k_knn2_part_items<w><<<grid, kQ * kWaves, 0, s>>>(ditems, dix, f1.desc, dtix, n1, slice, part); break;
-    CASE(1) CASE(2) CASE(4) CASE(8) CASE(16) CASE(32) CASE(64)
-#undef CASE
-    default: return mfail(SFM_EINVAL, "descriptor width must be <= 512 bytes");
-  }
-  hipEventRecord(h->ev[1], s);
-  k_accept_items<<<dim3((max_n0 + 255) / 256, by), 256, 0, s>>>(ditems, dix, nslice, part, f1.pts, dtix, ratio_test,
-                                                                 min_distance * min_distance,
-                                                                 max_distance * max_distance, key, dfirst);
-  k_mark_first_items<<<dim3((n1 + 255) / 256, by), 256, 0, s>>>(ditems, n1, dfirst, slot);
-  k_compact_slots_items<<<by, 1024, 0, s>>>(ditems, slot, key, out);
-  int* dhead = reinterpret_cast<int*>(dblk);
-  sfm::launch_pair_points_first(s, ditems, dpa, n_pairs, max_n0, out, dix, dtix, f1.pts, dXall, dks, dks + total, dhead,
-                                dhead + hi, dhead + hi + cap, dblk + hi / 2 + cap);
-  hipEventRecord(h->ev[2], s);
-  hipMemcpyAsync(hblk, dblk, sizeof(double) * blk, hipMemcpyDeviceToHost, s);
-  if (hipStreamSynchronize(s) != hipSuccess) return mfail(SFM_EIO, "point-creation kernels failed");
-  hipEventElapsedTime(&h->last_knn_ms, h->ev[0], h->ev[1]);
-  hipEventElapsedTime(&h->last_total_ms, h->ev[0], h->ev[2]);
-  const int* hh = reinterpret_cast<const int*>(hblk);
-  *first = hh[0];
-  std::memcpy(n_kept, hh + 1, sizeof(int) * B);
-  std::memcpy(n_matched, hh + 1 + B, sizeof(int) * B);
-  if (hh[0] < 0) return 0;
-  const int kept = n_kept[hh[0]];
-  if (kept > capacity)
-    return mfail(SFM_EINVAL, "capacity " + std::to_string(capacity) + " < " + std::to_string(kept) + " kept matches");
-  std::memcpy(m0, hh + hi, sizeof(int) * size_t(kept));
-  std::memcpy(m1, hh + hi + cap, sizeof(int) * size_t(kept));
-  std::memcpy(X, hblk + hi / 2 + cap, sizeof(double) * 3 * size_t(kept));
-  return 0;
+  return pair_points_run(h, n_pairs, slot0, idx0, idx0_off, f1, idx1, n1, ratio_test, min_distance, max_distance,
+                         pa.data(), capacity, first, m0, m1, X, n_kept, n_matched);
 }
 
 // The re-finding of new points in one keyframe in between (CSfM.cpp:191-221):
@@ -1063,14 +1046,13 @@ int sfm_matcher_refind_points(sfm_matcher* h, int32_t q_slot, const int32_t* q_i
     if (!std::isfinite(t3[i])) return mfail(SFM_EINVAL, "non-finite matrix");
   const MatchFrame& fq = h->kf[size_t(q_slot)];
   const MatchFrame& ft = h->kf[size_t(t_slot)];
+  if (!rows_in_range(q_idx, n_q, fq.n)) return mfail(SFM_EINVAL, "query index out of range");
   std::vector<char> seen(size_t(fq.n), 0);
   for (int32_t i = 0; i < n_q; ++i) {
-    if (q_idx[i] < 0 || q_idx[i] >= fq.n) return mfail(SFM_EINVAL, "query index out of range");
     if (seen[size_t(q_idx[i])]) return mfail(SFM_EINVAL, "query index repeated");
     seen[size_t(q_idx[i])] = 1;
   }
-  for (int32_t i = 0; i < n_t; ++i)
-    if (t_idx[i] < 0 || t_idx[i] >= ft.n) return mfail(SFM_EINVAL, "train index out of range");
+  if (!rows_in_range(t_idx, n_t, ft.n)) return mfail(SFM_EINVAL, "train index out of range");
   if (n_q == 0 || n_t < 2) return 0;  // reference UB with < 2 train rows: no matches
   if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
   int rc = 0;
@@ -1090,10 +1072,7 @@ int sfm_matcher_refind_points(sfm_matcher* h, int32_t q_slot, const int32_t* q_i
   if ((rc = run_match(h, fq.desc, d, duv, n_q, ft.desc, d + n_q, ft.pts, n_t, ratio_test, min_distance, max_distance,
                       &res)))
     return rc;
-  const int m = res[2 * n_q];
-  std::memcpy(idx0, res, sizeof(int) * size_t(m));
-  std::memcpy(idx1, res + n_q, sizeof(int) * size_t(m));
-  *n_matches = m;
+  copy_matches(res, n_q, idx0, idx1, n_matches);
   return 0;
 }
 
@@ -1267,7 +1246,8 @@ int sfm_track_pnp(sfm_matcher* h, sfm_map* map, int32_t n_prev, const int32_t* p
                   double reproj_err, double confidence, double* rvec, double* tvec, int32_t* found,
                   int32_t* n_matches, int32_t capacity, int32_t* inl_kp, int32_t* inl_pt3d, int32_t* n_inliers) {
   SFM_TRACE("sfm_track_pnp");
-  if (!h || !map || !found || !n_matches || !n_inliers || !rvec || !tvec || !K9) return mfail(SFM_EINVAL, "NULL argument");
+  if (!h || !map || !found || !n_matches || !n_inliers || !rvec || !tvec || !K9 || !inl_kp || !inl_pt3d)
+    return mfail(SFM_EINVAL, "NULL argument");
   *found = 0;
   *n_matches = 0;
   *n_inliers = 0;

@@ -12,6 +12,7 @@ PnP, the device map store and the BA, on synthetic detector output.
   adjusted keyframe poses and map points match the stream's ground truth
   after a similarity alignment (the reference's BA holds no block constant,
   CTracker.cpp:670-702, so the gauge floats)."""
+import ctypes
 import json
 import os
 
@@ -20,7 +21,8 @@ import pytest
 
 import lm_cases as L
 from oracle import ffi as O
-from sfm_amd.live import KeypointStream, LiveSfM, _project
+from sfm_amd._ffi import lib, ptr
+from sfm_amd.live import MAX_REPR_ERR, MIN_FEATURES, KeypointStream, LiveSfM, _project
 from sfm_amd.mapping import _rodrigues
 
 pytestmark = pytest.mark.gpu
@@ -125,6 +127,37 @@ def test_fused_tracking_equals_the_composed_calls():
     assert a[3] == b[3]
     for x, y in zip(a[4:], b[4:]):
         assert np.array_equal(x, y)
+
+
+def test_track_pnp_refuses_null_inlier_lists():
+    """NULL inl_kp / inl_pt3d: -22 before any device call, and the next good
+    call gives what the one before gave."""
+    s = LiveSfM(KeypointStream())
+    try:
+        s.run(12)
+        assert s.lost == 0 and s.stats["tracked"] == 12 - 5 - 1
+        pts, desc, _ = s.stream.frame(12)
+        s.matcher.push_frame(pts, desc)
+
+        def track():
+            return s.matcher.track_pnp(s.map, s.prev.pt3d, s.K, MIN_FEATURES, 20, MAX_REPR_ERR, 0.99)
+
+        good = track()
+        assert good[0] >= MIN_FEATURES and good[1] and len(good[4]) == len(good[5]) > 0
+        p3 = np.ascontiguousarray(s.prev.pt3d, np.int32)
+        K9 = np.ascontiguousarray(s.K, np.float64).reshape(9)
+        cap = int((p3 >= 0).sum())
+        kp, pt, rvec, tvec = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.ones(3), np.ones(3)
+        found, nm, ni = (ctypes.c_int32(7) for _ in range(3))
+        for outs in ((None, ptr(pt)), (ptr(kp), None)):
+            rc = lib().sfm_track_pnp(s.matcher._h, s.map._h, len(p3), ptr(p3), 0.8, 1.5, 40.0, MIN_FEATURES, ptr(K9),
+                                     20, MAX_REPR_ERR, 0.99, ptr(rvec), ptr(tvec), ctypes.byref(found),
+                                     ctypes.byref(nm), cap, *outs, ctypes.byref(ni))
+            assert rc == -22 and lib().sfm_last_error()
+        again = track()
+        assert again[:2] == good[:2] and all(np.array_equal(x, y) for x, y in zip(good[2:], again[2:]))
+    finally:
+        s.close()
 
 
 def test_every_keyframe_ba_matches_oracle(run80):

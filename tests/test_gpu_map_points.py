@@ -10,6 +10,7 @@ import pytest
 
 import map_points_cases as C
 import map_points_ref as ref
+from map_points_composed import composed
 from oracle import ffi as O
 from sfm_amd._ffi import SfmError, lib, ptr
 from sfm_amd.cmap import DeviceMap
@@ -52,13 +53,8 @@ class _Pair:
                                   self.R1 if R1 is None else R1, self.t1 if t1 is None else t1, MAX_REPR_ERR, **kw)
 
     def composed(self, idx0, idx1):
-        idx0, idx1 = np.asarray(idx0, np.int32), np.asarray(idx1, np.int32)
-        pi, ci = self.m.match_keyframes(0, idx0, 1, idx1)
-        uv0, uv1 = self.p0[idx0[pi]], self.p1[idx1[ci]]
-        P = np.stack([ref.compose_P(self.K, self.R0, self.t0), ref.compose_P(self.K, self.R1, self.t1)])
-        X = triangulate_points(np.zeros(len(pi), np.int32), np.ones(len(pi), np.int32), uv0, uv1, P)
-        keep = ref.filter_matches(uv0, uv1, X, self.K, self.R0, self.t0, self.K, self.R1, self.t1, MAX_REPR_ERR)
-        return pi, ci, X, keep
+        return composed(self.m, 0, self.p0, idx0, 1, self.p1, idx1, self.K, self.R0, self.t0, self.R1, self.t1,
+                        MAX_REPR_ERR)
 
 
 @pytest.fixture(scope="module")
@@ -119,6 +115,24 @@ def test_pair_points_degenerate_poses_keep_nothing(pairs):
     m0, m1, X, nm = p.fused(i0, i1, R1=p.R0, t1=p.t0)
     assert len(m0) == len(m1) == len(X) == 0
     assert nm == len(p.m.match_keyframes(0, i0, 1, i1)[0]) > 50
+
+
+def test_last_time_covers_a_pair_points_call(pairs):
+    """On a handle whose only device call was pair_points."""
+    p = pairs(1200)
+    m = FeatureMatcher(64)
+    try:
+        m.store_keyframe(0, p.p0, p.d0)
+        m.store_keyframe(1, p.p1, p.d1)
+        assert m.last_time_ms() == (0.0, 0.0)
+        m0 = m.pair_points(0, np.arange(len(p.p0)), 1, np.arange(len(p.p1)), p.K, p.R0, p.t0, p.K, p.R1, p.t1,
+                           MAX_REPR_ERR)[0]
+        knn_ms, total_ms = m.last_time_ms()
+    finally:
+        m.close()
+    print(f"pair_points device time: 2-NN {knn_ms:.4f} ms, whole call {total_ms:.4f} ms")
+    assert len(m0) > 0
+    assert np.isfinite(knn_ms) and np.isfinite(total_ms) and 0 < knn_ms <= total_ms
 
 
 def test_filter_matches_equals_the_restatement():
@@ -257,6 +271,10 @@ def test_errors_leave_the_handles_usable(pairs):
     rc = lib().sfm_matcher_refind_points(p.m._h, 0, ptr(i0), 1, ptr(X), ptr(m9[0]), ptr(m9[1]), ptr(t0), 1, ptr(i1),
                                          len(i1), 0.8, 0.0, 7.0, None, ptr(o), ctypes.byref(c))
     assert rc == -22
+    for outs in ((None, ptr(o)), (ptr(o), None)):
+        rc = lib().sfm_matcher_match_keyframes(p.m._h, 0, ptr(i0), len(i0), None, 1, ptr(i1), len(i1), 0.8, 1.5, 40.0,
+                                               *outs, ctypes.byref(c))
+        assert rc == -22 and lib().sfm_last_error()
     Xq = good[2][:2]
     refused(p.m.refind_points, 0, [5, 5], Xq, K, R1, t1, 1, i1)                     # repeated q_idx
     refused(p.m.refind_points, 9, [5, 6], Xq, K, R1, t1, 1, i1)

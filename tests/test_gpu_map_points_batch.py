@@ -7,6 +7,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from map_points_composed import composed
 from sfm_amd._ffi import SfmError, lib, ptr
 from sfm_amd.live import MAX_REPR_ERR, KeypointStream, LiveSfM
 from sfm_amd.mapping import _rodrigues
@@ -34,11 +35,12 @@ class _Keyframes:
         st = KeypointStream(n_landmarks=n_landmarks, desc_bytes=desc_bytes)
         self.K = st.K
         self.m = FeatureMatcher(desc_bytes)
-        self.n, self.R, self.t = [], [], []
+        self.n, self.R, self.t, self.pts = [], [], [], []
         for slot, k in enumerate(OLD + (NEW,)):
             pts, desc, _ = st.frame(k)
             r, t = st.pose(k)
             self.m.store_keyframe(slot, pts, desc)
+            self.pts.append(pts)
             self.n.append(len(pts))
             self.R.append(_rodrigues(r))
             self.t.append(np.asarray(t, np.float64))
@@ -98,6 +100,37 @@ def kfs():
     yield get
     for f in made.values():
         f.m.close()
+
+
+def test_single_call_equals_match_triangulate_filter(kfs):
+    """The reference of check(), _Keyframes.single, runs the batch's own host
+    path and kernels with one pair, so here it is pinned itself -- on the
+    kinds of item the cases below use -- against the calls it fuses
+    (map_points_composed: match_keyframes, sfm_triangulate_points and the CPU
+    restatement of the filter), which share none of that code."""
+    f, f32 = kfs(1200), kfs(1200, 32)
+
+    def pinned(g, it, label):
+        m0, m1, X, n_matched = g.single(it, g.all1)
+        pi, ci, Xa, keep = composed(g.m, it[0], g.pts[it[0]], it[1], NEW_SLOT, g.pts[NEW_SLOT], g.all1, g.K, it[2],
+                                    it[3], g.R[NEW_SLOT], g.t[NEW_SLOT], MAX_REPR_ERR)
+        print(f"{label}: rows {len(it[1])} x {len(g.all1)}, matched {n_matched}, kept {len(m0)}")
+        assert n_matched == len(pi)
+        assert np.array_equal(m0, pi[keep]) and np.array_equal(m1, ci[keep])
+        assert _bits(X, Xa[keep])
+        return n_matched, len(m0)
+
+    assert pinned(f, f.item(0), "slot 0")[1] == 0
+    assert pinned(f, f.item(4), "slot 4")[1] >= 1
+    nm5, nk5 = pinned(f, f.item(5), "slot 5")
+    assert nk5 >= 1
+    assert pinned(f, f.item(5, pose=NEW_SLOT), "slot 5, F = 0") == (nm5, 0) and nm5 > 0
+    good = f.rows(5)[f.single(f.item(5), f.all1)[0]]          # rows that give a point go first, as in the cases below
+    rows = np.concatenate([good, np.setdiff1d(f.rows(5), good)]).astype(np.int32)
+    for n in (1, 63, 65):
+        pinned(f, f.item(5, rows[:n]), f"slot 5, {n} rows")
+    assert pinned(f, f.item(5, f.rows(5)[::-1].copy()), "slot 5, reversed")[1] >= 1
+    assert pinned(f32, f32.item(5), "slot 5, desc_bytes = 32")[1] >= 1
 
 
 @pytest.mark.parametrize("n_landmarks", [1200, 8000])

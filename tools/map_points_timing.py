@@ -13,7 +13,15 @@ profiles/map_points_timing.txt, or --out PATH):
   every call's pair count B, its device time (the handle's HIP events) and
   the pairs computed behind the first productive one, which are discarded.
 
-Every run is a fresh child process (this file with --child)."""
+With --ab PARENT_LIB the device and the batched variant are run on two
+builds of the library instead, PARENT_LIB and the tree's own, alternating
+(writes profiles/pair_points_single_ab.txt, or --out PATH): every round's
+frames/s and point-creation time, the medians, and per variant whether the
+tree's median point-creation time lies inside the min-max range of
+PARENT_LIB's rounds (or below it).
+
+Every run is a fresh child process (this file with --child; a library other
+than the tree's own is selected with SFM_AMD_LIB in the child's environment)."""
 import argparse
 import json
 import os
@@ -99,10 +107,14 @@ def child(device: bool, batch: bool, count: bool) -> None:
     print("RESULT " + json.dumps(out), flush=True)
 
 
-def run_child(device: bool, batch: bool = False, count: bool = False) -> dict:
+def run_child(device: bool, batch: bool = False, count: bool = False, lib: str | None = None) -> dict:
     cmd = [sys.executable, os.path.abspath(__file__), "--child"] + (["--device"] if device else []) + \
         (["--batch"] if batch else []) + (["--count"] if count else [])
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    env = dict(os.environ)
+    env.pop("SFM_AMD_LIB", None)
+    if lib:
+        env["SFM_AMD_LIB"] = os.path.abspath(lib)
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
     if out.returncode != 0:
         raise RuntimeError(out.stdout + out.stderr)
     return json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
@@ -113,6 +125,42 @@ def med(v):
     return v[len(v) // 2]
 
 
+def ab(parent_lib: str, rounds: int, out: str) -> None:
+    variants = (("device", False), ("batched", True))
+    runs = {(name, who): [] for name, _ in variants for who in ("parent", "tree")}
+    for _ in range(rounds):
+        for name, batch in variants:
+            runs[(name, "parent")].append(run_child(True, batch, lib=parent_lib))
+            runs[(name, "tree")].append(run_child(True, batch))
+    lines = [f"live loop, {N} frames of synthetic detector output, map-point creation on the device pair by pair "
+             f"(device: device_mapping=True) and with all older keyframes in one call (batched: batch_pairs=True), on "
+             f"two builds of the library: the parent commit's (parent) and this tree's (tree), in which "
+             f"sfm_matcher_pair_points is the n_pairs = 1 case of sfm_matcher_pair_points_first; one session, {rounds} "
+             f"rounds, parent and tree alternating, a fresh process per run; medians (every round's value in brackets)"]
+    ok = True
+    for name, _ in variants:
+        for who in ("parent", "tree"):
+            r = runs[(name, who)]
+            lines.append(f"{name:7s} {who:6s}: {med([x['frames_per_s'] for x in r]):7.1f} frames/s "
+                         f"[{', '.join('%.1f' % x['frames_per_s'] for x in r)}], point creation (mapping - BA) "
+                         f"{med([x['create_s'] for x in r]):.4f} s [{', '.join('%.4f' % x['create_s'] for x in r)}], "
+                         f"{r[-1]['keyframes']} keyframes, {r[-1]['map_points']} map points, "
+                         f"{r[-1]['observations']} observations, tracked {r[-1]['tracked']}, lost {r[-1]['lost']}")
+        p = [x["create_s"] for x in runs[(name, "parent")]]
+        m = med([x["create_s"] for x in runs[(name, "tree")]])
+        good = m <= max(p)
+        ok = ok and good
+        lines.append(f"{name:7s} verdict: tree median {m:.4f} s against the parent's rounds {min(p):.4f} .. {max(p):.4f} s: "
+                     + ("inside the range" if min(p) <= m <= max(p) else "below the range (faster)" if good
+                        else "ABOVE the range (slower)"))
+    lines.append("verdict: " + ("not slower than the parent by the criterion above" if ok else "SLOWER than the parent"))
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(text)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", action="store_true")
@@ -120,11 +168,16 @@ def main() -> None:
     ap.add_argument("--batch", action="store_true")
     ap.add_argument("--count", action="store_true")
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(R, "profiles", "map_points_timing.txt"))
+    ap.add_argument("--ab", metavar="PARENT_LIB", help="compare the tree's library with this build of an earlier one")
+    ap.add_argument("--out")
     a = ap.parse_args()
     if a.child:
         child(a.device, a.batch, a.count)
         return
+    if a.ab:
+        ab(a.ab, a.rounds, a.out or os.path.join(R, "profiles", "pair_points_single_ab.txt"))
+        return
+    a.out = a.out or os.path.join(R, "profiles", "map_points_timing.txt")
     cols = {"host": [], "device": [], "batched": []}
     for _ in range(a.rounds):
         cols["host"].append(run_child(False))
