@@ -17,27 +17,31 @@
 
 #include "ba_device.h"
 #include "ba_host_layout.h"
+#include "dev_mem.h"
 #include "../../include/sfm_amd.h"
-
-// the calling thread's last error (ba_solver.hip holds it)
-void sfm_internal_set_error(const std::string& msg);
-inline int fail(int code, const std::string& msg) {
-  sfm_internal_set_error(msg);
-  return code;
-}
-
-#define HIPCHK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return fail(SFM_EIO, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 enum Phase { kPhJac = 0, kPhCamRed, kPhPtEval, kPhPtPrep, kPhSchur, kPhChol, kPhBack, kPhBacksub, kPhOther, kNumPh };
 
+// The distributed factor's panel layout: plain data, assigned afresh by
+// dist_prepare whenever the problem, the panel width or the ranks changed.
+struct DistLayout {
+  int pt = 0, nblk = 0, n = 0, nranks = 0, rank = 0;  // the layout below was made for
+  int64_t total = 0;                // doubles of all panel rectangles
+  int64_t bcast_cap = 0;            // largest broadcast (doubles)
+  std::vector<int64_t> count, poff; // per panel: rectangle doubles, offset in the panel image
+};
+
+// The streams first (stream, then those that work beside it): members are
+// destroyed in reverse order, so the buffers and events go before them.
 struct sfm_ba_handle {
+  sfm::Stream stream;
+  // set_problem's uploads beside the layout kernels (large problems): the
+  // parameters (uev), and uv from a worker thread (uev_uv)
+  sfm::Stream ustream;
+  sfm::Event uev, uev_uv;
   int device = 0;
-  hipStream_t stream = nullptr;
   sfm::DevProblem d;
+  sfm::PinArr<double> scal_host;  // d.scal_host: the scalars' pinned mirror, kept for the handle's life
   int32_t bs_epoch = 0;          // stamp of the last back-substitution launch (k_backsolve flags)
   int32_t chol_epoch = 0;        // launches of the fused Cholesky since the last set_problem
   // ba_plan.h: the switches (the problem's half read by set_problem, the
@@ -65,25 +69,20 @@ struct sfm_ba_handle {
   // block-cyclic column panels of dist_pt 64-column tiles; 0 = every rank
   // factors the all-reduced system (replicated)
   int dist_pt = 0;
-  struct DistBufs {
-    int pt = 0, nblk = 0, n = 0, nranks = 0, rank = 0;  // the layout below was made for
-    int64_t total = 0;                // doubles of all panel rectangles
-    int64_t bcast_cap = 0;            // largest broadcast (doubles)
-    std::vector<int64_t> count, poff; // per panel: rectangle doubles, offset in the panel image
-    double* send = nullptr;           // [total] this rank's partial panels (own ones: zeros)
-    double* recv = nullptr;           // [total] the other ranks' sums of the own panels
-    double* bcast = nullptr;          // [2][bcast_cap]: panel k travels in half k % 2
-    hipStream_t cstream = nullptr;    // RCCL: the collectives' own stream (look-ahead)
-    hipEvent_t ev_packed = nullptr, ev_free[2] = {nullptr, nullptr}, ev_arrived[2] = {nullptr, nullptr};
-    hipEvent_t ev_sent = nullptr;     // the partial panels are packed
-    std::vector<hipEvent_t> ev_red;   // [np] panel k's reduce has landed (owner)
-    int64_t* off_send = nullptr;      // [np] panel offset in send, -1 for own panels (device)
-    int64_t* off_recv = nullptr;      // (unused)
+  // ... and what outlives a layout: the collectives' stream, the events, the buffers
+  struct DistBufs : DistLayout {
+    sfm::Stream cstream;            // RCCL: the collectives' own stream (look-ahead)
+    sfm::Event ev_packed, ev_free[2], ev_arrived[2];
+    sfm::Event ev_sent;             // the partial panels are packed
+    std::vector<sfm::Event> ev_red; // [np] panel k's reduce has landed (owner)
+    sfm::DevArr<double> send;       // [total] this rank's partial panels (own ones: zeros)
+    sfm::DevArr<double> recv;       // [total] the other ranks' sums of the own panels
+    sfm::DevArr<double> bcast;      // [2][bcast_cap]: panel k travels in half k % 2
+    sfm::DevArr<int64_t> off_send;  // [np] panel offset in send, -1 for own panels (device)
   } dist;
   // out-of-place target of the collectives enqueued inside a gated phase of
   // the device LM loop (allreduce below); grown on demand
-  double* ar_tmp = nullptr;
-  size_t ar_tmp_cap = 0;
+  sfm::DevArr<double> ar_tmp;
   // SFM_EMULATE_IDENTICAL_RANKS=k (tests, read by sfm_ba_set_comm): every sum
   // collective returns k times its one-rank result, i.e. the sum over k
   // ranks holding the same shard, so a one-GPU run sees the stale-buffer
@@ -92,26 +91,24 @@ struct sfm_ba_handle {
   // device-driven LM loop: the state block (ba_lm.h; the host driver keeps
   // its own on the stack), its pinned mirror and the trace buffer (grown to
   // the iteration cap)
-  sfm::LmCtl* lm_ctl = nullptr;
-  sfm::LmCtl* lm_ctl_host = nullptr;
+  sfm::DevArr<sfm::LmCtl> lm_ctl;
+  sfm::PinArr<sfm::LmCtl> lm_ctl_host;
   // (pinned host memory: the deciding workgroups write the few entries
   // straight to the host, which reads them after the batch's synchronisation)
-  sfm_ba_iteration* lm_trace = nullptr;
+  sfm::PinArr<sfm_ba_iteration> lm_trace;
   int lm_trace_cap = 0;
   // one-shot sfm_ba_solve on a small problem: every batch's control readback
   // also brings the parameters (cam | X) into param_host, so the final
   // download needs no further round trip (param_host_valid until consumed)
   bool prefetch_params = false;
   bool param_host_valid = false;
-  double* param_host = nullptr;
-  size_t param_host_cap = 0;
+  sfm::PinArr<double> param_host;
   // pinned staging for every host <-> device transfer of set_problem,
   // get_parameters and the LM trace: a pageable copy goes through the
   // runtime's own staging (C1: the 320-KB uv upload took 131 us, the 49-KB
   // parameter download ~100 us), a pinned one is a single DMA.  Grown
   // geometrically, only while the stream is idle.
-  uint8_t* stage = nullptr;
-  size_t stage_cap = 0;
+  sfm::PinArr<uint8_t> stage;
   // device LM loop: the evaluation's k_cam_prep also makes the accepted
   // candidate current (k_lm_accept folded in; its grid covers the copy)
   int accept_grid = 0;  // < 0: done by the deciding reduction (AcceptFold)
@@ -132,13 +129,9 @@ struct sfm_ba_handle {
   // they are.
   bool cams_staged = false;
   int n_cu = 0;  // compute units of the device (queried once)
-  // set_problem's uploads beside the layout kernels (large problems): the
-  // parameters (uev), and uv from a worker thread (uev_uv)
-  hipStream_t ustream = nullptr;
-  hipEvent_t uev = nullptr, uev_uv = nullptr;
   // profiling
   bool profiling = false;
-  std::vector<hipEvent_t> ev;
+  std::vector<sfm::Event> ev;
   int ev_used = 0;
   std::vector<std::pair<int, int>> ev_marks;  // (phase, event index of start); end = start + 1
   double phase_ms[kNumPh] = {0};
@@ -194,7 +187,7 @@ inline void retire_tmps(sfm_ba_handle* h) {
 // keyframe-sized set_problem, which returns with its uploads from the stage
 // still in flight, is always followed by a synchronising call before the
 // stage is written again.  The rule is checked there: a stream found busy is
-// drained first (and counted, so a test can see the rule broken).
+// drained first.
 int stage_reserve(sfm_ba_handle* h, size_t bytes);
 using sfm::kStageMaxBytes;  // transfers above it bypass the stage (ba_host_layout.h)
 using sfm::hostlayout::StageLayout;
@@ -209,9 +202,8 @@ inline void free_problem(sfm_ba_handle* h) {
   for (auto& a : h->allocs) h->pool.insert(a);
   h->allocs.clear();
   retire_tmps(h);
-  double* keep = h->d.scal_host;  // pinned mirror: kept for the handle's life
   h->d = sfm::DevProblem();
-  h->d.scal_host = keep;
+  h->d.scal_host = h->scal_host;
   h->has_problem = false;
 }
 

@@ -152,8 +152,8 @@ void fill_param_stage(const Setup& c, uint8_t* ps) {
 }
 int ensure_side_stream(sfm_ba_handle* h) {
   if (h->ustream) return 0;
-  HIPCHK(hipStreamCreateWithFlags(&h->ustream, hipStreamNonBlocking));
-  HIPCHK(hipEventCreateWithFlags(&h->uev, hipEventDisableTiming));
+  HIPCHK(h->ustream.create(hipStreamNonBlocking));
+  HIPCHK(h->uev.create(hipEventDisableTiming));
   return 0;
 }
 // Side route: from the caller's pageable arrays on the side stream, while the
@@ -205,7 +205,7 @@ int open_uploads(Setup& c, const double* K9, const double* rot, const double* t)
 int start_uv_worker(Setup& c) {
   sfm_ba_handle* h = c.h;
   if (int rc = ensure_side_stream(h)) return rc;
-  if (!h->uev_uv) HIPCHK(hipEventCreateWithFlags(&h->uev_uv, hipEventDisableTiming));
+  HIPCHK(h->uev_uv.create(hipEventDisableTiming));
   Setup* cp = &c;
   auto uv_job = [cp]() {
     Setup& c = *cp;
@@ -552,10 +552,9 @@ int alloc_pair_lists(Setup& c) {
   d.n_pairs = c.plan.host_counts && !c.cam_slice.empty() ? c.pairs_est : c.n_pairs;
   c.shape.n_pairs = d.n_pairs;
   plan_from_shape(c);  // (the shape is complete: the plan is final)
-  if (!d.scal_host && hipHostMalloc(&d.scal_host, sizeof(double) * (kNumScalars + 1 + 17)) != hipSuccess) {
-    d.scal_host = nullptr;
-    return fail(SFM_ENOMEM, "hipHostMalloc failed");
-  }
+  constexpr size_t kScalHostBytes = sizeof(double) * (kNumScalars + 1 + 17);
+  if (c.h->scal_host.reserve(kScalHostBytes, kScalHostBytes, nullptr)) return fail(SFM_ENOMEM, "hipHostMalloc failed");
+  d.scal_host = c.h->scal_host;
   c.grp_host = reinterpret_cast<int64_t*>(d.scal_host + kNumScalars + 1);
   c.uv_err_host = reinterpret_cast<int32_t*>(c.grp_host + 16);
   // (and the wave-major stream's, its slot total known by now: filled once

@@ -12,7 +12,6 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <map>
-#include <atomic>
 
 #include <algorithm>
 #include <array>
@@ -36,7 +35,6 @@
 
 namespace {
 thread_local std::string g_err;
-std::atomic<int> g_stage_busy_regrows{0};
 }  // namespace
 
 void sfm_internal_set_error(const std::string& msg) { g_err = msg; }
@@ -51,20 +49,11 @@ using namespace sfm;
 
 // The pinned staging buffer with room for `bytes` (the rule it checks: ba_handle.h).
 int stage_reserve(sfm_ba_handle* h, size_t bytes) {
-  if (bytes <= h->stage_cap) return 0;
-  if (h->stage && hipStreamQuery(h->stream) == hipErrorNotReady) {
-    g_stage_busy_regrows.fetch_add(1);
-    if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(SFM_EIO, "stream error before the stage regrows");
-  }
-  const size_t cap = std::max<size_t>({bytes, size_t(1) << 20, 2 * h->stage_cap});
-  if (h->stage) (void)hipHostFree(h->stage);
-  h->stage = nullptr;
-  h->stage_cap = 0;
-  if (hipHostMalloc(reinterpret_cast<void**>(&h->stage), cap) != hipSuccess) {
-    h->stage = nullptr;
+  if (bytes <= h->stage.bytes()) return 0;
+  if (h->stage && hipStreamQuery(h->stream) == hipErrorNotReady && hipStreamSynchronize(h->stream) != hipSuccess)
+    return fail(SFM_EIO, "stream error before the stage regrows");
+  if (h->stage.reserve(bytes, std::max<size_t>({bytes, size_t(1) << 20, 2 * h->stage.bytes()}), nullptr))
     return fail(SFM_ENOMEM, "hipHostMalloc failed (staging buffer)");
-  }
-  h->stage_cap = cap;
   return 0;
 }
 
@@ -78,7 +67,7 @@ void mark_begin(sfm_ba_handle* h, int ph) {
   if (h->ev_used + 2 > int(h->ev.size())) {
     const size_t old = h->ev.size();
     h->ev.resize(old + 256);
-    for (size_t i = old; i < h->ev.size(); ++i) hipEventCreate(&h->ev[i]);
+    for (size_t i = old; i < h->ev.size(); ++i) (void)h->ev[i].create(hipEventDefault);
   }
   h->ev_marks.push_back({ph, h->ev_used});
   hipEventRecord(h->ev[h->ev_used], h->stream);
@@ -241,17 +230,10 @@ int allreduce(sfm_ba_handle* h, double* buf, size_t count, ncclRedOp_t op) {
     if (scale != 1.0) launch_gated_copy(buf, buf, int64_t(count), scale, nullptr, h->stream);
     return 0;
   }
-  if (h->ar_tmp_cap < count) {
+  if (h->ar_tmp.bytes() < count * sizeof(double)) {
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->ar_tmp) (void)hipFree(h->ar_tmp);
-    h->ar_tmp = nullptr;
-    h->ar_tmp_cap = 0;
-    const size_t cap = std::max<size_t>(count, 4096);
-    if (hipMalloc(reinterpret_cast<void**>(&h->ar_tmp), cap * sizeof(double)) != hipSuccess) {
-      h->ar_tmp = nullptr;
+    if (h->ar_tmp.reserve(count * sizeof(double), std::max<size_t>(count, 4096) * sizeof(double), nullptr))
       return fail(SFM_ENOMEM, "hipMalloc failed (collective scratch)");
-    }
-    h->ar_tmp_cap = cap;
   }
   NCCLCHK(ncclAllReduce(buf, h->ar_tmp, count, ncclDouble, op, h->comm, h->stream));
   launch_gated_copy(h->ar_tmp, buf, int64_t(count), scale, h->d.gate, h->stream);
@@ -333,23 +315,13 @@ int dist_prepare(sfm_ba_handle* h) {
   const int pt = h->dist_pt;
   if (D.send && D.pt == pt && D.nblk == d.nblk && D.n == d.n && D.nranks == h->nranks && D.rank == h->rank) return 0;
   HIPCHK(hipStreamSynchronize(h->stream));
-  for (void* p : {static_cast<void*>(D.send), static_cast<void*>(D.recv), static_cast<void*>(D.bcast),
-                  static_cast<void*>(D.off_send), static_cast<void*>(D.off_recv)})
-    if (p) (void)hipFree(p);
-  const hipStream_t cs = D.cstream;
-  const hipEvent_t evs[5] = {D.ev_packed, D.ev_free[0], D.ev_free[1], D.ev_arrived[0], D.ev_arrived[1]};
-  std::vector<hipEvent_t> ev_red = std::move(D.ev_red);
-  const hipEvent_t ev_sent = D.ev_sent;
-  D = sfm_ba_handle::DistBufs();
-  D.ev_red = std::move(ev_red);
-  D.ev_sent = ev_sent;
-  D.cstream = cs;  // (kept for the handle's life)
-  D.ev_packed = evs[0]; D.ev_free[0] = evs[1]; D.ev_free[1] = evs[2]; D.ev_arrived[0] = evs[3]; D.ev_arrived[1] = evs[4];
-  if (!D.cstream) {
-    HIPCHK(hipStreamCreateWithFlags(&D.cstream, hipStreamNonBlocking));
-    for (hipEvent_t* e : {&D.ev_packed, &D.ev_free[0], &D.ev_free[1], &D.ev_arrived[0], &D.ev_arrived[1]})
-      HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-  }
+  for (DevBuf* b : {static_cast<DevBuf*>(&D.send), static_cast<DevBuf*>(&D.recv), static_cast<DevBuf*>(&D.bcast),
+                    static_cast<DevBuf*>(&D.off_send)})
+    b->reset();
+  static_cast<DistLayout&>(D) = DistLayout();  // (the stream and the events stay: made once)
+  HIPCHK(D.cstream.create(hipStreamNonBlocking));
+  for (Event* e : {&D.ev_packed, &D.ev_free[0], &D.ev_free[1], &D.ev_arrived[0], &D.ev_arrived[1], &D.ev_sent})
+    HIPCHK(e->create(hipEventDisableTiming));
   const int np = (d.nblk + pt - 1) / pt, N = h->nranks;
   D.count.assign(size_t(np), 0);
   D.poff.assign(size_t(np), 0);
@@ -362,22 +334,21 @@ int dist_prepare(sfm_ba_handle* h) {
   }
   std::vector<int64_t> os(static_cast<size_t>(np));
   for (int J = 0; J < np; ++J) os[J] = J % N == h->rank ? -1 : D.poff[J];
-  auto grab = [&](void** p, size_t bytes) { return hipMalloc(p, std::max<size_t>(bytes, 256)) == hipSuccess; };
-  if (!grab(reinterpret_cast<void**>(&D.send), sizeof(double) * size_t(D.total)) ||
-      !grab(reinterpret_cast<void**>(&D.recv), sizeof(double) * size_t(D.total)) ||
-      !grab(reinterpret_cast<void**>(&D.bcast), 2 * sizeof(double) * size_t(D.bcast_cap)) ||
-      !grab(reinterpret_cast<void**>(&D.off_send), sizeof(int64_t) * np))
+  auto grab = [](DevBuf& b, size_t bytes) {
+    return b.reserve(std::max<size_t>(bytes, 256), std::max<size_t>(bytes, 256), nullptr) == 0;
+  };
+  if (!grab(D.send, sizeof(double) * size_t(D.total)) || !grab(D.recv, sizeof(double) * size_t(D.total)) ||
+      !grab(D.bcast, 2 * sizeof(double) * size_t(D.bcast_cap)) || !grab(D.off_send, sizeof(int64_t) * np))
     return fail(SFM_ENOMEM, "hipMalloc failed (distributed factor buffers)");
   HIPCHK(hipMemcpy(D.off_send, os.data(), sizeof(int64_t) * np, hipMemcpyHostToDevice));
   // the own panels' regions of send stay zero: the owner's partial is
   // updated in place and the others' sum is added just before its factor
   HIPCHK(hipMemsetAsync(D.send, 0, sizeof(double) * size_t(D.total), h->stream));
   while (int(D.ev_red.size()) < np) {
-    hipEvent_t e;
-    HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    D.ev_red.push_back(e);
+    Event e;
+    HIPCHK(e.create(hipEventDisableTiming));
+    D.ev_red.push_back(std::move(e));
   }
-  if (!D.ev_sent) HIPCHK(hipEventCreateWithFlags(&D.ev_sent, hipEventDisableTiming));
   D.pt = pt; D.nblk = d.nblk; D.n = d.n; D.nranks = N; D.rank = h->rank;
   return 0;
 }
@@ -903,28 +874,14 @@ int run_device_lm(sfm_ba_handle* h, const sfm_ba_options& opts, sfm_ba_summary* 
   hipStream_t s = h->stream;
   HostTimer timer;
   timer.tag = "solve";
-  if (!h->lm_ctl) {
-    if (hipMalloc(reinterpret_cast<void**>(&h->lm_ctl), sizeof(LmCtl)) != hipSuccess) {
-      h->lm_ctl = nullptr;
-      return fail(SFM_ENOMEM, "hipMalloc failed (LM control)");
-    }
-    if (hipHostMalloc(reinterpret_cast<void**>(&h->lm_ctl_host), sizeof(LmCtl)) != hipSuccess) {
-      h->lm_ctl_host = nullptr;
-      return fail(SFM_ENOMEM, "hipHostMalloc failed (LM control)");
-    }
-  }
+  if (h->lm_ctl.reserve(sizeof(LmCtl), sizeof(LmCtl), nullptr)) return fail(SFM_ENOMEM, "hipMalloc failed (LM control)");
+  if (h->lm_ctl_host.reserve(sizeof(LmCtl), sizeof(LmCtl), nullptr))
+    return fail(SFM_ENOMEM, "hipHostMalloc failed (LM control)");
   const int cap = std::max(1, opts.max_num_iterations + 1);
   if (h->lm_trace_cap < cap) {
-    if (h->lm_trace) {
-      (void)hipStreamSynchronize(s);
-      (void)hipHostFree(h->lm_trace);
-    }
-    h->lm_trace = nullptr;
     h->lm_trace_cap = 0;
-    if (hipHostMalloc(reinterpret_cast<void**>(&h->lm_trace), sizeof(sfm_ba_iteration) * size_t(cap)) != hipSuccess) {
-      h->lm_trace = nullptr;
+    if (h->lm_trace.reserve(sizeof(sfm_ba_iteration) * size_t(cap), sizeof(sfm_ba_iteration) * size_t(cap), s))
       return fail(SFM_ENOMEM, "hipMalloc failed (LM trace)");
-    }
     h->lm_trace_cap = cap;
   }
   LmCtl& c = *h->lm_ctl_host;
@@ -1035,7 +992,7 @@ int sfm_ba_create(int32_t device, sfm_ba_handle** out) {
   HIPCHK(hipSetDevice(device));
   auto* h = new sfm_ba_handle();
   h->device = device;
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+  if (h->stream.create(hipStreamNonBlocking) != hipSuccess) {
     delete h;
     return fail(SFM_EIO, "hipStreamCreate failed");
   }
@@ -1050,35 +1007,7 @@ int sfm_ba_destroy(sfm_ba_handle* h) {
   hipStreamSynchronize(h->stream);
   free_problem(h);
   release_pool(h);
-  if (h->d.scal_host) hipHostFree(h->d.scal_host);
-  if (h->lm_ctl) hipFree(h->lm_ctl);
-  if (h->lm_ctl_host) hipHostFree(h->lm_ctl_host);
-  if (h->lm_trace) hipHostFree(h->lm_trace);
-  if (h->param_host) hipHostFree(h->param_host);
-  if (h->stage) hipHostFree(h->stage);
-  if (h->ar_tmp) hipFree(h->ar_tmp);
-  for (void* p : {static_cast<void*>(h->dist.send), static_cast<void*>(h->dist.recv),
-                  static_cast<void*>(h->dist.bcast), static_cast<void*>(h->dist.off_send),
-                  static_cast<void*>(h->dist.off_recv)})
-    if (p) hipFree(p);
-  if (h->dist.cstream) {
-    hipStreamSynchronize(h->dist.cstream);
-    hipStreamDestroy(h->dist.cstream);
-    for (hipEvent_t e : {h->dist.ev_packed, h->dist.ev_free[0], h->dist.ev_free[1], h->dist.ev_arrived[0],
-                         h->dist.ev_arrived[1]})
-      hipEventDestroy(e);
-  }
-  for (hipEvent_t e : h->dist.ev_red) hipEventDestroy(e);
-  if (h->dist.ev_sent) hipEventDestroy(h->dist.ev_sent);
-  if (h->ustream) {
-    hipStreamSynchronize(h->ustream);
-    hipStreamDestroy(h->ustream);
-    hipEventDestroy(h->uev);
-    if (h->uev_uv) hipEventDestroy(h->uev_uv);
-  }
-  for (auto e : h->ev) hipEventDestroy(e);
   if (h->comm) ncclCommDestroy(h->comm);
-  hipStreamDestroy(h->stream);
   delete h;
   return 0;
 }
@@ -1271,37 +1200,20 @@ int sfm_ba_solve(const sfm_ba_options* opts, int32_t mode, int64_t n_obs, const 
   // (measured at C1: create 1.7 ms + destroy 2.2 ms against a 1.9-ms solve).
   // The cache owns its handles: they are destroyed (stream, pinned mirror,
   // pooled device buffers) when the calling thread exits.
-  struct HandleCache {
-    std::map<int, sfm_ba_handle*> by_dev;
-    ~HandleCache() {
-      for (auto& kv : by_dev)
-        if (kv.second) sfm_ba_destroy(kv.second);
-    }
+  struct Cached {
+    sfm_ba_handle* h = nullptr;
+    int init(int dev) { return sfm_ba_create(dev, &h); }
+    ~Cached() { sfm_ba_destroy(h); }
   };
-  static thread_local HandleCache cache;
-  sfm_ba_handle*& h = cache.by_dev[dev];
   int rc = 0;
-  if (!h && (rc = sfm_ba_create(dev, &h))) {
-    h = nullptr;
-    return rc;
-  }
+  Cached* cached = thread_ctx<Cached>(dev, &rc);
+  if (!cached) return rc;
+  sfm_ba_handle* h = cached->h;
   rc = sfm_ba_set_problem(h, n_obs, obs_uv, cam_idx, pt_idx, n_cams, K9, rot, t, n_pts, X);
   // small problems: the parameters ride in the solve's last control readback
   const size_t np = 6 * size_t(std::max(0, n_cams)) + 3 * size_t(std::max(0, n_pts));
   if (!rc && np * sizeof(double) <= kParamPrefetchMaxBytes) {
-    if (h->param_host_cap < np) {
-      if (h->param_host) {
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipHostFree(h->param_host);
-      }
-      h->param_host = nullptr;
-      h->param_host_cap = 0;
-      if (hipHostMalloc(reinterpret_cast<void**>(&h->param_host), std::max<size_t>(np, 4096) * sizeof(double)) ==
-          hipSuccess)
-        h->param_host_cap = std::max<size_t>(np, 4096);
-      else
-        h->param_host = nullptr;
-    }
+    (void)h->param_host.reserve(np * sizeof(double), std::max<size_t>(np, 4096) * sizeof(double), h->stream);
     h->prefetch_params = h->param_host != nullptr;
   }
   h->param_host_valid = false;
@@ -1370,6 +1282,49 @@ int sfm_ba_evaluate(sfm_ba_handle* h, double* cost, double* res, double* jac) {
   return 0;
 }
 
+}  // extern "C"
+
+namespace {
+// The bare dense system of order n the factor and the back substitution work
+// on (sfm_dist_factor_profile, dense_solve), from owners: S, invL and the
+// flags zeroed (cflags and the 8-byte-aligned cticket inside them), ysol, fail.
+int alloc_failed(int hip_error) {  // (SFM_EIO: what HIPCHK(hipMalloc(...)) gave these entry points)
+  return fail(SFM_EIO, std::string("hipMalloc: ") + hipGetErrorString(hipError_t(hip_error)));
+}
+struct DenseProblem {
+  Stream s;  // first: members are destroyed in reverse order, so it goes last
+  DevArr<double> S, invL, ysol;
+  DevArr<int> fail_word, flags;
+  DevProblem d;
+  size_t bytes = 0;  // of S
+  int init(int device, int n) {
+    d.n = n;
+    d.ld = ((n + 1 + kNB - 1) / kNB) * kNB;
+    d.nblk = d.ld / kNB;
+    bytes = sizeof(double) * size_t(d.ld) * d.ld;
+    const size_t b_inv = sizeof(double) * size_t(d.nblk) * kNB * kNB;
+    const size_t n_pre = d.nblk + 2 * size_t(d.nblk) * d.nblk, b_flag = sizeof(int) * (n_pre + 16);
+    HIPCHK(s.create(hipStreamDefault));
+    auto fixed = [](DevBuf& b, size_t n_bytes) { return b.reserve(n_bytes, n_bytes, nullptr); };
+    int e = 0;
+    if ((e = fixed(S, bytes)) || (e = fixed(invL, b_inv)) || (e = fixed(flags, b_flag)) ||
+        (e = fixed(ysol, sizeof(double) * d.ld)) || (e = fixed(fail_word, sizeof(int))))
+      return alloc_failed(e);
+    HIPCHK(hipMemset(invL, 0, b_inv));
+    HIPCHK(hipMemset(flags, 0, b_flag));
+    HIPCHK(hipMemset(fail_word, 0, sizeof(int)));
+    d.S = S; d.invL = invL; d.ysol = ysol; d.fail = fail_word; d.flags = flags;
+    d.cflags = flags + d.nblk;
+    d.cticket = reinterpret_cast<unsigned long long*>(flags + n_pre);
+    if (reinterpret_cast<uintptr_t>(d.cticket) % 8) d.cticket = reinterpret_cast<unsigned long long*>(flags + n_pre + 1);
+    d.n_cu = device_cus(device);
+    return 0;
+  }
+};
+}  // namespace
+
+extern "C" {
+
 int sfm_dist_factor_profile(int32_t device, int32_t n, int32_t nranks, int32_t panel_tiles, double* fac_ms,
                             double* pack_ms, double* unpack_ms, double* upd_ms, double* misc_ms) {
   if (n <= 0 || nranks < 1 || panel_tiles < 1 || !fac_ms || !pack_ms || !unpack_ms || !upd_ms || !misc_ms)
@@ -1377,36 +1332,20 @@ int sfm_dist_factor_profile(int32_t device, int32_t n, int32_t nranks, int32_t p
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(SFM_ENODEV, "no device");
   HIPCHK(hipSetDevice(device));
-  DevProblem d;
-  d.n = n;
-  d.ld = ((n + 1 + kNB - 1) / kNB) * kNB;
-  d.nblk = d.ld / kNB;
+  DenseProblem dp;
+  if (int rc = dp.init(device, n)) return rc;
+  DevProblem& d = dp.d;
   const int pt = panel_tiles, np = (d.nblk + pt - 1) / pt;
-  const size_t bytes = sizeof(double) * size_t(d.ld) * d.ld;
-  hipStream_t s = nullptr;
-  HIPCHK(hipStreamCreate(&s));
-  double *S = nullptr, *invd = nullptr, *ys = nullptr, *buf = nullptr;
-  int *fl = nullptr, *flags = nullptr;
-  const size_t nflag = d.nblk + 2 * size_t(d.nblk) * d.nblk + 16;
-  HIPCHK(hipMalloc(&S, bytes));
-  HIPCHK(hipMalloc(&invd, sizeof(double) * size_t(d.nblk) * kNB * kNB));
-  HIPCHK(hipMemset(invd, 0, sizeof(double) * size_t(d.nblk) * kNB * kNB));
-  HIPCHK(hipMalloc(&flags, sizeof(int) * nflag));
-  HIPCHK(hipMemset(flags, 0, sizeof(int) * nflag));
-  HIPCHK(hipMalloc(&ys, sizeof(double) * d.ld));
-  HIPCHK(hipMalloc(&fl, sizeof(int)));
-  HIPCHK(hipMemset(fl, 0, sizeof(int)));
+  const size_t bytes = dp.bytes;
+  hipStream_t s = dp.s;
+  double *S = dp.S, *ys = dp.ysol;
   // one panel rectangle (the broadcast buffer) / the whole lower image (the
   // reduce-scatter's send buffer)
-  HIPCHK(hipMalloc(&buf, bytes));
+  DevArr<double> buf;
+  if (int e = buf.reserve(bytes, bytes, nullptr)) return alloc_failed(e);
   HIPCHK(hipMemset(buf, 0, bytes));
-  d.S = S; d.invL = invd; d.ysol = ys; d.fail = fl; d.flags = flags;
-  d.cflags = flags + d.nblk;
-  d.cticket = reinterpret_cast<unsigned long long*>(flags + d.nblk + 2 * size_t(d.nblk) * d.nblk);
-  if (reinterpret_cast<uintptr_t>(d.cticket) % 8) d.cticket = reinterpret_cast<unsigned long long*>(flags + d.nblk + 2 * size_t(d.nblk) * d.nblk + 1);
-  d.n_cu = device_cus(device);
-  std::vector<hipEvent_t> ev(4 * size_t(np) + 8);
-  for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+  std::vector<Event> ev(4 * size_t(np) + 8);
+  for (auto& e : ev) HIPCHK(e.create(hipEventDefault));
   auto el = [&](hipEvent_t a, hipEvent_t b) {
     float m = 0.f;
     (void)hipEventElapsedTime(&m, a, b);
@@ -1420,8 +1359,8 @@ int sfm_dist_factor_profile(int32_t device, int32_t n, int32_t nranks, int32_t p
     const int c0 = J * pt * kNB, c1 = std::min((J + 1) * pt * kNB, n + 1);
     tot += c1 > c0 ? int64_t(c1 - c0) * (n + 1 - c0) : 0;
   }
-  int64_t* doff = nullptr;
-  HIPCHK(hipMalloc(&doff, sizeof(int64_t) * np));
+  DevArr<int64_t> doff;
+  if (int e = doff.reserve(sizeof(int64_t) * np, sizeof(int64_t) * np, nullptr)) return alloc_failed(e);
   HIPCHK(hipMemcpy(doff, off.data(), sizeof(int64_t) * np, hipMemcpyHostToDevice));
   int epoch = 0;
   for (int rank = 0; rank < nranks; ++rank) {
@@ -1473,12 +1412,9 @@ int sfm_dist_factor_profile(int32_t device, int32_t n, int32_t nranks, int32_t p
     }
   }
   int f = 0;
-  HIPCHK(hipMemcpy(&f, fl, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&f, d.fail, sizeof(int), hipMemcpyDeviceToHost));
   misc_ms[3] = f;
   misc_ms[4] = double(tot);  // doubles of the whole panel image
-  for (auto e : ev) hipEventDestroy(e);
-  hipFree(S); hipFree(invd); hipFree(flags); hipFree(ys); hipFree(fl); hipFree(buf); hipFree(doff);
-  hipStreamDestroy(s);
   return 0;
 }
 
@@ -1495,38 +1431,25 @@ static int dense_solve(int32_t device, int32_t n, const double* A, const double*
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(SFM_ENODEV, "no device");
   HIPCHK(hipSetDevice(device));
-  DevProblem d;
-  d.n = n;
-  d.ld = ((n + 1 + kNB - 1) / kNB) * kNB;
-  d.nblk = d.ld / kNB;
+  DenseProblem dp;
+  if (int rc = dp.init(device, n)) return rc;
+  DevProblem& d = dp.d;
   // augmented column-major-lower image: (i, j) at j*ld + i, i >= j
   std::vector<double> img(size_t(d.ld) * d.ld, 0.0);
   for (int j = 0; j < n; ++j)
     for (int i = j; i < n; ++i) img[size_t(j) * d.ld + i] = A[size_t(j) * n + i];  // row-major upper (j, i)
   for (int j = 0; j < n; ++j) img[size_t(j) * d.ld + n] = b[j];
   for (int j = n; j < d.ld; ++j) img[size_t(j) * d.ld + j] = 1.0;
-  double *S = nullptr, *S0 = nullptr, *invd = nullptr, *ys = nullptr;
-  int *fl = nullptr, *flags = nullptr;
-  const size_t bytes = sizeof(double) * img.size();
-  hipStream_t s = nullptr;
-  HIPCHK(hipStreamCreate(&s));
-  HIPCHK(hipMalloc(&S, bytes));
-  HIPCHK(hipMalloc(&S0, bytes));
-  HIPCHK(hipMalloc(&invd, sizeof(double) * size_t(d.nblk) * kNB * kNB));
-  HIPCHK(hipMemset(invd, 0, sizeof(double) * size_t(d.nblk) * kNB * kNB));
-  HIPCHK(hipMalloc(&flags, sizeof(int) * (d.nblk + 2 * size_t(d.nblk) * d.nblk + 16)));
-  HIPCHK(hipMemset(flags, 0, sizeof(int) * (d.nblk + 2 * size_t(d.nblk) * d.nblk + 16)));
-  HIPCHK(hipMalloc(&ys, sizeof(double) * d.ld));
-  HIPCHK(hipMalloc(&fl, sizeof(int)));
+  const size_t bytes = dp.bytes;
+  hipStream_t s = dp.s;
+  double *S = dp.S, *ys = dp.ysol;
+  int* fl = dp.fail_word;
+  DevArr<double> S0;
+  if (int e = S0.reserve(bytes, bytes, nullptr)) return alloc_failed(e);
   HIPCHK(hipMemcpy(S0, img.data(), bytes, hipMemcpyHostToDevice));
-  d.S = S; d.invL = invd; d.ysol = ys; d.fail = fl; d.flags = flags;
-  d.cflags = flags + d.nblk;
-  d.cticket = reinterpret_cast<unsigned long long*>(flags + d.nblk + 2 * size_t(d.nblk) * d.nblk);
-  if (reinterpret_cast<uintptr_t>(d.cticket) % 8) d.cticket = reinterpret_cast<unsigned long long*>(flags + d.nblk + 2 * size_t(d.nblk) * d.nblk + 1);
-  d.n_cu = device_cus(device);
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0));
-  HIPCHK(hipEventCreate(&e1));
+  Event e0, e1;
+  HIPCHK(e0.create(hipEventDefault));
+  HIPCHK(e1.create(hipEventDefault));
   float total = 0.f;
   int pepoch = 0;  // the panels' flag epoch: one per panel launch
   for (int r = 0; r < reps; ++r) {
@@ -1554,9 +1477,6 @@ static int dense_solve(int32_t device, int32_t n, const double* A, const double*
   HIPCHK(hipMemcpy(y, ys, sizeof(double) * n, hipMemcpyDeviceToHost));
   if (ms) *ms = total / (reps > 1 ? reps - 1 : 1);
   if (chol_fail) *chol_fail = f;
-  hipEventDestroy(e0); hipEventDestroy(e1);
-  hipFree(S); hipFree(S0); hipFree(invd); hipFree(flags); hipFree(ys); hipFree(fl);
-  hipStreamDestroy(s);
   return 0;
 }
 
@@ -1578,9 +1498,9 @@ int sfm_ba_bench_jacobian(sfm_ba_handle* h, int32_t reps, double* avg_ms) {
   int rc;
   if ((rc = ensure_records(h))) return rc;
   launch_cam_prep(d, d.cam, false, h->stream);
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0));
-  HIPCHK(hipEventCreate(&e1));
+  Event e0, e1;
+  HIPCHK(e0.create(hipEventDefault));
+  HIPCHK(e1.create(hipEventDefault));
   launch_jacobian(d, true, h->stream, true);  // warm (the record-writing pass is what is measured)
   HIPCHK(hipEventRecord(e0, h->stream));
   for (int i = 0; i < reps; ++i) launch_jacobian(d, true, h->stream, true);
@@ -1588,8 +1508,6 @@ int sfm_ba_bench_jacobian(sfm_ba_handle* h, int32_t reps, double* avg_ms) {
   HIPCHK(hipEventSynchronize(e1));
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
   if (avg_ms) *avg_ms = double(ms) / reps;
   return 0;
 }

@@ -7,8 +7,7 @@
 #include <algorithm>
 #include <string>
 #include "../../include/sfm_amd.h"
-
-void sfm_internal_set_error(const std::string& msg);
+#include "dev_mem.h"
 
 namespace {
 
@@ -41,30 +40,22 @@ __global__ __launch_bounds__(256) void k_stream_copy(const v4f* __restrict__ a, 
 }  // namespace
 
 extern "C" int sfm_bench_stream_copy(int32_t device, int64_t bytes, int32_t reps, double* best_gbs) {
-  if (bytes < (1 << 20) || reps < 1 || !best_gbs) {
-    sfm_internal_set_error("sfm_bench_stream_copy: bytes >= 1 MiB, reps >= 1");
-    return SFM_EINVAL;
-  }
-  if (hipSetDevice(device) != hipSuccess) {
-    sfm_internal_set_error("sfm_bench_stream_copy: hipSetDevice failed");
-    return SFM_ENODEV;
-  }
+  if (bytes < (1 << 20) || reps < 1 || !best_gbs)
+    return fail(SFM_EINVAL, "sfm_bench_stream_copy: bytes >= 1 MiB, reps >= 1");
+  if (hipSetDevice(device) != hipSuccess) return fail(SFM_ENODEV, "sfm_bench_stream_copy: hipSetDevice failed");
   hipDeviceProp_t prop;
   int cus = 256;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
   const int64_t n = bytes / 16;
-  v4f *a = nullptr, *b = nullptr;
-  if (hipMalloc(&a, n * 16) != hipSuccess || hipMalloc(&b, n * 16) != hipSuccess) {
-    if (a) (void)hipFree(a);
-    sfm_internal_set_error("sfm_bench_stream_copy: hipMalloc failed");
-    return SFM_ENOMEM;
-  }
-  hipStream_t s;
-  (void)hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+  sfm::Stream s;  // (first: destroyed after the buffers and events)
+  sfm::DevArr<v4f> a, b;
+  sfm::Event e0, e1;
+  if (a.reserve(n * 16, n * 16, nullptr) || b.reserve(n * 16, n * 16, nullptr))
+    return fail(SFM_ENOMEM, "sfm_bench_stream_copy: hipMalloc failed");
+  (void)s.create(hipStreamNonBlocking);
   (void)hipMemsetAsync(a, 0, n * 16, s);
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0);
-  (void)hipEventCreate(&e1);
+  (void)e0.create(hipEventDefault);
+  (void)e1.create(hipEventDefault);
   double best = 0.0;
   // a few grid / unroll shapes, best of `reps` each (the figure is the best
   // copy the device sustains, not a property of one launch shape)
@@ -84,15 +75,7 @@ extern "C" int sfm_bench_stream_copy(int32_t device, int64_t bytes, int32_t reps
         if (r > 0 && ms > 0.f) best = std::max(best, 2.0 * double(n) * 16.0 / (double(ms) * 1e-3) / 1e9);
       }
   const hipError_t err = hipStreamSynchronize(s);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipStreamDestroy(s);
-  (void)hipFree(a);
-  (void)hipFree(b);
-  if (err != hipSuccess) {
-    sfm_internal_set_error(std::string("sfm_bench_stream_copy: ") + hipGetErrorString(err));
-    return SFM_EIO;
-  }
+  if (err != hipSuccess) return fail(SFM_EIO, std::string("sfm_bench_stream_copy: ") + hipGetErrorString(err));
   *best_gbs = best;
   return 0;
 }

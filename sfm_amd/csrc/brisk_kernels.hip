@@ -27,8 +27,7 @@
 #include "sfm_trace.h"
 #include "../../include/sfm_amd.h"
 #include "frame_internal.h"
-
-void sfm_internal_set_error(const std::string& msg);  // ba_solver.hip
+#include "dev_mem.h"
 
 namespace sfm {
 namespace {
@@ -36,10 +35,7 @@ namespace {
 constexpr int kRot = 1024, kScales = 64, kPts = 60;
 constexpr float kScaleRange = 30.0f, kBasicSize = 12.0f;
 
-int bfail(int code, const std::string& m) {
-  sfm_internal_set_error("brisk: " + m);
-  return code;
-}
+int bfail(int code, const std::string& m) { return fail(code, "brisk: " + m); }
 
 struct BriskPattern {
   std::vector<float> xy;      // [scales][rot][points][2]
@@ -108,30 +104,35 @@ struct DevPattern {
   int n_long = 0, n_short = 0;
 };
 
-// one copy per device, built on first use
+// one copy per device, built on first use and kept for the life of the
+// process (never freed: no teardown at exit): the arrays, and the view of
+// them that the kernels take by value
+struct PatternStore {
+  DevBuf xy, sigma, size_list, longp, shortp;
+  DevPattern view;
+};
 DevPattern* device_pattern(int device, int* rc) {
   static std::mutex mu;
-  static std::vector<DevPattern*> per_dev(64, nullptr);
+  static std::vector<PatternStore*> per_dev(64, nullptr);
   std::lock_guard<std::mutex> lock(mu);
   if (device < 0 || device >= 64) { *rc = bfail(SFM_ENODEV, "device index"); return nullptr; }
-  if (per_dev[device]) return per_dev[device];
+  if (per_dev[device]) return &per_dev[device]->view;
   static BriskPattern host = make_pattern();
-  auto* d = new DevPattern;
-  d->n_long = int(host.longp.size() / 4);
-  d->n_short = int(host.shortp.size() / 2);
-  bool ok = hipMalloc(&d->xy, host.xy.size() * sizeof(float)) == hipSuccess &&
-            hipMalloc(&d->sigma, host.sigma.size() * sizeof(float)) == hipSuccess &&
-            hipMalloc(&d->size_list, sizeof(int32_t) * kScales) == hipSuccess &&
-            hipMalloc(&d->longp, host.longp.size() * sizeof(int32_t)) == hipSuccess &&
-            hipMalloc(&d->shortp, host.shortp.size() * sizeof(int32_t)) == hipSuccess;
-  ok = ok && hipMemcpy(d->xy, host.xy.data(), host.xy.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy(d->sigma, host.sigma.data(), host.sigma.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy(d->size_list, host.size_list, sizeof(int32_t) * kScales, hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy(d->longp, host.longp.data(), host.longp.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy(d->shortp, host.shortp.data(), host.shortp.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+  std::unique_ptr<PatternStore> d(new PatternStore);
+  // allocates and fills one array
+  auto put = [](DevBuf& b, const void* src, size_t bytes) {
+    return b.reserve(bytes, bytes, nullptr) == 0 && hipMemcpy(b.get(), src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+  };
+  const bool ok = put(d->xy, host.xy.data(), host.xy.size() * sizeof(float)) &&
+                  put(d->sigma, host.sigma.data(), host.sigma.size() * sizeof(float)) &&
+                  put(d->size_list, host.size_list, sizeof(int32_t) * kScales) &&
+                  put(d->longp, host.longp.data(), host.longp.size() * sizeof(int32_t)) &&
+                  put(d->shortp, host.shortp.data(), host.shortp.size() * sizeof(int32_t));
   if (!ok) { *rc = bfail(SFM_ENOMEM, "pattern upload failed"); return nullptr; }
-  per_dev[device] = d;
-  return d;
+  d->view = DevPattern{d->xy.as<float2>(), d->sigma.as<float>(), d->size_list.as<int32_t>(), d->longp.as<int4>(),
+                       d->shortp.as<int2>(), int(host.longp.size() / 4), int(host.shortp.size() / 2)};
+  per_dev[device] = d.release();
+  return &per_dev[device]->view;
 }
 
 // integral image [h+1][w+1] (int32: 255 * 1280 * 720 < 2^31), exact
@@ -780,40 +781,21 @@ __global__ void k_cand_keys(const Cand* __restrict__ c, int n, unsigned long lon
 
 // grow-only per-device workspace of the detector (one frame per call)
 struct BriskWork {
-  std::vector<std::pair<void*, size_t>> buf;
+  std::vector<DevBuf> buf;
   void* get(int slot, size_t bytes, int* rc) {
-    if (int(buf.size()) <= slot) buf.resize(slot + 1, {nullptr, 0});
-    auto& e = buf[slot];
-    if (e.second < bytes) {
-      if (e.first) (void)hipFree(e.first);
-      e = {nullptr, 0};
-      if (hipMalloc(&e.first, std::max<size_t>(bytes, 256)) != hipSuccess) {
-        *rc = bfail(SFM_ENOMEM, "hipMalloc failed (detector workspace)");
-        return nullptr;
-      }
-      e.second = std::max<size_t>(bytes, 256);
-    }
-    return e.first;
+    if (int(buf.size()) <= slot) buf.resize(slot + 1);
+    if (buf[slot].reserve(bytes, std::max<size_t>(bytes, 256), nullptr))
+      *rc = bfail(SFM_ENOMEM, "hipMalloc failed (detector workspace)");
+    return buf[slot].get();
   }
   // pinned host staging of the one packed download (six pageable copies of
   // the per-keypoint outputs before: BRISK 1.0 -> 0.74 ms per frame)
-  void* host = nullptr;
-  size_t host_cap = 0;
-  hipEvent_t installed = nullptr;  // end of the last hand-off's reads of the packed buffer
+  PinBuf host;
+  Event installed;  // end of the last hand-off's reads of the packed buffer
   void* pinned(size_t bytes, int* rc) {
-    if (host_cap < bytes) {
-      const size_t cap = std::max(bytes, 2 * host_cap);
-      if (host) (void)hipHostFree(host);
-      host = nullptr;
-      host_cap = 0;
-      if (hipHostMalloc(&host, cap) != hipSuccess) {
-        host = nullptr;
-        *rc = bfail(SFM_ENOMEM, "hipHostMalloc failed (detector staging)");
-        return nullptr;
-      }
-      host_cap = cap;
-    }
-    return host;
+    if (host.reserve(bytes, std::max(bytes, 2 * host.bytes()), nullptr))
+      *rc = bfail(SFM_ENOMEM, "hipHostMalloc failed (detector staging)");
+    return host.get();
   }
 };
 BriskWork* work_for(int device) {
@@ -846,23 +828,21 @@ extern "C" int sfm_brisk_describe(int32_t device, const uint8_t* img, int32_t w,
   DevPattern* P = device_pattern(device, &rc);
   if (!P) return rc;
   const size_t npx = size_t(w) * h, nii = size_t(w + 1) * (h + 1);
-  uint8_t *d_img = nullptr, *d_desc = nullptr;
-  int32_t *d_ii = nullptr, *d_keep = nullptr;
-  float *d_kps = nullptr, *d_ang = nullptr;
   const int n_bytes = ((P->n_short + 127) / 128) * 16;
-  bool ok = hipMalloc(&d_img, npx) == hipSuccess && hipMalloc(&d_ii, nii * 4) == hipSuccess &&
-            hipMalloc(&d_kps, size_t(n) * 12) == hipSuccess && hipMalloc(&d_keep, size_t(n) * 4) == hipSuccess &&
-            hipMalloc(&d_ang, size_t(n) * 4) == hipSuccess && hipMalloc(&d_desc, size_t(n) * n_bytes) == hipSuccess;
+  DevArr<uint8_t> d_img, d_desc;
+  DevArr<int32_t> d_ii, d_keep, d_band;
+  DevArr<float> d_kps, d_ang;
+  auto fixed = [](DevBuf& b, size_t bytes) { return b.reserve(bytes, bytes, nullptr) == 0; };
+  bool ok = fixed(d_img, npx) && fixed(d_ii, nii * 4) && fixed(d_kps, size_t(n) * 12) && fixed(d_keep, size_t(n) * 4) &&
+            fixed(d_ang, size_t(n) * 4) && fixed(d_desc, size_t(n) * n_bytes);
   if (ok) {
     ok = hipMemcpy(d_img, img, npx, hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(d_kps, kps, size_t(n) * 12, hipMemcpyHostToDevice) == hipSuccess;
-    int32_t* d_band = nullptr;
-    ok = hipMalloc(&d_band, sizeof(int32_t) * integral_band_ints(w, h)) == hipSuccess;
+    ok = ok && fixed(d_band, sizeof(int32_t) * integral_band_ints(w, h));
     if (ok) {
       integral_image(d_img, w, h, d_ii, d_band);
       k_brisk_describe<<<n, 64>>>(d_img, w, h, d_ii, *P, d_kps, n, d_keep, d_ang, d_desc);
     }
-    if (d_band) (void)hipFree(d_band);
     std::vector<int32_t> kp(n);
     std::vector<float> an(n);
     std::vector<uint8_t> de(size_t(n) * n_bytes);
@@ -882,8 +862,6 @@ extern "C" int sfm_brisk_describe(int32_t device, const uint8_t* img, int32_t w,
       *n_kept = m;
     }
   }
-  for (void* p : {(void*)d_img, (void*)d_ii, (void*)d_kps, (void*)d_keep, (void*)d_ang, (void*)d_desc})
-    if (p) (void)hipFree(p);
   return ok ? 0 : bfail(SFM_EIO, "allocation, kernel or copy failed");
 }
 
@@ -1056,8 +1034,7 @@ int brisk_detect_describe_impl(int32_t device, const uint8_t* img, bool img_on_d
       hipStream_t ms = nullptr;
       if ((rc = frame_install(fx->mt, n, kept, ob, kp3, und, reinterpret_cast<const int32_t*>(ob + o_keep), &ms)))
         return rc;
-      if (!W->installed && hipEventCreateWithFlags(&W->installed, hipEventDisableTiming) != hipSuccess)
-        return bfail(SFM_EIO, "hipEventCreate failed");
+      if (W->installed.create(hipEventDisableTiming) != hipSuccess) return bfail(SFM_EIO, "hipEventCreate failed");
       if (hipEventRecord(W->installed, ms) != hipSuccess || hipStreamWaitEvent(nullptr, W->installed, 0) != hipSuccess)
         return bfail(SFM_EIO, "stream ordering failed");
     }

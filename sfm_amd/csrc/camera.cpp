@@ -8,27 +8,19 @@
 #include <cstdint>
 #include <string>
 #include "camera_model.h"
-
-void sfm_internal_set_error(const std::string& msg);  // ba_solver.hip
-
-namespace {
-int cfail(const std::string& m) {
-  sfm_internal_set_error(m);
-  return SFM_EINVAL;
-}
-}  // namespace
+#include "sfm_error.h"
 
 extern "C" int sfm_camera_init(sfm_camera* cam, const double* K9, const double* d, int32_t n_d, int32_t width,
                                int32_t height) {
-  if (!cam || !K9) return cfail("NULL argument");
-  if (!sfm::lens_nd_ok(n_d)) return cfail("n_d must be 0, 4, 5 or 8");
-  if (n_d && !d) return cfail("d is NULL");
-  if (width < 2 || height < 2) return cfail("image size must be at least 2 x 2");
+  if (!cam || !K9) return fail(SFM_EINVAL, "NULL argument");
+  if (!sfm::lens_nd_ok(n_d)) return fail(SFM_EINVAL, "n_d must be 0, 4, 5 or 8");
+  if (n_d && !d) return fail(SFM_EINVAL, "d is NULL");
+  if (width < 2 || height < 2) return fail(SFM_EINVAL, "image size must be at least 2 x 2");
   for (int i = 0; i < 9; ++i)
-    if (!std::isfinite(K9[i])) return cfail("K is not finite");
+    if (!std::isfinite(K9[i])) return fail(SFM_EINVAL, "K is not finite");
   for (int i = 0; i < n_d; ++i)
-    if (!std::isfinite(d[i])) return cfail("d is not finite");
-  if (!(K9[0] > 0.0) || !(K9[4] > 0.0)) return cfail("fx and fy must be positive");
+    if (!std::isfinite(d[i])) return fail(SFM_EINVAL, "d is not finite");
+  if (!(K9[0] > 0.0) || !(K9[4] > 0.0)) return fail(SFM_EINVAL, "fx and fy must be positive");
   for (int i = 0; i < 9; ++i) cam->K9[i] = K9[i];
   for (int i = 0; i < 8; ++i) cam->d[i] = i < n_d ? d[i] : 0.0;
   cam->n_d = n_d;
@@ -54,7 +46,7 @@ extern "C" int sfm_camera_init(sfm_camera* cam, const double* K9, const double* 
     }
   const float rw = X1 - X0, rh = Y1 - Y0;
   if (!(rw > 0.0f) || !(rh > 0.0f) || !std::isfinite(rw) || !std::isfinite(rh))
-    return cfail("the lens leaves no valid rectangle (getOptimalNewCameraMatrix)");
+    return fail(SFM_EINVAL, "the lens leaves no valid rectangle (getOptimalNewCameraMatrix)");
   const double fx = double(width - 1) / double(rw), fy = double(height - 1) / double(rh);
   cam->Kopt9[0] = fx;
   cam->Kopt9[4] = fy;

@@ -27,16 +27,10 @@
 #include "frame_internal.h"
 #include "klt_internal.h"
 #include "ordered_compact.h"
-
-void sfm_internal_set_error(const std::string& msg);  // ba_solver.hip
+#include "dev_mem.h"
 
 namespace sfm {
 namespace {
-
-int ffail(int code, const std::string& m) {
-  sfm_internal_set_error(m);
-  return code;
-}
 
 // g = (c0*4899 + c1*9617 + c2*1868 + 8192) >> 14; c0 is the first channel in
 // memory (the reference hands VideoCapture's BGR frames to CV_RGB2GRAY: the
@@ -118,14 +112,14 @@ __global__ __launch_bounds__(256) void k_frame_install(int m, const int* __restr
 }
 
 int check_camera(const sfm_camera* cam) {
-  if (!cam) return ffail(SFM_EINVAL, "cam is NULL");
-  if (!lens_nd_ok(cam->n_d)) return ffail(SFM_EINVAL, "n_d must be 0, 4, 5 or 8");
-  if (cam->width < 2 || cam->height < 2) return ffail(SFM_EINVAL, "image size must be at least 2 x 2");
+  if (!cam) return fail(SFM_EINVAL, "cam is NULL");
+  if (!lens_nd_ok(cam->n_d)) return fail(SFM_EINVAL, "n_d must be 0, 4, 5 or 8");
+  if (cam->width < 2 || cam->height < 2) return fail(SFM_EINVAL, "image size must be at least 2 x 2");
   for (int i = 0; i < 9; ++i)
-    if (!std::isfinite(cam->K9[i]) || !std::isfinite(cam->Kopt9[i])) return ffail(SFM_EINVAL, "K or Kopt is not finite");
+    if (!std::isfinite(cam->K9[i]) || !std::isfinite(cam->Kopt9[i])) return fail(SFM_EINVAL, "K or Kopt is not finite");
   for (int i = 0; i < cam->n_d; ++i)
-    if (!std::isfinite(cam->d[i])) return ffail(SFM_EINVAL, "d is not finite");
-  if (!(cam->K9[0] > 0.0) || !(cam->K9[4] > 0.0)) return ffail(SFM_EINVAL, "fx and fy must be positive");
+    if (!std::isfinite(cam->d[i])) return fail(SFM_EINVAL, "d is not finite");
+  if (!(cam->K9[0] > 0.0) || !(cam->K9[4] > 0.0)) return fail(SFM_EINVAL, "fx and fy must be positive");
   return 0;
 }
 
@@ -152,7 +146,7 @@ int frame_install(sfm_matcher* mt, int n, int m, const uint8_t* d_desc, const fl
     k_frame_install<<<(8 * m + 255) / 256, 256, 0, slot.stream>>>(m, slot.scratch,
                                                                   reinterpret_cast<const uint64_t*>(d_desc), d_kp3,
                                                                   d_und, slot.desc, slot.pts, slot.ptsd);
-    if (hipGetLastError() != hipSuccess) return ffail(SFM_EIO, "frame install launch failed");
+    if (hipGetLastError() != hipSuccess) return fail(SFM_EIO, "frame install launch failed");
   }
   matcher_install_commit(mt, m);
   return 0;
@@ -167,63 +161,55 @@ extern "C" {
 int sfm_undistort_points(int32_t device, const sfm_camera* cam, int32_t n, const double* pts_dist, double* pts) {
   SFM_TRACE("sfm_undistort_points");
   if (int rc = check_camera(cam)) return rc;
-  if (n < 0 || (n > 0 && (!pts_dist || !pts))) return ffail(SFM_EINVAL, "bad point arguments");
+  if (n < 0 || (n > 0 && (!pts_dist || !pts))) return fail(SFM_EINVAL, "bad point arguments");
   if (n == 0) return 0;
-  if (hipSetDevice(device) != hipSuccess) return ffail(SFM_ENODEV, "hipSetDevice failed");
+  if (hipSetDevice(device) != hipSuccess) return fail(SFM_ENODEV, "hipSetDevice failed");
   const size_t bytes = 16 * size_t(n);
-  double* d_in = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&d_in), 2 * bytes) != hipSuccess)
-    return ffail(SFM_ENOMEM, "hipMalloc failed (undistort)");
+  DevArr<double> d_in;
+  if (d_in.reserve(2 * bytes, 2 * bytes, nullptr)) return fail(SFM_ENOMEM, "hipMalloc failed (undistort)");
   double* d_out = d_in + 2 * size_t(n);
   bool ok = hipMemcpy(d_in, pts_dist, bytes, hipMemcpyHostToDevice) == hipSuccess;
   if (ok) {
     k_undistort_points<false><<<(n + 255) / 256, 256>>>(lens_args(*cam), d_in, n, d_out);
     ok = hipGetLastError() == hipSuccess && hipMemcpy(pts, d_out, bytes, hipMemcpyDeviceToHost) == hipSuccess;
   }
-  (void)hipFree(d_in);
-  return ok ? 0 : ffail(SFM_EIO, "copy or kernel failed (undistort)");
+  return ok ? 0 : fail(SFM_EIO, "copy or kernel failed (undistort)");
 }
 
 int sfm_rgb_to_grey(int32_t device, const uint8_t* rgb, int32_t w, int32_t h, int32_t stride, uint8_t* grey) {
   SFM_TRACE("sfm_rgb_to_grey");
-  if (!rgb || !grey) return ffail(SFM_EINVAL, "NULL argument");
-  if (w < 1 || h < 1 || int64_t(stride) < 3 * int64_t(w)) return ffail(SFM_EINVAL, "bad sizes (stride >= 3 * w)");
-  if (hipSetDevice(device) != hipSuccess) return ffail(SFM_ENODEV, "hipSetDevice failed");
+  if (!rgb || !grey) return fail(SFM_EINVAL, "NULL argument");
+  if (w < 1 || h < 1 || int64_t(stride) < 3 * int64_t(w)) return fail(SFM_EINVAL, "bad sizes (stride >= 3 * w)");
+  if (hipSetDevice(device) != hipSuccess) return fail(SFM_ENODEV, "hipSetDevice failed");
   const size_t in_bytes = size_t(h - 1) * stride + 3 * size_t(w), out_bytes = size_t(w) * h;
-  uint8_t *d_rgb = nullptr, *d_grey = nullptr;
-  bool ok = hipMalloc(reinterpret_cast<void**>(&d_rgb), in_bytes) == hipSuccess &&
-            hipMalloc(reinterpret_cast<void**>(&d_grey), out_bytes) == hipSuccess;
-  if (!ok) {
-    if (d_rgb) (void)hipFree(d_rgb);
-    return ffail(SFM_ENOMEM, "hipMalloc failed (grey conversion)");
-  }
-  ok = hipMemcpy(d_rgb, rgb, in_bytes, hipMemcpyHostToDevice) == hipSuccess;
+  DevArr<uint8_t> d_rgb, d_grey;
+  if (d_rgb.reserve(in_bytes, in_bytes, nullptr) || d_grey.reserve(out_bytes, out_bytes, nullptr))
+    return fail(SFM_ENOMEM, "hipMalloc failed (grey conversion)");
+  bool ok = hipMemcpy(d_rgb, rgb, in_bytes, hipMemcpyHostToDevice) == hipSuccess;
   if (ok) {
     launch_rgb_to_grey(nullptr, d_rgb, w, h, stride, d_grey);
     ok = hipGetLastError() == hipSuccess && hipMemcpy(grey, d_grey, out_bytes, hipMemcpyDeviceToHost) == hipSuccess;
   }
-  (void)hipFree(d_rgb);
-  (void)hipFree(d_grey);
-  return ok ? 0 : ffail(SFM_EIO, "copy or kernel failed (grey conversion)");
+  return ok ? 0 : fail(SFM_EIO, "copy or kernel failed (grey conversion)");
 }
 
 int sfm_frame_detect(sfm_matcher* mt, sfm_klt_handle* klt, const uint8_t* img, int32_t channels, int32_t stride,
                      const sfm_camera* cam, int32_t threshold, int32_t octaves, int32_t capacity, float* kps,
                      int32_t* octave, uint8_t* desc, double* pts, int32_t* n_out) {
   SFM_TRACE("sfm_frame_detect");
-  if (!n_out) return ffail(SFM_EINVAL, "n_out is NULL");
+  if (!n_out) return fail(SFM_EINVAL, "n_out is NULL");
   *n_out = 0;
   if (int rc = check_camera(cam)) return rc;
-  if (!img) return ffail(SFM_EINVAL, "img is NULL");
-  if (channels != 1 && channels != 3) return ffail(SFM_EINVAL, "channels must be 1 or 3");
+  if (!img) return fail(SFM_EINVAL, "img is NULL");
+  if (channels != 1 && channels != 3) return fail(SFM_EINVAL, "channels must be 1 or 3");
   const int w = cam->width, h = cam->height;
-  if (int64_t(stride) < int64_t(channels) * w) return ffail(SFM_EINVAL, "stride < channels * width");
-  if (capacity < 0 || (capacity && (!kps || !octave || !pts))) return ffail(SFM_EINVAL, "NULL argument");
+  if (int64_t(stride) < int64_t(channels) * w) return fail(SFM_EINVAL, "stride < channels * width");
+  if (capacity < 0 || (capacity && (!kps || !octave || !pts))) return fail(SFM_EINVAL, "NULL argument");
   int device = 0;
   KltFrame kf{};
   if (mt) {
-    if (matcher_desc_bytes(mt) != 64) return ffail(SFM_EINVAL, "the matcher's descriptors are not 64 bytes");
-    if (!desc) return ffail(SFM_EINVAL, "the hand-off to a matcher needs descriptors");
+    if (matcher_desc_bytes(mt) != 64) return fail(SFM_EINVAL, "the matcher's descriptors are not 64 bytes");
+    if (!desc) return fail(SFM_EINVAL, "the hand-off to a matcher needs descriptors");
     device = matcher_device(mt);
   }
   FrameExtras fx;
@@ -237,8 +223,8 @@ int sfm_frame_detect(sfm_matcher* mt, sfm_klt_handle* klt, const uint8_t* img, i
     // (pyramid and all); BRISK then runs on that resident frame
     const int kw = sfm_internal_klt_size(klt, &kf);
     if (kw != 0) return kw;
-    if (kf.w != w || kf.h != h) return ffail(SFM_EINVAL, "the KLT handle's frame size is not the camera's");
-    if (mt && kf.device != device) return ffail(SFM_EINVAL, "matcher and KLT handle are on different devices");
+    if (kf.w != w || kf.h != h) return fail(SFM_EINVAL, "the KLT handle's frame size is not the camera's");
+    if (mt && kf.device != device) return fail(SFM_EINVAL, "matcher and KLT handle are on different devices");
     device = kf.device;
     if (int rc = klt_push_frame_any(klt, img, stride, channels)) return rc;
     if (int rc = sfm_internal_klt_frame(klt, &kf)) return rc;
@@ -247,7 +233,7 @@ int sfm_frame_detect(sfm_matcher* mt, sfm_klt_handle* klt, const uint8_t* img, i
     return brisk_detect_describe_impl(device, kf.img, true, w, h, threshold, octaves, capacity, kps, octave, desc,
                                       n_out, &fx);
   }
-  if (!mt && hipGetDevice(&device) != hipSuccess) return ffail(SFM_ENODEV, "no HIP device");
+  if (!mt && hipGetDevice(&device) != hipSuccess) return fail(SFM_ENODEV, "no HIP device");
   return brisk_detect_describe_impl(device, img, false, w, h, threshold, octaves, capacity, kps, octave, desc, n_out,
                                     &fx);
 }

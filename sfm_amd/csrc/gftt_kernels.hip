@@ -42,8 +42,7 @@
 #include <vector>
 #include "../../include/sfm_amd.h"
 #include "klt_internal.h"
-
-void sfm_internal_set_error(const std::string& msg);  // ba_solver.hip
+#include "dev_mem.h"
 
 namespace {
 
@@ -54,11 +53,6 @@ constexpr int kMaxCorners = 4096;      // LDS list of accepted corners
 constexpr int kMaxCells = 4096;        // k_select cell grids (LDS)
 constexpr int kMaxWin = 7;             // cornerSubPix half window
 constexpr int kMaxSub = (2 * kMaxWin + 3) * (2 * kMaxWin + 3);
-
-int gfail(int code, const std::string& m) {
-  sfm_internal_set_error(m);
-  return code;
-}
 
 __device__ __forceinline__ int r101(int i, int n) {
   if (n == 1) return 0;
@@ -373,50 +367,41 @@ __global__ __launch_bounds__(64) void k_subpix(const uint8_t* __restrict__ img, 
 // Per-handle device state (lives in the KLT handle, freed with it).
 struct GfttState {
   int w = 0, h = 0;
-  float* eig = nullptr;
-  unsigned long long* keys = nullptr;
-  unsigned long long* keys_sorted = nullptr;
-  int* ints = nullptr;              // [0] max_ord, [1] candidate count, [2] corner count
-  float2* corners = nullptr;        // [kMaxCorners]
-  float* mask = nullptr;            // [(2 kMaxWin + 1)^2]
-  void* sort_tmp = nullptr;
+  sfm::DevArr<float> eig;
+  sfm::DevArr<unsigned long long> keys, keys_sorted;
+  sfm::DevBuf ints_mem;
+  int* ints = nullptr;              // [0] max_ord, [1] candidate count, [2] corner count (in ints_mem)
+  sfm::DevArr<float2> corners;      // [kMaxCorners]
+  sfm::DevArr<float> mask;          // [(2 kMaxWin + 1)^2]
+  sfm::DevArr<char> sort_tmp;
   size_t sort_tmp_bytes = 0;
-  hipEvent_t ev[2] = {};
+  sfm::Event ev[2];
 };
-
-void free_state(GfttState* g) {
-  if (!g) return;
-  void* bufs[] = {g->eig, g->keys, g->keys_sorted, g->ints, g->corners, g->mask, g->sort_tmp};
-  for (void* b : bufs)
-    if (b) hipFree(b);
-  for (auto& e : g->ev)
-    if (e) hipEventDestroy(e);
-  delete g;
-}
 
 int ensure_state(void** slot, int w, int h) {
   auto* g = static_cast<GfttState*>(*slot);
   if (g && g->w == w && g->h == h) return 0;
-  free_state(g);
+  delete g;
   *slot = nullptr;
   g = new GfttState();
   g->w = w;
   g->h = h;
   const size_t npx = size_t(w) * h;
-  bool ok = hipMalloc(&g->eig, npx * sizeof(float)) == hipSuccess &&
-            hipMalloc(&g->keys, npx * sizeof(unsigned long long)) == hipSuccess &&
-            hipMalloc(&g->keys_sorted, npx * sizeof(unsigned long long)) == hipSuccess &&
-            hipMalloc(&g->ints, 4 * sizeof(int)) == hipSuccess &&
-            hipMalloc(&g->corners, kMaxCorners * sizeof(float2)) == hipSuccess &&
-            hipMalloc(&g->mask, (2 * kMaxWin + 1) * (2 * kMaxWin + 1) * sizeof(float)) == hipSuccess;
+  auto fixed = [](sfm::DevBuf& b, size_t bytes) { return b.reserve(bytes, bytes, nullptr) == 0; };
+  bool ok = fixed(g->eig, npx * sizeof(float)) && fixed(g->keys, npx * sizeof(unsigned long long)) &&
+            fixed(g->keys_sorted, npx * sizeof(unsigned long long)) && fixed(g->ints_mem, 4 * sizeof(int)) &&
+            fixed(g->corners, kMaxCorners * sizeof(float2)) &&
+            fixed(g->mask, (2 * kMaxWin + 1) * (2 * kMaxWin + 1) * sizeof(float));
+  g->ints = g->ints_mem.as<int>();
   if (ok) {
-    hipcub::DeviceRadixSort::SortKeysDescending(nullptr, g->sort_tmp_bytes, g->keys, g->keys_sorted, int(npx));
-    ok = hipMalloc(&g->sort_tmp, std::max<size_t>(g->sort_tmp_bytes, 16)) == hipSuccess &&
-         hipEventCreate(&g->ev[0]) == hipSuccess && hipEventCreate(&g->ev[1]) == hipSuccess;
+    hipcub::DeviceRadixSort::SortKeysDescending(nullptr, g->sort_tmp_bytes, g->keys.as<unsigned long long>(),
+                                                g->keys_sorted.as<unsigned long long>(), int(npx));
+    ok = fixed(g->sort_tmp, std::max<size_t>(g->sort_tmp_bytes, 16)) &&
+         g->ev[0].create(hipEventDefault) == hipSuccess && g->ev[1].create(hipEventDefault) == hipSuccess;
   }
   if (!ok) {
-    free_state(g);
-    return gfail(SFM_ENOMEM, "hipMalloc failed (gftt state)");
+    delete g;
+    return fail(SFM_ENOMEM, "hipMalloc failed (gftt state)");
   }
   *slot = g;
   return 0;
@@ -440,7 +425,7 @@ std::vector<float> subpix_mask(int win) {
 
 }  // namespace
 
-void sfm_internal_gftt_free(void* state) { free_state(static_cast<GfttState*>(state)); }
+void sfm_internal_gftt_free(void* state) { delete static_cast<GfttState*>(state); }
 
 extern "C" {
 
@@ -456,19 +441,19 @@ void sfm_gftt_default_params(sfm_gftt_params* p) {
 
 int sfm_klt_detect_features(sfm_klt_handle* kh, const sfm_gftt_params* params, float* pts, int32_t capacity,
                             int32_t* n_pts) {
-  if (!kh || !pts || !n_pts) return gfail(SFM_EINVAL, "NULL argument");
+  if (!kh || !pts || !n_pts) return fail(SFM_EINVAL, "NULL argument");
   sfm_gftt_params prm;
   if (params) prm = *params;
   else sfm_gftt_default_params(&prm);
   if (prm.max_corners < 1 || prm.max_corners > kMaxCorners)
-    return gfail(SFM_ENOTSUP, "max_corners must be in [1, 4096]");
-  if (capacity < prm.max_corners) return gfail(SFM_EINVAL, "capacity < max_corners");
-  if (prm.subpix_win < 0 || prm.subpix_win > kMaxWin) return gfail(SFM_ENOTSUP, "subpix_win must be in [0, 7]");
-  if (!(prm.quality_level > 0.0) || !(prm.min_distance >= 0.0)) return gfail(SFM_EINVAL, "bad quality / distance");
+    return fail(SFM_ENOTSUP, "max_corners must be in [1, 4096]");
+  if (capacity < prm.max_corners) return fail(SFM_EINVAL, "capacity < max_corners");
+  if (prm.subpix_win < 0 || prm.subpix_win > kMaxWin) return fail(SFM_ENOTSUP, "subpix_win must be in [0, 7]");
+  if (!(prm.quality_level > 0.0) || !(prm.min_distance >= 0.0)) return fail(SFM_EINVAL, "bad quality / distance");
   KltFrame f{};
   int rc = sfm_internal_klt_frame(kh, &f);
   if (rc) return rc;
-  if (f.w < 3 || f.h < 3) return gfail(SFM_EINVAL, "frame smaller than 3x3");
+  if (f.w < 3 || f.h < 3) return fail(SFM_EINVAL, "frame smaller than 3x3");
   if ((rc = ensure_state(f.gftt_slot, f.w, f.h))) return rc;
   auto* g = static_cast<GfttState*>(*f.gftt_slot);
   hipStream_t s = f.stream;
@@ -484,12 +469,13 @@ int sfm_klt_detect_features(sfm_klt_handle* kh, const sfm_gftt_params* params, f
   int n_cand = 0;
   if (hipMemcpyAsync(&n_cand, g->ints + 1, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
-    return gfail(SFM_EIO, "corner response failed");
+    return fail(SFM_EIO, "corner response failed");
   if (n_cand > 0) {
     size_t tmp = g->sort_tmp_bytes;
-    if (hipcub::DeviceRadixSort::SortKeysDescending(g->sort_tmp, tmp, g->keys, g->keys_sorted, n_cand, 0, 64, s) !=
+    if (hipcub::DeviceRadixSort::SortKeysDescending(g->sort_tmp, tmp, g->keys.as<unsigned long long>(),
+                                                        g->keys_sorted.as<unsigned long long>(), n_cand, 0, 64, s) !=
         hipSuccess)
-      return gfail(SFM_EIO, "candidate sort failed");
+      return fail(SFM_EIO, "candidate sort failed");
     // cells at least min_distance wide and few enough for LDS
     int cs = std::max(1, int(std::ceil(prm.min_distance)));
     while (size_t((f.w + cs - 1) / cs) * size_t((f.h + cs - 1) / cs) > size_t(kMaxCells)) ++cs;
@@ -505,18 +491,18 @@ int sfm_klt_detect_features(sfm_klt_handle* kh, const sfm_gftt_params* params, f
   }
   hipEventRecord(g->ev[1], s);
   int n = 0;
-  if (hipGetLastError() != hipSuccess) return gfail(SFM_EIO, "corner detector launch failed");
+  if (hipGetLastError() != hipSuccess) return fail(SFM_EIO, "corner detector launch failed");
   if (hipMemcpyAsync(&n, g->ints + 2, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
-    return gfail(SFM_EIO, "corner detector failed");
+    return fail(SFM_EIO, "corner detector failed");
   if (n > 0 && hipMemcpy(pts, g->corners, size_t(n) * sizeof(float2), hipMemcpyDeviceToHost) != hipSuccess)
-    return gfail(SFM_EIO, "corner download failed");
+    return fail(SFM_EIO, "corner download failed");
   *n_pts = n;
   return 0;
 }
 
 int sfm_klt_detect_time(sfm_klt_handle* kh, double* ms) {
-  if (!kh || !ms) return gfail(SFM_EINVAL, "NULL argument");
+  if (!kh || !ms) return fail(SFM_EINVAL, "NULL argument");
   KltFrame f{};
   int rc = sfm_internal_klt_frame(kh, &f);
   if (rc) return rc;

@@ -12,8 +12,7 @@
 #include <utility>
 #include <vector>
 #include "guidance_internal.h"
-
-void sfm_internal_set_error(const std::string& msg);  // ba_solver.hip
+#include "sfm_error.h"
 
 namespace sfm {
 
@@ -182,10 +181,8 @@ void sfm_guidance_default_options(sfm_guidance_options* o) {
 }
 
 int sfm_min_area_rect(int32_t n, const int32_t* pts_xy, float* box5) {
-  if (n < 0 || !box5 || (n && !pts_xy)) {
-    sfm_internal_set_error("sfm_min_area_rect: NULL argument or negative size");
-    return SFM_EINVAL;
-  }
+  if (n < 0 || !box5 || (n && !pts_xy))
+    return fail(SFM_EINVAL, "sfm_min_area_rect: NULL argument or negative size");
   std::vector<sfm::GPoint> p(static_cast<size_t>(n));
   for (int32_t i = 0; i < n; ++i) p[size_t(i)] = {pts_xy[2 * size_t(i)], pts_xy[2 * size_t(i) + 1]};
   sfm::guidance_min_area_rect(p, box5);

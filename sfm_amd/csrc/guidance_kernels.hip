@@ -34,16 +34,12 @@
 #include "guidance_internal.h"
 #include "map_internal.h"
 #include "sfm_trace.h"
-
-void sfm_internal_set_error(const std::string& msg);  // ba_solver.hip
+#include "dev_mem.h"
 
 namespace sfm {
 namespace {
 
-int gfail(int code, const std::string& m) {
-  sfm_internal_set_error("sfm_guidance: " + m);
-  return code;
-}
+int gfail(int code, const std::string& m) { return fail(code, "sfm_guidance: " + m); }
 
 constexpr int kProjectBlock = 256;
 constexpr int kHullBlock = 256;
@@ -375,33 +371,32 @@ bool finite_n(const double* v, int n) {
 
 using namespace sfm;
 
+// The stream first: members are destroyed in reverse order, so it goes last.
 struct sfm_guidance {
+  Stream s;
   int device = 0, W = 0, H = 0, ws = 0, hs = 0, nb = 0;
   sfm_guidance_options opt{};
-  hipStream_t s = nullptr;
-  hipEvent_t ev_map = nullptr, ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  uint8_t* d_img = nullptr;      // [H][3 W]
-  uint8_t* h_img = nullptr;      // pinned staging copy of the frame
-  uint8_t* d_ctl = nullptr;      // GuidHead | acc [hs][3] | ext [hs+2][2] | cnt [nb]   (zeroed every call)
-  uint8_t* h_ctl = nullptr;      // pinned: GuidHead | acc
-  int32_t* d_rowiv = nullptr;    // [hs][2] mask interval of each row
-  uint16_t* d_bins = nullptr;    // [hs][ws]
-  uint8_t* d_mask = nullptr;     // [hs][ws]
-  float* d_bproj = nullptr;      // [hs][ws]
-  float* d_state[2] = {nullptr, nullptr};  // the histogram state, double-buffered
+  Event ev_map, ev[4];
+  DevArr<uint8_t> d_img;         // [H][3 W]
+  PinArr<uint8_t> h_img;         // pinned staging copy of the frame
+  DevArr<uint8_t> d_ctl;         // GuidHead | acc [hs][3] | ext [hs+2][2] | cnt [nb]   (zeroed every call)
+  PinArr<uint8_t> h_ctl;         // pinned: GuidHead | acc
+  DevArr<int32_t> d_rowiv;       // [hs][2] mask interval of each row
+  DevArr<uint16_t> d_bins;       // [hs][ws]
+  DevArr<uint8_t> d_mask;        // [hs][ws]
+  DevArr<float> d_bproj;         // [hs][ws]
+  DevArr<float> d_state[2];      // the histogram state, double-buffered
   int cur = 0;                   // d_state[cur] is _hist
   bool have_state = false;
-  double* d_pts = nullptr;       // sfm_guidance_update_points' upload
-  int64_t pts_cap = 0;
-  double* d_partial = nullptr;   // [blocks][3]
-  int64_t partial_cap = 0;
+  DevArr<double> d_pts;          // sfm_guidance_update_points' upload
+  DevArr<double> d_partial;      // [blocks][3]
   std::vector<int32_t> extents;  // [hs][2] of the last update
   bool updated = false;
   float ms[3] = {0.f, 0.f, 0.f};
 
   size_t head_bytes() const { return sizeof(GuidHead) + sizeof(int32_t) * 3 * size_t(hs); }
   size_t ctl_bytes() const { return head_bytes() + sizeof(int32_t) * (2 * size_t(hs + 2) + size_t(nb)); }
-  GuidHead* head() const { return reinterpret_cast<GuidHead*>(d_ctl); }
+  GuidHead* head() const { return d_ctl.as<GuidHead>(); }
   int32_t* acc() const { return reinterpret_cast<int32_t*>(d_ctl + sizeof(GuidHead)); }
   int32_t* ext() const { return acc() + 3 * size_t(hs); }
   int32_t* cnt() const { return ext() + 2 * size_t(hs + 2); }
@@ -409,19 +404,12 @@ struct sfm_guidance {
 
 namespace {
 
-template <class T>
-int reserve(T** p, int64_t* cap, int64_t need, hipStream_t s) {
-  if (need <= *cap) return 0;
-  const int64_t want = std::max<int64_t>({need, 2 * *cap, 1024});
-  if (*p) {
-    (void)hipStreamSynchronize(s);  // (growth only)
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-  }
-  if (hipMalloc(reinterpret_cast<void**>(p), size_t(want) * sizeof(T)) != hipSuccess)
+// Room for `need` doubles (contents dropped when it grows).
+int reserve(DevArr<double>& b, int64_t need, hipStream_t s) {
+  const int64_t cap = int64_t(b.bytes() / sizeof(double));
+  const int64_t want = std::max<int64_t>({need, 2 * cap, 1024});
+  if (b.reserve(size_t(need) * sizeof(double), size_t(want) * sizeof(double), s))
     return gfail(SFM_ENOMEM, "hipMalloc failed (points)");
-  *cap = want;
   return 0;
 }
 
@@ -438,7 +426,7 @@ int run(sfm_guidance* h, const double* X, const uint8_t* live, int n_slots, int 
         int32_t stride, const double* R9, const double* t3, const double* K9, sfm_guidance_result* out) {
   const int W = h->W, H = h->H, ws = h->ws, hs = h->hs;
   const int n_blocks = (n_slots + kProjectBlock - 1) / kProjectBlock;
-  if (int rc = reserve(&h->d_partial, &h->partial_cap, 3 * int64_t(std::max(n_blocks, 1)), h->s)) return rc;
+  if (int rc = reserve(h->d_partial, 3 * int64_t(std::max(n_blocks, 1)), h->s)) return rc;
   for (int y = 0; y < H; ++y) std::memcpy(h->h_img + size_t(y) * 3 * W, img + size_t(y) * stride, 3 * size_t(W));
   bool ok = hipEventRecord(h->ev[0], h->s) == hipSuccess;
   ok = ok && hipMemcpyAsync(h->d_img, h->h_img, size_t(H) * 3 * W, hipMemcpyHostToDevice, h->s) == hipSuccess;
@@ -543,19 +531,16 @@ int sfm_guidance_create(int32_t device, int32_t width, int32_t height, const sfm
   h->opt = o;
   h->extents.assign(2 * size_t(h->hs), 0);
   const size_t px = size_t(h->ws) * h->hs;
-  bool ok = hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipEventCreateWithFlags(&h->ev_map, hipEventDisableTiming) == hipSuccess;
-  for (auto& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&h->d_img), size_t(height) * 3 * width) == hipSuccess;
-  ok = ok && hipHostMalloc(reinterpret_cast<void**>(&h->h_img), size_t(height) * 3 * width) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&h->d_ctl), h->ctl_bytes()) == hipSuccess;
-  ok = ok && hipHostMalloc(reinterpret_cast<void**>(&h->h_ctl), h->head_bytes()) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&h->d_rowiv), sizeof(int32_t) * 2 * size_t(h->hs)) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&h->d_bins), sizeof(uint16_t) * px) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&h->d_mask), px) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&h->d_bproj), sizeof(float) * px) == hipSuccess;
+  auto fixed = [](auto& buf, size_t bytes) { return buf.reserve(bytes, bytes, nullptr) == 0; };
+  bool ok = h->s.create(hipStreamNonBlocking) == hipSuccess;
+  ok = ok && h->ev_map.create(hipEventDisableTiming) == hipSuccess;
+  for (auto& e : h->ev) ok = ok && e.create(hipEventDefault) == hipSuccess;
+  ok = ok && fixed(h->d_img, size_t(height) * 3 * width) && fixed(h->h_img, size_t(height) * 3 * width);
+  ok = ok && fixed(h->d_ctl, h->ctl_bytes()) && fixed(h->h_ctl, h->head_bytes());
+  ok = ok && fixed(h->d_rowiv, sizeof(int32_t) * 2 * size_t(h->hs)) && fixed(h->d_bins, sizeof(uint16_t) * px);
+  ok = ok && fixed(h->d_mask, px) && fixed(h->d_bproj, sizeof(float) * px);
   for (auto& st : h->d_state) {
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&st), sizeof(float) * size_t(h->nb)) == hipSuccess;
+    ok = ok && fixed(st, sizeof(float) * size_t(h->nb));
     ok = ok && hipMemset(st, 0, sizeof(float) * size_t(h->nb)) == hipSuccess;
   }
   if (!ok) {
@@ -570,16 +555,6 @@ int sfm_guidance_destroy(sfm_guidance* h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
   if (h->s) (void)hipStreamSynchronize(h->s);
-  for (void* p : {(void*)h->d_img, (void*)h->d_ctl, (void*)h->d_rowiv, (void*)h->d_bins, (void*)h->d_mask,
-                  (void*)h->d_bproj, (void*)h->d_state[0], (void*)h->d_state[1], (void*)h->d_pts,
-                  (void*)h->d_partial})
-    if (p) (void)hipFree(p);
-  if (h->h_img) (void)hipHostFree(h->h_img);
-  if (h->h_ctl) (void)hipHostFree(h->h_ctl);
-  if (h->ev_map) (void)hipEventDestroy(h->ev_map);
-  for (auto e : h->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (h->s) (void)hipStreamDestroy(h->s);
   delete h;
   return 0;
 }
@@ -603,7 +578,7 @@ int sfm_guidance_update_points(sfm_guidance* h, int32_t n, const double* pts3d, 
   if (int rc = check_args(h, img, stride, R9, t3, K9, out)) return rc;
   if (n < 0 || (n && !pts3d)) return gfail(SFM_EINVAL, n < 0 ? "negative size" : "NULL argument");
   if (hipSetDevice(h->device) != hipSuccess) return gfail(SFM_ENODEV, "hipSetDevice failed");
-  if (int rc = reserve(&h->d_pts, &h->pts_cap, 3 * int64_t(n), h->s)) return rc;
+  if (int rc = reserve(h->d_pts, 3 * int64_t(n), h->s)) return rc;
   if (n && hipMemcpyAsync(h->d_pts, pts3d, sizeof(double) * 3 * size_t(n), hipMemcpyHostToDevice, h->s) != hipSuccess)
     return gfail(SFM_EIO, "upload failed (points)");
   return run(h, h->d_pts, nullptr, n, n, img, stride, R9, t3, K9, out);

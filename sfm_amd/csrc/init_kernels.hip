@@ -35,14 +35,13 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <string>
 #include "sfm_trace.h"
 #include "../../include/sfm_amd.h"
 #include "cv_linalg.h"
 #include "tri_point.h"
+#include "dev_mem.h"
 
-void sfm_internal_set_error(const std::string& msg);
 
 namespace sfm {
 namespace {
@@ -828,32 +827,45 @@ __global__ __launch_bounds__(kBlock) void k_tv_final(TvArgs a, const float* __re
   }
 }
 
+constexpr size_t kHeadBytes = sizeof(double) * hHead;
+constexpr size_t out_bytes(size_t m) { return kHeadBytes + sizeof(double) * 3 * m + 2 * m; }
+
+// The calling thread's context on one device (thread_ctx).  The stream first:
+// members are destroyed in reverse order, so it goes last.
 struct TvCtx {
-  hipStream_t stream = nullptr;
-  size_t cap = 0;
-  float* pts = nullptr;     // p0 [n][2] | p1 [n][2]
-  uint8_t* out = nullptr;   // head | X [n][3] | f_mask [n] | keep [n]
-  uint8_t* pin = nullptr;   // pinned staging: the points up, the block down
-  int* sub = nullptr;
+  Stream stream;
+  size_t cap = 0;         // points the three buffers below have room for
+  DevArr<float> pts;      // p0 [n][2] | p1 [n][2]
+  DevArr<uint8_t> out;    // head | X [n][3] | f_mask [n] | keep [n]
+  PinArr<uint8_t> pin;    // pinned staging: the points up, the block down
+  DevArr<int> sub;
   int sub_n = -1, sub_iters = -1;
-  double* models = nullptr;
-  int* nm = nullptr;
-  int* cnt = nullptr;
-  double* cand = nullptr;
-  int* votes = nullptr;
-  ~TvCtx() {
-    if (stream) (void)hipStreamSynchronize(stream);
-    (void)hipFree(pts); (void)hipFree(out); (void)hipFree(sub); (void)hipFree(models); (void)hipFree(nm);
-    (void)hipFree(cnt); (void)hipFree(cand); (void)hipFree(votes);
-    if (pin) (void)hipHostFree(pin);
-    if (stream) (void)hipStreamDestroy(stream);
+  DevArr<double> models;
+  DevArr<int> nm, cnt;
+  DevArr<double> cand;
+  DevArr<int> votes;
+  int init(int /*device*/) {
+    if (stream.create(hipStreamNonBlocking) != hipSuccess) return fail(SFM_EIO, "hipStreamCreate failed");
+    auto fixed = [](DevBuf& b, size_t bytes) { return b.reserve(bytes, bytes, nullptr); };
+    if (fixed(sub, sizeof(int) * kSub * kTvMaxIters) || fixed(models, sizeof(double) * 27 * kTvMaxIters) ||
+        fixed(nm, sizeof(int) * kTvMaxIters) || fixed(cnt, sizeof(int) * 3 * kTvMaxIters) ||
+        fixed(cand, sizeof(double) * 12 * kMaxCand) || fixed(votes, sizeof(int) * 2 * kMaxCand))
+      return fail(SFM_ENOMEM, "hipMalloc failed");
+    return 0;
+  }
+  // room for n points; the three buffers grow together
+  int reserve(size_t n) {
+    if (n <= cap) return 0;
+    cap = 0;
+    const size_t want = std::max<size_t>(n, 1024);
+    if (pts.reserve(sizeof(float) * 4 * n, sizeof(float) * 4 * want, stream) ||
+        out.reserve(out_bytes(n), out_bytes(want), stream) ||
+        pin.reserve(sizeof(float) * 4 * n + out_bytes(n), sizeof(float) * 4 * want + out_bytes(want), stream))
+      return fail(SFM_ENOMEM, "hipMalloc failed");
+    cap = want;
+    return 0;
   }
 };
-
-int tfail(int code, const char* msg) {
-  sfm_internal_set_error(msg);
-  return code;
-}
 
 }  // namespace
 }  // namespace sfm
@@ -882,24 +894,24 @@ extern "C" int sfm_two_view_init(int32_t device, int32_t n, const float* pts0, c
                                  double* F9, uint8_t* f_mask, double* scores, double* avg_err, double* R9, double* t3,
                                  uint8_t* keep, double* X, int32_t* n_kept) {
   SFM_TRACE("sfm_two_view_init");
-  if (!model) return tfail(SFM_EINVAL, "NULL model");
+  if (!model) return fail(SFM_EINVAL, "NULL model");
   *model = 0;
-  if (n < 0) return tfail(SFM_EINVAL, "negative n");
-  if (!K0 || !K1 || (n > 0 && (!pts0 || !pts1))) return tfail(SFM_EINVAL, "NULL argument");
+  if (n < 0) return fail(SFM_EINVAL, "negative n");
+  if (!K0 || !K1 || (n > 0 && (!pts0 || !pts1))) return fail(SFM_EINVAL, "NULL argument");
   TvArgs a;
   if (opts) a.o = *opts;
   else sfm_two_view_default_options(&a.o);
   const sfm_two_view_options& o = a.o;
-  if (o.f_max_iters < 0 || o.f_max_iters > kTvMaxIters) return tfail(SFM_EINVAL, "f_max_iters out of range");
-  if (!(o.f_confidence > 0.0 && o.f_confidence < 1.0)) return tfail(SFM_EINVAL, "f_confidence must lie in (0, 1)");
+  if (o.f_max_iters < 0 || o.f_max_iters > kTvMaxIters) return fail(SFM_EINVAL, "f_max_iters out of range");
+  if (!(o.f_confidence > 0.0 && o.f_confidence < 1.0)) return fail(SFM_EINVAL, "f_confidence must lie in (0, 1)");
   const double ov[] = {o.f_ransac_threshold, o.h_score_th, o.h_score_gamma, o.f_score_th, o.f_score_gamma, o.h_ratio,
                        o.max_repr_err, o.min_good_fraction, o.ambiguity_ratio, o.min_parallax_deg};
   for (double v : ov)
-    if (!std::isfinite(v)) return tfail(SFM_EINVAL, "non-finite option");
+    if (!std::isfinite(v)) return fail(SFM_EINVAL, "non-finite option");
   for (int i = 0; i < 9; ++i)
-    if (!std::isfinite(K0[i]) || !std::isfinite(K1[i])) return tfail(SFM_EINVAL, "non-finite intrinsics");
+    if (!std::isfinite(K0[i]) || !std::isfinite(K1[i])) return fail(SFM_EINVAL, "non-finite intrinsics");
   for (size_t i = 0; i < 2 * size_t(n); ++i)
-    if (!std::isfinite(pts0[i]) || !std::isfinite(pts1[i])) return tfail(SFM_EINVAL, "non-finite point");
+    if (!std::isfinite(pts0[i]) || !std::isfinite(pts1[i])) return fail(SFM_EINVAL, "non-finite point");
   // the outputs of "no initialisation"
   if (H9) std::memset(H9, 0, sizeof(double) * 9);
   if (F9) std::memset(F9, 0, sizeof(double) * 9);
@@ -913,46 +925,12 @@ extern "C" int sfm_two_view_init(int32_t device, int32_t n, const float* pts0, c
   if (X && n > 0) std::memset(X, 0, sizeof(double) * 3 * size_t(n));
   if (n < kMinPoints) return 0;  // OpenCV's LMedS range: not restated
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return tfail(SFM_ENODEV, "no device");
-  if (hipSetDevice(device) != hipSuccess) return tfail(SFM_ENODEV, "hipSetDevice failed");
-  struct Cache {
-    std::map<int, TvCtx*> m;
-    ~Cache() {
-      for (auto& kv : m) delete kv.second;
-    }
-  };
-  static thread_local Cache cache;
-  TvCtx*& c = cache.m[device];
-  if (!c) {
-    c = new TvCtx();
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-      delete c;
-      c = nullptr;
-      return tfail(SFM_EIO, "hipStreamCreate failed");
-    }
-    if (hipMalloc(&c->sub, sizeof(int) * kSub * kTvMaxIters) != hipSuccess ||
-        hipMalloc(&c->models, sizeof(double) * 27 * kTvMaxIters) != hipSuccess ||
-        hipMalloc(&c->nm, sizeof(int) * kTvMaxIters) != hipSuccess ||
-        hipMalloc(&c->cnt, sizeof(int) * 3 * kTvMaxIters) != hipSuccess ||
-        hipMalloc(&c->cand, sizeof(double) * 12 * kMaxCand) != hipSuccess ||
-        hipMalloc(&c->votes, sizeof(int) * 2 * kMaxCand) != hipSuccess) {
-      delete c;
-      c = nullptr;
-      return tfail(SFM_ENOMEM, "hipMalloc failed");
-    }
-  }
-  constexpr size_t kHeadBytes = sizeof(double) * hHead;
-  auto out_bytes = [](size_t m) { return kHeadBytes + sizeof(double) * 3 * m + 2 * m; };
-  if (size_t(n) > c->cap) {
-    (void)hipFree(c->pts); (void)hipFree(c->out);
-    if (c->pin) (void)hipHostFree(c->pin);
-    c->pts = nullptr; c->out = nullptr; c->pin = nullptr; c->cap = 0;
-    const size_t cap = std::max<size_t>(size_t(n), 1024);
-    if (hipMalloc(&c->pts, sizeof(float) * 4 * cap) != hipSuccess || hipMalloc(&c->out, out_bytes(cap)) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&c->pin), sizeof(float) * 4 * cap + out_bytes(cap)) != hipSuccess)
-      return tfail(SFM_ENOMEM, "hipMalloc failed");
-    c->cap = cap;
-  }
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(SFM_ENODEV, "no device");
+  if (hipSetDevice(device) != hipSuccess) return fail(SFM_ENODEV, "hipSetDevice failed");
+  int rc = 0;
+  TvCtx* c = thread_ctx<TvCtx>(device, &rc);
+  if (!c) return rc;
+  if ((rc = c->reserve(size_t(n)))) return rc;
   std::memcpy(a.K0, K0, sizeof(a.K0));
   std::memcpy(a.K1, K1, sizeof(a.K1));
   a.n = n;
@@ -961,15 +939,15 @@ extern "C" int sfm_two_view_init(int32_t device, int32_t n, const float* pts0, c
   a.cos_par = std::cos(o.min_parallax_deg * (M_PI / 180.0));
   hipStream_t s = c->stream;
   // ONE upload through the pinned stage (the previous call drained the stream)
-  float* pin_pts = reinterpret_cast<float*>(c->pin);
+  float* pin_pts = c->pin.as<float>();
   uint8_t* pin_out = c->pin + sizeof(float) * 4 * c->cap;
   std::memcpy(pin_pts, pts0, sizeof(float) * 2 * size_t(n));
   std::memcpy(pin_pts + 2 * size_t(n), pts1, sizeof(float) * 2 * size_t(n));
   if (hipMemcpyAsync(c->pts, pin_pts, sizeof(float) * 4 * size_t(n), hipMemcpyHostToDevice, s) != hipSuccess)
-    return tfail(SFM_EIO, "upload failed");
+    return fail(SFM_EIO, "upload failed");
   const float* d_p0 = c->pts;
   const float* d_p1 = c->pts + 2 * size_t(n);
-  double* d_head = reinterpret_cast<double*>(c->out);
+  double* d_head = c->out.as<double>();
   double* d_X = d_head + hHead;
   uint8_t* d_mask = reinterpret_cast<uint8_t*>(d_X + 3 * size_t(n));
   uint8_t* d_keep = d_mask + n;
@@ -989,7 +967,7 @@ extern "C" int sfm_two_view_init(int32_t device, int32_t n, const float* pts0, c
   if (hipGetLastError() != hipSuccess || hipMemcpyAsync(pin_out, c->out, down, hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess) {
     c->sub_n = -1;
-    return tfail(SFM_EIO, "two-view kernels failed");
+    return fail(SFM_EIO, "two-view kernels failed");
   }
   const double* head = reinterpret_cast<const double*>(pin_out);
   const uint8_t* h_mask = pin_out + kHeadBytes + sizeof(double) * 3 * size_t(n);

@@ -32,8 +32,7 @@
 #include "../../include/sfm_amd.h"
 #include "ordered_compact.h"
 #include "klt_internal.h"
-
-void sfm_internal_set_error(const std::string& msg);  // ba_solver.hip
+#include "dev_mem.h"
 
 namespace {
 
@@ -44,11 +43,6 @@ struct Pyr {
   const short2* dxy[kMaxLv];
   int w[kMaxLv], h[kMaxLv];
 };
-
-int kfail(int code, const std::string& m) {
-  sfm_internal_set_error(m);
-  return code;
-}
 
 // BORDER_REFLECT_101 (cv::borderInterpolate), repeated for tiny levels.
 __device__ __forceinline__ int r101(int i, int n) {
@@ -307,9 +301,9 @@ int launch_lk(const Pyr& I, const Pyr& J, int n, const float2* prev, float2* nex
     CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
     CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15) CASE(16)
 #undef CASE
-    default: return kfail(SFM_ENOTSUP, "window larger than 31x31 is not supported");
+    default: return fail(SFM_ENOTSUP, "window larger than 31x31 is not supported");
   }
-  return hipGetLastError() == hipSuccess ? 0 : kfail(SFM_EIO, "k_lk launch failed");
+  return hipGetLastError() == hipSuccess ? 0 : fail(SFM_EIO, "k_lk launch failed");
 }
 
 // buildOpticalFlowPyramid's level count: stop once a level would not exceed
@@ -329,33 +323,35 @@ int pyramid_levels(int w, int h, int max_level, int win) {
 
 #include "frame_internal.h"  // brisk_detect_describe_impl, launch_rgb_to_grey
 
+// The stream first: members are destroyed in reverse order, so it goes last.
 struct sfm_klt_handle {
+  sfm::Stream stream;
   int device = 0;
-  hipStream_t stream = nullptr;
   int w = 0, h = 0, levels = 0;
   sfm_klt_params prm{};
   int lw[kMaxLv] = {}, lh[kMaxLv] = {};
   size_t img_off[kMaxLv + 1] = {}, pix_total = 0;
-  uint8_t* img[2] = {nullptr, nullptr};
-  short2* dxy[2] = {nullptr, nullptr};
-  uint8_t* rgb = nullptr;  // upload stage of a 3-channel frame (push_frame_rgb), grow-only
-  size_t rgb_cap = 0;
+  sfm::DevArr<uint8_t> img[2];
+  sfm::DevArr<short2> dxy[2];
+  sfm::DevArr<uint8_t> rgb;  // upload stage of a 3-channel frame (push_frame_rgb), grow-only
   int n_frames = 0;  // frames pushed so far
   int cur = 0;       // slot of the current frame (prev = cur ^ 1)
   // point buffers
   int cap_n = 0, cap_m = 0;
-  float2* d_prev = nullptr;
-  float2* d_next = nullptr;
-  uint8_t* d_status = nullptr;
-  int* d_slot = nullptr;
-  int* d_out = nullptr;  // [2n + 1]
-  double2* d_curr = nullptr;
-  unsigned long long* d_key = nullptr;
-  int* d_first = nullptr;
+  sfm::DevArr<float2> d_prev, d_next;
+  sfm::DevArr<uint8_t> d_status;
+  sfm::DevArr<int> d_slot;
+  sfm::DevArr<int> d_out;  // [2n + 1]
+  sfm::DevArr<double2> d_curr;
+  sfm::DevArr<unsigned long long> d_key;
+  sfm::DevArr<int> d_first;
   // phase timing: [0,1] pyramid, [2,3] lk, [4,5] association
-  hipEvent_t ev[6] = {};
+  sfm::Event ev[6];
   bool timed_push = false, timed_flow = false, timed_assoc = false;
   void* gftt = nullptr;  // corner-detector state (gftt_kernels.hip)
+  ~sfm_klt_handle() {
+    if (gftt) sfm_internal_gftt_free(gftt);
+  }
 
   Pyr pyr(int slot) const {
     Pyr p{};
@@ -371,35 +367,30 @@ struct sfm_klt_handle {
 
 namespace {
 
-// (Re)allocates a device buffer to hold `count` elements (contents dropped).
-template <typename T>
-bool realloc_dev(T** p, size_t count) {
-  if (*p) hipFree(*p);
-  *p = nullptr;
-  return hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)) == hipSuccess;
-}
-
+// Room for n tracked points and m detections (exact sizes, contents dropped).
 int ensure_points(sfm_klt_handle* h, int n, int m) {
+  auto exact = [h](sfm::DevBuf& b, size_t bytes) { return b.reserve(bytes, bytes, h->stream) == 0; };
   if (n > h->cap_n) {
     h->cap_n = 0;
-    if (!realloc_dev(&h->d_prev, n) || !realloc_dev(&h->d_next, n) || !realloc_dev(&h->d_status, n) ||
-        !realloc_dev(&h->d_slot, n) || !realloc_dev(&h->d_out, 2 * size_t(n) + 1))
-      return kfail(SFM_ENOMEM, "hipMalloc failed (klt points)");
+    if (!exact(h->d_prev, sizeof(float2) * n) || !exact(h->d_next, sizeof(float2) * n) || !exact(h->d_status, n) ||
+        !exact(h->d_slot, sizeof(int) * n) || !exact(h->d_out, sizeof(int) * (2 * size_t(n) + 1)))
+      return fail(SFM_ENOMEM, "hipMalloc failed (klt points)");
     h->cap_n = n;
   }
   if (m > h->cap_m) {
     h->cap_m = 0;
-    if (!realloc_dev(&h->d_curr, m) || !realloc_dev(&h->d_key, m) || !realloc_dev(&h->d_first, m))
-      return kfail(SFM_ENOMEM, "hipMalloc failed (klt detections)");
+    if (!exact(h->d_curr, sizeof(double2) * m) || !exact(h->d_key, sizeof(unsigned long long) * m) ||
+        !exact(h->d_first, sizeof(int) * m))
+      return fail(SFM_ENOMEM, "hipMalloc failed (klt detections)");
     h->cap_m = m;
   }
   return 0;
 }
 
 int check_params(const sfm_klt_params* p) {
-  if (p->win_size < 3 || (p->win_size & 1) == 0) return kfail(SFM_EINVAL, "win_size must be odd and >= 3");
-  if (p->win_size > 31) return kfail(SFM_ENOTSUP, "win_size > 31 is not supported");
-  if (p->max_level < 0) return kfail(SFM_EINVAL, "max_level must be >= 0");
+  if (p->win_size < 3 || (p->win_size & 1) == 0) return fail(SFM_EINVAL, "win_size must be odd and >= 3");
+  if (p->win_size > 31) return fail(SFM_ENOTSUP, "win_size > 31 is not supported");
+  if (p->max_level < 0) return fail(SFM_EINVAL, "max_level must be >= 0");
   return 0;
 }
 
@@ -421,8 +412,8 @@ namespace sfm {
 // it (channels 3: one upload of the colour frame, converted on the device
 // straight into the level-0 slot).
 int klt_push_frame_any(sfm_klt_handle* h, const uint8_t* src, int32_t stride, int channels) {
-  if (!h || !src) return kfail(SFM_EINVAL, "NULL argument");
-  if (stride < channels * h->w) return kfail(SFM_EINVAL, channels == 1 ? "stride < width" : "stride < 3 * width");
+  if (!h || !src) return fail(SFM_EINVAL, "NULL argument");
+  if (stride < channels * h->w) return fail(SFM_EINVAL, channels == 1 ? "stride < width" : "stride < 3 * width");
   hipSetDevice(h->device);
   const int slot = h->n_frames == 0 ? 0 : (h->cur ^ 1);
   hipStream_t s = h->stream;
@@ -431,21 +422,14 @@ int klt_push_frame_any(sfm_klt_handle* h, const uint8_t* src, int32_t stride, in
     // pinned stage measured no faster for the 0.9-MB frame: the runtime
     // pipelines its staging copies with the DMA).
     if (hipMemcpy2DAsync(h->img[slot], h->w, src, stride, h->w, h->h, hipMemcpyHostToDevice, s) != hipSuccess)
-      return kfail(SFM_EIO, "frame upload failed");
+      return fail(SFM_EIO, "frame upload failed");
   } else {
     // the rows as the caller holds them, in one copy; the last row ends at
     // its 3 * w bytes
     const size_t bytes = size_t(h->h - 1) * stride + 3 * size_t(h->w);
-    if (h->rgb_cap < bytes) {
-      if (h->rgb) hipFree(h->rgb);
-      h->rgb = nullptr;
-      h->rgb_cap = 0;
-      if (hipMalloc(reinterpret_cast<void**>(&h->rgb), bytes) != hipSuccess)
-        return kfail(SFM_ENOMEM, "hipMalloc failed (klt colour stage)");
-      h->rgb_cap = bytes;
-    }
+    if (h->rgb.reserve(bytes, bytes, s)) return fail(SFM_ENOMEM, "hipMalloc failed (klt colour stage)");
     if (hipMemcpyAsync(h->rgb, src, bytes, hipMemcpyHostToDevice, s) != hipSuccess)
-      return kfail(SFM_EIO, "frame upload failed");
+      return fail(SFM_EIO, "frame upload failed");
     launch_rgb_to_grey(s, h->rgb, h->w, h->h, stride, h->img[slot]);
   }
   hipEventRecord(h->ev[0], s);
@@ -459,8 +443,8 @@ int klt_push_frame_any(sfm_klt_handle* h, const uint8_t* src, int32_t stride, in
     k_scharr<<<g, 256, 0, s>>>(h->img[slot] + h->img_off[l], h->lw[l], h->lh[l], h->dxy[slot] + h->img_off[l]);
   }
   hipEventRecord(h->ev[1], s);
-  if (hipGetLastError() != hipSuccess) return kfail(SFM_EIO, "pyramid launch failed");
-  if (hipStreamSynchronize(s) != hipSuccess) return kfail(SFM_EIO, "pyramid build failed");
+  if (hipGetLastError() != hipSuccess) return fail(SFM_EIO, "pyramid launch failed");
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(SFM_EIO, "pyramid build failed");
   h->cur = slot;
   ++h->n_frames;
   h->timed_push = true;
@@ -486,14 +470,14 @@ void sfm_klt_default_params(sfm_klt_params* p) {
 
 int sfm_klt_create(int32_t device, int32_t width, int32_t height, const sfm_klt_params* params,
                    sfm_klt_handle** out) {
-  if (!out) return kfail(SFM_EINVAL, "out is NULL");
+  if (!out) return fail(SFM_EINVAL, "out is NULL");
   *out = nullptr;
-  if (width <= 0 || height <= 0) return kfail(SFM_EINVAL, "bad frame size");
+  if (width <= 0 || height <= 0) return fail(SFM_EINVAL, "bad frame size");
   sfm_klt_params p;
   sfm_klt_default_params(&p);
   if (params) p = *params;
   if (int rc = check_params(&p)) return rc;
-  if (hipSetDevice(device) != hipSuccess) return kfail(SFM_ENODEV, "hipSetDevice failed");
+  if (hipSetDevice(device) != hipSuccess) return fail(SFM_ENODEV, "hipSetDevice failed");
   auto* h = new sfm_klt_handle();
   h->device = device;
   h->w = width;
@@ -513,15 +497,13 @@ int sfm_klt_create(int32_t device, int32_t width, int32_t height, const sfm_klt_
   }
   h->img_off[h->levels + 1] = off;
   h->pix_total = off;
-  bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
-  for (int s = 0; s < 2 && ok; ++s) {
-    ok = hipMalloc(reinterpret_cast<void**>(&h->img[s]), off) == hipSuccess &&
-         hipMalloc(reinterpret_cast<void**>(&h->dxy[s]), off * sizeof(short2)) == hipSuccess;
-  }
-  for (int e = 0; e < 6 && ok; ++e) ok = hipEventCreate(&h->ev[e]) == hipSuccess;
+  bool ok = h->stream.create(hipStreamNonBlocking) == hipSuccess;
+  for (int s = 0; s < 2 && ok; ++s)
+    ok = h->img[s].reserve(off, off, nullptr) == 0 && h->dxy[s].reserve(off * sizeof(short2), off * sizeof(short2), nullptr) == 0;
+  for (int e = 0; e < 6 && ok; ++e) ok = h->ev[e].create(hipEventDefault) == hipSuccess;
   if (!ok) {
     sfm_klt_destroy(h);
-    return kfail(SFM_ENOMEM, "device allocation failed (klt frames)");
+    return fail(SFM_ENOMEM, "device allocation failed (klt frames)");
   }
   *out = h;
   return 0;
@@ -531,18 +513,6 @@ int sfm_klt_destroy(sfm_klt_handle* h) {
   if (!h) return 0;
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
-  for (int s = 0; s < 2; ++s) {
-    if (h->img[s]) hipFree(h->img[s]);
-    if (h->dxy[s]) hipFree(h->dxy[s]);
-  }
-  if (h->rgb) hipFree(h->rgb);
-  void* bufs[] = {h->d_prev, h->d_next, h->d_status, h->d_slot, h->d_out, h->d_curr, h->d_key, h->d_first};
-  for (void* b : bufs)
-    if (b) hipFree(b);
-  for (auto& e : h->ev)
-    if (e) hipEventDestroy(e);
-  if (h->gftt) sfm_internal_gftt_free(h->gftt);
-  if (h->stream) hipStreamDestroy(h->stream);
   delete h;
   return 0;
 }
@@ -561,21 +531,21 @@ int sfm_klt_push_frame_rgb(sfm_klt_handle* h, const uint8_t* rgb, int32_t stride
 
 int sfm_klt_brisk_detect_describe(sfm_klt_handle* h, int32_t threshold, int32_t octaves, int32_t capacity,
                                   float* kps, int32_t* octave, uint8_t* desc, int32_t* n_out) {
-  if (!h || !n_out) return kfail(SFM_EINVAL, "NULL argument");
-  if (h->n_frames == 0) return kfail(SFM_EINVAL, "no frame pushed");
+  if (!h || !n_out) return fail(SFM_EINVAL, "NULL argument");
+  if (h->n_frames == 0) return fail(SFM_EINVAL, "no frame pushed");
   hipSetDevice(h->device);
   // (push_frame left its stream drained; this keeps any later use ordered)
-  if (hipStreamSynchronize(h->stream) != hipSuccess) return kfail(SFM_EIO, "klt stream failed");
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(SFM_EIO, "klt stream failed");
   return sfm::brisk_detect_describe_impl(h->device, h->img[h->cur], true, h->w, h->h, threshold, octaves, capacity,
                                          kps, octave, desc, n_out, nullptr);
 }
 
 int sfm_klt_get_level(sfm_klt_handle* h, int32_t which, int32_t level, uint8_t* img, int16_t* dxy, int32_t* w,
                       int32_t* hh) {
-  if (!h) return kfail(SFM_EINVAL, "NULL handle");
-  if (level < 0 || level > h->levels) return kfail(SFM_EINVAL, "level out of range");
-  if (which != 0 && which != 1) return kfail(SFM_EINVAL, "which must be 0 (previous) or 1 (current)");
-  if (h->n_frames < (which == 0 ? 2 : 1)) return kfail(SFM_EINVAL, "frame not pushed yet");
+  if (!h) return fail(SFM_EINVAL, "NULL handle");
+  if (level < 0 || level > h->levels) return fail(SFM_EINVAL, "level out of range");
+  if (which != 0 && which != 1) return fail(SFM_EINVAL, "which must be 0 (previous) or 1 (current)");
+  if (h->n_frames < (which == 0 ? 2 : 1)) return fail(SFM_EINVAL, "frame not pushed yet");
   hipSetDevice(h->device);
   const int slot = which == 1 ? h->cur : (h->cur ^ 1);
   const size_t np = size_t(h->lw[level]) * h->lh[level];
@@ -583,17 +553,17 @@ int sfm_klt_get_level(sfm_klt_handle* h, int32_t which, int32_t level, uint8_t* 
   if (hh) *hh = h->lh[level];
   hipStreamSynchronize(h->stream);
   if (img && hipMemcpy(img, h->img[slot] + h->img_off[level], np, hipMemcpyDeviceToHost) != hipSuccess)
-    return kfail(SFM_EIO, "copy failed");
+    return fail(SFM_EIO, "copy failed");
   if (dxy && hipMemcpy(dxy, h->dxy[slot] + h->img_off[level], np * sizeof(short2), hipMemcpyDeviceToHost) !=
                  hipSuccess)
-    return kfail(SFM_EIO, "copy failed");
+    return fail(SFM_EIO, "copy failed");
   return 0;
 }
 
 int sfm_klt_calc_flow(sfm_klt_handle* h, const float* prev_pts, int32_t n, float* next_pts, uint8_t* status) {
-  if (!h) return kfail(SFM_EINVAL, "NULL handle");
-  if (n < 0 || (n > 0 && (!prev_pts || !next_pts || !status))) return kfail(SFM_EINVAL, "bad point arrays");
-  if (h->n_frames < 2) return kfail(SFM_EINVAL, "calc_flow needs two pushed frames");
+  if (!h) return fail(SFM_EINVAL, "NULL handle");
+  if (n < 0 || (n > 0 && (!prev_pts || !next_pts || !status))) return fail(SFM_EINVAL, "bad point arrays");
+  if (h->n_frames < 2) return fail(SFM_EINVAL, "calc_flow needs two pushed frames");
   if (n == 0) return 0;
   hipSetDevice(h->device);
   if (int rc = ensure_points(h, n, 0)) return rc;
@@ -607,7 +577,7 @@ int sfm_klt_calc_flow(sfm_klt_handle* h, const float* prev_pts, int32_t n, float
   hipEventRecord(h->ev[3], s);
   hipMemcpyAsync(next_pts, h->d_next, sizeof(float2) * n, hipMemcpyDeviceToHost, s);
   hipMemcpyAsync(status, h->d_status, n, hipMemcpyDeviceToHost, s);
-  if (hipStreamSynchronize(s) != hipSuccess) return kfail(SFM_EIO, "k_lk failed");
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(SFM_EIO, "k_lk failed");
   h->timed_flow = true;
   h->timed_assoc = false;
   return 0;
@@ -616,13 +586,13 @@ int sfm_klt_calc_flow(sfm_klt_handle* h, const float* prev_pts, int32_t n, float
 int sfm_klt_compute_optical_flow(sfm_klt_handle* h, const double* prev_pts_dist, int32_t n_prev,
                                  const double* curr_pts_dist, int32_t n_curr, int32_t* prev_idx, int32_t* curr_idx,
                                  int32_t* n_matches, float* flowed, uint8_t* status) {
-  if (!h || !n_matches) return kfail(SFM_EINVAL, "NULL argument");
+  if (!h || !n_matches) return fail(SFM_EINVAL, "NULL argument");
   *n_matches = 0;
-  if (n_prev < 0 || n_curr < 0) return kfail(SFM_EINVAL, "negative point count");
-  if (h->n_frames < 2) return kfail(SFM_EINVAL, "compute_optical_flow needs two pushed frames");
+  if (n_prev < 0 || n_curr < 0) return fail(SFM_EINVAL, "negative point count");
+  if (h->n_frames < 2) return fail(SFM_EINVAL, "compute_optical_flow needs two pushed frames");
   if (n_prev == 0) return 0;
   if (!prev_pts_dist || (n_curr > 0 && (!curr_pts_dist || !prev_idx || !curr_idx)))
-    return kfail(SFM_EINVAL, "bad point arrays");
+    return fail(SFM_EINVAL, "bad point arrays");
   hipSetDevice(h->device);
   if (int rc = ensure_points(h, n_prev, n_curr)) return rc;
   hipStream_t s = h->stream;
@@ -649,16 +619,16 @@ int sfm_klt_compute_optical_flow(sfm_klt_handle* h, const double* prev_pts_dist,
     sfm::k_compact_slots<true><<<1, 1024, 0, s>>>(n_prev, h->d_slot, h->d_key, h->d_out, h->d_out + n_prev,
                                                   h->d_out + 2 * n_prev);
     hipEventRecord(h->ev[5], s);
-    if (hipGetLastError() != hipSuccess) return kfail(SFM_EIO, "association launch failed");
+    if (hipGetLastError() != hipSuccess) return fail(SFM_EIO, "association launch failed");
     hipMemcpyAsync(&m, h->d_out + 2 * n_prev, sizeof(int), hipMemcpyDeviceToHost, s);
   }
   if (flowed) hipMemcpyAsync(flowed, h->d_next, sizeof(float2) * n_prev, hipMemcpyDeviceToHost, s);
   if (status) hipMemcpyAsync(status, h->d_status, n_prev, hipMemcpyDeviceToHost, s);
-  if (hipStreamSynchronize(s) != hipSuccess) return kfail(SFM_EIO, "optical flow kernels failed");
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(SFM_EIO, "optical flow kernels failed");
   if (m > 0) {
     if (hipMemcpy(prev_idx, h->d_out, sizeof(int) * m, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(curr_idx, h->d_out + n_prev, sizeof(int) * m, hipMemcpyDeviceToHost) != hipSuccess)
-      return kfail(SFM_EIO, "copy failed");
+      return fail(SFM_EIO, "copy failed");
   }
   *n_matches = m;
   h->timed_flow = true;
@@ -667,7 +637,7 @@ int sfm_klt_compute_optical_flow(sfm_klt_handle* h, const double* prev_pts_dist,
 }
 
 int sfm_klt_phase_times(sfm_klt_handle* h, double* ms3) {
-  if (!h || !ms3) return kfail(SFM_EINVAL, "NULL argument");
+  if (!h || !ms3) return fail(SFM_EINVAL, "NULL argument");
   hipSetDevice(h->device);
   hipStreamSynchronize(h->stream);
   ms3[0] = h->timed_push ? ms_between(h->ev[0], h->ev[1]) : 0.0;
@@ -691,8 +661,8 @@ int sfm_calc_optical_flow_pyr_lk(int32_t device, const uint8_t* prev, const uint
 }  // extern "C"
 
 int sfm_internal_klt_frame(sfm_klt_handle* h, KltFrame* out) {
-  if (!h || !out) return kfail(SFM_EINVAL, "NULL argument");
-  if (h->n_frames == 0) return kfail(SFM_EINVAL, "no frame pushed");
+  if (!h || !out) return fail(SFM_EINVAL, "NULL argument");
+  if (h->n_frames == 0) return fail(SFM_EINVAL, "no frame pushed");
   hipSetDevice(h->device);
   out->img = h->img[h->cur] + h->img_off[0];
   out->w = h->lw[0];
@@ -704,7 +674,7 @@ int sfm_internal_klt_frame(sfm_klt_handle* h, KltFrame* out) {
 }
 
 int sfm_internal_klt_size(sfm_klt_handle* h, KltFrame* out) {
-  if (!h || !out) return kfail(SFM_EINVAL, "NULL argument");
+  if (!h || !out) return fail(SFM_EINVAL, "NULL argument");
   *out = KltFrame{};
   out->w = h->lw[0];
   out->h = h->lh[0];

@@ -14,8 +14,7 @@
 #include <string>
 #include "../../include/sfm_amd.h"
 #include "cv_linalg.h"
-
-void sfm_internal_set_error(const std::string& msg);
+#include "dev_mem.h"
 
 namespace sfm {
 int probe_svd12(int batch, const double* d_in, double* d_out, hipStream_t s);  // pnp_kernels.hip
@@ -169,10 +168,6 @@ using namespace sfm;
 
 extern "C" int sfm_linalg_probe(int32_t device, int32_t op, int32_t variant, int32_t batch, const double* in,
                                 double* out) {
-  auto fail = [](int code, const char* m) {
-    sfm_internal_set_error(m);
-    return code;
-  };
   if (op < 0 || op >= SFM_LINALG_NUM_OPS) return fail(SFM_EINVAL, "linalg probe: unknown op");
   const OpShape sh = kOps[op];
   if (variant != 0 && variant != 1) return fail(SFM_EINVAL, "linalg probe: variant must be 0 or 1");
@@ -184,11 +179,11 @@ extern "C" int sfm_linalg_probe(int32_t device, int32_t op, int32_t variant, int
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(SFM_ENODEV, "no device");
   if (hipSetDevice(device) != hipSuccess) return fail(SFM_ENODEV, "hipSetDevice failed");
   const size_t b_in = sizeof(double) * sh.n_in * size_t(batch), b_out = sizeof(double) * sh.n_out * size_t(batch);
-  double *d_in = nullptr, *d_out = nullptr;
-  hipStream_t s = nullptr;
+  Stream s;  // (first: destroyed after the buffers)
+  DevArr<double> d_in, d_out;
   int rc = 0;
-  if (hipStreamCreate(&s) != hipSuccess) return fail(SFM_ENOMEM, "stream creation failed");
-  if (hipMalloc(&d_in, b_in) != hipSuccess || hipMalloc(&d_out, b_out) != hipSuccess)
+  if (s.create(hipStreamDefault) != hipSuccess) return fail(SFM_ENOMEM, "stream creation failed");
+  if (d_in.reserve(b_in, b_in, nullptr) || d_out.reserve(b_out, b_out, nullptr))
     rc = fail(SFM_ENOMEM, "device buffer allocation failed");
   if (!rc && (hipMemcpyAsync(d_in, in, b_in, hipMemcpyHostToDevice, s) != hipSuccess ||
               hipMemsetAsync(d_out, 0, b_out, s) != hipSuccess))
@@ -226,8 +221,5 @@ extern "C" int sfm_linalg_probe(int32_t device, int32_t op, int32_t variant, int
              hipStreamSynchronize(s) != hipSuccess)
       rc = fail(SFM_EIO, "linalg probe failed");
   }
-  if (d_in) (void)hipFree(d_in);
-  if (d_out) (void)hipFree(d_out);
-  (void)hipStreamDestroy(s);
   return rc;
 }

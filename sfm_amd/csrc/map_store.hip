@@ -54,16 +54,12 @@
 #include "map_internal.h"
 #include "mappoint_internal.h"
 #include "../../include/sfm_amd.h"
-
-void sfm_internal_set_error(const std::string& msg);  // ba_solver.hip
+#include "dev_mem.h"
 
 namespace sfm {
 namespace {
 
-int mapfail(int code, const std::string& m) {
-  sfm_internal_set_error("sfm_map: " + m);
-  return code;
-}
+int mapfail(int code, const std::string& m) { return fail(code, "sfm_map: " + m); }
 
 __global__ void k_mark_frames(int64_t n, const int32_t* __restrict__ ob_pt, const int32_t* __restrict__ ob_frame,
                               const uint8_t* __restrict__ ob_mm, const int32_t* __restrict__ fset, int nf,
@@ -510,7 +506,7 @@ __global__ void k_project(int n, const int32_t* __restrict__ n_dev, const int32_
 
 template <class T>
 struct DVec {
-  T* p = nullptr;
+  DevArr<T> p;
   int64_t n = 0, cap = 0;
 };
 
@@ -527,9 +523,10 @@ int matcher_keyframe_rows(sfm_matcher* h, int32_t slot, const uint64_t** desc, i
 
 using namespace sfm;
 
+// The stream first: members are destroyed in reverse order, so it goes last.
 struct sfm_map {
+  Stream s;
   int device = 0, desc_bytes = 0, W = 0;
-  hipStream_t s = nullptr;
   DVec<int32_t> ob_pt, ob_frame, ob_idx;  // observations, emplace order
   DVec<uint8_t> ob_mm;                     // 1: the observation's _frameViewsPointIdx entry exists
   DVec<double> X;                          // [n_pts][3]
@@ -541,41 +538,36 @@ struct sfm_map {
   DVec<uint64_t> desc;                     // [rows][W]
   DVec<int32_t> desc_pt;                   // point of each row
   bool ocsr = false, dcsr = false;         // per-point CSRs current?
-  int32_t *orow = nullptr, *ooff = nullptr, *drow = nullptr, *doff = nullptr;
-  std::map<std::string, std::pair<void*, size_t>> scratch;
-  hipEvent_t ev = nullptr;                 // sfm_map_match_frame: its queries are ready
-  int32_t* pin = nullptr;                  // sfm_map_match_frame's pinned readback
-  size_t pin_cap = 0;
+  int32_t *orow = nullptr, *ooff = nullptr, *drow = nullptr, *doff = nullptr;  // (views into scratch: build_csr)
+  std::map<std::string, DevBuf> scratch;
+  Event ev;                                // sfm_map_match_frame: its queries are ready
+  PinArr<int32_t> pin;                     // the handle's pinned block (pin_reserve)
 };
 
 namespace {
 
 void* scratch(sfm_map* h, const char* name, size_t bytes, int* rc) {
-  auto& e = h->scratch[name];
-  if (e.second >= bytes && e.first) return e.first;
+  DevBuf& b = h->scratch[name];
   // grow by half again at least: the map grows every keyframe, and a
   // reallocation costs a stream synchronisation plus hipFree / hipMalloc
-  const size_t want = std::max<size_t>({bytes, e.second + e.second / 2, 256});
-  if (e.first) { (void)hipStreamSynchronize(h->s); (void)hipFree(e.first); e.first = nullptr; e.second = 0; }
-  void* p = nullptr;
-  if (hipMalloc(&p, want) != hipSuccess) {
+  const size_t want = std::max<size_t>({bytes, b.bytes() + b.bytes() / 2, 256});
+  if (b.reserve(std::max<size_t>(bytes, 1), want, h->s))
     *rc = mapfail(SFM_ENOMEM, std::string("hipMalloc failed (") + name + ")");
-    return nullptr;
-  }
-  e = {p, want};
-  return p;
+  return b.get();
 }
 
+// The one place that keeps a buffer's contents across growth: a new buffer,
+// the n elements copied on the stream, then the swap.
 template <class T>
 int grow(sfm_map* h, DVec<T>& v, int64_t need) {
   if (need <= v.cap) return 0;
   const int64_t cap = std::max<int64_t>({need, 2 * v.cap, 1024});
-  T* p = nullptr;
-  if (hipMalloc(&p, size_t(cap) * sizeof(T)) != hipSuccess) return mapfail(SFM_ENOMEM, "hipMalloc failed (growth)");
+  DevArr<T> p;
+  if (p.reserve(size_t(cap) * sizeof(T), size_t(cap) * sizeof(T), nullptr))
+    return mapfail(SFM_ENOMEM, "hipMalloc failed (growth)");
   if (v.n) (void)hipMemcpyAsync(p, v.p, size_t(v.n) * sizeof(T), hipMemcpyDeviceToDevice, h->s);
   (void)hipStreamSynchronize(h->s);
-  if (v.p) (void)hipFree(v.p);
-  v.p = p;
+  v.p = std::move(p);
   v.cap = cap;
   return 0;
 }
@@ -591,17 +583,8 @@ int append(sfm_map* h, DVec<T>& v, const T* src, int64_t n) {
 
 // The handle's pinned block, at least n ints (grown while the stream is idle).
 int32_t* pin_reserve(sfm_map* h, size_t n, int* rc) {
-  if (h->pin_cap < n) {
-    if (h->pin) { (void)hipStreamSynchronize(h->s); (void)hipHostFree(h->pin); }
-    h->pin = nullptr;
-    h->pin_cap = 0;
-    const size_t cap = std::max<size_t>(n, 8192) * 3 / 2;
-    if (hipHostMalloc(reinterpret_cast<void**>(&h->pin), sizeof(int32_t) * cap) != hipSuccess) {
-      *rc = mapfail(SFM_ENOMEM, "hipHostMalloc failed");
-      return nullptr;
-    }
-    h->pin_cap = cap;
-  }
+  if (h->pin.reserve(sizeof(int32_t) * n, sizeof(int32_t) * (std::max<size_t>(n, 8192) * 3 / 2), h->s))
+    *rc = mapfail(SFM_ENOMEM, "hipHostMalloc failed");
   return h->pin;
 }
 int sync(sfm_map* h) {
@@ -886,7 +869,7 @@ int sfm_map_create(int32_t device, int32_t desc_bytes, sfm_map** out) {
   h->device = device;
   h->desc_bytes = desc_bytes;
   h->W = desc_bytes / 8;
-  if (hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking) != hipSuccess) {
+  if (h->s.create(hipStreamNonBlocking) != hipSuccess) {
     delete h;
     return mapfail(SFM_EIO, "hipStreamCreate failed");
   }
@@ -898,15 +881,6 @@ int sfm_map_destroy(sfm_map* h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->s);
-  for (void* p : {(void*)h->ob_pt.p, (void*)h->ob_frame.p, (void*)h->ob_idx.p, (void*)h->X.p, (void*)h->desc.p,
-                  (void*)h->desc_pt.p, (void*)h->ob_mm.p, (void*)h->pt_time.p, (void*)h->pt_kf.p,
-                  (void*)h->pt_views.p, (void*)h->pt_live.p})
-    if (p) (void)hipFree(p);
-  for (auto& e : h->scratch)
-    if (e.second.first) (void)hipFree(e.second.first);
-  if (h->ev) (void)hipEventDestroy(h->ev);
-  if (h->pin) (void)hipHostFree(h->pin);
-  (void)hipStreamDestroy(h->s);
   delete h;
   return 0;
 }
@@ -1062,15 +1036,8 @@ int sfm_map_get_points(sfm_map* h, int32_t n, const int32_t* pts3d_idx, double* 
   auto* di = static_cast<int32_t*>(scratch(h, "gi", sizeof(int32_t) * size_t(n), &rc));
   auto* dv = static_cast<double*>(scratch(h, "gv", sizeof(double) * 3 * size_t(n), &rc));
   if (rc) return rc;
-  if (h->pin_cap < 8 * size_t(n) + 8) {
-    if (h->pin) { (void)hipStreamSynchronize(h->s); (void)hipHostFree(h->pin); }
-    h->pin = nullptr;
-    h->pin_cap = 0;
-    const size_t cap = std::max<size_t>(8 * size_t(n) + 8, 8192) * 3 / 2;
-    if (hipHostMalloc(reinterpret_cast<void**>(&h->pin), sizeof(int32_t) * cap) != hipSuccess)
-      return mapfail(SFM_ENOMEM, "hipHostMalloc failed");
-    h->pin_cap = cap;
-  }
+  pin_reserve(h, 8 * size_t(n) + 8, &rc);
+  if (rc) return rc;
   (void)hipStreamSynchronize(h->s);  // (the pinned block may feed an earlier copy)
   std::memcpy(h->pin, pts3d_idx, sizeof(int32_t) * size_t(n));
   double* pv = reinterpret_cast<double*>(h->pin + ((size_t(n) + 1) & ~size_t(1)));
@@ -1372,17 +1339,9 @@ int sfm_map_match_frame(sfm_map* h, sfm_matcher* mt, int32_t n_frames, const int
   auto* out = static_cast<int32_t*>(scratch(h, "pout", sizeof(int32_t) * 2 * size_t(P), &rc));
   auto* dn = static_cast<int32_t*>(scratch(h, "pn", sizeof(int32_t), &rc));
   if (rc) return rc;
-  if (h->pin_cap < std::max(2 * size_t(P) + 1, n_up)) {
-    if (h->pin) { (void)hipStreamSynchronize(h->s); (void)hipHostFree(h->pin); }
-    h->pin = nullptr;
-    h->pin_cap = 0;
-    const size_t cap = std::max<size_t>(std::max(2 * size_t(P) + 1, n_up), 8192) * 3 / 2;
-    if (hipHostMalloc(reinterpret_cast<void**>(&h->pin), sizeof(int32_t) * cap) != hipSuccess)
-      return mapfail(SFM_ENOMEM, "hipHostMalloc failed");
-    h->pin_cap = cap;
-  }
-  if (!h->ev && hipEventCreateWithFlags(&h->ev, hipEventDisableTiming) != hipSuccess)
-    return mapfail(SFM_EIO, "hipEventCreate failed");
+  pin_reserve(h, std::max(2 * size_t(P) + 1, n_up), &rc);
+  if (rc) return rc;
+  if (h->ev.create(hipEventDisableTiming) != hipSuccess) return mapfail(SFM_EIO, "hipEventCreate failed");
   // frames, the frame's matched points and the train subset in one upload
   (void)hipStreamSynchronize(h->s);  // (the pinned block may feed an earlier copy)
   std::memcpy(h->pin, fs.data(), sizeof(int32_t) * fs.size());

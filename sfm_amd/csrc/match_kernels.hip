@@ -40,15 +40,15 @@
 #include "ordered_compact.h"
 #include "frame_internal.h"
 #include "mappoint_internal.h"
+#include "dev_mem.h"
 
-void sfm_internal_set_error(const std::string& msg);  // ba_solver.hip
+using sfm::DevArr;
+using sfm::DevBuf;
+using sfm::Event;
+using sfm::PinBuf;
+using sfm::Stream;
 
 namespace {
-
-int mfail(int code, const std::string& m) {
-  sfm_internal_set_error(m);
-  return code;
-}
 
 constexpr int kQ = 64;       // queries per workgroup (one per lane)
 constexpr int kWaves = 4;    // waves per workgroup, each a quarter of the train slice
@@ -308,26 +308,26 @@ __global__ __launch_bounds__(64) void k_repr(const uint64_t* __restrict__ d, con
 
 struct MatchFrame {
   int n = 0;
-  uint64_t* desc = nullptr;   // [n][W]; one allocation with the two below
+  DevArr<uint64_t> desc;      // [n][W]; one allocation with the two below
   double* pts = nullptr;      // [n][2] undistorted (CFrame::getPointsAt), right after desc
   double* ptsd = nullptr;     // [n][2] distorted (CFrame::getPointsDistorted), right after pts
-  size_t cap = 0;
 };
 
+// The stream first: members are destroyed in reverse order, so it goes last.
 struct sfm_matcher {
+  Stream stream;
   std::vector<MatchFrame> kf;  // keyframe store (sfm_matcher_store_keyframe)
   int device = 0;
   int desc_bytes = 64, W = 8;
   int n_cu = 256;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  hipEvent_t ev_rows = nullptr;  // matcher_keyframe_rows: the keyframe store's uploads are done
+  Event ev[3];
+  Event ev_rows;              // matcher_keyframe_rows: the keyframe store's uploads are done
   MatchFrame frame[2];        // [prev, curr] after the swap
   int cur = 1;                // index of the current frame in frame[]
   int frames_pushed = 0;
   // pooled scratch (grow-only)
-  std::map<std::string, std::pair<void*, size_t>> dev;
-  std::map<std::string, std::pair<void*, size_t>> pin;
+  std::map<std::string, DevBuf> dev;
+  std::map<std::string, PinBuf> pin;
   float last_knn_ms = 0.f, last_total_ms = 0.f;
 };
 
@@ -335,38 +335,30 @@ namespace {
 
 template <typename T>
 T* dbuf(sfm_matcher* h, const char* name, size_t count, int* rc) {
-  auto& e = h->dev[name];
   const size_t bytes = std::max<size_t>(1, count) * sizeof(T);
-  if (e.second < bytes) {
-    if (e.first) hipFree(e.first);
-    e.first = nullptr;
-    e.second = 0;
-    const size_t cap = std::max(bytes, size_t(4096)) * 3 / 2;
-    if (hipMalloc(&e.first, cap) != hipSuccess) {
-      *rc = mfail(SFM_ENOMEM, "hipMalloc failed (matcher scratch)");
-      return nullptr;
-    }
-    e.second = cap;
-  }
-  return static_cast<T*>(e.first);
+  DevBuf& b = h->dev[name];
+  if (b.reserve(bytes, std::max(bytes, size_t(4096)) * 3 / 2, h->stream))
+    *rc = fail(SFM_ENOMEM, "hipMalloc failed (matcher scratch)");
+  return b.as<T>();
 }
 
 template <typename T>
 T* pbuf(sfm_matcher* h, const char* name, size_t count, int* rc) {
-  auto& e = h->pin[name];
   const size_t bytes = std::max<size_t>(1, count) * sizeof(T);
-  if (e.second < bytes) {
-    if (e.first) hipHostFree(e.first);
-    e.first = nullptr;
-    e.second = 0;
-    const size_t cap = std::max(bytes, size_t(4096)) * 3 / 2;
-    if (hipHostMalloc(&e.first, cap) != hipSuccess) {
-      *rc = mfail(SFM_ENOMEM, "hipHostMalloc failed (matcher staging)");
-      return nullptr;
-    }
-    e.second = cap;
-  }
-  return static_cast<T*>(e.first);
+  PinBuf& b = h->pin[name];
+  if (b.reserve(bytes, std::max(bytes, size_t(4096)) * 3 / 2, h->stream))
+    *rc = fail(SFM_ENOMEM, "hipHostMalloc failed (matcher staging)");
+  return b.as<T>();
+}
+
+// Room for `need` rows of `row_bytes` in a frame's one allocation, `want`
+// rows when it has to grow (the rows it held are dropped).
+int frame_reserve(sfm_matcher* h, MatchFrame& f, int need, size_t want, size_t row_bytes, const char* what) {
+  const size_t bytes = size_t(std::max(need, 1)) * row_bytes;
+  if (f.desc.bytes() < bytes) f.pts = f.ptsd = nullptr;
+  if (f.desc.reserve(bytes, want * row_bytes, h->stream))
+    return fail(SFM_ENOMEM, std::string("hipMalloc failed (") + what + ")");
+  return 0;
 }
 
 // Train slices: enough workgroups to put ~8 waves on every CU, each slice
@@ -392,7 +384,7 @@ int launch_knn(sfm_matcher* h, const uint64_t* q, const int* qidx, int n0, const
     break;
     CASE(1) CASE(2) CASE(4) CASE(8) CASE(16) CASE(32) CASE(64)
 #undef CASE
-    default: return mfail(SFM_EINVAL, "descriptor width must be <= 512 bytes");
+    default: return fail(SFM_EINVAL, "descriptor width must be <= 512 bytes");
   }
   return 0;
 }
@@ -437,7 +429,7 @@ int run_match(sfm_matcher* h, const uint64_t* q, const int* qidx, const double* 
   if ((rc = run_match_async(h, q, qidx, p0, n0, tr, tidx, p1, n1, ratio, mn, mx, &out, n0_dev))) return rc;
   hipStream_t s = h->stream;
   hipMemcpyAsync(res, out, (2 * size_t(n0) + 1) * sizeof(int), hipMemcpyDeviceToHost, s);
-  if (hipStreamSynchronize(s) != hipSuccess) return mfail(SFM_EIO, "matcher kernels failed");
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(SFM_EIO, "matcher kernels failed");
   hipEventElapsedTime(&h->last_knn_ms, h->ev[0], h->ev[1]);
   hipEventElapsedTime(&h->last_total_ms, h->ev[0], h->ev[2]);
   *res_out = res;
@@ -567,7 +559,7 @@ int pair_points_run(sfm_matcher* h, int B_, const int32_t* slot0, const int32_t*
   case w: k_knn2_part_items<w><<<grid, kQ * kWaves, 0, s>>>(ditems, dix, f1.desc, dtix, n1, slice, part); break;
     CASE(1) CASE(2) CASE(4) CASE(8) CASE(16) CASE(32) CASE(64)
 #undef CASE
-    default: return mfail(SFM_EINVAL, "descriptor width must be <= 512 bytes");
+    default: return fail(SFM_EINVAL, "descriptor width must be <= 512 bytes");
   }
   hipEventRecord(h->ev[1], s);
   k_accept_items<<<dim3((max_n0 + 255) / 256, by), 256, 0, s>>>(ditems, dix, nslice, part, f1.pts, dtix, ratio_test,
@@ -580,7 +572,7 @@ int pair_points_run(sfm_matcher* h, int B_, const int32_t* slot0, const int32_t*
                                 dhead + hi, dhead + hi + cap, dblk + hi / 2 + cap);
   hipEventRecord(h->ev[2], s);
   hipMemcpyAsync(hblk, dblk, sizeof(double) * blk, hipMemcpyDeviceToHost, s);
-  if (hipStreamSynchronize(s) != hipSuccess) return mfail(SFM_EIO, "point-creation kernels failed");
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(SFM_EIO, "point-creation kernels failed");
   hipEventElapsedTime(&h->last_knn_ms, h->ev[0], h->ev[1]);
   hipEventElapsedTime(&h->last_total_ms, h->ev[0], h->ev[2]);
   const int* hh = reinterpret_cast<const int*>(hblk);
@@ -590,7 +582,7 @@ int pair_points_run(sfm_matcher* h, int B_, const int32_t* slot0, const int32_t*
   if (hh[0] < 0) return 0;
   const int kept = n_kept[hh[0]];
   if (kept > capacity)
-    return mfail(SFM_EINVAL, "capacity " + std::to_string(capacity) + " < " + std::to_string(kept) + " kept matches");
+    return fail(SFM_EINVAL, "capacity " + std::to_string(capacity) + " < " + std::to_string(kept) + " kept matches");
   std::memcpy(m0, hh + hi, sizeof(int) * size_t(kept));
   std::memcpy(m1, hh + hi + cap, sizeof(int) * size_t(kept));
   std::memcpy(X, hblk + hi / 2 + cap, sizeof(double) * 3 * size_t(kept));
@@ -617,10 +609,10 @@ const double* map_points_dev(sfm_map* h, int32_t* n_pts, int* device);
 int matcher_match_current_dev(sfm_matcher* h, hipEvent_t after, const uint64_t* q, const double* p0, int n0,
                               const int32_t* d_n0, const int32_t* d_train_idx, int n1, double ratio, double mn,
                               double mx, int** res) {
-  if (h->frames_pushed < 1) return mfail(SFM_EINVAL, "push the current frame first");
-  if (!ok_ratio_window(ratio, mn, mx)) return mfail(SFM_EINVAL, "non-finite threshold");
+  if (h->frames_pushed < 1) return fail(SFM_EINVAL, "push the current frame first");
+  if (!ok_ratio_window(ratio, mn, mx)) return fail(SFM_EINVAL, "non-finite threshold");
   const MatchFrame& fc = h->frame[h->cur];
-  if (after && hipStreamWaitEvent(h->stream, after, 0) != hipSuccess) return mfail(SFM_EIO, "stream wait failed");
+  if (after && hipStreamWaitEvent(h->stream, after, 0) != hipSuccess) return fail(SFM_EIO, "stream wait failed");
   return run_match(h, q, nullptr, p0, n0, fc.desc, d_train_idx, fc.pts, n1, ratio, mn, mx, res, d_n0);
 }
 int matcher_current_n(const sfm_matcher* h) { return h->frames_pushed < 1 ? -1 : h->frame[h->cur].n; }
@@ -632,10 +624,9 @@ int matcher_desc_bytes(const sfm_matcher* h) { return h->desc_bytes; }
 // keyframe `slot` ([*n][matcher_words]) and an event after which they are
 // complete (the store's upload runs on the matcher's stream).
 int matcher_keyframe_rows(sfm_matcher* h, int32_t slot, const uint64_t** desc, int* n, hipEvent_t* ready) {
-  if (slot < 0 || size_t(slot) >= h->kf.size()) return mfail(SFM_EINVAL, "keyframe slot not stored");
-  if (!h->ev_rows && hipEventCreateWithFlags(&h->ev_rows, hipEventDisableTiming) != hipSuccess)
-    return mfail(SFM_EIO, "hipEventCreate failed");
-  if (hipEventRecord(h->ev_rows, h->stream) != hipSuccess) return mfail(SFM_EIO, "hipEventRecord failed");
+  if (slot < 0 || size_t(slot) >= h->kf.size()) return fail(SFM_EINVAL, "keyframe slot not stored");
+  if (h->ev_rows.create(hipEventDisableTiming) != hipSuccess) return fail(SFM_EIO, "hipEventCreate failed");
+  if (hipEventRecord(h->ev_rows, h->stream) != hipSuccess) return fail(SFM_EIO, "hipEventRecord failed");
   *desc = h->kf[size_t(slot)].desc;
   *n = h->kf[size_t(slot)].n;
   *ready = h->ev_rows;
@@ -648,19 +639,10 @@ int matcher_keyframe_rows(sfm_matcher* h, int32_t slot, const uint64_t** desc, i
 // to be accepted) for m keypoints, laid out as push_frame does; commit is
 // the prev/curr swap.
 int matcher_install_begin(sfm_matcher* h, int n, int m, MatchSlot* out) {
-  if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
+  if (hipSetDevice(h->device) != hipSuccess) return fail(SFM_EIO, "hipSetDevice failed");
   MatchFrame& f = h->frame[h->cur ^ 1];
-  if (f.cap < size_t(std::max(m, 1))) {
-    hipStreamSynchronize(h->stream);
-    hipFree(f.desc);
-    f.desc = nullptr; f.pts = f.ptsd = nullptr;
-    f.cap = size_t(std::max(m, 1024)) * 3 / 2;
-    if (hipMalloc(&f.desc, f.cap * (h->W * 8 + 32)) != hipSuccess) {
-      f.cap = 0;
-      return mfail(SFM_ENOMEM, "hipMalloc failed (matcher frame)");
-    }
-  }
-  int rc = 0;
+  int rc = frame_reserve(h, f, m, size_t(std::max(m, 1024)) * 3 / 2, h->W * 8 + 32, "matcher frame");
+  if (rc) return rc;
   out->scratch = dbuf<int>(h, "install", size_t(n) + 1, &rc);
   if (rc) return rc;
   out->desc = f.desc;
@@ -682,13 +664,13 @@ void matcher_install_commit(sfm_matcher* h, int m) {
 extern "C" {
 
 int sfm_matcher_create(int32_t device, int32_t desc_bytes, sfm_matcher** out) {
-  if (!out) return mfail(SFM_EINVAL, "out is NULL");
+  if (!out) return fail(SFM_EINVAL, "out is NULL");
   *out = nullptr;
-  if (desc_bytes <= 0 || desc_bytes > 512) return mfail(SFM_EINVAL, "desc_bytes must be in 1..512");
+  if (desc_bytes <= 0 || desc_bytes > 512) return fail(SFM_EINVAL, "desc_bytes must be in 1..512");
   int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return mfail(SFM_ENODEV, "no HIP device visible");
-  if (device < 0 || device >= n) return mfail(SFM_EINVAL, "device ordinal out of range");
-  if (hipSetDevice(device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
+  if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return fail(SFM_ENODEV, "no HIP device visible");
+  if (device < 0 || device >= n) return fail(SFM_EINVAL, "device ordinal out of range");
+  if (hipSetDevice(device) != hipSuccess) return fail(SFM_EIO, "hipSetDevice failed");
   auto* h = new sfm_matcher();
   h->device = device;
   h->desc_bytes = desc_bytes;
@@ -696,11 +678,11 @@ int sfm_matcher_create(int32_t device, int32_t desc_bytes, sfm_matcher** out) {
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
     h->n_cu = prop.multiProcessorCount;
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+  if (h->stream.create(hipStreamNonBlocking) != hipSuccess) {
     delete h;
-    return mfail(SFM_EIO, "hipStreamCreate failed");
+    return fail(SFM_EIO, "hipStreamCreate failed");
   }
-  for (auto& e : h->ev) hipEventCreate(&e);
+  for (auto& e : h->ev) (void)e.create(hipEventDefault);
   *out = h;
   return 0;
 }
@@ -709,15 +691,6 @@ int sfm_matcher_destroy(sfm_matcher* h) {
   if (!h) return 0;
   hipSetDevice(h->device);
   hipStreamSynchronize(h->stream);
-  for (auto& f : h->kf) hipFree(f.desc);
-  for (auto& f : h->frame) {
-    hipFree(f.desc);
-  }
-  for (auto& kv : h->dev) hipFree(kv.second.first);
-  for (auto& kv : h->pin) hipHostFree(kv.second.first);
-  for (auto e : h->ev) hipEventDestroy(e);
-  if (h->ev_rows) hipEventDestroy(h->ev_rows);
-  hipStreamDestroy(h->stream);
   delete h;
   return 0;
 }
@@ -725,23 +698,14 @@ int sfm_matcher_destroy(sfm_matcher* h) {
 int sfm_matcher_push_frame(sfm_matcher* h, const double* pts, const double* pts_distorted, const uint8_t* desc,
                            int32_t n) {
   SFM_TRACE("sfm_matcher_push_frame");
-  if (!h) return mfail(SFM_EINVAL, "handle is NULL");
-  if (n < 0 || (n > 0 && (!pts || !desc))) return mfail(SFM_EINVAL, "bad frame arguments");
-  if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
+  if (!h) return fail(SFM_EINVAL, "handle is NULL");
+  if (n < 0 || (n > 0 && (!pts || !desc))) return fail(SFM_EINVAL, "bad frame arguments");
+  if (hipSetDevice(h->device) != hipSuccess) return fail(SFM_EIO, "hipSetDevice failed");
   // the current frame becomes the previous one (CSfM.cpp:626-629)
   h->cur ^= 1;
   MatchFrame& f = h->frame[h->cur];
-  int rc = 0;
-  if (f.cap < size_t(std::max(n, 1))) {
-    hipStreamSynchronize(h->stream);
-    hipFree(f.desc);
-    f.desc = nullptr; f.pts = f.ptsd = nullptr;
-    f.cap = size_t(std::max(n, 1024)) * 3 / 2;
-    if (hipMalloc(&f.desc, f.cap * (h->W * 8 + 32)) != hipSuccess) {
-      f.cap = 0;
-      return mfail(SFM_ENOMEM, "hipMalloc failed (matcher frame)");
-    }
-  }
+  int rc = frame_reserve(h, f, n, size_t(std::max(n, 1024)) * 3 / 2, h->W * 8 + 32, "matcher frame");
+  if (rc) return rc;
   f.n = n;
   // [desc n W | pts 2n | ptsd 2n] as laid out in the stage: one copy
   f.pts = reinterpret_cast<double*>(f.desc + size_t(n) * h->W);
@@ -768,18 +732,18 @@ int sfm_matcher_match_subset(sfm_matcher* h, const int32_t* prev_idx, int32_t n_
                              int32_t n_curr, double ratio_test, double min_distance, double max_distance,
                              int32_t* prev_match, int32_t* curr_match, int32_t* n_matches) {
   SFM_TRACE("sfm_matcher_match_subset");
-  if (!h || !n_matches) return mfail(SFM_EINVAL, "NULL argument");
+  if (!h || !n_matches) return fail(SFM_EINVAL, "NULL argument");
   *n_matches = 0;
-  if (h->frames_pushed < 2) return mfail(SFM_EINVAL, "push the previous and the current frame first");
+  if (h->frames_pushed < 2) return fail(SFM_EINVAL, "push the previous and the current frame first");
   if (n_prev < 0 || n_curr < 0 || (n_prev && !prev_idx) || (n_curr && !curr_idx))
-    return mfail(SFM_EINVAL, "bad index lists");
-  if (!ok_ratio_window(ratio_test, min_distance, max_distance)) return mfail(SFM_EINVAL, "non-finite threshold");
+    return fail(SFM_EINVAL, "bad index lists");
+  if (!ok_ratio_window(ratio_test, min_distance, max_distance)) return fail(SFM_EINVAL, "non-finite threshold");
   const MatchFrame& fp = h->frame[h->cur ^ 1];
   const MatchFrame& fc = h->frame[h->cur];
-  if (!rows_in_range(prev_idx, n_prev, fp.n)) return mfail(SFM_EINVAL, "prev index out of range");
-  if (!rows_in_range(curr_idx, n_curr, fc.n)) return mfail(SFM_EINVAL, "curr index out of range");
+  if (!rows_in_range(prev_idx, n_prev, fp.n)) return fail(SFM_EINVAL, "prev index out of range");
+  if (!rows_in_range(curr_idx, n_curr, fc.n)) return fail(SFM_EINVAL, "curr index out of range");
   if (n_prev == 0 || n_curr < 2) return 0;  // reference UB with < 2 train rows: no matches
-  if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
+  if (hipSetDevice(h->device) != hipSuccess) return fail(SFM_EIO, "hipSetDevice failed");
   int rc = 0;
   int* ix = pbuf<int>(h, "idx", size_t(n_prev) + n_curr, &rc);
   int* dix = dbuf<int>(h, "didx", size_t(n_prev) + n_curr, &rc);
@@ -804,14 +768,14 @@ int sfm_matcher_match_subset(sfm_matcher* h, const int32_t* prev_idx, int32_t n_
 
 int sfm_matcher_match_frames(sfm_matcher* h, int32_t distorted, double ratio_test, double min_distance,
                              double max_distance, int32_t* prev_idx, int32_t* curr_idx, int32_t* n_matches) {
-  if (!h || !n_matches) return mfail(SFM_EINVAL, "NULL argument");
+  if (!h || !n_matches) return fail(SFM_EINVAL, "NULL argument");
   *n_matches = 0;
-  if (h->frames_pushed < 2) return mfail(SFM_EINVAL, "push the previous and the current frame first");
-  if (!ok_ratio_window(ratio_test, min_distance, max_distance)) return mfail(SFM_EINVAL, "non-finite threshold");
+  if (h->frames_pushed < 2) return fail(SFM_EINVAL, "push the previous and the current frame first");
+  if (!ok_ratio_window(ratio_test, min_distance, max_distance)) return fail(SFM_EINVAL, "non-finite threshold");
   const MatchFrame& fp = h->frame[h->cur ^ 1];
   const MatchFrame& fc = h->frame[h->cur];
   if (fp.n == 0 || fc.n < 2) return 0;
-  if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
+  if (hipSetDevice(h->device) != hipSuccess) return fail(SFM_EIO, "hipSetDevice failed");
   int* res = nullptr;
   int rc = run_match(h, fp.desc, nullptr, distorted ? fp.ptsd : fp.pts, fp.n, fc.desc, nullptr,
                      distorted ? fc.ptsd : fc.pts, fc.n, ratio_test, min_distance, max_distance, &res);
@@ -824,13 +788,13 @@ int sfm_matcher_match(sfm_matcher* h, const double* pts0, const uint8_t* desc0, 
                       const uint8_t* desc1, int32_t n1, double ratio_test, double min_distance, double max_distance,
                       int32_t* idx0, int32_t* idx1, int32_t* n_matches) {
   SFM_TRACE("sfm_matcher_match");
-  if (!h || !n_matches) return mfail(SFM_EINVAL, "NULL argument");
+  if (!h || !n_matches) return fail(SFM_EINVAL, "NULL argument");
   *n_matches = 0;
-  if (n0 < 0 || n1 < 0) return mfail(SFM_EINVAL, "negative size");
-  if ((n0 && (!pts0 || !desc0)) || (n1 && (!pts1 || !desc1))) return mfail(SFM_EINVAL, "NULL array");
-  if (!ok_ratio_window(ratio_test, min_distance, max_distance)) return mfail(SFM_EINVAL, "non-finite threshold");
+  if (n0 < 0 || n1 < 0) return fail(SFM_EINVAL, "negative size");
+  if ((n0 && (!pts0 || !desc0)) || (n1 && (!pts1 || !desc1))) return fail(SFM_EINVAL, "NULL array");
+  if (!ok_ratio_window(ratio_test, min_distance, max_distance)) return fail(SFM_EINVAL, "non-finite threshold");
   if (n0 == 0 || n1 < 2) return 0;  // reference UB with < 2 train rows: no matches
-  if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
+  if (hipSetDevice(h->device) != hipSuccess) return fail(SFM_EIO, "hipSetDevice failed");
   int rc = 0;
   const size_t w0 = size_t(n0) * h->W, w1 = size_t(n1) * h->W;
   auto* st = pbuf<uint64_t>(h, "in", w0 + w1 + 2 * (size_t(n0) + n1), &rc);
@@ -856,22 +820,13 @@ int sfm_matcher_match(sfm_matcher* h, const double* pts0, const uint8_t* desc0, 
 // slot `slot` takes pts [n][2] and desc [n][desc_bytes] once, resident.
 int sfm_matcher_store_keyframe(sfm_matcher* h, int32_t slot, const double* pts, const uint8_t* desc, int32_t n) {
   SFM_TRACE("sfm_matcher_store_keyframe");
-  if (!h) return mfail(SFM_EINVAL, "handle is NULL");
-  if (slot < 0 || slot > (1 << 20) || n < 0 || (n > 0 && (!pts || !desc))) return mfail(SFM_EINVAL, "bad keyframe arguments");
-  if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
+  if (!h) return fail(SFM_EINVAL, "handle is NULL");
+  if (slot < 0 || slot > (1 << 20) || n < 0 || (n > 0 && (!pts || !desc))) return fail(SFM_EINVAL, "bad keyframe arguments");
+  if (hipSetDevice(h->device) != hipSuccess) return fail(SFM_EIO, "hipSetDevice failed");
   if (size_t(slot) >= h->kf.size()) h->kf.resize(size_t(slot) + 1);
   MatchFrame& f = h->kf[size_t(slot)];
-  int rc = 0;
-  if (f.cap < size_t(std::max(n, 1))) {
-    hipStreamSynchronize(h->stream);
-    hipFree(f.desc);
-    f.desc = nullptr;
-    f.cap = size_t(std::max(n, 1));
-    if (hipMalloc(&f.desc, f.cap * (h->W * 8 + 16)) != hipSuccess) {
-      f.cap = 0;
-      return mfail(SFM_ENOMEM, "hipMalloc failed (matcher keyframe)");
-    }
-  }
+  int rc = frame_reserve(h, f, n, size_t(std::max(n, 1)), h->W * 8 + 16, "matcher keyframe");
+  if (rc) return rc;
   f.n = n;
   f.pts = reinterpret_cast<double*>(f.desc + size_t(n) * h->W);
   f.ptsd = f.pts;
@@ -896,25 +851,25 @@ int sfm_matcher_match_keyframes(sfm_matcher* h, int32_t q_slot, const int32_t* q
                                 double min_distance, double max_distance, int32_t* idx0, int32_t* idx1,
                                 int32_t* n_matches) {
   SFM_TRACE("sfm_matcher_match_keyframes");
-  if (!h || !n_matches || !idx0 || !idx1) return mfail(SFM_EINVAL, "NULL argument");
+  if (!h || !n_matches || !idx0 || !idx1) return fail(SFM_EINVAL, "NULL argument");
   *n_matches = 0;
   if (q_slot < 0 || t_slot < 0 || size_t(q_slot) >= h->kf.size() || size_t(t_slot) >= h->kf.size())
-    return mfail(SFM_EINVAL, "keyframe slot not stored");
-  if (n_q < 0 || n_t < 0 || (n_q && !q_idx) || (n_t && !t_idx)) return mfail(SFM_EINVAL, "bad index lists");
-  if (!ok_ratio_window(ratio_test, min_distance, max_distance)) return mfail(SFM_EINVAL, "non-finite threshold");
+    return fail(SFM_EINVAL, "keyframe slot not stored");
+  if (n_q < 0 || n_t < 0 || (n_q && !q_idx) || (n_t && !t_idx)) return fail(SFM_EINVAL, "bad index lists");
+  if (!ok_ratio_window(ratio_test, min_distance, max_distance)) return fail(SFM_EINVAL, "non-finite threshold");
   const MatchFrame& fq = h->kf[size_t(q_slot)];
   const MatchFrame& ft = h->kf[size_t(t_slot)];
-  if (!rows_in_range(q_idx, n_q, fq.n)) return mfail(SFM_EINVAL, "query index out of range");
+  if (!rows_in_range(q_idx, n_q, fq.n)) return fail(SFM_EINVAL, "query index out of range");
   if (q_pts) {
     std::vector<char> seen(size_t(fq.n), 0);
     for (int32_t i = 0; i < n_q; ++i) {
-      if (seen[size_t(q_idx[i])]) return mfail(SFM_EINVAL, "query index repeated with given positions");
+      if (seen[size_t(q_idx[i])]) return fail(SFM_EINVAL, "query index repeated with given positions");
       seen[size_t(q_idx[i])] = 1;
     }
   }
-  if (!rows_in_range(t_idx, n_t, ft.n)) return mfail(SFM_EINVAL, "train index out of range");
+  if (!rows_in_range(t_idx, n_t, ft.n)) return fail(SFM_EINVAL, "train index out of range");
   if (n_q == 0 || n_t < 2) return 0;  // reference UB with < 2 train rows: no matches
-  if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
+  if (hipSetDevice(h->device) != hipSuccess) return fail(SFM_EIO, "hipSetDevice failed");
   int rc = 0;
   // stage: q_idx | t_idx | (8-B aligned) query positions at their rows
   const size_t ni = (size_t(n_q) + n_t + 1) & ~size_t(1);
@@ -950,24 +905,24 @@ int sfm_matcher_pair_points(sfm_matcher* h, int32_t slot0, const int32_t* idx0, 
                             int32_t capacity, int32_t* m0, int32_t* m1, double* X, int32_t* n_kept,
                             int32_t* n_matched) {
   SFM_TRACE("sfm_matcher_pair_points");
-  if (!h || !n_kept || !n_matched || !m0 || !m1 || !X) return mfail(SFM_EINVAL, "NULL argument");
+  if (!h || !n_kept || !n_matched || !m0 || !m1 || !X) return fail(SFM_EINVAL, "NULL argument");
   *n_kept = 0;
   *n_matched = 0;
-  if (!K9_0 || !R9_0 || !t3_0 || !K9_1 || !R9_1 || !t3_1) return mfail(SFM_EINVAL, "NULL matrix");
+  if (!K9_0 || !R9_0 || !t3_0 || !K9_1 || !R9_1 || !t3_1) return fail(SFM_EINVAL, "NULL matrix");
   if (slot0 < 0 || slot1 < 0 || size_t(slot0) >= h->kf.size() || size_t(slot1) >= h->kf.size())
-    return mfail(SFM_EINVAL, "keyframe slot not stored");
-  if (n0 < 0 || n1 < 0 || capacity < 0 || (n0 && !idx0) || (n1 && !idx1)) return mfail(SFM_EINVAL, "bad index lists");
+    return fail(SFM_EINVAL, "keyframe slot not stored");
+  if (n0 < 0 || n1 < 0 || capacity < 0 || (n0 && !idx0) || (n1 && !idx1)) return fail(SFM_EINVAL, "bad index lists");
   if (!ok_ratio_window(ratio_test, min_distance, max_distance) || !std::isfinite(max_err))
-    return mfail(SFM_EINVAL, "non-finite threshold");
+    return fail(SFM_EINVAL, "non-finite threshold");
   sfm::PairArgs pa;
   if (!sfm::compose_pair(K9_0, R9_0, t3_0, K9_1, R9_1, t3_1, max_err, &pa))
-    return mfail(SFM_EINVAL, "K must be finite and upper triangular with K[8] = 1, R and t finite");
+    return fail(SFM_EINVAL, "K must be finite and upper triangular with K[8] = 1, R and t finite");
   const MatchFrame& f1 = h->kf[size_t(slot1)];
   if (!rows_in_range(idx0, n0, h->kf[size_t(slot0)].n))
-    return mfail(SFM_EINVAL, "row index out of range (older keyframe)");
-  if (!rows_in_range(idx1, n1, f1.n)) return mfail(SFM_EINVAL, "row index out of range (new keyframe)");
+    return fail(SFM_EINVAL, "row index out of range (older keyframe)");
+  if (!rows_in_range(idx1, n1, f1.n)) return fail(SFM_EINVAL, "row index out of range (new keyframe)");
   if (n0 == 0 || n1 < 2) return 0;  // reference UB with < 2 train rows: no matches
-  if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
+  if (hipSetDevice(h->device) != hipSuccess) return fail(SFM_EIO, "hipSetDevice failed");
   const int32_t off[2] = {0, n0};
   int32_t first = -1, kept = 0, matched = 0;
   const int rc = pair_points_run(h, 1, &slot0, idx0, off, f1, idx1, n1, ratio_test, min_distance, max_distance, &pa,
@@ -990,37 +945,37 @@ int sfm_matcher_pair_points_first(sfm_matcher* h, int32_t n_pairs, const int32_t
                                   const double* t3_1, double max_err, int32_t capacity, int32_t* first, int32_t* m0,
                                   int32_t* m1, double* X, int32_t* n_kept, int32_t* n_matched) {
   SFM_TRACE("sfm_matcher_pair_points_first");
-  if (!h || !first || !n_kept || !n_matched || !m0 || !m1 || !X) return mfail(SFM_EINVAL, "NULL argument");
+  if (!h || !first || !n_kept || !n_matched || !m0 || !m1 || !X) return fail(SFM_EINVAL, "NULL argument");
   *first = -1;
-  if (n_pairs < 0 || n_pairs > 65535) return mfail(SFM_EINVAL, "n_pairs must be in 0..65535");
+  if (n_pairs < 0 || n_pairs > 65535) return fail(SFM_EINVAL, "n_pairs must be in 0..65535");
   for (int32_t b = 0; b < n_pairs; ++b) n_kept[b] = n_matched[b] = 0;
   if (n_pairs == 0) return 0;
-  if (!slot0 || !idx0_off) return mfail(SFM_EINVAL, "NULL pair list");
-  if (!K9_0 || !R9_0 || !t3_0 || !K9_1 || !R9_1 || !t3_1) return mfail(SFM_EINVAL, "NULL matrix");
-  if (slot1 < 0 || size_t(slot1) >= h->kf.size()) return mfail(SFM_EINVAL, "keyframe slot not stored");
-  if (n1 < 0 || capacity < 0 || (n1 && !idx1)) return mfail(SFM_EINVAL, "bad index lists");
-  if (idx0_off[0] != 0) return mfail(SFM_EINVAL, "idx0_off[0] must be 0");
+  if (!slot0 || !idx0_off) return fail(SFM_EINVAL, "NULL pair list");
+  if (!K9_0 || !R9_0 || !t3_0 || !K9_1 || !R9_1 || !t3_1) return fail(SFM_EINVAL, "NULL matrix");
+  if (slot1 < 0 || size_t(slot1) >= h->kf.size()) return fail(SFM_EINVAL, "keyframe slot not stored");
+  if (n1 < 0 || capacity < 0 || (n1 && !idx1)) return fail(SFM_EINVAL, "bad index lists");
+  if (idx0_off[0] != 0) return fail(SFM_EINVAL, "idx0_off[0] must be 0");
   for (int32_t b = 0; b < n_pairs; ++b)
-    if (idx0_off[b + 1] < idx0_off[b]) return mfail(SFM_EINVAL, "idx0_off must not decrease");
+    if (idx0_off[b + 1] < idx0_off[b]) return fail(SFM_EINVAL, "idx0_off must not decrease");
   const int total = idx0_off[n_pairs];
-  if (total && !idx0) return mfail(SFM_EINVAL, "bad index lists");
+  if (total && !idx0) return fail(SFM_EINVAL, "bad index lists");
   if (!ok_ratio_window(ratio_test, min_distance, max_distance) || !std::isfinite(max_err))
-    return mfail(SFM_EINVAL, "non-finite threshold");
+    return fail(SFM_EINVAL, "non-finite threshold");
   const MatchFrame& f1 = h->kf[size_t(slot1)];
-  if (!rows_in_range(idx1, n1, f1.n)) return mfail(SFM_EINVAL, "row index out of range (new keyframe)");
+  if (!rows_in_range(idx1, n1, f1.n)) return fail(SFM_EINVAL, "row index out of range (new keyframe)");
   std::vector<sfm::PairArgs> pa;
   pa.resize(size_t(n_pairs));
   for (int32_t b = 0; b < n_pairs; ++b) {
-    if (slot0[b] < 0 || size_t(slot0[b]) >= h->kf.size()) return mfail(SFM_EINVAL, "keyframe slot not stored");
-    if (slot0[b] == slot1) return mfail(SFM_EINVAL, "an older keyframe's slot is the new keyframe's");
+    if (slot0[b] < 0 || size_t(slot0[b]) >= h->kf.size()) return fail(SFM_EINVAL, "keyframe slot not stored");
+    if (slot0[b] == slot1) return fail(SFM_EINVAL, "an older keyframe's slot is the new keyframe's");
     if (!rows_in_range(idx0 + idx0_off[b], idx0_off[b + 1] - idx0_off[b], h->kf[size_t(slot0[b])].n))
-      return mfail(SFM_EINVAL, "row index out of range (older keyframe)");
+      return fail(SFM_EINVAL, "row index out of range (older keyframe)");
     if (!sfm::compose_pair(K9_0 + 9 * size_t(b), R9_0 + 9 * size_t(b), t3_0 + 3 * size_t(b), K9_1, R9_1, t3_1, max_err,
                            &pa[size_t(b)]))
-      return mfail(SFM_EINVAL, "K must be finite and upper triangular with K[8] = 1, R and t finite");
+      return fail(SFM_EINVAL, "K must be finite and upper triangular with K[8] = 1, R and t finite");
   }
   if (total == 0 || n1 < 2) return 0;  // reference UB with < 2 train rows: no matches
-  if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
+  if (hipSetDevice(h->device) != hipSuccess) return fail(SFM_EIO, "hipSetDevice failed");
   return pair_points_run(h, n_pairs, slot0, idx0, idx0_off, f1, idx1, n1, ratio_test, min_distance, max_distance,
                          pa.data(), capacity, first, m0, m1, X, n_kept, n_matched);
 }
@@ -1033,28 +988,28 @@ int sfm_matcher_refind_points(sfm_matcher* h, int32_t q_slot, const int32_t* q_i
                               const int32_t* t_idx, int32_t n_t, double ratio_test, double min_distance,
                               double max_distance, int32_t* idx0, int32_t* idx1, int32_t* n_matches) {
   SFM_TRACE("sfm_matcher_refind_points");
-  if (!h || !n_matches || !idx0 || !idx1) return mfail(SFM_EINVAL, "NULL argument");
+  if (!h || !n_matches || !idx0 || !idx1) return fail(SFM_EINVAL, "NULL argument");
   *n_matches = 0;
-  if (!K9 || !R9 || !t3) return mfail(SFM_EINVAL, "NULL matrix");
+  if (!K9 || !R9 || !t3) return fail(SFM_EINVAL, "NULL matrix");
   if (q_slot < 0 || t_slot < 0 || size_t(q_slot) >= h->kf.size() || size_t(t_slot) >= h->kf.size())
-    return mfail(SFM_EINVAL, "keyframe slot not stored");
-  if (n_q < 0 || n_t < 0 || (n_q && (!q_idx || !X)) || (n_t && !t_idx)) return mfail(SFM_EINVAL, "bad index lists");
-  if (!ok_ratio_window(ratio_test, min_distance, max_distance)) return mfail(SFM_EINVAL, "non-finite threshold");
+    return fail(SFM_EINVAL, "keyframe slot not stored");
+  if (n_q < 0 || n_t < 0 || (n_q && (!q_idx || !X)) || (n_t && !t_idx)) return fail(SFM_EINVAL, "bad index lists");
+  if (!ok_ratio_window(ratio_test, min_distance, max_distance)) return fail(SFM_EINVAL, "non-finite threshold");
   for (int i = 0; i < 9; ++i)
-    if (!std::isfinite(K9[i]) || !std::isfinite(R9[i])) return mfail(SFM_EINVAL, "non-finite matrix");
+    if (!std::isfinite(K9[i]) || !std::isfinite(R9[i])) return fail(SFM_EINVAL, "non-finite matrix");
   for (int i = 0; i < 3; ++i)
-    if (!std::isfinite(t3[i])) return mfail(SFM_EINVAL, "non-finite matrix");
+    if (!std::isfinite(t3[i])) return fail(SFM_EINVAL, "non-finite matrix");
   const MatchFrame& fq = h->kf[size_t(q_slot)];
   const MatchFrame& ft = h->kf[size_t(t_slot)];
-  if (!rows_in_range(q_idx, n_q, fq.n)) return mfail(SFM_EINVAL, "query index out of range");
+  if (!rows_in_range(q_idx, n_q, fq.n)) return fail(SFM_EINVAL, "query index out of range");
   std::vector<char> seen(size_t(fq.n), 0);
   for (int32_t i = 0; i < n_q; ++i) {
-    if (seen[size_t(q_idx[i])]) return mfail(SFM_EINVAL, "query index repeated");
+    if (seen[size_t(q_idx[i])]) return fail(SFM_EINVAL, "query index repeated");
     seen[size_t(q_idx[i])] = 1;
   }
-  if (!rows_in_range(t_idx, n_t, ft.n)) return mfail(SFM_EINVAL, "train index out of range");
+  if (!rows_in_range(t_idx, n_t, ft.n)) return fail(SFM_EINVAL, "train index out of range");
   if (n_q == 0 || n_t < 2) return 0;  // reference UB with < 2 train rows: no matches
-  if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
+  if (hipSetDevice(h->device) != hipSuccess) return fail(SFM_EIO, "hipSetDevice failed");
   int rc = 0;
   // stage: q_idx | t_idx | (8-B aligned) X
   const size_t ni = (size_t(n_q) + n_t + 1) & ~size_t(1);
@@ -1078,10 +1033,10 @@ int sfm_matcher_refind_points(sfm_matcher* h, int32_t q_slot, const int32_t* q_i
 
 int sfm_matcher_knn2(sfm_matcher* h, const uint8_t* desc0, int32_t n0, const uint8_t* desc1, int32_t n1,
                      int32_t* best_idx, int32_t* best_dist, int32_t* second_idx, int32_t* second_dist) {
-  if (!h) return mfail(SFM_EINVAL, "handle is NULL");
-  if (n0 < 0 || n1 < 0 || (n0 && !desc0) || (n1 && !desc1)) return mfail(SFM_EINVAL, "bad arguments");
+  if (!h) return fail(SFM_EINVAL, "handle is NULL");
+  if (n0 < 0 || n1 < 0 || (n0 && !desc0) || (n1 && !desc1)) return fail(SFM_EINVAL, "bad arguments");
   if (n0 == 0) return 0;
-  if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
+  if (hipSetDevice(h->device) != hipSuccess) return fail(SFM_EIO, "hipSetDevice failed");
   int rc = 0;
   const size_t w0 = size_t(n0) * h->W, w1 = size_t(n1) * h->W;
   auto* st = pbuf<uint64_t>(h, "in", w0 + w1, &rc);
@@ -1098,7 +1053,7 @@ int sfm_matcher_knn2(sfm_matcher* h, const uint8_t* desc0, int32_t n0, const uin
   if ((rc = launch_knn(h, d, nullptr, n0, d + w0, nullptr, n1, part, nslice))) return rc;
   k_knn2_merge<<<(n0 + 255) / 256, 256, 0, h->stream>>>(part, n0, nslice, out);
   hipMemcpyAsync(res, out, 4 * size_t(n0) * sizeof(int), hipMemcpyDeviceToHost, h->stream);
-  if (hipStreamSynchronize(h->stream) != hipSuccess) return mfail(SFM_EIO, "matcher kernels failed");
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(SFM_EIO, "matcher kernels failed");
   std::memcpy(best_idx, res, n0 * sizeof(int));
   std::memcpy(best_dist, res + n0, n0 * sizeof(int));
   std::memcpy(second_idx, res + 2 * size_t(n0), n0 * sizeof(int));
@@ -1107,31 +1062,28 @@ int sfm_matcher_knn2(sfm_matcher* h, const uint8_t* desc0, int32_t n0, const uin
 }
 
 int sfm_matcher_last_time(sfm_matcher* h, double* ms2) {
-  if (!h || !ms2) return mfail(SFM_EINVAL, "NULL argument");
+  if (!h || !ms2) return fail(SFM_EINVAL, "NULL argument");
   ms2[0] = h->last_knn_ms;
   ms2[1] = h->last_total_ms;
   return 0;
 }
 
-// One-shot forms: a cached matcher per (device, calling thread), destroyed
-// at thread exit, so repeated calls allocate nothing.
+// One-shot forms: a cached matcher per (device, descriptor width) and calling
+// thread, destroyed at thread exit, so repeated calls allocate nothing.
 static sfm_matcher* cached_matcher(int32_t device, int32_t desc_bytes, int* rc) {
-  struct Cache {
-    std::map<std::pair<int, int>, sfm_matcher*> m;
-    ~Cache() {
-      for (auto& kv : m) sfm_matcher_destroy(kv.second);
-    }
+  struct Cached {
+    sfm_matcher* h = nullptr;
+    int init(const std::pair<int, int>& key) { return sfm_matcher_create(key.first, key.second, &h); }
+    ~Cached() { sfm_matcher_destroy(h); }
   };
-  static thread_local Cache cache;
-  sfm_matcher*& h = cache.m[{device, desc_bytes}];
-  if (!h && (*rc = sfm_matcher_create(device, desc_bytes, &h))) h = nullptr;
-  return h;
+  Cached* c = sfm::thread_ctx<Cached>(std::pair<int, int>(device, desc_bytes), rc);
+  return c ? c->h : nullptr;
 }
 
 int sfm_knn2_hamming(int32_t device, const uint8_t* desc0, int32_t n0, const uint8_t* desc1, int32_t n1,
                      int32_t desc_bytes, int32_t* best_idx, int32_t* best_dist, int32_t* second_idx,
                      int32_t* second_dist) {
-  if (n0 < 0 || n1 < 0 || desc_bytes <= 0 || desc_bytes > 512) return mfail(SFM_EINVAL, "bad sizes");
+  if (n0 < 0 || n1 < 0 || desc_bytes <= 0 || desc_bytes > 512) return fail(SFM_EINVAL, "bad sizes");
   if (n0 == 0) return 0;
   int rc = 0;
   sfm_matcher* h = cached_matcher(device, desc_bytes, &rc);
@@ -1142,9 +1094,9 @@ int sfm_knn2_hamming(int32_t device, const uint8_t* desc0, int32_t n0, const uin
 int sfm_match_features(int32_t device, const double* pts0, const uint8_t* desc0, int32_t n0, const double* pts1,
                        const uint8_t* desc1, int32_t n1, int32_t desc_bytes, double ratio_test, double min_distance,
                        double max_distance, int32_t* idx0, int32_t* idx1, int32_t* n_matches) {
-  if (!n_matches) return mfail(SFM_EINVAL, "n_matches is NULL");
+  if (!n_matches) return fail(SFM_EINVAL, "n_matches is NULL");
   *n_matches = 0;
-  if (n0 < 0 || n1 < 0 || desc_bytes <= 0 || desc_bytes > 512) return mfail(SFM_EINVAL, "bad sizes");
+  if (n0 < 0 || n1 < 0 || desc_bytes <= 0 || desc_bytes > 512) return fail(SFM_EINVAL, "bad sizes");
   if (n0 == 0 || n1 < 2) return 0;  // reference UB with < 2 train rows: no matches
   int rc = 0;
   sfm_matcher* h = cached_matcher(device, desc_bytes, &rc);
@@ -1160,19 +1112,19 @@ int sfm_match_features(int32_t device, const double* pts0, const uint8_t* desc0,
 int sfm_filter_matches(int32_t device, int32_t n, const double* uv0, const double* uv1, const double* X,
                        const double* K9_0, const double* R9_0, const double* t3_0, const double* K9_1,
                        const double* R9_1, const double* t3_1, double max_err, uint8_t* status, double* F9) {
-  if (n < 0) return mfail(SFM_EINVAL, "negative size");
-  if (!K9_0 || !R9_0 || !t3_0 || !K9_1 || !R9_1 || !t3_1) return mfail(SFM_EINVAL, "NULL matrix");
-  if (n && (!uv0 || !uv1 || !X || !status)) return mfail(SFM_EINVAL, "NULL argument");
-  if (!std::isfinite(max_err)) return mfail(SFM_EINVAL, "non-finite threshold");
+  if (n < 0) return fail(SFM_EINVAL, "negative size");
+  if (!K9_0 || !R9_0 || !t3_0 || !K9_1 || !R9_1 || !t3_1) return fail(SFM_EINVAL, "NULL matrix");
+  if (n && (!uv0 || !uv1 || !X || !status)) return fail(SFM_EINVAL, "NULL argument");
+  if (!std::isfinite(max_err)) return fail(SFM_EINVAL, "non-finite threshold");
   sfm::PairArgs pa;
   if (!sfm::compose_pair(K9_0, R9_0, t3_0, K9_1, R9_1, t3_1, max_err, &pa))
-    return mfail(SFM_EINVAL, "K must be finite and upper triangular with K[8] = 1, R and t finite");
+    return fail(SFM_EINVAL, "K must be finite and upper triangular with K[8] = 1, R and t finite");
   if (F9) std::memcpy(F9, pa.F, sizeof(pa.F));
   if (n == 0) return 0;
   int rc = 0;
   sfm_matcher* h = cached_matcher(device, 64, &rc);
   if (!h) return rc;
-  if (hipSetDevice(device) != hipSuccess) return mfail(SFM_ENODEV, "hipSetDevice failed");
+  if (hipSetDevice(device) != hipSuccess) return fail(SFM_ENODEV, "hipSetDevice failed");
   double* st = pbuf<double>(h, "fin", 7 * size_t(n), &rc);
   double* d = dbuf<double>(h, "dfin", 7 * size_t(n), &rc);
   uint8_t* ds = dbuf<uint8_t>(h, "fst", size_t(n), &rc);
@@ -1185,24 +1137,24 @@ int sfm_filter_matches(int32_t device, int32_t n, const double* uv0, const doubl
   hipMemcpyAsync(d, st, sizeof(double) * 7 * size_t(n), hipMemcpyHostToDevice, h->stream);
   sfm::launch_filter(h->stream, n, d, d + 2 * size_t(n), d + 4 * size_t(n), pa, ds);
   hipMemcpyAsync(hs, ds, size_t(n), hipMemcpyDeviceToHost, h->stream);
-  if (hipStreamSynchronize(h->stream) != hipSuccess) return mfail(SFM_EIO, "filter kernel failed");
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(SFM_EIO, "filter kernel failed");
   std::memcpy(status, hs, size_t(n));
   return 0;
 }
 
 int sfm_representative_descriptors(int32_t device, const uint8_t* desc, const int32_t* row_off, int32_t n_pts,
                                    int32_t desc_bytes, int32_t* best, uint8_t* out) {
-  if (n_pts < 0 || desc_bytes <= 0 || desc_bytes > 512) return mfail(SFM_EINVAL, "bad sizes");
+  if (n_pts < 0 || desc_bytes <= 0 || desc_bytes > 512) return fail(SFM_EINVAL, "bad sizes");
   if (n_pts == 0) return 0;
-  if (!desc || !row_off || !best) return mfail(SFM_EINVAL, "NULL argument");
-  if (row_off[0] != 0) return mfail(SFM_EINVAL, "row_off[0] must be 0");
+  if (!desc || !row_off || !best) return fail(SFM_EINVAL, "NULL argument");
+  if (row_off[0] != 0) return fail(SFM_EINVAL, "row_off[0] must be 0");
   for (int32_t i = 0; i < n_pts; ++i)
     if (row_off[i + 1] <= row_off[i])
-      return mfail(SFM_EINVAL, "every point needs at least one descriptor (the reference reads row -1 otherwise)");
+      return fail(SFM_EINVAL, "every point needs at least one descriptor (the reference reads row -1 otherwise)");
   int rc = 0;
   sfm_matcher* h = cached_matcher(device, desc_bytes, &rc);
   if (!h) return rc;
-  if (hipSetDevice(device) != hipSuccess) return mfail(SFM_ENODEV, "hipSetDevice failed");
+  if (hipSetDevice(device) != hipSuccess) return fail(SFM_ENODEV, "hipSetDevice failed");
   const int W = h->W;
   const int rows = row_off[n_pts];
   auto* st = pbuf<uint64_t>(h, "in", size_t(rows) * W + size_t(n_pts) + 1, &rc);
@@ -1220,10 +1172,10 @@ int sfm_representative_descriptors(int32_t device, const uint8_t* desc, const in
 #define CASE(w) case w: k_repr<w><<<n_pts, 64, 0, h->stream>>>(d, o, n_pts, r); break;
     CASE(1) CASE(2) CASE(4) CASE(8) CASE(16) CASE(32) CASE(64)
 #undef CASE
-    default: return mfail(SFM_EINVAL, "descriptor width must be <= 512 bytes");
+    default: return fail(SFM_EINVAL, "descriptor width must be <= 512 bytes");
   }
   hipMemcpyAsync(res, r, size_t(n_pts) * sizeof(int), hipMemcpyDeviceToHost, h->stream);
-  if (hipStreamSynchronize(h->stream) != hipSuccess) return mfail(SFM_EIO, "kernel or copy failed");
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(SFM_EIO, "kernel or copy failed");
   std::memcpy(best, res, size_t(n_pts) * sizeof(int));
   if (out)
     for (int32_t i = 0; i < n_pts; ++i)
@@ -1247,32 +1199,32 @@ int sfm_track_pnp(sfm_matcher* h, sfm_map* map, int32_t n_prev, const int32_t* p
                   int32_t* n_matches, int32_t capacity, int32_t* inl_kp, int32_t* inl_pt3d, int32_t* n_inliers) {
   SFM_TRACE("sfm_track_pnp");
   if (!h || !map || !found || !n_matches || !n_inliers || !rvec || !tvec || !K9 || !inl_kp || !inl_pt3d)
-    return mfail(SFM_EINVAL, "NULL argument");
+    return fail(SFM_EINVAL, "NULL argument");
   *found = 0;
   *n_matches = 0;
   *n_inliers = 0;
   for (int i = 0; i < 3; ++i) rvec[i] = tvec[i] = 0.0;
-  if (h->frames_pushed < 2) return mfail(SFM_EINVAL, "push the previous and the current frame first");
-  if (!ok_ratio_window(ratio_test, min_distance, max_distance)) return mfail(SFM_EINVAL, "non-finite threshold");
-  if (iterations < 0 || iterations > sfm::pnp_max_iters()) return mfail(SFM_EINVAL, "bad iterations");
-  if (!(confidence > 0.0 && confidence < 1.0)) return mfail(SFM_EINVAL, "confidence must lie in (0, 1)");
+  if (h->frames_pushed < 2) return fail(SFM_EINVAL, "push the previous and the current frame first");
+  if (!ok_ratio_window(ratio_test, min_distance, max_distance)) return fail(SFM_EINVAL, "non-finite threshold");
+  if (iterations < 0 || iterations > sfm::pnp_max_iters()) return fail(SFM_EINVAL, "bad iterations");
+  if (!(confidence > 0.0 && confidence < 1.0)) return fail(SFM_EINVAL, "confidence must lie in (0, 1)");
   const MatchFrame& fp = h->frame[h->cur ^ 1];
   const MatchFrame& fc = h->frame[h->cur];
-  if (n_prev != fp.n || (n_prev && !prev_pt3d)) return mfail(SFM_EINVAL, "prev_pt3d must hold one entry per previous keypoint");
+  if (n_prev != fp.n || (n_prev && !prev_pt3d)) return fail(SFM_EINVAL, "prev_pt3d must hold one entry per previous keypoint");
   int32_t P = 0;
   int mdev = 0;
   const double* X = sfm::map_points_dev(map, &P, &mdev);
-  if (mdev != h->device) return mfail(SFM_EINVAL, "the map and the matcher are on different devices");
+  if (mdev != h->device) return fail(SFM_EINVAL, "the map and the matcher are on different devices");
   std::vector<int32_t> pidx;
   pidx.reserve(size_t(n_prev));
   for (int32_t i = 0; i < n_prev; ++i) {
-    if (prev_pt3d[i] >= P) return mfail(SFM_EINVAL, "map point index out of range");
+    if (prev_pt3d[i] >= P) return fail(SFM_EINVAL, "map point index out of range");
     if (prev_pt3d[i] >= 0) pidx.push_back(i);
   }
   const int n0 = int(pidx.size()), n1 = fc.n;
   if (n0 == 0 || n1 < 2) return 0;  // (as sfm_matcher_match_subset: no matches)
-  if (capacity < n0) return mfail(SFM_EINVAL, "capacity below the previous frame's matched keypoints");
-  if (hipSetDevice(h->device) != hipSuccess) return mfail(SFM_EIO, "hipSetDevice failed");
+  if (capacity < n0) return fail(SFM_EINVAL, "capacity below the previous frame's matched keypoints");
+  if (hipSetDevice(h->device) != hipSuccess) return fail(SFM_EIO, "hipSetDevice failed");
   int rc = 0;
   const int iters = iterations > 0 ? iterations : 1;
   const size_t n_up = size_t(n0) + size_t(n1) + size_t(n_prev);
@@ -1307,7 +1259,7 @@ int sfm_track_pnp(sfm_matcher* h, sfm_map* map, int32_t n_prev, const int32_t* p
                            confidence, dsub, dmodel, dcnt, dblk + 4, inl)))
     return rc;
   hipMemcpyAsync(hblk, dblk, sizeof(int) * blk, hipMemcpyDeviceToHost, h->stream);
-  if (hipStreamSynchronize(h->stream) != hipSuccess) return mfail(SFM_EIO, "tracking kernels failed");
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(SFM_EIO, "tracking kernels failed");
   const int m = hblk[0];
   *n_matches = m;
   if (m < min_matches || !hblk[4]) return 0;

@@ -1,0 +1,80 @@
+// Ownership templates shared by every handle.  No HIP includes: the growth
+// logic and the per-thread cache compile with a plain C++ compiler, so the
+// host sanitizer program (tests/asan) runs them over malloc / free.  The two
+// HIP memory policies, Stream and Event are in dev_mem.h.
+#pragma once
+#include <cstddef>
+#include <map>
+#include <memory>
+#include <utility>
+
+namespace sfm {
+
+// Move-only owner of one allocation.  Mem supplies
+//   static int alloc(void** p, size_t bytes)   (0 on success)
+//   static void release(void* p)
+//   static void drain(Stream s)                 (wait for the work on s)
+//   using Stream = ...
+template <typename Mem>
+class Buf {
+ public:
+  Buf() = default;
+  Buf(Buf&& o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr, o.bytes_ = 0; }
+  Buf& operator=(Buf&& o) noexcept {
+    if (this != &o) {
+      reset();
+      p_ = o.p_, bytes_ = o.bytes_;
+      o.p_ = nullptr, o.bytes_ = 0;
+    }
+    return *this;
+  }
+  Buf(const Buf&) = delete;
+  Buf& operator=(const Buf&) = delete;
+  ~Buf() { reset(); }
+
+  // Room for `need` bytes; the contents are DROPPED when it grows.  A buffer
+  // that has to grow first waits for `drain` (non-null: the stream whose
+  // work may still use the old allocation), releases, then allocates `want`
+  // (>= need) bytes.  Non-zero (Mem::alloc's code) on failure, the buffer
+  // then empty.
+  int reserve(size_t need, size_t want, typename Mem::Stream drain) {
+    if (bytes_ >= need) return 0;
+    if (drain && p_) Mem::drain(drain);
+    reset();
+    void* q = nullptr;
+    const int rc = Mem::alloc(&q, want);
+    if (rc) return rc;
+    p_ = q, bytes_ = want;
+    return 0;
+  }
+  void reset() {
+    if (p_) Mem::release(p_);
+    p_ = nullptr, bytes_ = 0;
+  }
+  size_t bytes() const { return bytes_; }
+  void* get() const { return p_; }
+  template <typename T>
+  T* as() const { return static_cast<T*>(p_); }
+
+ private:
+  void* p_ = nullptr;
+  size_t bytes_ = 0;
+};
+
+// The calling thread's context for `key` (the device, or whatever else the
+// context was made for), destroyed when the thread exits.  A context enters
+// the cache only after its init(key) returned 0: after a failed init nothing
+// is cached, *rc holds init's code, and the next call tries again.
+template <typename Ctx, typename Key>
+Ctx* thread_ctx(const Key& key, int* rc) {
+  static thread_local std::map<Key, std::unique_ptr<Ctx>> cache;
+  *rc = 0;
+  auto it = cache.find(key);
+  if (it != cache.end()) return it->second.get();
+  std::unique_ptr<Ctx> c(new Ctx());
+  *rc = c->init(key);
+  if (*rc) return nullptr;
+  return (cache[key] = std::move(c)).get();
+}
+
+}  // namespace sfm

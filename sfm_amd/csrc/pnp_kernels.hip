@@ -26,14 +26,12 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 #include "sfm_trace.h"
 #include "../../include/sfm_amd.h"
 #include "cv_linalg.h"
-
-void sfm_internal_set_error(const std::string& msg);
+#include "dev_mem.h"
 
 namespace sfm {
 namespace {
@@ -1064,33 +1062,48 @@ __global__ __launch_bounds__(64) void k_pnp_select(int n_arg, const int* __restr
   }
 }
 
+// result block: counts (4 ints = 16 B) | winner's model (6 doubles) | inliers
+constexpr size_t kOutHead = 16 + 6 * sizeof(double);
+
+// The calling thread's context on one device (thread_ctx).  The stream first:
+// members are destroyed in reverse order, so it goes last.
 struct PnPCtx {
-  hipStream_t stream = nullptr;
-  size_t cap = 0;
-  double* obj = nullptr;
-  double* img = nullptr;
+  Stream stream;
+  size_t cap = 0;  // points the four buffers below have room for
+  DevArr<double> obj, img;
   // one device block returned by ONE download: counts (4 ints), the
   // winner's model (6 doubles), the inlier list (cap ints)
-  int* out = nullptr;
-  int* inl = nullptr;
-  uint8_t* pin = nullptr;  // pinned staging: the points up, the block down
-  size_t pin_cap = 0;
-  int* sub = nullptr;
+  DevArr<int> out;
+  int* inl = nullptr;  // the list inside `out`
+  PinArr<uint8_t> pin;  // pinned staging: the points up, the block down
+  DevArr<int> sub;
   int sub_n = -1, sub_iters = -1;  // the (n, iterations) whose subsets `sub` holds
-  double* model = nullptr;
-  int* cnt = nullptr;
-  ~PnPCtx() {
-    if (stream) hipStreamSynchronize(stream);
-    hipFree(obj); hipFree(img); hipFree(out); hipFree(sub); hipFree(model); hipFree(cnt);
-    if (pin) hipHostFree(pin);
-    if (stream) hipStreamDestroy(stream);
+  DevArr<double> model;
+  DevArr<int> cnt;
+  int init(int /*device*/) {
+    if (stream.create(hipStreamNonBlocking) != hipSuccess) return fail(SFM_EIO, "hipStreamCreate failed");
+    if (sub.reserve(sizeof(int) * kModel * kMaxIters, sizeof(int) * kModel * kMaxIters, nullptr) ||
+        model.reserve(sizeof(double) * 6 * kMaxIters, sizeof(double) * 6 * kMaxIters, nullptr) ||
+        cnt.reserve(sizeof(int) * kMaxIters, sizeof(int) * kMaxIters, nullptr))
+      return fail(SFM_ENOMEM, "hipMalloc failed");
+    return 0;
+  }
+  // room for n points; the four buffers grow together
+  int reserve(size_t n) {
+    if (n <= cap) return 0;
+    cap = 0;
+    const size_t want = std::max<size_t>(n, 1024);
+    const size_t need_pin = sizeof(double) * 5 * n + kOutHead + sizeof(int) * n;
+    if (obj.reserve(sizeof(double) * 3 * n, sizeof(double) * 3 * want, stream) ||
+        img.reserve(sizeof(double) * 2 * n, sizeof(double) * 2 * want, stream) ||
+        out.reserve(kOutHead + sizeof(int) * n, kOutHead + sizeof(int) * want, stream) ||
+        pin.reserve(need_pin, sizeof(double) * 5 * want + kOutHead + sizeof(int) * want, stream))
+      return fail(SFM_ENOMEM, "hipMalloc failed");
+    inl = reinterpret_cast<int*>(out.as<uint8_t>() + kOutHead);
+    cap = want;
+    return 0;
   }
 };
-
-int pfail(int code, const char* msg) {
-  sfm_internal_set_error(msg);
-  return code;
-}
 
 }  // namespace
 }  // namespace sfm
@@ -1105,8 +1118,8 @@ namespace sfm {
 int pnp_ransac_dev(hipStream_t s, const int* d_n, int gate, const double* d_obj, const double* d_img, const double* K9,
                    int iterations, double reproj_err, double confidence, int* d_sub, double* d_model, int* d_cnt,
                    int* d_res, int* d_inl) {
-  if (iterations < 0 || iterations > kMaxIters) return pfail(SFM_EINVAL, "bad iterations");
-  if (!(confidence > 0.0 && confidence < 1.0)) return pfail(SFM_EINVAL, "confidence must lie in (0, 1)");
+  if (iterations < 0 || iterations > kMaxIters) return fail(SFM_EINVAL, "bad iterations");
+  if (!(confidence > 0.0 && confidence < 1.0)) return fail(SFM_EINVAL, "confidence must lie in (0, 1)");
   const PnPCam k{K9[0], K9[4], K9[2], K9[5]};
   const int iters = iterations > 0 ? iterations : 1;
   const float thr = float(reproj_err * reproj_err);
@@ -1115,7 +1128,7 @@ int pnp_ransac_dev(hipStream_t s, const int* d_n, int gate, const double* d_obj,
   k_pnp_epnp<<<iters, 192, 0, s>>>(d_obj, d_img, d_sub, k, d_model);
   k_pnp_count<<<iters, 256, 0, s>>>(0, d_n, d_obj, d_img, d_model, k, thr, d_cnt);
   k_pnp_select<<<1, 64, 0, s>>>(0, d_n, gate, iters, confidence, d_obj, d_img, d_model, d_cnt, k, thr, d_res, d_inl);
-  return hipGetLastError() == hipSuccess ? 0 : pfail(SFM_EIO, "PnP launch failed");
+  return hipGetLastError() == hipSuccess ? 0 : fail(SFM_EIO, "PnP launch failed");
 }
 int pnp_max_iters() { return kMaxIters; }
 // sfm_linalg_probe's 12x12 op (device buffers, stream s; no synchronisation)
@@ -1132,67 +1145,34 @@ extern "C" int sfm_pnp_ransac(int32_t device, int32_t n, const double* obj, cons
                               int32_t iterations, double reproj_err, double confidence, double* rvec, double* tvec,
                               int32_t* inliers, int32_t* n_inliers, int32_t* found) {
   SFM_TRACE("sfm_pnp_ransac");
-  if (!found || !n_inliers || !rvec || !tvec || !K9) return pfail(SFM_EINVAL, "NULL argument");
+  if (!found || !n_inliers || !rvec || !tvec || !K9) return fail(SFM_EINVAL, "NULL argument");
   *found = 0;
   *n_inliers = 0;
-  if (n < 0 || iterations < 0 || iterations > kMaxIters) return pfail(SFM_EINVAL, "bad n or iterations");
-  if (!(confidence > 0.0 && confidence < 1.0)) return pfail(SFM_EINVAL, "confidence must lie in (0, 1)");
-  if (n > 0 && (!obj || !img)) return pfail(SFM_EINVAL, "NULL point arrays");
+  if (n < 0 || iterations < 0 || iterations > kMaxIters) return fail(SFM_EINVAL, "bad n or iterations");
+  if (!(confidence > 0.0 && confidence < 1.0)) return fail(SFM_EINVAL, "confidence must lie in (0, 1)");
+  if (n > 0 && (!obj || !img)) return fail(SFM_EINVAL, "NULL point arrays");
   if (n < kModel) return 0;  // RANSAC needs a full subset: no model (as cv::solvePnPRansac's false)
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return pfail(SFM_ENODEV, "no device");
-  if (hipSetDevice(device) != hipSuccess) return pfail(SFM_ENODEV, "hipSetDevice failed");
-  struct Cache {
-    std::map<int, PnPCtx*> m;
-    ~Cache() {
-      for (auto& kv : m) delete kv.second;
-    }
-  };
-  static thread_local Cache cache;
-  PnPCtx*& c = cache.m[device];
-  if (!c) {
-    c = new PnPCtx();
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-      delete c;
-      c = nullptr;
-      return pfail(SFM_EIO, "hipStreamCreate failed");
-    }
-    if (hipMalloc(&c->sub, sizeof(int) * kModel * kMaxIters) != hipSuccess ||
-        hipMalloc(&c->model, sizeof(double) * 6 * kMaxIters) != hipSuccess ||
-        hipMalloc(&c->cnt, sizeof(int) * kMaxIters) != hipSuccess)
-      return pfail(SFM_ENOMEM, "hipMalloc failed");
-  }
-  // result block: counts (4 ints = 16 B) | winner's model (6 doubles) | inliers
-  constexpr size_t kOutHead = 16 + 6 * sizeof(double);
-  if (size_t(n) > c->cap) {
-    hipFree(c->obj); hipFree(c->img); hipFree(c->out);
-    c->obj = nullptr; c->img = nullptr; c->out = nullptr; c->inl = nullptr; c->cap = 0;
-    if (c->pin) hipHostFree(c->pin);
-    c->pin = nullptr;
-    const size_t cap = std::max<size_t>(size_t(n), 1024);
-    if (hipMalloc(&c->obj, sizeof(double) * 3 * cap) != hipSuccess ||
-        hipMalloc(&c->img, sizeof(double) * 2 * cap) != hipSuccess ||
-        hipMalloc(&c->out, kOutHead + sizeof(int) * cap) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&c->pin), sizeof(double) * 5 * cap + kOutHead + sizeof(int) * cap) !=
-            hipSuccess)
-      return pfail(SFM_ENOMEM, "hipMalloc failed");
-    c->inl = reinterpret_cast<int*>(reinterpret_cast<uint8_t*>(c->out) + kOutHead);
-    c->cap = cap;
-  }
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(SFM_ENODEV, "no device");
+  if (hipSetDevice(device) != hipSuccess) return fail(SFM_ENODEV, "hipSetDevice failed");
+  int rc = 0;
+  PnPCtx* c = thread_ctx<PnPCtx>(device, &rc);
+  if (!c) return rc;
+  if ((rc = c->reserve(size_t(n)))) return rc;
   const PnPCam k{K9[0], K9[4], K9[2], K9[5]};
   const int iters = iterations > 0 ? iterations : 1;
   const float thr = float(reproj_err * reproj_err);
   hipStream_t s = c->stream;
   // the points through the pinned stage (the previous call has drained the
   // stream: it synchronised before returning)
-  double* pin_obj = reinterpret_cast<double*>(c->pin);
+  double* pin_obj = c->pin.as<double>();
   double* pin_img = pin_obj + 3 * size_t(n);
   uint8_t* pin_out = c->pin + sizeof(double) * 5 * c->cap;
   std::memcpy(pin_obj, obj, sizeof(double) * 3 * size_t(n));
   std::memcpy(pin_img, img, sizeof(double) * 2 * size_t(n));
   if (hipMemcpyAsync(c->obj, pin_obj, sizeof(double) * 3 * size_t(n), hipMemcpyHostToDevice, s) != hipSuccess ||
       hipMemcpyAsync(c->img, pin_img, sizeof(double) * 2 * size_t(n), hipMemcpyHostToDevice, s) != hipSuccess)
-    return pfail(SFM_EIO, "upload failed");
+    return fail(SFM_EIO, "upload failed");
   // the subsets depend on (n, iterations) alone (cv::RNG(-1) restarted per
   // call): drawn once per pair, then reused
   if (c->sub_n != n || c->sub_iters != iters) {
@@ -1208,7 +1188,7 @@ extern "C" int sfm_pnp_ransac(int32_t device, int32_t n, const double* obj, cons
   const size_t down = kOutHead + (inliers ? sizeof(int) * size_t(n) : 0);
   if (hipMemcpyAsync(pin_out, c->out, down, hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
-    return pfail(SFM_EIO, "PnP kernels failed");
+    return fail(SFM_EIO, "PnP kernels failed");
   int res[4];
   double mdl[6];
   std::memcpy(res, pin_out, sizeof(res));

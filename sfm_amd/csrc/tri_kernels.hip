@@ -8,13 +8,11 @@
 // so the K[R|t] composition is the build's reading (parity unpinned; oracle:
 // oracle/pnp_oracle.py triangulate_points).  One lane per point.
 #include <hip/hip_runtime.h>
-#include <map>
 #include <string>
 #include "../../include/sfm_amd.h"
 #include "cv_linalg.h"
 #include "tri_point.h"
-
-void sfm_internal_set_error(const std::string& msg);
+#include "dev_mem.h"
 
 namespace sfm {
 namespace {
@@ -39,37 +37,15 @@ __global__ __launch_bounds__(256) void k_triangulate(int n, const int32_t* __res
 // Per calling thread and device: a stream and a grow-only buffer, kept
 // between calls (triangulation runs once per keyframe pair in the mapping
 // loop: creating a stream and allocating per call cost ~4 ms per call).
+// The stream first: members are destroyed in reverse order, so it goes last.
 struct TriCtx {
-  hipStream_t s = nullptr;
-  char* buf = nullptr;
-  size_t cap = 0;
-};
-struct TriCache {
-  std::map<int, TriCtx> by_dev;
-  ~TriCache() {
-    for (auto& kv : by_dev) {
-      (void)hipSetDevice(kv.first);
-      if (kv.second.s) (void)hipStreamDestroy(kv.second.s);
-      if (kv.second.buf) (void)hipFree(kv.second.buf);
-    }
+  Stream s;
+  DevArr<char> buf;
+  int init(int /*device*/) {
+    if (s.create(hipStreamNonBlocking) == hipSuccess) return 0;
+    return fail(SFM_ENOMEM, "stream or device buffer allocation failed");
   }
 };
-TriCtx* tri_ctx(int device, size_t bytes) {
-  static thread_local TriCache cache;
-  TriCtx& c = cache.by_dev[device];
-  if (!c.s && hipStreamCreateWithFlags(&c.s, hipStreamNonBlocking) != hipSuccess) {
-    c.s = nullptr;
-    return nullptr;
-  }
-  if (c.cap < bytes) {
-    if (c.buf) (void)hipFree(c.buf);
-    c.buf = nullptr;
-    c.cap = 0;
-    if (hipMalloc(&c.buf, bytes) != hipSuccess) return nullptr;
-    c.cap = bytes;
-  }
-  return &c;
-}
 
 }  // namespace
 }  // namespace sfm
@@ -79,10 +55,6 @@ using namespace sfm;
 extern "C" int sfm_triangulate_points(int32_t device, int32_t n, const int32_t* cam0, const int32_t* cam1,
                                       const double* uv0, const double* uv1, int32_t n_cams, const double* P,
                                       double* X) {
-  auto fail = [](int code, const char* m) {
-    sfm_internal_set_error(m);
-    return code;
-  };
   if (n < 0 || n_cams < 0) return fail(SFM_EINVAL, "negative size");
   if (n == 0) return 0;
   if (!cam0 || !cam1 || !uv0 || !uv1 || !P || !X) return fail(SFM_EINVAL, "NULL argument");
@@ -95,15 +67,17 @@ extern "C" int sfm_triangulate_points(int32_t device, int32_t n, const int32_t* 
   // one buffer for inputs and output (keyframe-sized batches), kept per thread
   const size_t b_idx = sizeof(int32_t) * 2 * size_t(n), b_uv = sizeof(double) * 4 * size_t(n),
                b_P = sizeof(double) * 12 * size_t(n_cams), b_X = sizeof(double) * 3 * size_t(n);
-  TriCtx* ctx = tri_ctx(device, b_idx + b_uv + b_P + b_X + 64);
-  if (!ctx) return fail(SFM_ENOMEM, "stream or device buffer allocation failed");
+  const size_t bytes = b_idx + b_uv + b_P + b_X + 64;
+  int rc = 0;
+  TriCtx* ctx = thread_ctx<TriCtx>(device, &rc);
+  if (!ctx) return rc;
+  if (ctx->buf.reserve(bytes, bytes, ctx->s)) return fail(SFM_ENOMEM, "stream or device buffer allocation failed");
   char* buf = ctx->buf;
   int32_t* d_c = reinterpret_cast<int32_t*>(buf);
   double* d_uv = reinterpret_cast<double*>(buf + ((b_idx + 15) & ~size_t(15)));
   double* d_P = d_uv + 4 * size_t(n);
   double* d_X = d_P + 12 * size_t(n_cams);
   hipStream_t s = ctx->s;
-  int rc = 0;
   if (hipMemcpyAsync(d_c, cam0, sizeof(int32_t) * n, hipMemcpyHostToDevice, s) != hipSuccess ||
       hipMemcpyAsync(d_c + n, cam1, sizeof(int32_t) * n, hipMemcpyHostToDevice, s) != hipSuccess ||
       hipMemcpyAsync(d_uv, uv0, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s) != hipSuccess ||

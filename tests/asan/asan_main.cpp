@@ -12,6 +12,11 @@
 //     path's degree limit at 64 / 65 observations); and the
 //     plan of set_problem (regimes, parameter routes, the stage's regions)
 //     over a grid of sizes around every threshold, with the Schur shape;
+//   * sfm_amd/csrc/owner.h -- Buf's growth (no-op below capacity, one release
+//     per growth, a failed allocation leaves it empty and the next reserve
+//     succeeds, moves free nothing twice) over a malloc / free policy that
+//     fails its k-th allocation, and thread_ctx (a failed init caches nothing,
+//     one context per thread, destroyed at thread exit: the leak check);
 //   * sfm_amd/csrc/ba_lm.h -- the LM trust-region state machine both loop
 //     drivers run: the oracle's 18 branch traces replayed through it
 //     (tests/golden/lm_replay.txt), and the branches no scene reaches from
@@ -34,6 +39,7 @@
 #include <map>
 #include <numeric>
 #include <random>
+#include <thread>
 #include <vector>
 
 #include "../../include/sfm_amd.h"
@@ -41,6 +47,7 @@
 #include "../../sfm_amd/csrc/ba_host_layout.h"
 #include "../../sfm_amd/csrc/ba_lm.h"
 #include "../../sfm_amd/csrc/ba_plan.h"
+#include "../../sfm_amd/csrc/owner.h"
 
 // ---- the oracle's C entry points (oracle/*.cpp, linked in) ----
 extern "C" {
@@ -409,6 +416,103 @@ static void check_plan() {
   }
   std::printf("  plan: %d grid points, %zu literal rows, Schur shape, small-path bounds ok\n", n,
               sizeof(rows) / sizeof(rows[0]));
+}
+
+// ---- the ownership templates (sfm_amd/csrc/owner.h) ----
+// malloc / free with counters; allocation number fail_at (counted from 1) fails
+struct TestMem {
+  using Stream = const char*;  // "drained" when non-null
+  static int allocs, releases, drains, fail_at;
+  static int alloc(void** p, size_t bytes) {
+    if (++allocs == fail_at) return 7;
+    *p = std::malloc(bytes);
+    return *p ? 0 : 1;
+  }
+  static void release(void* p) {
+    ++releases;
+    std::free(p);
+  }
+  static void drain(Stream) { ++drains; }
+  static void reset_counts() { allocs = releases = drains = fail_at = 0; }
+};
+int TestMem::allocs = 0, TestMem::releases = 0, TestMem::drains = 0, TestMem::fail_at = 0;
+
+struct TestCtx {
+  static int inits, fail_inits, live;
+  sfm::Buf<TestMem> buf;
+  int key = -1;
+  TestCtx() { ++live; }
+  ~TestCtx() { --live; }
+  int init(int k) {
+    ++inits;
+    if (fail_inits > 0) return --fail_inits, 5;
+    key = k;
+    return buf.reserve(64, 64, nullptr);
+  }
+};
+int TestCtx::inits = 0, TestCtx::fail_inits = 0, TestCtx::live = 0;
+
+static void check_owner() {
+  using B = sfm::Buf<TestMem>;
+  TestMem::reset_counts();
+  {
+    B b;
+    CHECK(b.get() == nullptr && b.bytes() == 0);
+    CHECK(b.reserve(0, 0, "s") == 0 && TestMem::allocs == 0);  // nothing needed: nothing made
+    CHECK(b.reserve(100, 150, "s") == 0 && b.bytes() == 150 && b.get() != nullptr);
+    CHECK(TestMem::allocs == 1 && TestMem::releases == 0 && TestMem::drains == 0);  // (no allocation yet: no drain)
+    std::memset(b.get(), 0xAB, 150);
+    void* p = b.get();
+    CHECK(b.reserve(150, 999, "s") == 0 && b.get() == p && b.bytes() == 150);  // below capacity: untouched
+    CHECK(b.reserve(1, 1, nullptr) == 0 && b.get() == p && TestMem::allocs == 1);
+    CHECK(b.reserve(151, 300, "s") == 0 && b.bytes() == 300);  // growth: one drain, one release
+    CHECK(TestMem::allocs == 2 && TestMem::releases == 1 && TestMem::drains == 1);
+    std::memset(b.as<uint8_t>(), 0xCD, 300);
+    CHECK(b.reserve(301, 400, nullptr) == 0 && TestMem::drains == 1 && TestMem::releases == 2);  // no stream: no drain
+    // a failed allocation: empty and consistent, the error returned; the next reserve succeeds
+    TestMem::fail_at = TestMem::allocs + 1;
+    CHECK(b.reserve(401, 500, "s") == 7);
+    CHECK(b.get() == nullptr && b.bytes() == 0 && TestMem::releases == 3);
+    CHECK(b.reserve(10, 20, "s") == 0 && b.bytes() == 20 && TestMem::drains == 2);  // (empty: nothing to drain)
+    // moves: the source is left empty, nothing is freed twice
+    B c(std::move(b));
+    CHECK(b.get() == nullptr && b.bytes() == 0 && c.bytes() == 20 && TestMem::releases == 3);
+    B e;
+    CHECK(e.reserve(8, 8, nullptr) == 0);
+    e = std::move(c);  // releases e's own allocation, takes c's
+    CHECK(c.get() == nullptr && c.bytes() == 0 && e.bytes() == 20 && TestMem::releases == 4);
+    B& self = e;
+    e = std::move(self);
+    CHECK(e.bytes() == 20 && TestMem::releases == 4);
+    std::vector<B> v(3);
+    CHECK(v[2].reserve(5, 5, nullptr) == 0);
+    v.resize(40);  // relocates by move
+    CHECK(v[2].bytes() == 5);
+  }
+  CHECK(TestMem::releases == 5 + 1 && TestMem::allocs == TestMem::releases + 1);  // (one allocation failed)
+  // thread_ctx
+  int rc = -1;
+  TestCtx::fail_inits = 2;
+  CHECK(sfm::thread_ctx<TestCtx>(3, &rc) == nullptr && rc == 5 && TestCtx::live == 0);  // nothing cached ...
+  CHECK(sfm::thread_ctx<TestCtx>(3, &rc) == nullptr && rc == 5 && TestCtx::inits == 2);  // ... so init runs again
+  TestCtx* a = sfm::thread_ctx<TestCtx>(3, &rc);
+  CHECK(a && rc == 0 && a->key == 3 && TestCtx::inits == 3 && TestCtx::live == 1);
+  CHECK(sfm::thread_ctx<TestCtx>(3, &rc) == a && rc == 0 && TestCtx::inits == 3);  // cached
+  TestCtx* other_key = sfm::thread_ctx<TestCtx>(4, &rc);
+  CHECK(other_key && other_key != a && other_key->key == 4 && TestCtx::live == 2);
+  TestCtx* in_thread = nullptr;
+  int live_in_thread = 0;
+  std::thread t([&] {
+    int r = -1;
+    in_thread = sfm::thread_ctx<TestCtx>(3, &r);
+    CHECK(in_thread && r == 0 && sfm::thread_ctx<TestCtx>(3, &r) == in_thread);
+    live_in_thread = TestCtx::live;
+  });
+  t.join();
+  CHECK(in_thread != a && in_thread != other_key && live_in_thread == 3);
+  CHECK(TestCtx::live == 2);  // the thread's context went with the thread (its buffer: the leak check)
+  CHECK(sfm::thread_ctx<TestCtx>(3, &rc) == a);
+  std::printf("  Buf: growth, failed allocation, moves ok; thread_ctx: failed init not cached, per thread ok\n");
 }
 
 // ---- the LM trust-region state machine (sfm_amd/csrc/ba_lm.h) ----
@@ -1283,6 +1387,9 @@ int main() {
   std::printf("asan: set_problem's host plan (ba_host_layout.h)\n");
   check_plan();
   check_solve_plan();
+
+  std::printf("asan: ownership templates (owner.h)\n");
+  check_owner();
 
   std::printf("asan: LM trust-region state machine (ba_lm.h)\n");
   check_lm_replay();

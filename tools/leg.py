@@ -5,5 +5,6 @@ import bench
 name = sys.argv[1]
 cpu = len(sys.argv) > 2 and sys.argv[2] == "cpu"
 fn = getattr(bench, name + "_leg")
-out = fn(0, cpu) if name not in ("tracker",) else fn(0, 20, cpu)
+steps = {"tracker": 20, "matcher": 50}  # the legs that take a step count
+out = fn(0, steps[name], cpu) if name in steps else fn(0, cpu)
 print(json.dumps(out, indent=1))
