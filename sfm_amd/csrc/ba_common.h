@@ -232,6 +232,17 @@ __device__ __forceinline__ double wave_sum32(double (&v)[32], int l) {
   return v[0] + __shfl_xor(v[0], 1);
 }
 __device__ __forceinline__ double2 ld2(const double* p) { return *reinterpret_cast<const double2*>(p); }
+// kN doubles (an even count) of a 16-B aligned record by 16-byte loads: from
+// LDS one ds_read_b128 per pair, whatever the compiler can prove of the address
+template <int kN>
+__device__ __forceinline__ void ld_rec(const double* p, double (&v)[kN]) {
+  static_assert(kN % 2 == 0, "whole 16-byte pairs");
+#pragma unroll
+  for (int i = 0; i < kN; i += 2) {
+    const double2 x = ld2(p + i);
+    v[i] = x.x; v[i + 1] = x.y;
+  }
+}
 
 // IEEE divisions by one shared denominator: the compiler's f64 division is
 // v_div_scale (denominator) -> v_rcp -> two Newton steps -> v_div_scale

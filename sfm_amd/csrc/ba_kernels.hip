@@ -1732,7 +1732,10 @@ __global__ __launch_bounds__(kThreads, 2) void k_schur_pairs_rot_pw(const int4* 
   if (gate && *gate == 0) return;  // device LM loop: phase skipped
   constexpr int kPer = 64 / kSub, kW = kThreads / 64;
   const int W = int(gridDim.x / 8) * kW;  // waves per list
-  __shared__ __attribute__((aligned(16))) double cst[2][kW][kPer][2 * kCamSR];
+  // (a block's two records at the padded stride kCamSRP: the blocks whose
+  // lanes one 16-byte LDS read serves together lie on different banks, ba_device.h)
+  __shared__ __attribute__((aligned(16))) double cst[2][kW][kPer][kCamSRP];
+  static_assert(2 * sizeof(cst) <= 160 * 1024, "two workgroups per CU");
   const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, g = l / kSub, sl = l % kSub;
   const int xl = blockIdx.x & 7;
   // group t of list xl: wave t % kW of the list's workgroup-sized group t / kW
@@ -1746,9 +1749,10 @@ __global__ __launch_bounds__(kThreads, 2) void k_schur_pairs_rot_pw(const int4* 
     i0 = bpts[kb + sl < ke ? kb + sl : 0];
     i1 = bpts[kb + sl + kSub < ke ? kb + sl + kSub : 0];
   };
-  // the group's 2 (64 / kSub) camera records, 16 B per lane and round: doubles
-  // 2 e2, 2 e2 + 1 of the wave's buffer are entries 2 e2 % 32.. of side
-  // (e2 / 16) % 2 of block e2 / 32, whose slot record lane (e2 / 32) kSub holds
+  // the group's 2 (64 / kSub) camera records, 16 B per lane and round: lane
+  // and round e2 copies entries 2 e2 % 32.. of side (e2 / 16) % 2 of block
+  // e2 / 32, whose slot record lane (e2 / 32) kSub holds, to the block's
+  // kCamSRP doubles of the wave's buffer
   auto stage = [&](const int4 r, int buf) {
     double* cs_wave = &cst[buf][wv][0][0];
 #pragma unroll
@@ -1757,7 +1761,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_schur_pairs_rot_pw(const int4* 
       const int q = min(e2 / kCamSR, kPer - 1), side = (e2 / (kCamSR / 2)) & 1, hl = 2 * (e2 % (kCamSR / 2));
       const int c1 = __shfl(r.x, q * kSub), c2 = __shfl(r.y, q * kSub);
       const double2 v = ld2(camS + size_t(kCamSR) * max(side ? c2 : c1, 0) + hl);
-      if (e2 < kPer * kCamSR) *reinterpret_cast<double2*>(cs_wave + (2 * q + side) * kCamSR + hl) = v;
+      if (e2 < kPer * kCamSR) *reinterpret_cast<double2*>(cs_wave + q * kCamSRP + side * kCamSR + hl) = v;
     }
   };
   // (the groups a wave holds ascend, so the first one past the end ends the wave)
@@ -1929,7 +1933,7 @@ __global__ void k_pad_init(double* __restrict__ S, int ld, int n, int* __restric
 __device__ __forceinline__ void cam_pm_pack(int c, const double* __restrict__ camR, const double* __restrict__ cam,
                                             const double* __restrict__ Kc, const double* __restrict__ ysol,
                                             const double* __restrict__ scale_c, double* __restrict__ o) {
-  // o: the camera's record (LDS); its candidate part (23..34) is the caller's
+  // o: the camera's record (LDS); its candidate part (kCamPMNew..) is the caller's
   const double* cr = camR + size_t(kCamR) * c;
   double R[9], sy[6];
   for (int i = 0; i < 9; ++i) R[i] = cr[i];
@@ -1958,8 +1962,8 @@ __device__ __forceinline__ void cam_pm_pack(int c, const double* __restrict__ ca
   for (int i = 0; i < 3; ++i) o[9 + i] = cam[6 * c + 3 + i];
   for (int i = 0; i < 5; ++i) o[12 + i] = Kc[5 * size_t(c) + i];
   for (int i = 0; i < 3; ++i) { o[17 + i] = om[i]; o[20 + i] = sy[3 + i]; }
-  o[35] = first_order ? 1.0 : 0.0;
-  o[36] = 0.0;
+  o[kCamPMFlag] = first_order ? 1.0 : 0.0;
+  o[kCamPM - 2] = o[kCamPM - 1] = 0.0;
 }
 
 __global__ __launch_bounds__(kThreads) void k_cam_update(int C, const double* __restrict__ cam,
@@ -2200,7 +2204,7 @@ __device__ __forceinline__ void cam_step_record(int c, const CamStepFold& cu, do
     for (int k = 0; k < 6; ++k) cu.cam_new[6 * c + k] = xn[k];
     for (int i = 0; i < 12; ++i) cu.camRn[12 * size_t(c) + i] = rn[i];
   }
-  for (int i = 0; i < 12; ++i) o[23 + i] = rn[i];
+  for (int i = 0; i < 12; ++i) o[kCamPMNew + i] = rn[i];
   cam_pm_pack(c, cu.camR, cu.cam, cu.Kc, cu.ysol, cu.scale_c, o);
 }
 
@@ -2225,7 +2229,7 @@ __global__ __launch_bounds__(kThreads * kGroups) void k_backsub_pm(
   if (gate && *gate == 0) return;  // device LM loop: phase skipped
   static_assert(kThreads * kGroups >= kCamPMMax, "one thread per camera record");
   __shared__ double sh[4 * kGroups];
-  __shared__ double cst[kCamPMMax * kCamPM];
+  __shared__ __attribute__((aligned(16))) double cst[kCamPMMax * kCamPM];
   const int nbp = (P + kThreads - 1) / kThreads;
   const int grp = int(threadIdx.x) / kThreads, tg = int(threadIdx.x) % kThreads;
   const int vb = int(blockIdx.x) * kGroups + grp;  // the 256-thread block this group stands for
@@ -2274,7 +2278,8 @@ __global__ __launch_bounds__(kThreads * kGroups) void k_backsub_pm(
     double2 uv_n = cnt > 0 ? ld2(ps.uv + 2 * q) : make_double2(0.0, 0.0);
     double h0 = 0.0, h1 = 0.0, h2 = 0.0;  // sum J_X^T e
     for (int i = 0; i < cnt; ++i) {
-      const double* k = cst + kCamPM * c_n;
+      double k[kCamPMNew];  // R, t, K, omega, tau, flag: twelve 16-byte LDS reads
+      ld_rec(cst + kCamPM * c_n, k);
       const double2 uvo = uv_n;
       if (i + 1 < cnt) {
         q += size_t(qs);
@@ -2292,7 +2297,7 @@ __global__ __launch_bounds__(kThreads * kGroups) void k_backsub_pm(
       const double a0 = fx * iz, a1 = sk * iz, a2 = -(fx * xp + sk * yp) * iz;
       const double b1 = fy * iz, b2 = -fy * yp * iz;
       // e = A (omega x yt + tau), yt = R X (X for a first-order camera)
-      const bool fo = k[35] != 0.0;
+      const bool fo = k[kCamPMFlag] != 0.0;
       const double t0 = fo ? Xp[0] : y0, t1 = fo ? Xp[1] : y1, t2 = fo ? Xp[2] : y2;
       const double d0 = k[18] * t2 - k[19] * t1 + k[20];
       const double d1 = k[19] * t0 - k[17] * t2 + k[21];
@@ -2334,22 +2339,27 @@ __global__ __launch_bounds__(kThreads * kGroups) void k_backsub_pm(
     c_n = cnt > 0 ? ps.cam[q] : 0;
     uv_n = cnt > 0 ? ld2(ps.uv + 2 * q) : make_double2(0.0, 0.0);
     for (int i = 0; i < cnt; ++i) {
-      const double* k = cst + kCamPM * c_n;
+      double k5[6], Rn[12];  // K (entries 12..17) and R_new, t_new: three and six 16-byte LDS reads
+      ld_rec(cst + kCamPM * c_n + 12, k5);
+      ld_rec(cst + kCamPM * c_n + kCamPMNew, Rn);
       const double2 uvo = uv_n;
       if (i + 1 < cnt) {
         q += size_t(qs);
         c_n = ps.cam[q];
         uv_n = ld2(ps.uv + 2 * q);
       }
-      const double* Rn = k + 23;
       double pc[3];
 #pragma unroll
       for (int j = 0; j < 3; ++j) pc[j] = Rn[3 * j] * Xn[0] + Rn[3 * j + 1] * Xn[1] + Rn[3 * j + 2] * Xn[2] + Rn[9 + j];
       const SharedDiv dz = shared_div(pc[2]);  // (bitwise the two divisions)
       const double xp = sdiv(dz, pc[0]), ypj = sdiv(dz, pc[1]);
-      const double rn0 = k[12] * xp + k[13] * ypj + k[14] - uvo.x;
-      const double rn1 = k[15] * ypj + k[16] - uvo.y;
-      ncost += 0.5 * (rn0 * rn0 + rn1 * rn1);
+      const double rn0 = k5[0] * xp + k5[1] * ypj + k5[2] - uvo.x;
+      const double rn1 = k5[3] * ypj + k5[4] - uvo.y;
+      // 0.5 (rn0 rn0 + rn1 rn1) with its roundings written out: of the two
+      // products the compiler fuses whichever its operand order puts first,
+      // and that order follows the form of the loads above; the recorded
+      // solves have rn1 rn1 rounded and rn0 rn0 fused
+      ncost = __builtin_fma(0.5, __builtin_fma(rn0, rn0, rn1 * rn1), ncost);
     }
   }
   // block_reduce per group: its four waves' values combined in wave order

@@ -32,6 +32,8 @@ namespace sfm {
 
 // cameras whose records (kCamPM doubles each) fit the 160-KB LDS of k_backsub_pm
 constexpr int kCamPMMax = 512;
+constexpr int kCamPMBytes = 304;  // one record (kCamPM doubles, ba_device.h)
+static_assert(kCamPMMax * kCamPMBytes + 128 <= 160 * 1024, "k_backsub_pm: the records and its reduction scratch in one CU's LDS");
 // sizes up to which the deciding workgroup also makes the accepted step current (AcceptFold)
 constexpr int kAcceptFoldMaxCams = 256;
 constexpr int64_t kAcceptFoldMaxX = 3 * 8192;
