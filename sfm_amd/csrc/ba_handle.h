@@ -10,7 +10,6 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <map>
 #include <string>
 #include <utility>
 #include <vector>
@@ -49,13 +48,22 @@ struct sfm_ba_handle {
   // lies with the problem (d.plan)
   sfm::SolveKnobs knobs;
   sfm::SolvePlan plan;
-  std::vector<std::pair<size_t, void*>> allocs;  // (bytes, buffer) of the resident problem
-  std::vector<std::pair<size_t, void*>> tmps;    // set_problem's scratch (back to the pool when it returns)
-  std::multimap<size_t, void*> pool;             // buffers of earlier problems, reused by size
-  bool has_problem = false;
   // multi-GPU
-  ncclComm_t comm = nullptr;
+  struct CommDestroy { void operator()(ncclComm_t c) const { ncclCommDestroy(c); } };
+  std::unique_ptr<ncclComm, CommDestroy> comm;
   int nranks = 1, rank = 0;
+  void set_ranks(int n, int r) { comm.reset(), nranks = n, rank = r; }  // (every way to set the collectives starts here)
+  // every buffer d points into, set_problem's scratch, earlier problems' for reuse: keyframe-sized solves
+  // (CSfM::bundleAdjustment after every keyframe) allocate nothing; set_problem initialises what it relies on
+  sfm::DevPool pool;
+  bool has_problem = false;
+  // The problem is gone, its buffers free for the next one.
+  void drop_problem(const sfm::DevPool::Drained& idle) {
+    pool.retire_all(idle);
+    d = sfm::DevProblem();
+    d.scal_host = scal_host;
+    has_problem = false;
+  }
   // host-callback collective (sfm_ba_set_host_comm: tests run the sharded
   // path with several ranks on one GPU, where RCCL allows one rank per GPU)
   sfm_allreduce_fn host_fn = nullptr;
@@ -138,49 +146,6 @@ struct sfm_ba_handle {
   int phase_count[kNumPh] = {0};
 };
 
-// Device buffers are taken from the handle's pool (the previous problem's
-// buffers, best fit within 2x) before hipMalloc: repeated keyframe-sized
-// solves (CSfM::bundleAdjustment after every keyframe) then allocate
-// nothing.  Contents are never assumed: set_problem initialises every
-// buffer it relies on.
-template <typename T>
-int dalloc(sfm_ba_handle* h, T** p, size_t count) {
-  if (count == 0) count = 1;
-  const size_t bytes = (count * sizeof(T) + 255) & ~size_t(255);
-  auto it = h->pool.lower_bound(bytes);
-  void* q = nullptr;
-  size_t got = bytes;
-  if (it != h->pool.end() && it->first <= 2 * bytes) {
-    q = it->second;
-    got = it->first;
-    h->pool.erase(it);
-  } else {
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) return fail(SFM_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-  }
-  h->allocs.push_back({got, q});
-  *p = static_cast<T*>(q);
-  return 0;
-}
-// set_problem scratch: retired into the pool when set_problem returns after
-// its synchronisation, or -- a keyframe-sized set_problem returns without one
-// -- by the next set_problem's free_problem, which synchronises first.  So a
-// pooled buffer is never handed out while a kernel of this stream may still
-// use it: every path that moves tmps into the pool (retire_tmps) runs behind
-// a hipStreamSynchronize of the handle's stream.
-template <typename T>
-int dalloc_tmp(sfm_ba_handle* h, T** p, size_t count) {
-  const int rc = dalloc(h, p, count);
-  if (rc) return rc;
-  h->tmps.push_back(h->allocs.back());
-  h->allocs.pop_back();
-  return 0;
-}
-inline void retire_tmps(sfm_ba_handle* h) {
-  for (auto& a : h->tmps) h->pool.insert(a);
-  h->tmps.clear();
-}
-
 // The pinned staging buffer with room for `bytes` (ba_solver.hip).  Growing it
 // frees the old buffer, so nothing may still read or write it: every caller
 // has synchronised the stream (set_problem, get_parameters), and a
@@ -191,21 +156,6 @@ inline void retire_tmps(sfm_ba_handle* h) {
 int stage_reserve(sfm_ba_handle* h, size_t bytes);
 using sfm::kStageMaxBytes;  // transfers above it bypass the stage (ba_host_layout.h)
 using sfm::hostlayout::StageLayout;
-
-inline void release_pool(sfm_ba_handle* h) {
-  for (auto& kv : h->pool) hipFree(kv.second);
-  h->pool.clear();
-}
-
-// Retires the problem's buffers into the pool (freed by release_pool).
-inline void free_problem(sfm_ba_handle* h) {
-  for (auto& a : h->allocs) h->pool.insert(a);
-  h->allocs.clear();
-  retire_tmps(h);
-  h->d = sfm::DevProblem();
-  h->d.scal_host = h->scal_host;
-  h->has_problem = false;
-}
 
 using sfm::env_flag;  // (ba_plan.h)
 

@@ -59,7 +59,7 @@ struct Setup {
   // pass's shape, ...) is made from, filled in as the passes learn it
   ProblemShape shape;
 
-  // device scratch (h->tmps) and pieces of resident blobs the setup alone reads
+  // device scratch (the pool's) and pieces of resident blobs the setup alone reads
   uint8_t* in_blob = nullptr;
   double* in_uv = nullptr;
   int32_t *in_cam = nullptr, *in_pt = nullptr, *cnt_p = nullptr, *cnt_c = nullptr;
@@ -102,9 +102,11 @@ struct Setup {
         cam_cnt(size_t(n_cams) + 4) {}
 
   template <typename T>
-  bool alloc(T*& p, size_t count) { return (rc = dalloc(h, &p, count)) == 0; }  // resident
+  bool alloc(T*& p, size_t count, bool scratch = false) {  // resident
+    return (rc = hip_rc(SFM_ENOMEM, "hipMalloc", h->pool.take(&p, count, scratch))) == 0;
+  }
   template <typename T>
-  bool tmp(T*& p, size_t count) { return (rc = dalloc_tmp(h, &p, count)) == 0; }  // back to the pool at the end
+  bool tmp(T*& p, size_t count) { return alloc(p, count, true); }  // back to the pool at the end
 };
 
 // waves of 64 points (the wave-major stream's woff has one more entry)
@@ -115,14 +117,14 @@ size_t wm_waves(int P) { return (size_t(P) + 63) / 64; }
 // the pair count and the wave-major slot total are in.
 void plan_from_shape(Setup& c) { c.d.plan = plan_problem(c.shape, c.h->knobs); }
 
-// Any failure returns through here: the buffers go back to the pool.
+// Any failure returns through here: the worker joined and both streams idle, the buffers go back to the pool.
 struct ProblemGuard {
   Setup& c;
   bool committed = false;
   ~ProblemGuard() {
     if (committed) return;
     c.worker.join();
-    free_problem(c.h);
+    c.h->drop_problem({c.h->stream, c.h->ustream});
   }
 };
 
@@ -725,12 +727,10 @@ int finish_params(Setup& c) {
 // Small problems end without a synchronisation: every host-to-device copy
 // came from the pinned stage, nothing is read back, so the pair lists and
 // uploads run on while the caller enqueues the solve (stream order covers
-// every reader; the scratch buffers stay out of the pool until the next
-// set_problem's free_problem, after its synchronisation, and the stage is
-// next written by a call that synchronises first).  Otherwise: the
-// k_schur_pts group sizes come back, copies from pageable host memory (the
-// caller's arrays, this call's vectors) complete, and the scratch buffers
-// return to the pool.
+// every reader; the scratch buffers stay scratch, and the stage is next
+// written by a call that synchronises first).  Otherwise: the k_schur_pts
+// group sizes come back, copies from pageable host memory (the caller's
+// arrays, this call's vectors) complete, and the scratch buffers are retired.
 // (SFM_SYNC_SETUP=1: always synchronise, so that a fault in a layout kernel
 // is reported by set_problem itself, not by the next call)
 int finish(Setup& c) {
@@ -756,7 +756,8 @@ int finish(Setup& c) {
   const bool deferred_uv = c.plan.deferred_uv;
   if (deferred_uv) HIPCHK(hipStreamWaitEvent(s, h->uev_uv, 0));
   if (c.d.plan.small_setup && c.plan.route == ParamRoute::Early && !c.bperm_per && !sync_setup) return 0;
-  HIPCHK(hipStreamSynchronize(s));
+  const DevPool::Drained idle{s};
+  if (int rc = hip_rc(SFM_EIO, "hipStreamSynchronize(s)", idle.rc)) return rc;
   if (deferred_uv && *c.uv_err_host != INT32_MAX)
     return fail(SFM_EINVAL, "non-finite observation at " + std::to_string(*c.uv_err_host));
   if (c.bperm_per) {
@@ -764,7 +765,7 @@ int finish(Setup& c) {
     for (int x = 0; x < 8; ++x) m_max = std::max<int64_t>(m_max, (c.grp_host[8 + x] + c.bperm_per - 1) / c.bperm_per);
     d.n_bslots = m_max * 8 * c.bperm_per;
   }
-  retire_tmps(h);
+  h->pool.retire_scratch(idle);
   c.timer.mark("pair lists + uploads (device)");
   return 0;
 }
@@ -797,7 +798,7 @@ int run_setup(Setup& c, const double* K9, const double* rot, const double* t) {
   if (c.d.plan.small_setup) pair_lists_small(c);
   else if ((rc = pair_lists_sorted(c))) return rc;
   if ((rc = alloc_solver_arrays(c))) return rc;
-  release_pool(c.h);  // earlier problems' buffers this one did not reuse
+  c.h->pool.trim();  // earlier problems' buffers this one did not reuse
   if (plan.deferred_uv && (rc = layout_deferred_uv(c))) return rc;
   if (!plan.deferred_uv) layout_wave_major(c, c.s);
   if (side && c.d.plan.small_setup && (rc = enqueue_side_params(c))) return rc;  // Side, small path: no layout round trip to hide behind
@@ -820,8 +821,9 @@ int sfm_ba_set_problem(sfm_ba_handle* h, int64_t n_obs, const double* obs_uv, co
     return fail(SFM_EINVAL, "more than 2^31-1 observations per shard");
   Setup c(h, n_obs, obs_uv, cam_idx, pt_idx, n_cams, n_pts, X);
   HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  free_problem(h);
+  const DevPool::Drained idle{h->stream};
+  if (int rc = hip_rc(SFM_EIO, "hipStreamSynchronize(h->stream)", idle.rc)) return rc;
+  h->drop_problem(idle);
   read_knobs(&h->knobs, kKnobsProblem);
   c.timer.mark("sync + free");
   h->d.C = n_cams;

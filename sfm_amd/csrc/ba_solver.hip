@@ -226,7 +226,7 @@ int allreduce(sfm_ba_handle* h, double* buf, size_t count, ncclRedOp_t op) {
   // and unpack are gated themselves) and stays in place.
   const bool gated = h->d.gate != nullptr && buf != h->d.Spack;
   if (!gated) {
-    NCCLCHK(ncclAllReduce(buf, buf, count, ncclDouble, op, h->comm, h->stream));
+    NCCLCHK(ncclAllReduce(buf, buf, count, ncclDouble, op, h->comm.get(), h->stream));
     if (scale != 1.0) launch_gated_copy(buf, buf, int64_t(count), scale, nullptr, h->stream);
     return 0;
   }
@@ -235,7 +235,7 @@ int allreduce(sfm_ba_handle* h, double* buf, size_t count, ncclRedOp_t op) {
     if (h->ar_tmp.reserve(count * sizeof(double), std::max<size_t>(count, 4096) * sizeof(double), nullptr))
       return fail(SFM_ENOMEM, "hipMalloc failed (collective scratch)");
   }
-  NCCLCHK(ncclAllReduce(buf, h->ar_tmp, count, ncclDouble, op, h->comm, h->stream));
+  NCCLCHK(ncclAllReduce(buf, h->ar_tmp, count, ncclDouble, op, h->comm.get(), h->stream));
   launch_gated_copy(h->ar_tmp, buf, int64_t(count), scale, h->d.gate, h->stream);
   return 0;
 }
@@ -276,14 +276,14 @@ int host_collective(sfm_ba_handle* h, int kind, double* buf, double* out, int64_
 int broadcast(sfm_ba_handle* h, double* buf, int64_t count, int root) {
   if (h->host_fn || h->coll_fn) return host_collective(h, SFM_COLL_BROADCAST, buf, nullptr, count, root);
   if (!h->comm) return 0;
-  NCCLCHK(ncclBroadcast(buf, buf, size_t(count), ncclDouble, root, h->comm, h->stream));
+  NCCLCHK(ncclBroadcast(buf, buf, size_t(count), ncclDouble, root, h->comm.get(), h->stream));
   return 0;
 }
 
 int reduce_scatter(sfm_ba_handle* h, double* send, double* recv, int64_t count) {
   if (h->host_fn || h->coll_fn) return host_collective(h, SFM_COLL_REDUCE_SCATTER, send, recv, count, 0);
   if (!h->comm) return 0;
-  NCCLCHK(ncclReduceScatter(send, recv, size_t(count), ncclDouble, ncclSum, h->comm, h->stream));
+  NCCLCHK(ncclReduceScatter(send, recv, size_t(count), ncclDouble, ncclSum, h->comm.get(), h->stream));
   return 0;
 }
 
@@ -303,7 +303,7 @@ int reduce_to(sfm_ba_handle* h, double* send, double* recv, int64_t count, int r
     return 0;
   }
   if (!h->comm) return 0;
-  NCCLCHK(ncclReduce(send, recv, size_t(count), ncclDouble, ncclSum, root, h->comm, st));
+  NCCLCHK(ncclReduce(send, recv, size_t(count), ncclDouble, ncclSum, root, h->comm.get(), st));
   return 0;
 }
 
@@ -448,7 +448,7 @@ int dist_factor_enqueue(sfm_ba_handle* h) {
         // the half is packed (owner) / no longer read by panel k-2's unpack
         if (me == owner) HIPCHK(hipStreamWaitEvent(cs, D.ev_packed, 0));
         else HIPCHK(hipStreamWaitEvent(cs, D.ev_free[k & 1], 0));
-        NCCLCHK(ncclBroadcast(b, b, size_t(cnt), ncclDouble, owner, h->comm, cs));
+        NCCLCHK(ncclBroadcast(b, b, size_t(cnt), ncclDouble, owner, h->comm.get(), cs));
         HIPCHK(hipEventRecord(D.ev_arrived[k & 1], cs));
       } else if ((rc = broadcast(h, b, cnt, owner))) {
         return rc;
@@ -1005,9 +1005,6 @@ int sfm_ba_destroy(sfm_ba_handle* h) {
   if (!h) return 0;
   hipSetDevice(h->device);
   hipStreamSynchronize(h->stream);
-  free_problem(h);
-  release_pool(h);
-  if (h->comm) ncclCommDestroy(h->comm);
   delete h;
   return 0;
 }
@@ -1023,16 +1020,16 @@ int sfm_comm_unique_id(uint8_t out[128]) {
 int sfm_ba_set_comm(sfm_ba_handle* h, int32_t nranks, int32_t rank, const uint8_t id[128]) {
   if (!h || nranks < 1 || rank < 0 || rank >= nranks) return fail(SFM_EINVAL, "bad communicator arguments");
   HIPCHK(hipSetDevice(h->device));
-  if (h->comm) { ncclCommDestroy(h->comm); h->comm = nullptr; }
+  h->set_ranks(nranks, rank);
   h->host_fn = nullptr;
   h->coll_fn = nullptr;
-  h->nranks = nranks;
-  h->rank = rank;
   // a one-rank communicator is created too: it runs every collective of the
   // sharded path (identities over one rank), which the one-GPU tests use
   ncclUniqueId uid;
+  ncclComm_t c = nullptr;
   std::memcpy(&uid, id, 128);
-  NCCLCHK(ncclCommInitRank(&h->comm, nranks, uid, rank));
+  NCCLCHK(ncclCommInitRank(&c, nranks, uid, rank));
+  h->comm.reset(c);
   h->emulate_ranks = 1;
   if (const char* e = std::getenv("SFM_EMULATE_IDENTICAL_RANKS")) h->emulate_ranks = std::max(1, std::atoi(e));
   return 0;
@@ -1040,9 +1037,7 @@ int sfm_ba_set_comm(sfm_ba_handle* h, int32_t nranks, int32_t rank, const uint8_
 
 int sfm_ba_set_host_comm(sfm_ba_handle* h, int32_t nranks, int32_t rank, sfm_allreduce_fn fn, void* user) {
   if (!h || nranks < 1 || rank < 0 || rank >= nranks || !fn) return fail(SFM_EINVAL, "bad communicator arguments");
-  if (h->comm) { ncclCommDestroy(h->comm); h->comm = nullptr; }
-  h->nranks = nranks;
-  h->rank = rank;
+  h->set_ranks(nranks, rank);
   h->host_fn = fn;
   h->host_user = user;
   h->coll_fn = nullptr;
@@ -1060,9 +1055,7 @@ int coll_as_allreduce(double* buf, int64_t count, int32_t op, void* user) {
 
 int sfm_ba_set_host_collectives(sfm_ba_handle* h, int32_t nranks, int32_t rank, sfm_collective_fn fn, void* user) {
   if (!h || nranks < 1 || rank < 0 || rank >= nranks || !fn) return fail(SFM_EINVAL, "bad communicator arguments");
-  if (h->comm) { ncclCommDestroy(h->comm); h->comm = nullptr; }
-  h->nranks = nranks;
-  h->rank = rank;
+  h->set_ranks(nranks, rank);
   h->coll_fn = fn;
   h->coll_user = user;
   h->host_fn = coll_as_allreduce;  // the sharded path's all-reduces
@@ -1238,9 +1231,8 @@ int sfm_ba_solve(const sfm_ba_options* opts, int32_t mode, int64_t n_obs, const 
 // The record array of the evaluate API (the solve writes no records):
 // allocated on first use, kept with the problem.
 static int ensure_records(sfm_ba_handle* h) {
-  DevProblem& d = h->d;
-  if (d.jrec || d.N_pad == 0) return 0;
-  return dalloc(h, &d.jrec, size_t(kJRec) * size_t(d.N_pad));
+  if (h->d.jrec || h->d.N_pad == 0) return 0;
+  return hip_rc(SFM_ENOMEM, "hipMalloc", h->pool.take(&h->d.jrec, size_t(kJRec) * size_t(h->d.N_pad), false));
 }
 
 int sfm_ba_evaluate(sfm_ba_handle* h, double* cost, double* res, double* jac) {
@@ -1288,9 +1280,8 @@ namespace {
 // The bare dense system of order n the factor and the back substitution work
 // on (sfm_dist_factor_profile, dense_solve), from owners: S, invL and the
 // flags zeroed (cflags and the 8-byte-aligned cticket inside them), ysol, fail.
-int alloc_failed(int hip_error) {  // (SFM_EIO: what HIPCHK(hipMalloc(...)) gave these entry points)
-  return fail(SFM_EIO, std::string("hipMalloc: ") + hipGetErrorString(hipError_t(hip_error)));
-}
+// (SFM_EIO: what HIPCHK(hipMalloc(...)) gave these entry points)
+int alloc_failed(int hip_error) { return hip_rc(SFM_EIO, "hipMalloc", hip_error); }
 struct DenseProblem {
   Stream s;  // first: members are destroyed in reverse order, so it goes last
   DevArr<double> S, invL, ysol;

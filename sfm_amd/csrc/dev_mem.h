@@ -14,10 +14,13 @@
 #include "owner.h"
 #include "sfm_error.h"
 
-#define HIPCHK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return fail(SFM_EIO, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+// 0, or `code` with "<what>: <error>" for the HIP error e (a hipError_t, or a memory policy's int)
+inline int hip_rc(int code, const char* what, int e) {
+  return e ? fail(code, std::string(what) + ": " + hipGetErrorString(hipError_t(e))) : 0;
+}
+#define HIPCHK(expr)                                                   \
+  do {                                                                 \
+    if (const int rc_ = hip_rc(SFM_EIO, #expr, int(expr))) return rc_; \
   } while (0)
 
 namespace sfm {
@@ -26,16 +29,17 @@ struct DeviceMem {
   using Stream = hipStream_t;
   static int alloc(void** p, size_t bytes) { return int(hipMalloc(p, bytes)); }
   static void release(void* p) { (void)hipFree(p); }
-  static void drain(hipStream_t s) { (void)hipStreamSynchronize(s); }
+  static int drain(hipStream_t s) { return int(hipStreamSynchronize(s)); }
 };
 struct PinnedMem {
   using Stream = hipStream_t;
   static int alloc(void** p, size_t bytes) { return int(hipHostMalloc(p, bytes)); }
   static void release(void* p) { (void)hipHostFree(p); }
-  static void drain(hipStream_t s) { (void)hipStreamSynchronize(s); }
+  static int drain(hipStream_t s) { return int(hipStreamSynchronize(s)); }
 };
 using DevBuf = Buf<DeviceMem>;
 using PinBuf = Buf<PinnedMem>;
+using DevPool = Pool<DeviceMem>;
 // a Buf that kernels, copies and pointer arithmetic take as a T*
 template <typename T, typename Mem>
 struct Arr : Buf<Mem> {

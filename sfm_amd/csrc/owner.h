@@ -7,13 +7,14 @@
 #include <map>
 #include <memory>
 #include <utility>
+#include <vector>
 
 namespace sfm {
 
 // Move-only owner of one allocation.  Mem supplies
 //   static int alloc(void** p, size_t bytes)   (0 on success)
 //   static void release(void* p)
-//   static void drain(Stream s)                 (wait for the work on s)
+//   static int drain(Stream s)                  (wait for the work on s; 0 on success)
 //   using Stream = ...
 template <typename Mem>
 class Buf {
@@ -39,7 +40,7 @@ class Buf {
   // then empty.
   int reserve(size_t need, size_t want, typename Mem::Stream drain) {
     if (bytes_ >= need) return 0;
-    if (drain && p_) Mem::drain(drain);
+    if (drain && p_) (void)Mem::drain(drain);
     reset();
     void* q = nullptr;
     const int rc = Mem::alloc(&q, want);
@@ -59,6 +60,58 @@ class Buf {
  private:
   void* p_ = nullptr;
   size_t bytes_ = 0;
+};
+
+// Allocations re-used by size across problems (the bundle adjuster's): the
+// resident problem's, the running set-up's scratch, and a free list, whose
+// smallest buffer of at least the request take() prefers if it is at most
+// twice that (among equals the one retired first).  A buffer enters the free
+// list only against a Drained, made by waiting for every stream that may
+// still touch it; scratch that nobody waited for stays scratch.
+template <typename Mem>
+class Pool {
+ public:
+  struct Drained {
+    int rc = 0;  // the first failed wait's code (Mem::drain's)
+    Drained(std::initializer_list<typename Mem::Stream> streams) {
+      for (auto s : streams)
+        if (const int e = s ? Mem::drain(s) : 0) rc = rc ? rc : e;
+    }
+  };
+  Pool() = default;
+  Pool(const Pool&) = delete;
+  Pool& operator=(const Pool&) = delete;
+  ~Pool() { retire(resident_), retire(scratch_), trim(); }
+  // `count` T (0 counts as 1) in a multiple of 256 bytes, contents undefined; Mem::alloc's code on failure
+  template <typename T>
+  int take(T** p, size_t count, bool scratch) {
+    if (count == 0) count = 1;
+    std::pair<size_t, void*> a((count * sizeof(T) + 255) & ~size_t(255), nullptr);  // (capacity, buffer)
+    auto it = free_.lower_bound(a.first);
+    if (it != free_.end() && it->first <= 2 * a.first) {
+      a = *it;  // (with its true capacity)
+      free_.erase(it);
+    } else if (const int rc = Mem::alloc(&a.second, a.first)) {
+      return rc;
+    }
+    (scratch ? scratch_ : resident_).push_back(a);
+    *p = static_cast<T*>(a.second);
+    return 0;
+  }
+  void retire_scratch(const Drained&) { retire(scratch_); }
+  void retire_all(const Drained&) { retire(resident_), retire(scratch_); }
+  void trim() {  // releases the free list
+    for (auto& kv : free_) Mem::release(kv.second);
+    free_.clear();
+  }
+
+ private:
+  void retire(std::vector<std::pair<size_t, void*>>& l) {
+    for (auto& a : l) free_.insert(a);  // (behind its equals: first retired, first out)
+    l.clear();
+  }
+  std::vector<std::pair<size_t, void*>> resident_, scratch_;
+  std::multimap<size_t, void*> free_;
 };
 
 // The calling thread's context for `key` (the device, or whatever else the

@@ -16,7 +16,12 @@
 //     per growth, a failed allocation leaves it empty and the next reserve
 //     succeeds, moves free nothing twice) over a malloc / free policy that
 //     fails its k-th allocation, and thread_ctx (a failed init caches nothing,
-//     one context per thread, destroyed at thread exit: the leak check);
+//     one context per thread, destroyed at thread exit: the leak check), and
+//     Pool, the bundle adjuster's problem pool: its hand-out rule against a
+//     restatement of the hand-kept one over seeded random scripts and at the
+//     literal edges, every allocation of a set-up failing in turn, and the
+//     order of stream waits and retirements over a large and a keyframe-sized
+//     set-up, a failing one and destroy;
 //   * sfm_amd/csrc/ba_lm.h -- the LM trust-region state machine both loop
 //     drivers run: the oracle's 18 branch traces replayed through it
 //     (tests/golden/lm_replay.txt), and the branches no scene reaches from
@@ -423,19 +428,35 @@ static void check_plan() {
 struct TestMem {
   using Stream = const char*;  // "drained" when non-null
   static int allocs, releases, drains, fail_at;
+  static size_t last_bytes;               // of the last successful allocation
+  static std::vector<void*> released;     // in order
+  static std::vector<std::string> log;    // "drain <stream>" per drain; the pool's checks add their own entries
   static int alloc(void** p, size_t bytes) {
     if (++allocs == fail_at) return 7;
     *p = std::malloc(bytes);
+    last_bytes = bytes;
     return *p ? 0 : 1;
   }
   static void release(void* p) {
     ++releases;
+    released.push_back(p);
     std::free(p);
   }
-  static void drain(Stream) { ++drains; }
-  static void reset_counts() { allocs = releases = drains = fail_at = 0; }
+  static int drain(Stream s) {
+    ++drains;
+    log.push_back(std::string("drain ") + s);
+    return 0;
+  }
+  static void reset_counts() {
+    allocs = releases = drains = fail_at = 0;
+    released.clear();
+    log.clear();
+  }
 };
 int TestMem::allocs = 0, TestMem::releases = 0, TestMem::drains = 0, TestMem::fail_at = 0;
+size_t TestMem::last_bytes = 0;
+std::vector<void*> TestMem::released;
+std::vector<std::string> TestMem::log;
 
 struct TestCtx {
   static int inits, fail_inits, live;
@@ -513,6 +534,314 @@ static void check_owner() {
   CHECK(TestCtx::live == 2);  // the thread's context went with the thread (its buffer: the leak check)
   CHECK(sfm::thread_ctx<TestCtx>(3, &rc) == a);
   std::printf("  Buf: growth, failed allocation, moves ok; thread_ctx: failed init not cached, per thread ok\n");
+}
+
+// ---- the bundle adjuster's problem pool (sfm::Pool, owner.h) ----
+// The hand-out rule as the handle kept it by hand before the pool existed
+// (dalloc / dalloc_tmp / retire_tmps / free_problem / release_pool over three
+// containers), with buffer ids in place of pointers.
+struct PoolModel {
+  std::vector<std::pair<size_t, int>> allocs, tmps;
+  std::multimap<size_t, int> pool;
+  int next_id = 0;
+  // the buffer handed out; *fresh_bytes: the size of a new allocation, 0 for a reused buffer
+  int dalloc(size_t count, size_t elem, bool tmp, size_t* fresh_bytes) {
+    if (count == 0) count = 1;
+    const size_t bytes = (count * elem + 255) & ~size_t(255);
+    auto it = pool.lower_bound(bytes);
+    std::pair<size_t, int> a(bytes, -1);
+    *fresh_bytes = 0;
+    if (it != pool.end() && it->first <= 2 * bytes) {
+      a = *it;
+      pool.erase(it);
+    } else {
+      a.second = next_id++;
+      *fresh_bytes = bytes;
+    }
+    (tmp ? tmps : allocs).push_back(a);
+    return a.second;
+  }
+  void retire_tmps() {
+    for (auto& a : tmps) pool.insert(a);
+    tmps.clear();
+  }
+  void free_problem() {
+    for (auto& a : allocs) pool.insert(a);
+    allocs.clear();
+    retire_tmps();
+  }
+  std::vector<int> release_pool() {  // the ids freed, in order
+    std::vector<int> ids;
+    for (auto& kv : pool) ids.push_back(kv.second);
+    pool.clear();
+    return ids;
+  }
+};
+
+using TestPool = sfm::Pool<TestMem>;
+
+// One request of `bytes` (as count elements of 1, 4 or 8 bytes) to both; the
+// same buffer must come out.  ptr_of: the model's ids as the pool's pointers.
+static void* pool_take_both(TestPool& pool, PoolModel& model, std::vector<void*>& ptr_of, size_t count, int elem,
+                            bool scratch) {
+  size_t fresh = 0;
+  const int id = model.dalloc(count, size_t(elem), scratch, &fresh);
+  const int allocs0 = TestMem::allocs;
+  void* p = nullptr;
+  int rc = -1;
+  if (elem == 1) {
+    uint8_t* q = nullptr;
+    rc = pool.take(&q, count, scratch);
+    p = q;
+  } else if (elem == 4) {
+    int32_t* q = nullptr;
+    rc = pool.take(&q, count, scratch);
+    p = q;
+  } else {
+    double* q = nullptr;
+    rc = pool.take(&q, count, scratch);
+    p = q;
+  }
+  CHECK(rc == 0 && p != nullptr);
+  if (fresh) {
+    CHECK(TestMem::allocs == allocs0 + 1 && TestMem::last_bytes == fresh && id == int(ptr_of.size()));
+    ptr_of.push_back(p);
+  } else {
+    CHECK(TestMem::allocs == allocs0 && ptr_of[size_t(id)] == p);
+  }
+  static_cast<uint8_t*>(p)[0] = static_cast<uint8_t*>(p)[std::max<size_t>(count, 1) * size_t(elem) - 1] = 0x5A;  // (the request fits: ASan checks both ends)
+  return p;
+}
+static void pool_trim_both(TestPool& pool, PoolModel& model, const std::vector<void*>& ptr_of) {
+  TestMem::released.clear();
+  pool.trim();
+  const std::vector<int> ids = model.release_pool();
+  CHECK(ids.size() == TestMem::released.size());
+  for (size_t k = 0; k < ids.size(); ++k) CHECK(ptr_of[size_t(ids[k])] == TestMem::released[k]);
+}
+
+static void check_pool_rule() {
+  // ---- seeded random scripts against the model ----
+  const size_t bases[] = {0, 1, 100, 256, 1000, 4096, 65536, 300000, size_t(1) << 20, size_t(3) << 20};
+  int n_takes = 0, n_reused = 0, n_trims = 0;
+  for (uint32_t seed = 0; seed < 3000; ++seed) {
+    std::mt19937 rng(seed);
+    TestMem::reset_counts();
+    {
+      TestPool pool;
+      PoolModel model;
+      std::vector<void*> ptr_of;
+      const int steps = 10 + int(rng() % 50);
+      // (a script stays with three bases, so that equal sizes and sizes about twice another meet often)
+      const size_t b3[3] = {bases[rng() % 10], bases[rng() % 10], bases[rng() % 10]};
+      for (int k = 0; k < steps; ++k) {
+        const uint32_t op = rng() % 16;
+        if (op < 10) {
+          // a size at or next to b, 2 b, b / 2: the 2x edge from both sides, in bytes and in 256-byte roundings
+          size_t b = b3[rng() % 3];
+          const uint32_t shape = rng() % 6;
+          if (shape == 1) b *= 2;
+          if (shape == 2) b /= 2;
+          if (shape == 3) b = 2 * ((b + 255) & ~size_t(255));
+          if (shape == 4) b = ((b + 255) & ~size_t(255)) / 2;
+          const int64_t nudge[] = {0, 0, 0, 1, -1, 256, -256, 257};
+          const int64_t want = int64_t(b) + nudge[rng() % 8];
+          const size_t bytes = want < 0 ? 0 : size_t(want);
+          const int elem = (rng() % 4 == 0) ? 8 : (rng() % 3 == 0) ? 4 : 1;
+          const int allocs0 = TestMem::allocs;
+          pool_take_both(pool, model, ptr_of, bytes / size_t(elem), elem, op >= 6);
+          ++n_takes;
+          n_reused += TestMem::allocs == allocs0;
+        } else if (op < 12) {
+          pool.retire_scratch(TestPool::Drained{"s"});
+          model.retire_tmps();
+        } else if (op < 15) {
+          pool.retire_all(TestPool::Drained{"s"});
+          model.free_problem();
+        } else {
+          pool_trim_both(pool, model, ptr_of);
+          ++n_trims;
+        }
+      }
+    }
+    CHECK(TestMem::allocs == TestMem::releases);  // the destructor released the rest, each once (and the leak check)
+  }
+  CHECK(n_reused > n_takes / 10 && n_reused < n_takes * 9 / 10);  // (both branches are well exercised)
+  // ---- the edges, literally ----
+  TestMem::reset_counts();
+  {
+    TestPool pool;
+    const TestPool::Drained idle{"s"};
+    uint8_t *a = nullptr, *b = nullptr, *c = nullptr, *d = nullptr;
+    // a count of 0 is a count of 1: a buffer of 256 bytes
+    CHECK(pool.take(&a, 0, false) == 0 && a != nullptr && TestMem::last_bytes == 256 && TestMem::allocs == 1);
+    pool.retire_all(idle);
+    pool.trim();
+    CHECK(TestMem::releases == 1);
+    // a free buffer of exactly twice the rounded request is reused, one of 256 bytes more is not
+    CHECK(pool.take(&a, 1024, false) == 0 && pool.take(&b, 1280, true) == 0 && TestMem::allocs == 3);
+    pool.retire_all(idle);
+    CHECK(pool.take(&c, 257, false) == 0 && c == a && TestMem::allocs == 3);  // 257 -> 512, 1024 <= 2 * 512
+    pool.retire_all(idle);
+    CHECK(pool.take(&c, 256, false) == 0 && c != a && c != b && TestMem::allocs == 4 && TestMem::last_bytes == 256);
+    CHECK(pool.take(&d, 513, false) == 0 && d == a);   // 513 -> 768: the smallest that fits, not b
+    CHECK(pool.take(&d, 640, false) == 0 && d == b);   // 640 -> 768 again: 1280 <= 1536
+    pool.retire_all(idle);
+    CHECK(pool.take(&d, 639, false) == 0 && d == a);   // (c's 256 bytes are free too, and too small)
+    CHECK(pool.take(&d, 639, false) == 0 && d == b);
+    // a reused buffer keeps its true capacity: a (1024) went out for 768 and still serves 1024
+    pool.retire_all(idle);
+    CHECK(pool.take(&d, 1024, false) == 0 && d == a && TestMem::allocs == 4);
+    pool.retire_all(idle);
+    pool.trim();
+    CHECK(TestMem::releases == 4);
+    // two equal free buffers: the one retired first comes out first -- the
+    // resident ones before the scratch, each in the order taken
+    uint8_t *r0 = nullptr, *r1 = nullptr, *s0 = nullptr, *s1 = nullptr, *o = nullptr;
+    CHECK(pool.take(&s0, 4096, true) == 0 && pool.take(&r0, 4096, false) == 0 && pool.take(&s1, 4096, true) == 0 &&
+          pool.take(&r1, 4096, false) == 0);
+    pool.retire_all(idle);
+    for (uint8_t* want : {r0, r1, s0, s1}) CHECK(pool.take(&o, 4000, true) == 0 && o == want);
+    pool.retire_scratch(idle);  // all four are scratch now, in that order
+    for (uint8_t* want : {r0, r1, s0, s1}) CHECK(pool.take(&o, 4096, false) == 0 && o == want);
+    CHECK(TestMem::allocs == 8);
+  }
+  CHECK(TestMem::allocs == TestMem::releases);
+  std::printf("  Pool: 3000 scripts against the hand-kept rule (%d requests, %d reused, %d trims), the edges ok\n", n_takes,
+              n_reused, n_trims);
+}
+
+// A set_problem-like sequence on the pool, as ba_problem.hip calls it: the
+// opening wait and drop, resident and scratch buffers, the trim after the
+// solver's arrays, then either the closing wait and the scratch's retirement
+// (`sync_end`) or nothing.  `side`: what the failure path waits for beside the
+// solve stream.  Stops at the first failed request with its code, as
+// run_setup does, and then retires as ProblemGuard does.
+static const size_t kSetupSizes[] = {48000, 4000, 320000, 64000, 64000, 1200, 9000, 250000, 16, 700000, 30000, 0};
+static const bool kSetupScratch[] = {false, true, true, true, true, false, false, true, false, false, false, false};
+static int pool_setup(TestPool& pool, size_t scale, bool sync_end, const char* side, std::vector<uint8_t*>* scratch) {
+  const TestPool::Drained idle{"stream"};
+  pool.retire_all(idle);
+  TestMem::log.push_back("retire all");
+  for (int k = 0; k < 12; ++k) {
+    uint8_t* p = nullptr;
+    const int allocs0 = TestMem::allocs, releases0 = TestMem::releases;
+    if (const int rc = pool.take(&p, kSetupSizes[k] * scale, kSetupScratch[k])) {
+      CHECK(rc == 7 && p == nullptr && TestMem::allocs == allocs0 + 1 && TestMem::releases == releases0);
+      pool.retire_all(TestPool::Drained{"stream", side});
+      TestMem::log.push_back("retire all");
+      return rc;
+    }
+    if (kSetupScratch[k] && scratch) scratch->push_back(p);
+    TestMem::log.push_back("take");
+    if (k == 8) pool.trim();  // (after the solver's arrays; three late requests follow: jrec and the like)
+  }
+  if (!sync_end) return 0;
+  const TestPool::Drained done{"stream"};
+  pool.retire_scratch(done);
+  TestMem::log.push_back("retire scratch");
+  return 0;
+}
+
+// In the log, every "retire ..." lies behind a drain of each stream in
+// `streams` with no "take" in between: nothing enters the free list while a
+// stream that was given work on it since may still run.
+static void check_retires_drained(std::initializer_list<const char*> streams) {
+  const auto& log = TestMem::log;
+  for (size_t k = 0; k < log.size(); ++k) {
+    if (log[k].rfind("retire", 0) != 0) continue;
+    for (const char* s : streams) {
+      bool found = false;
+      for (size_t j = k; j-- > 0 && log[j] != "take" && !found;) found = log[j] == std::string("drain ") + s;
+      CHECK(found);
+    }
+  }
+}
+
+static void check_pool_failure_and_drains() {
+  // ---- every allocation of two set-ups in a row failing in turn ----
+  int n_failed = 0;
+  for (int k = 1;; ++k) {
+    TestMem::reset_counts();
+    bool failed = false;
+    {
+      TestPool pool;
+      TestMem::fail_at = k;
+      int rc = pool_setup(pool, 1, true, "ustream", nullptr);
+      if (!rc) rc = pool_setup(pool, 3, false, "ustream", nullptr);  // (reuses little)
+      if (!rc) rc = pool_setup(pool, 2, true, nullptr, nullptr);     // (reuses most)
+      failed = rc != 0;
+      if (failed) {
+        CHECK(rc == 7 && TestMem::allocs == k);
+        uint8_t* p = nullptr;  // a later request succeeds, and so does a whole set-up
+        CHECK(pool.take(&p, 5000, false) == 0 && p != nullptr);
+        CHECK(pool_setup(pool, 1, true, "ustream", nullptr) == 0);
+      }
+    }
+    CHECK(TestMem::releases == TestMem::allocs - (failed ? 1 : 0));  // each released once, the failed one never recorded
+    if (!failed) break;
+    ++n_failed;
+  }
+  CHECK(n_failed > 12);  // (the first set-up allocates everything it asks for)
+  // ---- the drain rule over the four sequences ----
+  // a successful large set-up: the parent synchronises the solve stream at
+  // the start of sfm_ba_set_problem and once in finish(), and nowhere else
+  TestMem::reset_counts();
+  {
+    TestPool pool;
+    std::vector<uint8_t*> scratch;
+    CHECK(pool_setup(pool, 1, true, "ustream", &scratch) == 0);
+    CHECK(TestMem::drains == 2);
+    check_retires_drained({"stream"});
+    uint8_t* p = nullptr;  // the scratch is free again: its first buffer answers a request of its size
+    CHECK(pool.take(&p, kSetupSizes[1], false) == 0 && p == scratch[0]);
+    // a keyframe-sized one returns without synchronising: one wait, and the
+    // scratch is on no free list -- a request of its size is a new allocation
+    TestMem::reset_counts();
+    scratch.clear();
+    CHECK(pool_setup(pool, 1, false, "ustream", &scratch) == 0);
+    CHECK(TestMem::drains == 1);
+    check_retires_drained({"stream"});
+    const int allocs0 = TestMem::allocs;
+    CHECK(pool.take(&p, kSetupSizes[2], false) == 0 && TestMem::allocs == allocs0 + 1);
+    for (uint8_t* q : scratch) CHECK(p != q);
+    // ... until the next set-up's opening wait; this one fails at its second
+    // new allocation, after the side stream was given work: both streams are
+    // waited for before anything is retired, the solve stream first
+    TestMem::log.clear();
+    TestMem::drains = 0;
+    TestMem::fail_at = TestMem::allocs + 2;
+    CHECK(pool_setup(pool, 5, true, "ustream", nullptr) == 7);
+    CHECK(TestMem::drains == 3 && TestMem::log[TestMem::log.size() - 3] == "drain stream" &&
+          TestMem::log[TestMem::log.size() - 2] == "drain ustream" && TestMem::log.back() == "retire all");
+    check_retires_drained({"stream"});
+    {
+      const std::vector<std::string> all = TestMem::log;  // the failure's own retirement: both streams
+      TestMem::log.assign(all.end() - 4, all.end());
+      check_retires_drained({"stream", "ustream"});
+    }
+    // the same where the side stream was never created: it is skipped
+    TestMem::log.clear();
+    TestMem::drains = 0;
+    TestMem::fail_at = TestMem::allocs + 1;
+    CHECK(pool_setup(pool, 7, true, nullptr, nullptr) == 7 && TestMem::drains == 2);
+    // destroy: the caller's wait for the solve stream, then the destructor
+    // releases the resident buffers, the scratch and the free list, each once
+    CHECK(pool_setup(pool, 1, false, "ustream", nullptr) == 0);
+    TestMem::fail_at = 0;
+    TestMem::log.clear();
+    const TestPool::Drained at_destroy{"stream"};
+    CHECK(TestMem::log.size() == 1 && TestMem::log[0] == "drain stream");
+    TestMem::released.clear();
+  }
+  CHECK(TestMem::log.size() == 1);  // (the destructor waits for nothing itself)
+  {
+    std::vector<void*> r = TestMem::released;
+    std::sort(r.begin(), r.end());
+    CHECK(!r.empty() && std::adjacent_find(r.begin(), r.end()) == r.end());
+  }
+  std::printf("  Pool: %d failing allocations leave it consistent; drains: large set-up 2, keyframe-sized 1, failure both streams, destroy ok\n",
+              n_failed);
 }
 
 // ---- the LM trust-region state machine (sfm_amd/csrc/ba_lm.h) ----
@@ -1390,6 +1719,8 @@ int main() {
 
   std::printf("asan: ownership templates (owner.h)\n");
   check_owner();
+  check_pool_rule();
+  check_pool_failure_and_drains();
 
   std::printf("asan: LM trust-region state machine (ba_lm.h)\n");
   check_lm_replay();

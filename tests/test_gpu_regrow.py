@@ -10,7 +10,9 @@ Sizes: the smallest that cross each floor -- 1024 points (PnP, two-view),
 exact sizes (triangulation, KLT), the matcher's 4096-byte scratch floor and
 its frames' capacity, the map vectors' 1024 elements (whose contents must
 survive: DVec::grow is the one place that keeps them), the guidance points'
-doubling, the detector workspace's exact sizes."""
+doubling, the detector workspace's exact sizes, and for the bundle adjuster's
+problem pool a middle problem whose every array is less than twice the outer
+ones' (all reused) and one where each is more (none reused)."""
 import json
 import os
 import threading
@@ -318,6 +320,69 @@ def test_brisk_workspace_regrow(w, h):
     assert same(first, again) and same(big, big_again)
     if w >= 64:
         assert len(big[0]) > 0
+
+
+# ---- the bundle adjuster's problem pool ----
+
+def _ba_scenes(seq):
+    """(a): cameras, points and views of the middle problem about 1.4 times the
+    outer ones' -- 12 -> 17 cameras (78 -> 153 camera blocks), 400 -> 470 points,
+    4 -> 5 views (1600 -> 2350 observations, 6 -> 10 pairs per point: 2400 ->
+    4700) -- so every array of the third problem is smaller than the second's
+    and more than half of it: each buffer is a larger one of the pool, with
+    the second problem's contents.  (b): every ratio above 2 (and past 64
+    cameras), so nothing is reused and the trim frees the lot."""
+    from sfm_amd import scene
+    small = (12, 400, 4)
+    mid = {"a": (17, 470, 5), "b": (70, 1500, 6)}[seq]
+    return [scene.generate(c, p, views=v) for c, p, v in (small, mid, small)]
+
+
+def _summary_and_trace(sm, tr):
+    """The summary without its wall times, and the trace, as arrays (compared as bits: NaNs included)."""
+    keep = [k for k in sm.as_dict() if not k.endswith("_time_s")]
+    return (np.array([float(getattr(sm, k)) for k in keep]),
+            np.array([[float(it[k]) for k in sorted(it)] for it in tr]))
+
+
+def _two_iterations():
+    opts = sfm_amd.default_options()
+    opts.max_num_iterations = 2
+    return opts
+
+
+def _ba_resident(ba, s):
+    """set_problem, then evaluate() (its records come from the pool after the
+    set-up), a two-iteration solve, and the parameters."""
+    ba.set_problem(s.uv, s.cam_idx, s.pt_idx, s.K, s.rot, s.t, s.X)
+    cost, res, jac = ba.evaluate()
+    sm, tr = ba.solve(_two_iterations())
+    assert sm.num_iterations > 0 and len(tr) > 1 and np.isfinite(res).all() and np.abs(jac).max() > 0
+    return (cost, res, jac) + _summary_and_trace(sm, tr) + tuple(ba.parameters())
+
+
+@pytest.mark.parametrize("seq", ["a", "b"])
+def test_ba_problem_pool_regrow(seq):
+    with sfm_amd.BundleAdjuster() as ba:
+        for k, s in enumerate(_ba_scenes(seq)):
+            got = _ba_resident(ba, s)
+            with sfm_amd.BundleAdjuster() as fresh:
+                assert same(got, _ba_resident(fresh, s)), f"step {k} differs from a fresh handle"
+
+
+def _ba_one_shot(s):
+    r, t, X = s.copy_params()
+    sm, tr = sfm_amd.solve(s.uv, s.cam_idx, s.pt_idx, s.K, r, t, X, _two_iterations())
+    assert sm.num_iterations > 0 and len(tr) > 1
+    return _summary_and_trace(sm, tr) + (r, t, X)
+
+
+def test_ba_one_shot_regrow():
+    """sfm_ba_solve keeps one handle per thread: three problems through one thread's, each against a new thread's."""
+    scenes = _ba_scenes("a")
+    got = in_fresh_thread(lambda: [_ba_one_shot(s) for s in scenes])
+    for k, s in enumerate(scenes):
+        assert same(got[k], in_fresh_thread(_ba_one_shot, s)), f"step {k} differs from a fresh thread's handle"
 
 
 # ---- the dense solve's one-shot problem (built from owners now): the parent commit's bits ----

@@ -16,6 +16,7 @@ problem shape, through the C ABI (tolerances as in test_gpu_parity.py).
   points with a single observation.
 """
 
+import functools
 import os
 
 import numpy as np
@@ -225,6 +226,24 @@ def test_distributed_factor_on_one_rank(cfg, pt):
         assert np.array_equal(a, b)
 
 
+def _solve_bits(ba):
+    """A default solve of the handle's problem: the summary without its wall
+    times, the trace and the parameters, floats as their bits."""
+    sm, tr = ba.solve()
+    bits = lambda v: v.hex() if isinstance(v, float) else v
+    return ([(k, bits(v)) for k, v in sm.as_dict().items() if not k.endswith("_time_s")],
+            [[(k, bits(v)) for k, v in it.items()] for it in tr], [p.tobytes() for p in ba.parameters()])
+
+
+@functools.lru_cache(maxsize=None)
+def _fresh_solve_bits(cfg):
+    """_solve_bits of the configuration on a handle that never saw another call."""
+    s = scene.config(cfg)
+    with sfm_amd.BundleAdjuster() as ba:
+        ba.set_problem(s.uv, s.cam_idx, s.pt_idx, s.K, s.rot, s.t, s.X)
+        return _solve_bits(ba)
+
+
 @pytest.mark.parametrize("kind", ["cam", "pt", "uv"])
 def test_set_problem_rejects_bad_observations_at_the_first_index(kind):
     """The device-side validation of sfm_ba_set_problem (ba_setup.hip
@@ -244,10 +263,11 @@ def test_set_problem_rejects_bad_observations_at_the_first_index(kind):
         with pytest.raises(sfm_amd.SfmError) as ei:
             ba.set_problem(uv, cam, pt, s.K, s.rot, s.t, s.X)
         assert f"at {min(bad)}" in str(ei.value)
-        # the handle stays usable
+        # the handle stays usable: the solve of a handle that never saw the refused call, bit for bit
         ba.set_problem(s.uv, s.cam_idx, s.pt_idx, s.K, s.rot, s.t, s.X)
-        sm, _ = ba.solve()
-        assert sm.num_iterations > 0
+        got = _solve_bits(ba)
+    assert dict(got[0])["num_iterations"] > 0
+    assert got == _fresh_solve_bits("C1")
 
 
 @pytest.mark.parametrize("cfg", ["C2", "small-params"])
@@ -321,9 +341,11 @@ def test_large_set_problem_rejects_the_first_bad_observation(kind):
         with pytest.raises(sfm_amd.SfmError) as ei:
             ba.set_problem(uv, cam, s.pt_idx, s.K, s.rot, s.t, s.X)
         assert want in str(ei.value)
+        # the refused call's buffers are the pool's now: the good one reuses them, and solves to a fresh handle's bits
         ba.set_problem(s.uv, s.cam_idx, s.pt_idx, s.K, s.rot, s.t, s.X)
-        sm, _ = ba.solve()
-        assert sm.num_iterations > 0
+        got = _solve_bits(ba)
+    assert dict(got[0])["num_iterations"] > 0
+    assert got == _fresh_solve_bits("C2")
 
 
 def test_device_layout_keeps_caller_order_of_duplicates():
