@@ -30,6 +30,9 @@ struct DeviceMem {
   static int alloc(void** p, size_t bytes) { return int(hipMalloc(p, bytes)); }
   static void release(void* p) { (void)hipFree(p); }
   static int drain(hipStream_t s) { return int(hipStreamSynchronize(s)); }
+  static int copy(void* dst, const void* src, size_t bytes, hipStream_t s) {
+    return int(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
+  }
 };
 struct PinnedMem {
   using Stream = hipStream_t;

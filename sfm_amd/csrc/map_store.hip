@@ -19,14 +19,19 @@
 //   removeFrame / arePointsSeenByAtLeast CMap.cpp:483-558
 //   CSfM::cullKeyFrames                  CSfM.cpp:708-752 (one call)
 //
-// Layout: observations are kept in global emplace order, which is taken as
-// the multimap's order within one key (the reference's container is an
-// unordered_multimap, CMap.h:96-97, whose equal_range order is
-// implementation-defined; libc++, the reference's toolchain, keeps insertion
-// order) and is the order of each point's _frameNo/_pts2DIdx lists.  Descriptor rows are kept in append order with their point.  The
-// per-point CSRs (observations, descriptor rows) are rebuilt lazily by a
-// stable radix sort after appends.  Queries are flag + stable compaction
-// (hipcub DeviceSelect), so every result keeps the reference's order.
+// Layout: three row tables (RowTable, owner.h: observations, points,
+// descriptor rows), each with one count and one capacity.  Observations are
+// kept in global emplace order, which is taken as the multimap's order within
+// one key (the reference's container is an unordered_multimap, CMap.h:96-97,
+// whose equal_range order is implementation-defined; libc++, the reference's
+// toolchain, keeps insertion order) and is the order of each point's
+// _frameNo/_pts2DIdx lists.  Descriptor rows are kept in append order with
+// their point.  The per-point CSRs (observations, descriptor rows) are
+// rebuilt lazily by a stable radix sort after appends.  Queries are flag +
+// stable compaction (hipcub DeviceSelect), so every result keeps the
+// reference's order.  A call that changes the store reserves everything it
+// can need first (Room, Removal), then enqueues, synchronises once and only
+// then commits the counts and the live mirror and clears the CSR flags.
 //
 // Culling: every point carries _timeAlive / _kfAlive / _ptsViews (int32) and
 // a live flag (membership of _pts3DIdx) beside X, every observation a flag
@@ -48,6 +53,7 @@
 #include <cmath>
 #include <cstring>
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 #include "sfm_trace.h"
@@ -171,7 +177,7 @@ __global__ void k_frame_offsets(int nf, const int32_t* __restrict__ fcnt, int64_
 
 // one wave per queried point: the point's row (in append order) with the
 // smallest sum of Hamming distances to its other rows, the first on ties
-// (CMap.cpp:345-381)
+// (repr_row, mappoint_internal.h)
 template <int W>
 __global__ __launch_bounds__(64) void k_map_repr(const uint64_t* __restrict__ desc, const int32_t* __restrict__ drow,
                                                  const int32_t* __restrict__ doff, const int32_t* __restrict__ qpt,
@@ -186,22 +192,7 @@ __global__ __launch_bounds__(64) void k_map_repr(const uint64_t* __restrict__ de
     if (l < W) out[size_t(i) * W + l] = 0;
     return;
   }
-  unsigned long long key = ~0ull;  // (sum << 32 | local row)
-  for (int r = l; r - l < k; r += 64) {
-    uint64_t x[W];
-    const uint64_t* xr = desc + size_t(drow[r0 + (r < k ? r : 0)]) * W;
-#pragma unroll
-    for (int w = 0; w < W; ++w) x[w] = xr[w];
-    unsigned int sum = 0;
-    for (int q = 0; q < k; ++q) {
-      const uint64_t* y = desc + size_t(drow[r0 + q]) * W;
-#pragma unroll
-      for (int w = 0; w < W; ++w) sum += __popcll(x[w] ^ y[w]);
-    }
-    if (r < k) key = min(key, (static_cast<unsigned long long>(sum) << 32) | unsigned(r));
-  }
-  for (int o = 32; o >= 1; o >>= 1) key = min(key, static_cast<unsigned long long>(__shfl_xor(key, o)));
-  const int b = int(key & 0xffffffffu);
+  const int b = repr_row<W>(k, l, [=](int r) { return desc + size_t(drow[r0 + r]) * W; });
   if (l == 0) best_local[i] = b;
   if (l < W) out[size_t(i) * W + l] = desc[size_t(drow[r0 + b]) * W + l];
 }
@@ -504,12 +495,6 @@ __global__ void k_project(int n, const int32_t* __restrict__ n_dev, const int32_
   uv[2 * size_t(i) + 1] = c1 / c2 * fy + cy;
 }
 
-template <class T>
-struct DVec {
-  DevArr<T> p;
-  int64_t n = 0, cap = 0;
-};
-
 }  // namespace
 // match_kernels.hip
 int matcher_match_current_dev(sfm_matcher* h, hipEvent_t after, const uint64_t* q, const double* p0, int n0,
@@ -525,60 +510,46 @@ using namespace sfm;
 
 // The stream first: members are destroyed in reverse order, so it goes last.
 struct sfm_map {
+  explicit sfm_map(int words) : W(words), rows({sizeof(uint64_t) * size_t(words), sizeof(int32_t)}) {}
   Stream s;
-  int device = 0, desc_bytes = 0, W = 0;
-  DVec<int32_t> ob_pt, ob_frame, ob_idx;  // observations, emplace order
-  DVec<uint8_t> ob_mm;                     // 1: the observation's _frameViewsPointIdx entry exists
-  DVec<double> X;                          // [n_pts][3]
-  DVec<int32_t> pt_time, pt_kf, pt_views;  // _timeAlive, _kfAlive, _ptsViews
-  DVec<uint8_t> pt_live;                   // 1: the point is in _pts3DIdx
-  std::vector<uint8_t> live_h;             // pt_live's host mirror (argument checks make no readback)
+  int device = 0, W;
+  RowTable<DeviceMem, 4> obs{{4, 4, 4, 1}};      // observations, emplace order
+  RowTable<DeviceMem, 5> pts{{24, 4, 4, 4, 1}};  // point slots; n() is the number of points ever added
+  RowTable<DeviceMem, 2> rows;                    // descriptor rows, append order
+  std::vector<uint8_t> live_h;                    // pt_live's host mirror (argument checks make no readback)
   int32_t n_live = 0;
-  int32_t n_pts = 0;
-  DVec<uint64_t> desc;                     // [rows][W]
-  DVec<int32_t> desc_pt;                   // point of each row
-  bool ocsr = false, dcsr = false;         // per-point CSRs current?
+  bool ocsr = false, dcsr = false;                // per-point CSRs current?
   int32_t *orow = nullptr, *ooff = nullptr, *drow = nullptr, *doff = nullptr;  // (views into scratch: build_csr)
   std::map<std::string, DevBuf> scratch;
-  Event ev;                                // sfm_map_match_frame: its queries are ready
-  PinArr<int32_t> pin;                     // the handle's pinned block (pin_reserve)
+  Event ev;                                       // sfm_map_match_frame: its queries are ready
+  PinArr<int32_t> pin;                            // the handle's pinned block (pin_reserve)
+
+  int32_t n_pts() const { return int32_t(pts.n()); }
+  int32_t* ob_pt() const { return obs.col<int32_t>(0); }
+  int32_t* ob_frame() const { return obs.col<int32_t>(1); }
+  int32_t* ob_idx() const { return obs.col<int32_t>(2); }
+  uint8_t* ob_mm() const { return obs.col<uint8_t>(3); }  // 1: the observation's _frameViewsPointIdx entry exists
+  double* X() const { return pts.col<double>(0); }        // [n_pts][3]
+  int32_t* pt_time() const { return pts.col<int32_t>(1); }   // _timeAlive
+  int32_t* pt_kf() const { return pts.col<int32_t>(2); }     // _kfAlive
+  int32_t* pt_views() const { return pts.col<int32_t>(3); }  // _ptsViews
+  uint8_t* pt_live() const { return pts.col<uint8_t>(4); }   // 1: the point is in _pts3DIdx
+  uint64_t* desc() const { return rows.col<uint64_t>(0); }   // [rows][W]
+  int32_t* desc_pt() const { return rows.col<int32_t>(1); }  // point of each row
 };
 
 namespace {
 
-void* scratch(sfm_map* h, const char* name, size_t bytes, int* rc) {
+// the scratch buffer `name`, at least count T (contents dropped when it grows)
+template <class T = uint8_t>
+T* scratch(sfm_map* h, const char* name, size_t count, int* rc) {
   DevBuf& b = h->scratch[name];
   // grow by half again at least: the map grows every keyframe, and a
   // reallocation costs a stream synchronisation plus hipFree / hipMalloc
-  const size_t want = std::max<size_t>({bytes, b.bytes() + b.bytes() / 2, 256});
+  const size_t bytes = sizeof(T) * count, want = std::max<size_t>({bytes, b.bytes() + b.bytes() / 2, 256});
   if (b.reserve(std::max<size_t>(bytes, 1), want, h->s))
     *rc = mapfail(SFM_ENOMEM, std::string("hipMalloc failed (") + name + ")");
-  return b.get();
-}
-
-// The one place that keeps a buffer's contents across growth: a new buffer,
-// the n elements copied on the stream, then the swap.
-template <class T>
-int grow(sfm_map* h, DVec<T>& v, int64_t need) {
-  if (need <= v.cap) return 0;
-  const int64_t cap = std::max<int64_t>({need, 2 * v.cap, 1024});
-  DevArr<T> p;
-  if (p.reserve(size_t(cap) * sizeof(T), size_t(cap) * sizeof(T), nullptr))
-    return mapfail(SFM_ENOMEM, "hipMalloc failed (growth)");
-  if (v.n) (void)hipMemcpyAsync(p, v.p, size_t(v.n) * sizeof(T), hipMemcpyDeviceToDevice, h->s);
-  (void)hipStreamSynchronize(h->s);
-  v.p = std::move(p);
-  v.cap = cap;
-  return 0;
-}
-
-template <class T>
-int append(sfm_map* h, DVec<T>& v, const T* src, int64_t n) {
-  if (int rc = grow(h, v, v.n + n)) return rc;
-  if (n && hipMemcpyAsync(v.p + v.n, src, size_t(n) * sizeof(T), hipMemcpyHostToDevice, h->s) != hipSuccess)
-    return mapfail(SFM_EIO, "upload failed");
-  v.n += n;
-  return 0;
+  return b.as<T>();
 }
 
 // The handle's pinned block, at least n ints (grown while the stream is idle).
@@ -591,17 +562,53 @@ int sync(sfm_map* h) {
   return hipStreamSynchronize(h->s) == hipSuccess ? 0 : mapfail(SFM_EIO, "kernel or copy failed");
 }
 
-// CSR by point of `key` (n entries, keys < P): rows (entry ids grouped by
-// key, ascending within a key = append order) and offsets [P+1]
-int build_csr(sfm_map* h, const char* tag, const int32_t* key, int64_t n, int32_t** rows_out, int32_t** off_out) {
+// ---- the device primitives.  f(temporary, bytes) is a hipcub call: the size
+// query (host only, no data pointer read), the temporary from scratch `tag`,
+// the call.  run = false reserves: the later run with that tag and n allocates nothing.
+template <class F>
+int cub(sfm_map* h, const char* tag, bool run, const char* what, F f) {
   int rc = 0;
-  const int P = h->n_pts;
-  std::string t(tag);
-  auto* kk = static_cast<uint32_t*>(scratch(h, (t + "k").c_str(), sizeof(uint32_t) * std::max<int64_t>(n, 1), &rc));
-  auto* iv = static_cast<int32_t*>(scratch(h, (t + "i").c_str(), sizeof(int32_t) * std::max<int64_t>(n, 1), &rc));
-  auto* rows = static_cast<int32_t*>(scratch(h, (t + "r").c_str(), sizeof(int32_t) * std::max<int64_t>(n, 1), &rc));
-  auto* cnt = static_cast<int32_t*>(scratch(h, (t + "c").c_str(), sizeof(int32_t) * (size_t(P) + 1), &rc));
-  auto* off = static_cast<int32_t*>(scratch(h, (t + "o").c_str(), sizeof(int32_t) * (size_t(P) + 1), &rc));
+  size_t bytes = 0;
+  (void)f(nullptr, bytes);
+  void* tmp = scratch(h, tag, bytes, &rc);
+  if (rc || !run) return rc;
+  return f(tmp, bytes) == hipSuccess ? 0 : mapfail(SFM_EIO, what);
+}
+int exclusive_sum(sfm_map* h, const char* tag, const int32_t* in, int32_t* out, int n, bool run = true) {
+  return cub(h, tag, run, "scan failed",
+             [=](void* p, size_t& b) { return hipcub::DeviceScan::ExclusiveSum(p, b, in, out, n, h->s); });
+}
+// out[0 .. *n_out) = the indices i < n with flag[i] set, ascending (n_out on the device)
+int select_flagged(sfm_map* h, const char* tag, const uint8_t* flag, int32_t* out, int32_t* n_out, int n,
+                   bool run = true) {
+  const hipcub::CountingInputIterator<int32_t> iota(0);
+  return cub(h, tag, run, "select failed",
+             [=](void* p, size_t& b) { return hipcub::DeviceSelect::Flagged(p, b, iota, flag, out, n_out, n, h->s); });
+}
+// stable: (key, val) sorted by the keys' low `bits` bits into (key2, val2)
+int sort_pairs(sfm_map* h, const char* tag, const uint32_t* key, uint32_t* key2, const int32_t* val, int32_t* val2,
+               int n, int bits, const char* what) {
+  return cub(h, tag, true, what, [=](void* p, size_t& b) {
+    return hipcub::DeviceRadixSort::SortPairs(p, b, key, key2, val, val2, n, 0, bits, h->s);
+  });
+}
+
+// CSR by point of `key` (n entries, keys < P): rows (entry ids grouped by
+// key, ascending within a key = append order) and offsets [P+1].  *current is
+// set once the rebuild is enqueued (scratch, an in-order stream), cleared by
+// the commit that stales it.
+int build_csr(sfm_map* h, bool* current, const char* tag, const int32_t* key, int64_t n, int32_t** rows_out,
+              int32_t** off_out) {
+  if (*current) return 0;
+  int rc = 0;
+  const int P = h->n_pts();
+  const std::string t(tag);
+  const size_t n1 = size_t(std::max<int64_t>(n, 1));
+  auto* kk = scratch<uint32_t>(h, (t + "k").c_str(), n1, &rc);
+  auto* iv = scratch<int32_t>(h, (t + "i").c_str(), n1, &rc);
+  auto* rows = scratch<int32_t>(h, (t + "r").c_str(), n1, &rc);
+  auto* cnt = scratch<int32_t>(h, (t + "c").c_str(), size_t(P) + 1, &rc);
+  auto* off = scratch<int32_t>(h, (t + "o").c_str(), size_t(P) + 1, &rc);
   if (rc) return rc;
   (void)hipMemsetAsync(cnt, 0, sizeof(int32_t) * (size_t(P) + 1), h->s);
   if (n) {
@@ -609,159 +616,150 @@ int build_csr(sfm_map* h, const char* tag, const int32_t* key, int64_t n, int32_
     k_iota<<<grid(n), 256, 0, h->s>>>(n, iv);
     int bits = 1;
     while (bits < 32 && (1ll << bits) < P) ++bits;
-    size_t bytes = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, reinterpret_cast<const uint32_t*>(key), kk, iv, rows,
-                                             int(n), 0, bits, h->s);
-    void* tmp = scratch(h, (t + "t").c_str(), bytes, &rc);
-    if (rc) return rc;
-    if (hipcub::DeviceRadixSort::SortPairs(tmp, bytes, reinterpret_cast<const uint32_t*>(key), kk, iv, rows, int(n),
-                                           0, bits, h->s) != hipSuccess)
-      return mapfail(SFM_EIO, "radix sort failed");
+    if (int r = sort_pairs(h, (t + "t").c_str(), reinterpret_cast<const uint32_t*>(key), kk, iv, rows, int(n), bits,
+                           "radix sort failed"))
+      return r;
   }
-  size_t bytes = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, cnt, off, P + 1, h->s);
-  void* tmp = scratch(h, (t + "s").c_str(), bytes, &rc);
-  if (rc) return rc;
-  if (hipcub::DeviceScan::ExclusiveSum(tmp, bytes, cnt, off, P + 1, h->s) != hipSuccess)
-    return mapfail(SFM_EIO, "scan failed");
+  if (int r = exclusive_sum(h, (t + "s").c_str(), cnt, off, P + 1)) return r;
   *rows_out = rows;
   *off_out = off;
+  *current = true;
   return 0;
 }
-
-// n more entries of `value` (a byte pattern: 0, or 1 for the byte arrays)
-template <class T>
-int append_fill(sfm_map* h, DVec<T>& v, int value, int64_t n) {
-  if (int rc = grow(h, v, v.n + n)) return rc;
-  if (n && hipMemsetAsync(v.p + v.n, value, size_t(n) * sizeof(T), h->s) != hipSuccess)
-    return mapfail(SFM_EIO, "memset failed");
-  v.n += n;
-  return 0;
+int ensure_ocsr(sfm_map* h) { return build_csr(h, &h->ocsr, "ob", h->ob_pt(), h->obs.n(), &h->orow, &h->ooff); }
+int ensure_dcsr(sfm_map* h) { return build_csr(h, &h->dcsr, "de", h->desc_pt(), h->rows.n(), &h->drow, &h->doff); }
+int ensure_csrs(sfm_map* h) {
+  const int rc = ensure_ocsr(h);
+  return rc ? rc : ensure_dcsr(h);
 }
 
 // in range and still in the map (a removed point keeps its slot and its X,
 // and is refused everywhere but sfm_map_get_points / sfm_map_set_points)
-int check_live(const sfm_map* h, int32_t n, const int32_t* idx) {
+int check_pts(const sfm_map* h, int32_t n, const int32_t* idx, bool live = false) {
   for (int32_t i = 0; i < n; ++i) {
-    if (idx[i] < 0 || idx[i] >= h->n_pts)
+    if (idx[i] < 0 || idx[i] >= h->n_pts())
       return mapfail(SFM_EINVAL, "point index " + std::to_string(idx[i]) + " out of range at " + std::to_string(i));
-    if (!h->live_h[size_t(idx[i])])
+    if (live && !h->live_h[size_t(idx[i])])
       return mapfail(SFM_EINVAL, "point " + std::to_string(idx[i]) + " (at " + std::to_string(i) + ") was removed");
   }
   return 0;
 }
 
-int check_pts(const sfm_map* h, int32_t n, const int32_t* idx) {
-  for (int32_t i = 0; i < n; ++i)
-    if (idx[i] < 0 || idx[i] >= h->n_pts)
-      return mapfail(SFM_EINVAL, "point index " + std::to_string(idx[i]) + " out of range at " + std::to_string(i));
-  return 0;
+// The opening of a call over a point list (args: its arrays are there): (rc, go).  go: the device is set;
+// else the call ends with rc (0 when n = 0).
+std::pair<int, bool> open_list(sfm_map* h, int32_t n, const int32_t* idx, bool args, bool live) {
+  if (!h) return {mapfail(SFM_EINVAL, "NULL handle"), false};
+  if (n <= 0) return {n < 0 ? mapfail(SFM_EINVAL, "negative size") : 0, false};
+  if (!args) return {mapfail(SFM_EINVAL, "NULL argument"), false};
+  if (int rc = check_pts(h, n, idx, live)) return {rc, false};
+  if (hipSetDevice(h->device) != hipSuccess) return {mapfail(SFM_ENODEV, "hipSetDevice failed"), false};
+  return {0, true};
 }
 
-int ensure_csrs(sfm_map* h) {
-  if (!h->ocsr) {
-    if (int r = build_csr(h, "ob", h->ob_pt.p, h->ob_pt.n, &h->orow, &h->ooff)) return r;
-    h->ocsr = true;
+// Appends.  A Room exists only by growing all three tables for what a call
+// appends; a failed growth leaves every table as it was.  put / fill write
+// the rows past the counts; rc keeps the first failure and stops the rest.
+struct Room {
+  sfm_map* h;
+  int rc = 0;
+  Room(sfm_map* h, int64_t n_obs, int64_t n_pts, int64_t n_rows) : h(h) {
+    if (h->obs.reserve(h->obs.n() + n_obs, h->s) || h->pts.reserve(h->pts.n() + n_pts, h->s) ||
+        h->rows.reserve(h->rows.n() + n_rows, h->s))
+      rc = mapfail(SFM_ENOMEM, "hipMalloc failed (growth)");
   }
-  if (!h->dcsr) {
-    if (int r = build_csr(h, "de", h->desc_pt.p, h->desc.n / h->W, &h->drow, &h->doff)) return r;
-    h->dcsr = true;
+  template <class T>
+  void put(T* dst, const T* src, int64_t n) {
+    if (!rc && n && hipMemcpyAsync(dst, src, size_t(n) * sizeof(T), hipMemcpyHostToDevice, h->s) != hipSuccess)
+      rc = mapfail(SFM_EIO, "upload failed");
   }
-  return 0;
-}
-
-// Tombstones of one culling call: per observation and per descriptor row,
-// 0 kept, 1 removed (2: pending inside k_walk_keyframes).
-struct Tomb {
-  uint8_t *odead = nullptr, *ddead = nullptr;
+  template <class T>  // n entries of `value` (a byte pattern: 0, or 1 for the byte arrays)
+  void fill(T* dst, int value, int64_t n) {
+    if (!rc && n && hipMemsetAsync(dst, value, size_t(n) * sizeof(T), h->s) != hipSuccess)
+      rc = mapfail(SFM_EIO, "memset failed");
+  }
 };
 
-int tomb_begin(sfm_map* h, Tomb* t) {
+// Removals.  Everything one can need, taken before its first write to the
+// store: the tombstones (per observation and descriptor row: 0 kept, 1
+// removed, 2 pending inside k_walk_keyframes), the pinned block of n_pin ints
+// and, with `compacting`, compact's ten arrays and its two scans' temporaries.
+struct Removal {
   int rc = 0;
-  const size_t N = size_t(h->ob_pt.n), rows = size_t(h->desc.n / h->W);
-  t->odead = static_cast<uint8_t*>(scratch(h, "odead", std::max<size_t>(N, 1), &rc));
-  t->ddead = static_cast<uint8_t*>(scratch(h, "ddead", std::max<size_t>(rows, 1), &rc));
-  if (rc) return rc;
-  (void)hipMemsetAsync(t->odead, 0, std::max<size_t>(N, 1), h->s);
-  (void)hipMemsetAsync(t->ddead, 0, std::max<size_t>(rows, 1), h->s);
-  return 0;
+  int64_t N, rows;
+  uint8_t *odead, *ddead, *mm2;
+  int32_t *okeep, *opos, *dkeep, *dpos, *pt2, *fr2, *ix2, *dpt2, *pin;
+  uint64_t* desc2;
+  Removal(sfm_map* h, size_t n_pin, bool compacting = true) : N(h->obs.n()), rows(h->rows.n()) {
+    const size_t n1 = size_t(std::max<int64_t>(N, 1)), r1 = size_t(std::max<int64_t>(rows, 1));
+    odead = scratch<uint8_t>(h, "odead", n1, &rc);
+    ddead = scratch<uint8_t>(h, "ddead", r1, &rc);
+    pin = pin_reserve(h, n_pin, &rc);
+    if (!compacting) return;
+    okeep = scratch<int32_t>(h, "cok", n1, &rc);
+    opos = scratch<int32_t>(h, "cop", n1, &rc);
+    dkeep = scratch<int32_t>(h, "cdk", r1, &rc);
+    dpos = scratch<int32_t>(h, "cdp", r1, &rc);
+    pt2 = scratch<int32_t>(h, "cpt", n1, &rc);
+    fr2 = scratch<int32_t>(h, "cfr", n1, &rc);
+    ix2 = scratch<int32_t>(h, "cix", n1, &rc);
+    mm2 = scratch<uint8_t>(h, "cmm", n1, &rc);
+    desc2 = scratch<uint64_t>(h, "cde", r1 * h->W, &rc);
+    dpt2 = scratch<int32_t>(h, "cdq", r1, &rc);
+    if (int r = N ? exclusive_sum(h, "cos", okeep, opos, int(N), false) : 0) rc = r;
+    if (int r = rows ? exclusive_sum(h, "cds", dkeep, dpos, int(rows), false) : 0) rc = r;
+  }
+};
+
+void tomb_clear(sfm_map* h, const Removal& m) {
+  (void)hipMemsetAsync(m.odead, 0, size_t(std::max<int64_t>(m.N, 1)), h->s);
+  (void)hipMemsetAsync(m.ddead, 0, size_t(std::max<int64_t>(m.rows, 1)), h->s);
 }
 
-int exclusive_sum(sfm_map* h, const char* tag, const int32_t* in, int32_t* out, int n) {
-  int rc = 0;
-  size_t bytes = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, n, h->s);
-  void* tmp = scratch(h, tag, bytes, &rc);
-  if (rc) return rc;
-  if (hipcub::DeviceScan::ExclusiveSum(tmp, bytes, in, out, n, h->s) != hipSuccess)
-    return mapfail(SFM_EIO, "scan failed");
-  return 0;
-}
-
-// One stable compaction of the observation arrays and of desc / desc_pt past
-// the call's tombstones, enqueued on the stream: keep flags, their exclusive
-// scan (hipcub), a scatter into scratch copies, and the copies back.  tot
-// (device, 2 ints) receives the new sizes; the caller reads them with its one
-// readback and passes them to compact_done.
-int compact(sfm_map* h, const Tomb& t, int32_t* tot) {
-  int rc = 0;
-  const int64_t N = h->ob_pt.n, rows = h->desc.n / h->W;
-  const size_t n1 = size_t(std::max<int64_t>(N, 1)), r1 = size_t(std::max<int64_t>(rows, 1));
-  auto* okeep = static_cast<int32_t*>(scratch(h, "cok", sizeof(int32_t) * n1, &rc));
-  auto* opos = static_cast<int32_t*>(scratch(h, "cop", sizeof(int32_t) * n1, &rc));
-  auto* dkeep = static_cast<int32_t*>(scratch(h, "cdk", sizeof(int32_t) * r1, &rc));
-  auto* dpos = static_cast<int32_t*>(scratch(h, "cdp", sizeof(int32_t) * r1, &rc));
-  auto* pt2 = static_cast<int32_t*>(scratch(h, "cpt", sizeof(int32_t) * n1, &rc));
-  auto* fr2 = static_cast<int32_t*>(scratch(h, "cfr", sizeof(int32_t) * n1, &rc));
-  auto* ix2 = static_cast<int32_t*>(scratch(h, "cix", sizeof(int32_t) * n1, &rc));
-  auto* mm2 = static_cast<uint8_t*>(scratch(h, "cmm", n1, &rc));
-  auto* desc2 = static_cast<uint64_t*>(scratch(h, "cde", sizeof(uint64_t) * r1 * h->W, &rc));
-  auto* dpt2 = static_cast<int32_t*>(scratch(h, "cdq", sizeof(int32_t) * r1, &rc));
-  if (rc) return rc;
+// One stable compaction of the observation table and of the descriptor rows
+// past the call's tombstones, enqueued on the stream: keep flags, their
+// exclusive scan (hipcub), a scatter into scratch copies, and the copies back.
+// tot (device, 2 ints) receives the new sizes; the caller reads them with its
+// one readback and passes them to compact_done.
+int compact(sfm_map* h, const Removal& m, int32_t* tot) {
+  const int64_t N = m.N, rows = m.rows;
   if (N) {
-    k_keep<<<grid(N), 256, 0, h->s>>>(N, t.odead, okeep);
-    if (int r = exclusive_sum(h, "cos", okeep, opos, int(N))) return r;
+    k_keep<<<grid(N), 256, 0, h->s>>>(N, m.odead, m.okeep);
+    if (int r = exclusive_sum(h, "cos", m.okeep, m.opos, int(N))) return r;
+    k_compact_obs<<<grid(N), 256, 0, h->s>>>(N, m.odead, m.opos, h->ob_pt(), h->ob_frame(), h->ob_idx(), h->ob_mm(),
+                                             m.pt2, m.fr2, m.ix2, m.mm2);
+    (void)hipMemcpyAsync(h->ob_pt(), m.pt2, sizeof(int32_t) * size_t(N), hipMemcpyDeviceToDevice, h->s);
+    (void)hipMemcpyAsync(h->ob_frame(), m.fr2, sizeof(int32_t) * size_t(N), hipMemcpyDeviceToDevice, h->s);
+    (void)hipMemcpyAsync(h->ob_idx(), m.ix2, sizeof(int32_t) * size_t(N), hipMemcpyDeviceToDevice, h->s);
+    (void)hipMemcpyAsync(h->ob_mm(), m.mm2, size_t(N), hipMemcpyDeviceToDevice, h->s);
   }
   if (rows) {
-    k_keep<<<grid(rows), 256, 0, h->s>>>(rows, t.ddead, dkeep);
-    if (int r = exclusive_sum(h, "cds", dkeep, dpos, int(rows))) return r;
+    k_keep<<<grid(rows), 256, 0, h->s>>>(rows, m.ddead, m.dkeep);
+    if (int r = exclusive_sum(h, "cds", m.dkeep, m.dpos, int(rows))) return r;
+    k_compact_desc<<<grid(rows * h->W), 256, 0, h->s>>>(rows, h->W, m.ddead, m.dpos, h->desc(), h->desc_pt(), m.desc2,
+                                                        m.dpt2);
+    (void)hipMemcpyAsync(h->desc(), m.desc2, sizeof(uint64_t) * size_t(rows) * h->W, hipMemcpyDeviceToDevice, h->s);
+    (void)hipMemcpyAsync(h->desc_pt(), m.dpt2, sizeof(int32_t) * size_t(rows), hipMemcpyDeviceToDevice, h->s);
   }
-  k_totals<<<1, 1, 0, h->s>>>(N, rows, okeep, opos, dkeep, dpos, tot);
-  if (N) {
-    k_compact_obs<<<grid(N), 256, 0, h->s>>>(N, t.odead, opos, h->ob_pt.p, h->ob_frame.p, h->ob_idx.p, h->ob_mm.p, pt2,
-                                             fr2, ix2, mm2);
-    (void)hipMemcpyAsync(h->ob_pt.p, pt2, sizeof(int32_t) * size_t(N), hipMemcpyDeviceToDevice, h->s);
-    (void)hipMemcpyAsync(h->ob_frame.p, fr2, sizeof(int32_t) * size_t(N), hipMemcpyDeviceToDevice, h->s);
-    (void)hipMemcpyAsync(h->ob_idx.p, ix2, sizeof(int32_t) * size_t(N), hipMemcpyDeviceToDevice, h->s);
-    (void)hipMemcpyAsync(h->ob_mm.p, mm2, size_t(N), hipMemcpyDeviceToDevice, h->s);
-  }
-  if (rows) {
-    k_compact_desc<<<grid(rows * h->W), 256, 0, h->s>>>(rows, h->W, t.ddead, dpos, h->desc.p, h->desc_pt.p, desc2,
-                                                        dpt2);
-    (void)hipMemcpyAsync(h->desc.p, desc2, sizeof(uint64_t) * size_t(rows) * h->W, hipMemcpyDeviceToDevice, h->s);
-    (void)hipMemcpyAsync(h->desc_pt.p, dpt2, sizeof(int32_t) * size_t(rows), hipMemcpyDeviceToDevice, h->s);
-  }
+  k_totals<<<1, 1, 0, h->s>>>(N, rows, m.okeep, m.opos, m.dkeep, m.dpos, tot);
   return 0;
 }
 
 void compact_done(sfm_map* h, const int32_t* tot) {
-  if (tot[0] == h->ob_pt.n && int64_t(tot[1]) * h->W == h->desc.n) return;  // nothing left: the CSRs stand
-  h->ob_pt.n = h->ob_frame.n = h->ob_idx.n = h->ob_mm.n = tot[0];
-  h->desc.n = int64_t(tot[1]) * h->W;
-  h->desc_pt.n = tot[1];
+  if (tot[0] == h->obs.n() && tot[1] == h->rows.n()) return;  // nothing left: the CSRs stand
+  h->obs.truncate(tot[0]);
+  h->rows.truncate(tot[1]);
   h->ocsr = h->dcsr = false;
 }
 
 // The flagged points' removal and the compaction, enqueued (res: count,
 // tot[2], list [P], status [P] on the device)
-int kill_and_compact(sfm_map* h, const uint8_t* flag, const int32_t* n_dev, int capacity, int32_t* res) {
-  Tomb t;
-  if (int r = tomb_begin(h, &t)) return r;
-  const int P = h->n_pts;
-  const int64_t N = h->ob_pt.n, rows = h->desc.n / h->W;
-  k_kill_points<<<grid(std::max<int64_t>({P, N, rows})), 256, 0, h->s>>>(
-      P, N, rows, flag, n_dev, capacity, h->ob_pt.p, h->desc_pt.p, h->pt_live.p, t.odead, t.ddead, res + 3 + P);
-  return compact(h, t, res + 1);
+int kill_and_compact(sfm_map* h, const Removal& m, const uint8_t* flag, const int32_t* n_dev, int capacity,
+                     int32_t* res) {
+  const int P = h->n_pts();
+  tomb_clear(h, m);
+  k_kill_points<<<grid(std::max<int64_t>({P, m.N, m.rows})), 256, 0, h->s>>>(
+      P, m.N, m.rows, flag, n_dev, capacity, h->ob_pt(), h->desc_pt(), h->pt_live(), m.odead, m.ddead, res + 3 + P);
+  return compact(h, m, res + 1);
 }
 
 // CSfM::cullKeyFrames (mode 0), CMap::removeFrame (1) and
@@ -778,38 +776,35 @@ int walk_keyframes(sfm_map* h, int mode, int32_t n_kf, const int32_t* frame_no, 
     if (off[k + 1] < off[k]) return mapfail(SFM_EINVAL, "off must not decrease");
   const int32_t total = off[n_kf];
   if (total && !pts) return mapfail(SFM_EINVAL, "NULL point list");
-  if (int rc = check_live(h, total, pts)) return rc;
+  if (int rc = check_pts(h, total, pts, true)) return rc;
   if (mode != 1 && !(ratio == ratio)) return mapfail(SFM_EINVAL, "ratio is NaN");
   if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
   if (int rc = ensure_csrs(h)) return rc;
   int rc = 0;
-  const int P = h->n_pts;
-  const int64_t N = h->ob_pt.n;
+  const int P = h->n_pts();
+  const int64_t N = h->obs.n();
   // one upload: frame numbers, offsets, thresholds, lists
-  std::vector<int32_t> in(size_t(3) * n_kf + 1 + size_t(total));
-  int32_t* in_f = in.data();
-  int32_t* in_off = in_f + n_kf;
-  int32_t* in_thr = in_off + n_kf + 1;
-  int32_t* in_pts = in_thr + n_kf;
+  std::vector<int32_t> in(frame_no, frame_no + n_kf);
+  in.insert(in.end(), off, off + n_kf + 1);
   for (int k = 0; k < n_kf; ++k) {
-    in_f[k] = frame_no[k];
     // int ptsThreshold = ceil(ratioPtsThreshold * pts3DIdx.size()), the product in double (CMap.cpp:546)
     const double v = mode == 1 ? 0.0 : std::ceil(ratio * double(off[k + 1] - off[k]));
-    in_thr[k] = v >= double(INT_MAX) ? INT_MAX : v <= double(INT_MIN) ? INT_MIN : int32_t(v);
+    in.push_back(v >= double(INT_MAX) ? INT_MAX : v <= double(INT_MIN) ? INT_MIN : int32_t(v));
   }
-  std::memcpy(in_off, off, sizeof(int32_t) * (size_t(n_kf) + 1));
-  if (total) std::memcpy(in_pts, pts, sizeof(int32_t) * size_t(total));
-  auto* din = static_cast<int32_t*>(scratch(h, "kin", sizeof(int32_t) * in.size(), &rc));
-  auto* res = static_cast<int32_t*>(scratch(h, "kres", sizeof(int32_t) * (size_t(n_kf) + 6), &rc));
-  auto* nobs = static_cast<int32_t*>(scratch(h, "knobs", sizeof(int32_t) * size_t(std::max(P, 1)), &rc));
-  auto* cnt = static_cast<int32_t*>(scratch(h, "kcnt", sizeof(int32_t) * size_t(std::max(P, 1)), &rc));
-  auto* own = static_cast<uint8_t*>(scratch(h, "kown", size_t(std::max(total, 1)), &rc));
+  if (total) in.insert(in.end(), pts, pts + total);
+  const size_t nres = size_t(n_kf) + 6;  // culled [n_kf], err [4], the sizes after [2]
+  auto* din = scratch<int32_t>(h, "kin", in.size(), &rc);
+  auto* res = scratch<int32_t>(h, "kres", nres, &rc);
+  auto* nobs = scratch<int32_t>(h, "knobs", size_t(std::max(P, 1)), &rc);
+  auto* cnt = scratch<int32_t>(h, "kcnt", size_t(std::max(P, 1)), &rc);
+  auto* own = scratch<uint8_t>(h, "kown", size_t(std::max(total, 1)), &rc);
   if (rc) return rc;
-  Tomb t;
-  if (int r = tomb_begin(h, &t)) return r;
+  const Removal m(h, nres, mode != 2);
+  if (m.rc) return m.rc;
   if (hipMemcpyAsync(din, in.data(), sizeof(int32_t) * in.size(), hipMemcpyHostToDevice, h->s) != hipSuccess)
     return mapfail(SFM_EIO, "upload failed");
-  (void)hipMemsetAsync(res, 0, sizeof(int32_t) * (size_t(n_kf) + 6), h->s);
+  tomb_clear(h, m);
+  (void)hipMemsetAsync(res, 0, sizeof(int32_t) * nres, h->s);
   (void)hipMemsetAsync(cnt, 0, sizeof(int32_t) * size_t(std::max(P, 1)), h->s);
   if (P) k_nobs<<<grid(P), 256, 0, h->s>>>(P, h->ooff, nobs);
   KfWalk a;
@@ -820,27 +815,26 @@ int walk_keyframes(sfm_map* h, int mode, int32_t n_kf, const int32_t* frame_no, 
   a.off = din + n_kf;
   a.thr = din + 2 * size_t(n_kf) + 1;
   a.pts = din + 3 * size_t(n_kf) + 1;
-  a.ob_frame = h->ob_frame.p;
+  a.ob_frame = h->ob_frame();
   a.orow = h->orow;
   a.ooff = h->ooff;
   a.drow = h->drow;
   a.doff = h->doff;
-  a.odead = t.odead;
-  a.ddead = t.ddead;
+  a.odead = m.odead;
+  a.ddead = m.ddead;
   a.own = own;
   a.nobs = nobs;
-  a.views = h->pt_views.p;
+  a.views = h->pt_views();
   a.cnt = cnt;
   a.culled = res;
   a.err = res + n_kf;
   if (a.n_walk > 0) k_walk_keyframes<<<1, 1024, 0, h->s>>>(a);
   if (mode != 2) {
-    if (N) k_clear_mm<<<grid(N), 256, 0, h->s>>>(N, h->ob_frame.p, t.odead, n_kf, a.frame_no, res, h->ob_mm.p);
-    if (int r = compact(h, t, res + n_kf + 4)) return r;
+    if (N) k_clear_mm<<<grid(N), 256, 0, h->s>>>(N, h->ob_frame(), m.odead, n_kf, a.frame_no, res, h->ob_mm());
+    if (int r = compact(h, m, res + n_kf + 4)) return r;
   }
-  int32_t* ph = pin_reserve(h, size_t(n_kf) + 6, &rc);
-  if (rc) return rc;
-  (void)hipMemcpyAsync(ph, res, sizeof(int32_t) * (size_t(n_kf) + 6), hipMemcpyDeviceToHost, h->s);
+  const int32_t* ph = m.pin;
+  (void)hipMemcpyAsync(m.pin, res, sizeof(int32_t) * nres, hipMemcpyDeviceToHost, h->s);
   if (int r = sync(h)) return r;
   if (mode != 2) compact_done(h, ph + n_kf + 4);
   std::memcpy(culled, ph, sizeof(int32_t) * size_t(n_kf));
@@ -850,6 +844,32 @@ int walk_keyframes(sfm_map* h, int mode, int32_t n_kf, const int32_t* frame_no, 
                                    " of keyframe " + std::to_string(err[1]) +
                                    " does not hold the frame (with a descriptor row) where the bisection of its "
                                    "frame list ends; this keyframe was left as it was");
+  return 0;
+}
+
+// getPointsInFrames, enqueued, all on the device: the points with an observation (its multimap entry
+// standing) in any of the frames fset[0 .. nf) (ascending), minus the points minus[0 .. n_minus),
+// ascending in out[0 .. *dn) (out holds n_pts ints).
+int select_points_in_frames(sfm_map* h, const int32_t* fset, int nf, const int32_t* minus, int n_minus, int32_t* out,
+                            int32_t* dn) {
+  int rc = 0;
+  const int P = h->n_pts();
+  auto* mark = scratch<uint8_t>(h, "mark", size_t(P), &rc);
+  if (rc) return rc;
+  (void)hipMemsetAsync(mark, 0, size_t(P), h->s);
+  k_mark_frames<<<grid(h->obs.n()), 256, 0, h->s>>>(h->obs.n(), h->ob_pt(), h->ob_frame(), h->ob_mm(), fset, nf, mark);
+  if (n_minus) k_unmark<<<grid(n_minus), 256, 0, h->s>>>(n_minus, minus, mark);
+  return select_flagged(h, "psel", mark, out, dn, P);
+}
+
+// k_map_repr for the handle's descriptor width
+int launch_map_repr(sfm_map* h, int n, const int32_t* qpt, const int32_t* n_dev, int32_t* best, uint64_t* out) {
+  switch (h->W) {
+#define CASE(w) case w: k_map_repr<w><<<n, 64, 0, h->s>>>(h->desc(), h->drow, h->doff, qpt, n, n_dev, best, out); break;
+    CASE(1) CASE(2) CASE(4) CASE(8) CASE(16) CASE(32) CASE(64)
+#undef CASE
+    default: return mapfail(SFM_EINVAL, "descriptor width");  // excluded by sfm_map_create
+  }
   return 0;
 }
 
@@ -865,10 +885,8 @@ int sfm_map_create(int32_t device, int32_t desc_bytes, sfm_map** out) {
   int nd = 0;
   if (hipGetDeviceCount(&nd) != hipSuccess || device < 0 || device >= nd) return mapfail(SFM_ENODEV, "no such device");
   if (hipSetDevice(device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
-  auto* h = new sfm_map;
+  auto* h = new sfm_map(desc_bytes / 8);
   h->device = device;
-  h->desc_bytes = desc_bytes;
-  h->W = desc_bytes / 8;
   if (h->s.create(hipStreamNonBlocking) != hipSuccess) {
     delete h;
     return mapfail(SFM_EIO, "hipStreamCreate failed");
@@ -887,9 +905,9 @@ int sfm_map_destroy(sfm_map* h) {
 
 int sfm_map_size(sfm_map* h, int32_t* n_pts, int64_t* n_obs, int64_t* n_desc_rows) {
   if (!h) return mapfail(SFM_EINVAL, "NULL handle");
-  if (n_pts) *n_pts = h->n_pts;
-  if (n_obs) *n_obs = h->ob_pt.n;
-  if (n_desc_rows) *n_desc_rows = h->desc.n / h->W;
+  if (n_pts) *n_pts = h->n_pts();
+  if (n_obs) *n_obs = h->obs.n();
+  if (n_desc_rows) *n_desc_rows = h->rows.n();
   return 0;
 }
 
@@ -902,67 +920,72 @@ int sfm_map_add_new_points(sfm_map* h, int32_t n_pts, const double* pts3d, int32
   if (!pts3d || (n_frames && (!frame_no || !pts2d_idx))) return mapfail(SFM_EINVAL, "NULL argument");
   if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
   // emplace order of CMap.cpp:50-68: point i, then its frames j
-  const int64_t m = int64_t(n_pts) * n_frames;
+  const int64_t m = int64_t(n_pts) * n_frames, N = h->obs.n();
+  const int32_t P = h->n_pts();
   std::vector<int32_t> pt(m), fr(m), ix(m);
   for (int32_t i = 0; i < n_pts; ++i)
     for (int32_t j = 0; j < n_frames; ++j) {
       const int64_t e = int64_t(i) * n_frames + j;
-      pt[e] = h->n_pts + i;
+      pt[e] = P + i;
       fr[e] = frame_no[j];
       ix[e] = pts2d_idx[int64_t(j) * n_pts + i];
     }
-  if (int rc = append(h, h->X, pts3d, int64_t(n_pts) * 3)) return rc;
-  if (int rc = append(h, h->ob_pt, pt.data(), m)) return rc;
-  if (int rc = append(h, h->ob_frame, fr.data(), m)) return rc;
-  if (int rc = append(h, h->ob_idx, ix.data(), m)) return rc;
-  if (int rc = append_fill(h, h->ob_mm, 1, m)) return rc;
+  Room room(h, m, n_pts, 0);
+  room.put(h->X() + 3 * size_t(P), pts3d, int64_t(n_pts) * 3);
+  room.put(h->ob_pt() + N, pt.data(), m);
+  room.put(h->ob_frame() + N, fr.data(), m);
+  room.put(h->ob_idx() + N, ix.data(), m);
+  room.fill(h->ob_mm() + N, 1, m);
   // views = the frame count, ages 0, in _pts3DIdx (CMap.cpp:36-78)
-  if (int rc = append_fill(h, h->pt_time, 0, n_pts)) return rc;
-  if (int rc = append_fill(h, h->pt_kf, 0, n_pts)) return rc;
-  if (int rc = append_fill(h, h->pt_views, 0, n_pts)) return rc;
-  if (int rc = append_fill(h, h->pt_live, 1, n_pts)) return rc;
-  if (n_frames) k_fill_i32<<<grid(n_pts), 256, 0, h->s>>>(n_pts, h->pt_views.p + h->n_pts, n_frames);
-  h->live_h.resize(size_t(h->n_pts) + n_pts, 1);
+  room.fill(h->pt_time() + P, 0, n_pts);
+  room.fill(h->pt_kf() + P, 0, n_pts);
+  room.fill(h->pt_views() + P, 0, n_pts);
+  room.fill(h->pt_live() + P, 1, n_pts);
+  if (room.rc) return room.rc;
+  if (n_frames) k_fill_i32<<<grid(n_pts), 256, 0, h->s>>>(n_pts, h->pt_views() + P, n_frames);
+  if (int rc = sync(h)) return rc;
+  h->obs.commit(m);
+  h->pts.commit(n_pts);
+  h->live_h.resize(size_t(P) + n_pts, 1);
   h->n_live += n_pts;
   if (pts3d_idx)
-    for (int32_t i = 0; i < n_pts; ++i) pts3d_idx[i] = h->n_pts + i;
-  h->n_pts += n_pts;
+    for (int32_t i = 0; i < n_pts; ++i) pts3d_idx[i] = P + i;
   h->ocsr = h->dcsr = false;
-  return sync(h);
+  return 0;
 }
 
 int sfm_map_add_point_matches(sfm_map* h, int32_t n, const int32_t* pts3d_idx, const int32_t* pts2d_idx,
                               int32_t frame_no) {
-  if (!h) return mapfail(SFM_EINVAL, "NULL handle");
-  if (n < 0) return mapfail(SFM_EINVAL, "negative size");
-  if (n == 0) return 0;
-  if (!pts3d_idx || !pts2d_idx) return mapfail(SFM_EINVAL, "NULL argument");
-  if (int rc = check_live(h, n, pts3d_idx)) return rc;
-  if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
-  std::vector<int32_t> fr(size_t(n), frame_no);
-  if (int rc = append(h, h->ob_pt, pts3d_idx, n)) return rc;
-  if (int rc = append(h, h->ob_frame, fr.data(), n)) return rc;
-  if (int rc = append(h, h->ob_idx, pts2d_idx, n)) return rc;
-  if (int rc = append_fill(h, h->ob_mm, 1, n)) return rc;
-  k_add_views<<<grid(n), 256, 0, h->s>>>(n, h->ob_pt.p + h->ob_pt.n - n, h->pt_views.p);  // _ptsViews[idx]++
+  if (const auto [rc, go] = open_list(h, n, pts3d_idx, pts3d_idx && pts2d_idx, true); !go) return rc;
+  const std::vector<int32_t> fr(size_t(n), frame_no);
+  const int64_t N = h->obs.n();
+  Room room(h, n, 0, 0);
+  room.put(h->ob_pt() + N, pts3d_idx, n);
+  room.put(h->ob_frame() + N, fr.data(), n);
+  room.put(h->ob_idx() + N, pts2d_idx, n);
+  room.fill(h->ob_mm() + N, 1, n);
+  if (room.rc) return room.rc;
+  k_add_views<<<grid(n), 256, 0, h->s>>>(n, h->ob_pt() + N, h->pt_views());  // _ptsViews[idx]++
+  if (int rc = sync(h)) return rc;
+  h->obs.commit(n);
   h->ocsr = false;
-  return sync(h);
+  return 0;
 }
 
 int sfm_map_add_descriptors(sfm_map* h, int32_t n, const int32_t* pts3d_idx, const uint8_t* desc) {
-  if (!h) return mapfail(SFM_EINVAL, "NULL handle");
-  if (n < 0) return mapfail(SFM_EINVAL, "negative size");
-  if (n == 0) return 0;
-  if (!pts3d_idx || !desc) return mapfail(SFM_EINVAL, "NULL argument");
-  if (int rc = check_live(h, n, pts3d_idx)) return rc;
-  if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
+  if (const auto [rc, go] = open_list(h, n, pts3d_idx, pts3d_idx && desc, true); !go) return rc;
   // rows are desc_bytes = 8 W bytes: copy as words (unaligned host bytes)
   std::vector<uint64_t> words(size_t(n) * h->W);
-  std::memcpy(words.data(), desc, size_t(n) * h->desc_bytes);
-  if (int rc = append(h, h->desc, words.data(), int64_t(n) * h->W)) return rc;
-  if (int rc = append(h, h->desc_pt, pts3d_idx, n)) return rc;
+  std::memcpy(words.data(), desc, words.size() * sizeof(uint64_t));
+  const int64_t R = h->rows.n();
+  Room room(h, 0, 0, n);
+  room.put(h->desc() + size_t(R) * h->W, words.data(), int64_t(n) * h->W);
+  room.put(h->desc_pt() + R, pts3d_idx, n);
+  if (room.rc) return room.rc;
+  if (int rc = sync(h)) return rc;
+  h->rows.commit(n);
   h->dcsr = false;
-  return sync(h);
+  return 0;
 }
 
 // addPointMatches(pts3d_idx, rows, frame_no) (with_observations != 0) then
@@ -977,7 +1000,7 @@ int sfm_map_add_keyframe_rows(sfm_map* h, sfm_matcher* mt, int32_t slot, int32_t
   if (n && (!pts3d_idx || !rows)) return mapfail(SFM_EINVAL, "NULL argument");
   if (matcher_words(mt) != h->W || matcher_device(mt) != h->device)
     return mapfail(SFM_EINVAL, "the map and the matcher differ in descriptor width or device");
-  if (int rc = check_live(h, n, pts3d_idx)) return rc;
+  if (int rc = check_pts(h, n, pts3d_idx, true)) return rc;
   if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
   const uint64_t* kdesc = nullptr;
   int kn = 0;
@@ -988,14 +1011,12 @@ int sfm_map_add_keyframe_rows(sfm_map* h, sfm_matcher* mt, int32_t slot, int32_t
       return mapfail(SFM_EINVAL, "keyframe row " + std::to_string(rows[i]) + " out of range at " + std::to_string(i));
   if (n == 0) return 0;
   int rc = 0;
-  auto* up = static_cast<int32_t*>(scratch(h, "kfrows", sizeof(int32_t) * 2 * size_t(n), &rc));
+  auto* up = scratch<int32_t>(h, "kfrows", 2 * size_t(n), &rc);
   int32_t* pin = pin_reserve(h, 2 * size_t(n), &rc);
   if (rc) return rc;
-  const int64_t no = with_observations ? n : 0;
-  if ((rc = grow(h, h->ob_pt, h->ob_pt.n + no)) || (rc = grow(h, h->ob_frame, h->ob_frame.n + no)) ||
-      (rc = grow(h, h->ob_idx, h->ob_idx.n + no)) || (rc = grow(h, h->ob_mm, h->ob_mm.n + no)) ||
-      (rc = grow(h, h->desc, h->desc.n + int64_t(n) * h->W)) || (rc = grow(h, h->desc_pt, h->desc_pt.n + n)))
-    return rc;
+  const Room room(h, with_observations ? n : 0, 0, n);  // (written on the device below, not through put / fill)
+  if (room.rc) return room.rc;
+  const int64_t N = h->obs.n(), R = h->rows.n();
   // the keyframe's rows are the matcher's upload: ordered after its stream
   if (hipStreamWaitEvent(h->s, ready, 0) != hipSuccess) return mapfail(SFM_EIO, "stream wait failed");
   (void)hipStreamSynchronize(h->s);  // (the pinned block may feed an earlier copy)
@@ -1004,45 +1025,39 @@ int sfm_map_add_keyframe_rows(sfm_map* h, sfm_matcher* mt, int32_t slot, int32_t
   (void)hipMemcpyAsync(up, pin, sizeof(int32_t) * 2 * size_t(n), hipMemcpyHostToDevice, h->s);
   const size_t nb = sizeof(int32_t) * size_t(n);
   if (with_observations) {
-    (void)hipMemcpyAsync(h->ob_pt.p + h->ob_pt.n, up, nb, hipMemcpyDeviceToDevice, h->s);
-    (void)hipMemcpyAsync(h->ob_idx.p + h->ob_idx.n, up + n, nb, hipMemcpyDeviceToDevice, h->s);
-    k_fill_i32<<<grid(n), 256, 0, h->s>>>(n, h->ob_frame.p + h->ob_frame.n, frame_no);
-    (void)hipMemsetAsync(h->ob_mm.p + h->ob_mm.n, 1, size_t(n), h->s);
-    k_add_views<<<grid(n), 256, 0, h->s>>>(n, up, h->pt_views.p);  // _ptsViews[idx]++
-    h->ob_pt.n += n;
-    h->ob_frame.n += n;
-    h->ob_idx.n += n;
-    h->ob_mm.n += n;
+    (void)hipMemcpyAsync(h->ob_pt() + N, up, nb, hipMemcpyDeviceToDevice, h->s);
+    (void)hipMemcpyAsync(h->ob_idx() + N, up + n, nb, hipMemcpyDeviceToDevice, h->s);
+    k_fill_i32<<<grid(n), 256, 0, h->s>>>(n, h->ob_frame() + N, frame_no);
+    (void)hipMemsetAsync(h->ob_mm() + N, 1, size_t(n), h->s);
+    k_add_views<<<grid(n), 256, 0, h->s>>>(n, up, h->pt_views());  // _ptsViews[idx]++
+  }
+  launch_copy_desc_rows(h->s, n, up + n, kdesc, h->W, h->desc() + size_t(R) * h->W);
+  (void)hipMemcpyAsync(h->desc_pt() + R, up, nb, hipMemcpyDeviceToDevice, h->s);
+  if ((rc = sync(h))) return rc;
+  if (with_observations) {
+    h->obs.commit(n);
     h->ocsr = false;
   }
-  launch_copy_desc_rows(h->s, n, up + n, kdesc, h->W, h->desc.p + h->desc.n);
-  (void)hipMemcpyAsync(h->desc_pt.p + h->desc_pt.n, up, nb, hipMemcpyDeviceToDevice, h->s);
-  h->desc.n += int64_t(n) * h->W;
-  h->desc_pt.n += n;
+  h->rows.commit(n);
   h->dcsr = false;
-  return sync(h);
+  return 0;
 }
 
 int sfm_map_get_points(sfm_map* h, int32_t n, const int32_t* pts3d_idx, double* pts3d) {
   SFM_TRACE("sfm_map_get_points");
-  if (!h) return mapfail(SFM_EINVAL, "NULL handle");
-  if (n <= 0) return n < 0 ? mapfail(SFM_EINVAL, "negative size") : 0;
-  if (!pts3d_idx || !pts3d) return mapfail(SFM_EINVAL, "NULL argument");
-  if (int rc = check_pts(h, n, pts3d_idx)) return rc;
-  if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
+  if (const auto [rc, go] = open_list(h, n, pts3d_idx, pts3d_idx && pts3d, false); !go) return rc;
   // gathered on the device: the indices up, n points down (the whole X
   // array went down before: 140 KB per tracked frame at 6k points)
   int rc = 0;
-  auto* di = static_cast<int32_t*>(scratch(h, "gi", sizeof(int32_t) * size_t(n), &rc));
-  auto* dv = static_cast<double*>(scratch(h, "gv", sizeof(double) * 3 * size_t(n), &rc));
-  if (rc) return rc;
+  auto* di = scratch<int32_t>(h, "gi", size_t(n), &rc);
+  auto* dv = scratch<double>(h, "gv", 3 * size_t(n), &rc);
   pin_reserve(h, 8 * size_t(n) + 8, &rc);
   if (rc) return rc;
   (void)hipStreamSynchronize(h->s);  // (the pinned block may feed an earlier copy)
   std::memcpy(h->pin, pts3d_idx, sizeof(int32_t) * size_t(n));
   double* pv = reinterpret_cast<double*>(h->pin + ((size_t(n) + 1) & ~size_t(1)));
   (void)hipMemcpyAsync(di, h->pin, sizeof(int32_t) * size_t(n), hipMemcpyHostToDevice, h->s);
-  k_gather_points<<<grid(n), 256, 0, h->s>>>(n, di, h->X.p, dv);
+  k_gather_points<<<grid(n), 256, 0, h->s>>>(n, di, h->X(), dv);
   if (hipMemcpyAsync(pv, dv, sizeof(double) * 3 * size_t(n), hipMemcpyDeviceToHost, h->s) != hipSuccess)
     return mapfail(SFM_EIO, "download failed");
   if (int r = sync(h)) return r;
@@ -1051,19 +1066,15 @@ int sfm_map_get_points(sfm_map* h, int32_t n, const int32_t* pts3d_idx, double* 
 }
 
 int sfm_map_set_points(sfm_map* h, int32_t n, const int32_t* pts3d_idx, const double* pts3d) {
-  if (!h) return mapfail(SFM_EINVAL, "NULL handle");
-  if (n <= 0) return n < 0 ? mapfail(SFM_EINVAL, "negative size") : 0;
-  if (!pts3d_idx || !pts3d) return mapfail(SFM_EINVAL, "NULL argument");
-  if (int rc = check_pts(h, n, pts3d_idx)) return rc;
-  if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
+  if (const auto [rc, go] = open_list(h, n, pts3d_idx, pts3d_idx && pts3d, false); !go) return rc;
   int rc = 0;
-  auto* di = static_cast<int32_t*>(scratch(h, "si", sizeof(int32_t) * size_t(n), &rc));
-  auto* dv = static_cast<double*>(scratch(h, "sv", sizeof(double) * 3 * size_t(n), &rc));
+  auto* di = scratch<int32_t>(h, "si", size_t(n), &rc);
+  auto* dv = scratch<double>(h, "sv", 3 * size_t(n), &rc);
   if (rc) return rc;
   if (hipMemcpyAsync(di, pts3d_idx, sizeof(int32_t) * size_t(n), hipMemcpyHostToDevice, h->s) != hipSuccess ||
       hipMemcpyAsync(dv, pts3d, sizeof(double) * 3 * size_t(n), hipMemcpyHostToDevice, h->s) != hipSuccess)
     return mapfail(SFM_EIO, "upload failed");
-  k_scatter_points<<<grid(n), 256, 0, h->s>>>(n, di, dv, h->X.p);  // (indices expected unique)
+  k_scatter_points<<<grid(n), 256, 0, h->s>>>(n, di, dv, h->X());  // (indices expected unique)
   return sync(h);
 }
 
@@ -1072,30 +1083,18 @@ int sfm_map_points_in_frames(sfm_map* h, int32_t n_frames, const int32_t* frame_
   if (!h || !n_out) return mapfail(SFM_EINVAL, "NULL argument");
   *n_out = 0;
   if (n_frames < 0) return mapfail(SFM_EINVAL, "negative size");
-  if (n_frames == 0 || h->n_pts == 0 || h->ob_pt.n == 0) return 0;
+  if (n_frames == 0 || h->n_pts() == 0 || h->obs.n() == 0) return 0;
   if (!frame_no) return mapfail(SFM_EINVAL, "NULL frame list");
   if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
   int rc = 0;
-  const int P = h->n_pts;
-  std::vector<int32_t> fs(frame_no, frame_no + n_frames);
-  std::sort(fs.begin(), fs.end());
-  fs.erase(std::unique(fs.begin(), fs.end()), fs.end());
-  auto* fset = static_cast<int32_t*>(scratch(h, "fset", sizeof(int32_t) * fs.size(), &rc));
-  auto* mark = static_cast<uint8_t*>(scratch(h, "mark", size_t(P), &rc));
-  auto* out = static_cast<int32_t*>(scratch(h, "pout", sizeof(int32_t) * size_t(P), &rc));
-  auto* dn = static_cast<int32_t*>(scratch(h, "pn", sizeof(int32_t), &rc));
+  const std::set<int32_t> distinct(frame_no, frame_no + n_frames);  // ascending
+  const std::vector<int32_t> fs(distinct.begin(), distinct.end());
+  auto* fset = scratch<int32_t>(h, "fset", fs.size(), &rc);
+  auto* out = scratch<int32_t>(h, "pout", size_t(h->n_pts()), &rc);
+  auto* dn = scratch<int32_t>(h, "pn", 1, &rc);
   if (rc) return rc;
   (void)hipMemcpyAsync(fset, fs.data(), sizeof(int32_t) * fs.size(), hipMemcpyHostToDevice, h->s);
-  (void)hipMemsetAsync(mark, 0, size_t(P), h->s);
-  k_mark_frames<<<grid(h->ob_pt.n), 256, 0, h->s>>>(h->ob_pt.n, h->ob_pt.p, h->ob_frame.p, h->ob_mm.p, fset,
-                                                    int(fs.size()), mark);
-  hipcub::CountingInputIterator<int32_t> it(0);
-  size_t bytes = 0;
-  (void)hipcub::DeviceSelect::Flagged(nullptr, bytes, it, mark, out, dn, P, h->s);
-  void* tmp = scratch(h, "psel", bytes, &rc);
-  if (rc) return rc;
-  if (hipcub::DeviceSelect::Flagged(tmp, bytes, it, mark, out, dn, P, h->s) != hipSuccess)
-    return mapfail(SFM_EIO, "select failed");
+  if ((rc = select_points_in_frames(h, fset, int(fs.size()), nullptr, 0, out, dn))) return rc;
   int32_t n = 0;
   (void)hipMemcpyAsync(&n, dn, sizeof(int32_t), hipMemcpyDeviceToHost, h->s);
   if (int r = sync(h)) return r;
@@ -1110,51 +1109,36 @@ int sfm_map_points_in_frame(sfm_map* h, int32_t frame_no, int32_t capacity, int3
                             int32_t* pts2d_idx, int32_t* n2_out) {
   if (!h || !n3_out || !n2_out) return mapfail(SFM_EINVAL, "NULL argument");
   *n3_out = *n2_out = 0;
-  const int64_t N = h->ob_pt.n;
+  const int64_t N = h->obs.n();
   if (N == 0) return 0;
   if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
   int rc = 0;
-  if (!h->ocsr) {
-    if (int r = build_csr(h, "ob", h->ob_pt.p, N, &h->orow, &h->ooff)) return r;
-    h->ocsr = true;
-  }
-  const int32_t *orow = h->orow, *ooff = h->ooff;
-  auto* flag = static_cast<uint8_t*>(scratch(h, "fflag", size_t(N), &rc));
-  auto* sel = static_cast<int32_t*>(scratch(h, "fsel", sizeof(int32_t) * size_t(N), &rc));
-  auto* dn = static_cast<int32_t*>(scratch(h, "fn", sizeof(int32_t), &rc));
+  if (int r = ensure_ocsr(h)) return r;
+  auto* flag = scratch<uint8_t>(h, "fflag", size_t(N), &rc);
+  auto* sel = scratch<int32_t>(h, "fsel", size_t(N), &rc);
+  auto* dn = scratch<int32_t>(h, "fn", 1, &rc);
   if (rc) return rc;
-  k_flag_frame<<<grid(N), 256, 0, h->s>>>(N, h->ob_frame.p, h->ob_mm.p, frame_no, flag);
-  hipcub::CountingInputIterator<int32_t> it(0);
-  size_t bytes = 0;
-  (void)hipcub::DeviceSelect::Flagged(nullptr, bytes, it, flag, sel, dn, int(N), h->s);
-  void* tmp = scratch(h, "fselt", bytes, &rc);
-  if (rc) return rc;
-  if (hipcub::DeviceSelect::Flagged(tmp, bytes, it, flag, sel, dn, int(N), h->s) != hipSuccess)
-    return mapfail(SFM_EIO, "select failed");
+  k_flag_frame<<<grid(N), 256, 0, h->s>>>(N, h->ob_frame(), h->ob_mm(), frame_no, flag);
+  if (int r = select_flagged(h, "fselt", flag, sel, dn, int(N))) return r;
   int32_t n = 0;
   (void)hipMemcpyAsync(&n, dn, sizeof(int32_t), hipMemcpyDeviceToHost, h->s);
   if (int r = sync(h)) return r;
   if (n == 0) return 0;
-  auto* cnt = static_cast<int32_t*>(scratch(h, "fcnt", sizeof(int32_t) * size_t(n), &rc));
-  auto* off2 = static_cast<int32_t*>(scratch(h, "foff", sizeof(int32_t) * size_t(n), &rc));
-  auto* out3 = static_cast<int32_t*>(scratch(h, "fo3", sizeof(int32_t) * size_t(n), &rc));
+  auto* cnt = scratch<int32_t>(h, "fcnt", size_t(n), &rc);
+  auto* off2 = scratch<int32_t>(h, "foff", size_t(n), &rc);
+  auto* out3 = scratch<int32_t>(h, "fo3", size_t(n), &rc);
   if (rc) return rc;
-  k_dup_count<<<grid(n), 256, 0, h->s>>>(n, sel, h->ob_pt.p, h->ob_frame.p, orow, ooff, frame_no, cnt);
-  bytes = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, cnt, off2, n, h->s);
-  tmp = scratch(h, "fscan", bytes, &rc);
-  if (rc) return rc;
-  if (hipcub::DeviceScan::ExclusiveSum(tmp, bytes, cnt, off2, n, h->s) != hipSuccess)
-    return mapfail(SFM_EIO, "scan failed");
+  k_dup_count<<<grid(n), 256, 0, h->s>>>(n, sel, h->ob_pt(), h->ob_frame(), h->orow, h->ooff, frame_no, cnt);
+  if (int r = exclusive_sum(h, "fscan", cnt, off2, n)) return r;
   int32_t last[2] = {0, 0};
   (void)hipMemcpyAsync(last, off2 + n - 1, sizeof(int32_t), hipMemcpyDeviceToHost, h->s);
   (void)hipMemcpyAsync(last + 1, cnt + n - 1, sizeof(int32_t), hipMemcpyDeviceToHost, h->s);
   if (int r = sync(h)) return r;
   const int32_t n2 = last[0] + last[1];
-  auto* out2 = static_cast<int32_t*>(scratch(h, "fo2", sizeof(int32_t) * size_t(std::max(n2, 1)), &rc));
+  auto* out2 = scratch<int32_t>(h, "fo2", size_t(std::max(n2, 1)), &rc);
   if (rc) return rc;
-  k_dup_fill<<<grid(n), 256, 0, h->s>>>(n, sel, h->ob_pt.p, h->ob_frame.p, h->ob_idx.p, orow, ooff, frame_no, off2,
-                                        out3, out2);
+  k_dup_fill<<<grid(n), 256, 0, h->s>>>(n, sel, h->ob_pt(), h->ob_frame(), h->ob_idx(), h->orow, h->ooff, frame_no,
+                                        off2, out3, out2);
   if (int r = sync(h)) return r;
   *n3_out = n;
   *n2_out = n2;
@@ -1173,7 +1157,7 @@ int sfm_map_points_in_frame_multi(sfm_map* h, int32_t n_frames, const int32_t* f
   if (!h || !off3 || !off2 || (n_frames > 0 && !frame_no)) return mapfail(SFM_EINVAL, "NULL argument");
   if (n_frames < 0) return mapfail(SFM_EINVAL, "negative size");
   for (int i = 0; i <= n_frames; ++i) off3[i] = off2[i] = 0;
-  const int64_t N = h->ob_pt.n;
+  const int64_t N = h->obs.n();
   if (N == 0 || n_frames == 0) return 0;
   std::vector<int2> fr(static_cast<size_t>(n_frames));
   for (int i = 0; i < n_frames; ++i) fr[i] = make_int2(frame_no[i], i);
@@ -1182,47 +1166,34 @@ int sfm_map_points_in_frame_multi(sfm_map* h, int32_t n_frames, const int32_t* f
     if (fr[i].x == fr[i - 1].x) return mapfail(SFM_EINVAL, "frame " + std::to_string(fr[i].x) + " queried twice");
   if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
   int rc = 0;
-  if (!h->ocsr) {
-    if (int r = build_csr(h, "ob", h->ob_pt.p, N, &h->orow, &h->ooff)) return r;
-    h->ocsr = true;
-  }
+  if (int r = ensure_ocsr(h)) return r;
   // every observation keyed by its frame's position in the query list; a
   // stable sort groups them frame by frame, each frame's in emplace order
   // (its equal_range)
-  auto* dfr = static_cast<int2*>(scratch(h, "mfr", sizeof(int2) * size_t(n_frames), &rc));
-  auto* key = static_cast<uint32_t*>(scratch(h, "mk", sizeof(uint32_t) * size_t(N), &rc));
-  auto* key2 = static_cast<uint32_t*>(scratch(h, "mk2", sizeof(uint32_t) * size_t(N), &rc));
-  auto* iv = static_cast<int32_t*>(scratch(h, "mi", sizeof(int32_t) * size_t(N), &rc));
-  auto* sel = static_cast<int32_t*>(scratch(h, "msel", sizeof(int32_t) * size_t(N), &rc));
-  auto* fcnt = static_cast<int32_t*>(scratch(h, "mfc", sizeof(int32_t) * (size_t(n_frames) + 1), &rc));
+  auto* dfr = scratch<int2>(h, "mfr", size_t(n_frames), &rc);
+  auto* key = scratch<uint32_t>(h, "mk", size_t(N), &rc);
+  auto* key2 = scratch<uint32_t>(h, "mk2", size_t(N), &rc);
+  auto* iv = scratch<int32_t>(h, "mi", size_t(N), &rc);
+  auto* sel = scratch<int32_t>(h, "msel", size_t(N), &rc);
+  auto* fcnt = scratch<int32_t>(h, "mfc", size_t(n_frames) + 1, &rc);
   if (rc) return rc;
   (void)hipMemcpyAsync(dfr, fr.data(), sizeof(int2) * fr.size(), hipMemcpyHostToDevice, h->s);
   (void)hipMemsetAsync(fcnt, 0, sizeof(int32_t) * (size_t(n_frames) + 1), h->s);
-  k_frame_rank<<<grid(N), 256, 0, h->s>>>(N, h->ob_frame.p, h->ob_mm.p, dfr, n_frames, key, iv);
+  k_frame_rank<<<grid(N), 256, 0, h->s>>>(N, h->ob_frame(), h->ob_mm(), dfr, n_frames, key, iv);
   k_count_keys<<<grid(N), 256, 0, h->s>>>(N, reinterpret_cast<const int32_t*>(key), fcnt);
   int bits = 1;
   while ((1 << bits) <= n_frames) ++bits;
-  size_t bytes = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key, key2, iv, sel, int(N), 0, bits, h->s);
-  void* tmp = scratch(h, "msort", bytes, &rc);
-  if (rc) return rc;
-  if (hipcub::DeviceRadixSort::SortPairs(tmp, bytes, key, key2, iv, sel, int(N), 0, bits, h->s) != hipSuccess)
-    return mapfail(SFM_EIO, "sort failed");
+  if (int r = sort_pairs(h, "msort", key, key2, iv, sel, int(N), bits, "sort failed")) return r;
   // per sorted entry: how many 2D indices its point has in the entry's frame
   // (0 past the queried frames), their exclusive scan, then the frames'
   // offsets on the device: one readback of 2 (nf + 1) ints
-  auto* cnt = static_cast<int32_t*>(scratch(h, "mcnt", sizeof(int32_t) * size_t(N), &rc));
-  auto* eoff = static_cast<int32_t*>(scratch(h, "moff", sizeof(int32_t) * size_t(N), &rc));
-  auto* offs = static_cast<int32_t*>(scratch(h, "moffs", sizeof(int32_t) * 2 * (size_t(n_frames) + 1), &rc));
+  auto* cnt = scratch<int32_t>(h, "mcnt", size_t(N), &rc);
+  auto* eoff = scratch<int32_t>(h, "moff", size_t(N), &rc);
+  auto* offs = scratch<int32_t>(h, "moffs", 2 * (size_t(n_frames) + 1), &rc);
   if (rc) return rc;
-  k_dup_count_ranked<<<grid(N), 256, 0, h->s>>>(N, sel, key2, n_frames, h->ob_pt.p, h->ob_frame.p, h->orow, h->ooff,
+  k_dup_count_ranked<<<grid(N), 256, 0, h->s>>>(N, sel, key2, n_frames, h->ob_pt(), h->ob_frame(), h->orow, h->ooff,
                                                  cnt);
-  bytes = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, cnt, eoff, int(N), h->s);
-  tmp = scratch(h, "mscan", bytes, &rc);
-  if (rc) return rc;
-  if (hipcub::DeviceScan::ExclusiveSum(tmp, bytes, cnt, eoff, int(N), h->s) != hipSuccess)
-    return mapfail(SFM_EIO, "scan failed");
+  if (int r = exclusive_sum(h, "mscan", cnt, eoff, int(N))) return r;
   k_frame_offsets<<<1, 1, 0, h->s>>>(n_frames, fcnt, N, cnt, eoff, offs);
   // (readbacks through the pinned block: a pageable copy is staged by the
   // runtime, ~2x the time at these sizes)
@@ -1239,10 +1210,10 @@ int sfm_map_points_in_frame_multi(sfm_map* h, int32_t n_frames, const int32_t* f
   if (int64_t(n) > capacity || int64_t(n2) > capacity)
     return mapfail(SFM_EINVAL, "capacity " + std::to_string(capacity) + " < " + std::to_string(std::max(n, n2)));
   if (!pts3d_idx || !pts2d_idx) return mapfail(SFM_EINVAL, "NULL output");
-  auto* out3 = static_cast<int32_t*>(scratch(h, "mo3", sizeof(int32_t) * size_t(n), &rc));
-  auto* out2 = static_cast<int32_t*>(scratch(h, "mo2", sizeof(int32_t) * size_t(std::max(n2, 1)), &rc));
+  auto* out3 = scratch<int32_t>(h, "mo3", size_t(n), &rc);
+  auto* out2 = scratch<int32_t>(h, "mo2", size_t(std::max(n2, 1)), &rc);
   if (rc) return rc;
-  k_dup_fill<<<grid(n), 256, 0, h->s>>>(n, sel, h->ob_pt.p, h->ob_frame.p, h->ob_idx.p, h->orow, h->ooff, INT32_MIN,
+  k_dup_fill<<<grid(n), 256, 0, h->s>>>(n, sel, h->ob_pt(), h->ob_frame(), h->ob_idx(), h->orow, h->ooff, INT32_MIN,
                                         eoff, out3, out2);
   int32_t* ph = pin_reserve(h, size_t(n) + size_t(n2), &rc);
   if (rc) return rc;
@@ -1256,37 +1227,23 @@ int sfm_map_points_in_frame_multi(sfm_map* h, int32_t n_frames, const int32_t* f
 
 int sfm_map_representative_descriptors(sfm_map* h, int32_t n, const int32_t* pts3d_idx, uint8_t* desc_out,
                                        int32_t* best_row) {
-  if (!h) return mapfail(SFM_EINVAL, "NULL handle");
-  if (n <= 0) return n < 0 ? mapfail(SFM_EINVAL, "negative size") : 0;
-  if (!pts3d_idx || !desc_out) return mapfail(SFM_EINVAL, "NULL argument");
-  if (int rc = check_live(h, n, pts3d_idx)) return rc;
-  if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
+  if (const auto [rc, go] = open_list(h, n, pts3d_idx, pts3d_idx && desc_out, true); !go) return rc;
   int rc = 0;
-  const int64_t rows = h->desc.n / h->W;
-  if (!h->dcsr) {
-    if (int r = build_csr(h, "de", h->desc_pt.p, rows, &h->drow, &h->doff)) return r;
-    h->dcsr = true;
-  }
-  const int32_t *drow = h->drow, *doff = h->doff;
+  if (int r = ensure_dcsr(h)) return r;
   // every queried point needs a row (the reference reads row -1 otherwise)
-  std::vector<int32_t> off(size_t(h->n_pts) + 1);
-  (void)hipMemcpyAsync(off.data(), doff, sizeof(int32_t) * off.size(), hipMemcpyDeviceToHost, h->s);
+  std::vector<int32_t> off(size_t(h->n_pts()) + 1);
+  (void)hipMemcpyAsync(off.data(), h->doff, sizeof(int32_t) * off.size(), hipMemcpyDeviceToHost, h->s);
   if (int r = sync(h)) return r;
   for (int32_t i = 0; i < n; ++i)
     if (off[size_t(pts3d_idx[i]) + 1] == off[size_t(pts3d_idx[i])])
       return mapfail(SFM_EINVAL, "point " + std::to_string(pts3d_idx[i]) + " has no descriptor row");
-  auto* q = static_cast<int32_t*>(scratch(h, "rq", sizeof(int32_t) * size_t(n), &rc));
-  auto* best = static_cast<int32_t*>(scratch(h, "rb", sizeof(int32_t) * size_t(n), &rc));
-  auto* out = static_cast<uint64_t*>(scratch(h, "ro", sizeof(uint64_t) * size_t(n) * h->W, &rc));
+  auto* q = scratch<int32_t>(h, "rq", size_t(n), &rc);
+  auto* best = scratch<int32_t>(h, "rb", size_t(n), &rc);
+  auto* out = scratch<uint64_t>(h, "ro", size_t(n) * h->W, &rc);
   if (rc) return rc;
   (void)hipMemcpyAsync(q, pts3d_idx, sizeof(int32_t) * size_t(n), hipMemcpyHostToDevice, h->s);
-  switch (h->W) {
-#define CASE(w) case w: k_map_repr<w><<<n, 64, 0, h->s>>>(h->desc.p, drow, doff, q, n, nullptr, best, out); break;
-    CASE(1) CASE(2) CASE(4) CASE(8) CASE(16) CASE(32) CASE(64)
-#undef CASE
-    default: return mapfail(SFM_EINVAL, "descriptor width");  // excluded by sfm_map_create
-  }
-  (void)hipMemcpyAsync(desc_out, out, size_t(n) * h->desc_bytes, hipMemcpyDeviceToHost, h->s);
+  if (int r = launch_map_repr(h, n, q, nullptr, best, out)) return r;
+  (void)hipMemcpyAsync(desc_out, out, size_t(n) * h->W * sizeof(uint64_t), hipMemcpyDeviceToHost, h->s);
   std::vector<int32_t> b(static_cast<size_t>(n));
   (void)hipMemcpyAsync(b.data(), best, sizeof(int32_t) * size_t(n), hipMemcpyDeviceToHost, h->s);
   if (int r = sync(h)) return r;
@@ -1315,30 +1272,26 @@ int sfm_map_match_frame(sfm_map* h, sfm_matcher* mt, int32_t n_frames, const int
     return mapfail(SFM_EINVAL, "NULL argument");
   if (matcher_words(mt) != h->W || matcher_device(mt) != h->device)
     return mapfail(SFM_EINVAL, "the map and the matcher differ in descriptor width or device");
-  if (int rc = check_live(h, n_existing, existing_pts)) return rc;
+  if (int rc = check_pts(h, n_existing, existing_pts, true)) return rc;
   const int n_cur = matcher_current_n(mt);
   if (n_cur < 0) return mapfail(SFM_EINVAL, "push the current frame to the matcher first");
   for (int i = 0; i < n_train; ++i)
     if (train_idx[i] < 0 || train_idx[i] >= n_cur) return mapfail(SFM_EINVAL, "train index out of range");
-  if (n_frames == 0 || h->n_pts == 0 || h->ob_pt.n == 0 || n_train < 2) return 0;
+  if (n_frames == 0 || h->n_pts() == 0 || h->obs.n() == 0 || n_train < 2) return 0;
   if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
   int rc = 0;
-  const int P = h->n_pts;
-  std::vector<int32_t> fs(frame_no, frame_no + n_frames);
-  std::sort(fs.begin(), fs.end());
-  fs.erase(std::unique(fs.begin(), fs.end()), fs.end());
-  if (!h->dcsr) {
-    if (int r = build_csr(h, "de", h->desc_pt.p, h->desc.n / h->W, &h->drow, &h->doff)) return r;
-    h->dcsr = true;
-  }
+  const int P = h->n_pts();
+  const std::set<int32_t> distinct(frame_no, frame_no + n_frames);  // ascending
+  const std::vector<int32_t> fs(distinct.begin(), distinct.end());
+  if (int r = ensure_dcsr(h)) return r;
   const size_t n_up = fs.size() + size_t(n_existing) + size_t(n_train);
-  auto* fset = static_cast<int32_t*>(scratch(h, "fset", sizeof(int32_t) * n_up, &rc));
-  auto* mark = static_cast<uint8_t*>(scratch(h, "mark", size_t(P), &rc));
+  auto* fset = scratch<int32_t>(h, "fset", n_up, &rc);
   // the selected points, then (after k_map_repr) their representative rows:
   // one download for both
-  auto* out = static_cast<int32_t*>(scratch(h, "pout", sizeof(int32_t) * 2 * size_t(P), &rc));
-  auto* dn = static_cast<int32_t*>(scratch(h, "pn", sizeof(int32_t), &rc));
-  if (rc) return rc;
+  auto* out = scratch<int32_t>(h, "pout", 2 * size_t(P), &rc);
+  auto* dn = scratch<int32_t>(h, "pn", 1, &rc);
+  auto* qd = scratch<uint64_t>(h, "mq", size_t(P) * h->W, &rc);
+  auto* uv = scratch<double>(h, "muv", 2 * size_t(P), &rc);
   pin_reserve(h, std::max(2 * size_t(P) + 1, n_up), &rc);
   if (rc) return rc;
   if (h->ev.create(hipEventDisableTiming) != hipSuccess) return mapfail(SFM_EIO, "hipEventCreate failed");
@@ -1348,30 +1301,12 @@ int sfm_map_match_frame(sfm_map* h, sfm_matcher* mt, int32_t n_frames, const int
   if (n_existing) std::memcpy(h->pin + fs.size(), existing_pts, sizeof(int32_t) * size_t(n_existing));
   std::memcpy(h->pin + fs.size() + n_existing, train_idx, sizeof(int32_t) * size_t(n_train));
   (void)hipMemcpyAsync(fset, h->pin, sizeof(int32_t) * n_up, hipMemcpyHostToDevice, h->s);
-  (void)hipMemsetAsync(mark, 0, size_t(P), h->s);
-  k_mark_frames<<<grid(h->ob_pt.n), 256, 0, h->s>>>(h->ob_pt.n, h->ob_pt.p, h->ob_frame.p, h->ob_mm.p, fset,
-                                                    int(fs.size()), mark);
-  if (n_existing) k_unmark<<<grid(n_existing), 256, 0, h->s>>>(n_existing, fset + fs.size(), mark);
-  hipcub::CountingInputIterator<int32_t> it(0);
-  size_t bytes = 0;
-  (void)hipcub::DeviceSelect::Flagged(nullptr, bytes, it, mark, out, dn, P, h->s);
-  void* tmp = scratch(h, "psel", bytes, &rc);
-  if (rc) return rc;
-  if (hipcub::DeviceSelect::Flagged(tmp, bytes, it, mark, out, dn, P, h->s) != hipSuccess)
-    return mapfail(SFM_EIO, "select failed");
+  if ((rc = select_points_in_frames(h, fset, int(fs.size()), fset + fs.size(), n_existing, out, dn))) return rc;
   // no readback of the count here: the kernels below run on its bound P and
   // read the count itself (k_map_repr, k_project, the matcher's acceptance)
   int32_t* best = out + P;
-  auto* qd = static_cast<uint64_t*>(scratch(h, "mq", sizeof(uint64_t) * size_t(P) * h->W, &rc));
-  auto* uv = static_cast<double*>(scratch(h, "muv", sizeof(double) * 2 * size_t(P), &rc));
-  if (rc) return rc;
-  switch (h->W) {
-#define CASE(w) case w: k_map_repr<w><<<P, 64, 0, h->s>>>(h->desc.p, h->drow, h->doff, out, P, dn, best, qd); break;
-    CASE(1) CASE(2) CASE(4) CASE(8) CASE(16) CASE(32) CASE(64)
-#undef CASE
-    default: return mapfail(SFM_EINVAL, "descriptor width");
-  }
-  k_project<<<grid(P), 256, 0, h->s>>>(P, dn, out, h->X.p, R9[0], R9[1], R9[2], R9[3], R9[4], R9[5], R9[6], R9[7],
+  if (int r = launch_map_repr(h, P, out, dn, best, qd)) return r;
+  k_project<<<grid(P), 256, 0, h->s>>>(P, dn, out, h->X(), R9[0], R9[1], R9[2], R9[3], R9[4], R9[5], R9[6], R9[7],
                                        R9[8], t3[0], t3[1], t3[2], K9[0], K9[4], K9[2], K9[5], uv);
   // points, representative rows and the count in one download
   (void)hipMemcpyAsync(h->pin, out, sizeof(int32_t) * 2 * size_t(P), hipMemcpyDeviceToHost, h->s);
@@ -1401,25 +1336,21 @@ int sfm_map_match_frame(sfm_map* h, sfm_matcher* mt, int32_t n_frames, const int
 // a stale CSR's rebuild, which enqueue only.
 
 int sfm_map_update_point_views(sfm_map* h, int32_t n, const int32_t* pts3d_idx) {
-  if (!h) return mapfail(SFM_EINVAL, "NULL handle");
-  if (n <= 0) return n < 0 ? mapfail(SFM_EINVAL, "negative size") : 0;
-  if (!pts3d_idx) return mapfail(SFM_EINVAL, "NULL argument");
-  if (int rc = check_live(h, n, pts3d_idx)) return rc;
-  if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
+  if (const auto [rc, go] = open_list(h, n, pts3d_idx, pts3d_idx != nullptr, true); !go) return rc;
   int rc = 0;
-  auto* di = static_cast<int32_t*>(scratch(h, "vi", sizeof(int32_t) * size_t(n), &rc));
+  auto* di = scratch<int32_t>(h, "vi", size_t(n), &rc);
   if (rc) return rc;
   if (hipMemcpyAsync(di, pts3d_idx, sizeof(int32_t) * size_t(n), hipMemcpyHostToDevice, h->s) != hipSuccess)
     return mapfail(SFM_EIO, "upload failed");
-  k_add_views<<<grid(n), 256, 0, h->s>>>(n, di, h->pt_views.p);
+  k_add_views<<<grid(n), 256, 0, h->s>>>(n, di, h->pt_views());
   return sync(h);
 }
 
 int sfm_map_increment_age(sfm_map* h, int32_t t_inc, int32_t kf_inc) {
   if (!h) return mapfail(SFM_EINVAL, "NULL handle");
-  if (h->n_pts == 0) return 0;
+  if (h->n_pts() == 0) return 0;
   if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
-  k_age<<<grid(h->n_pts), 256, 0, h->s>>>(h->n_pts, h->pt_live.p, h->pt_time.p, h->pt_kf.p, t_inc, kf_inc);
+  k_age<<<grid(h->n_pts()), 256, 0, h->s>>>(h->n_pts(), h->pt_live(), h->pt_time(), h->pt_kf(), t_inc, kf_inc);
   return sync(h);
 }
 
@@ -1430,19 +1361,15 @@ int sfm_map_n_live(sfm_map* h, int32_t* n) {
 }
 
 int sfm_map_point_state(sfm_map* h, int32_t n, const int32_t* pts3d_idx, int32_t* out) {
-  if (!h) return mapfail(SFM_EINVAL, "NULL handle");
-  if (n <= 0) return n < 0 ? mapfail(SFM_EINVAL, "negative size") : 0;
-  if (!pts3d_idx || !out) return mapfail(SFM_EINVAL, "NULL argument");
-  if (int rc = check_pts(h, n, pts3d_idx)) return rc;
-  if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
+  if (const auto [rc, go] = open_list(h, n, pts3d_idx, pts3d_idx && out, false); !go) return rc;
   if (int rc = ensure_csrs(h)) return rc;
   int rc = 0;
-  auto* di = static_cast<int32_t*>(scratch(h, "vi", sizeof(int32_t) * size_t(n), &rc));
-  auto* dout = static_cast<int32_t*>(scratch(h, "vo", sizeof(int32_t) * 5 * size_t(n), &rc));
+  auto* di = scratch<int32_t>(h, "vi", size_t(n), &rc);
+  auto* dout = scratch<int32_t>(h, "vo", 5 * size_t(n), &rc);
   if (rc) return rc;
   if (hipMemcpyAsync(di, pts3d_idx, sizeof(int32_t) * size_t(n), hipMemcpyHostToDevice, h->s) != hipSuccess)
     return mapfail(SFM_EIO, "upload failed");
-  k_point_state<<<grid(n), 256, 0, h->s>>>(n, di, h->pt_time.p, h->pt_kf.p, h->pt_views.p, h->ooff, h->pt_live.p,
+  k_point_state<<<grid(n), 256, 0, h->s>>>(n, di, h->pt_time(), h->pt_kf(), h->pt_views(), h->ooff, h->pt_live(),
                                            dout);
   if (hipMemcpyAsync(out, dout, sizeof(int32_t) * 5 * size_t(n), hipMemcpyDeviceToHost, h->s) != hipSuccess)
     return mapfail(SFM_EIO, "download failed");
@@ -1456,28 +1383,23 @@ int sfm_map_remove_points_threshold(sfm_map* h, int32_t kf_threshold, float trac
   *n_cull = 0;
   if (capacity < 0 || kf_threshold < 0) return mapfail(SFM_EINVAL, "negative size or threshold");
   if (capacity && !cull_idx) return mapfail(SFM_EINVAL, "NULL output");
-  const int P = h->n_pts;
+  const int P = h->n_pts();
   if (P == 0) return 0;
   if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
   if (int rc = ensure_csrs(h)) return rc;
   int rc = 0;
   const size_t nres = 3 + 2 * size_t(P);  // count, sizes after, the culled list, the status
-  auto* res = static_cast<int32_t*>(scratch(h, "cres", sizeof(int32_t) * nres, &rc));
-  auto* flag = static_cast<uint8_t*>(scratch(h, "cflag", size_t(P), &rc));
-  if (rc) return rc;
-  k_cull_flag<<<grid(P), 256, 0, h->s>>>(P, h->pt_live.p, h->pt_time.p, h->pt_kf.p, h->pt_views.p, h->ooff,
+  auto* res = scratch<int32_t>(h, "cres", nres, &rc);
+  auto* flag = scratch<uint8_t>(h, "cflag", size_t(P), &rc);
+  if (rc || (rc = select_flagged(h, "csel", flag, res + 3, res, P, false))) return rc;
+  const Removal m(h, nres);
+  if (m.rc) return m.rc;
+  k_cull_flag<<<grid(P), 256, 0, h->s>>>(P, h->pt_live(), h->pt_time(), h->pt_kf(), h->pt_views(), h->ooff,
                                          kf_threshold, track_threshold, flag);
-  hipcub::CountingInputIterator<int32_t> it(0);
-  size_t bytes = 0;
-  (void)hipcub::DeviceSelect::Flagged(nullptr, bytes, it, flag, res + 3, res, P, h->s);
-  void* tmp = scratch(h, "csel", bytes, &rc);
-  if (rc) return rc;
-  if (hipcub::DeviceSelect::Flagged(tmp, bytes, it, flag, res + 3, res, P, h->s) != hipSuccess)
-    return mapfail(SFM_EIO, "select failed");
-  if (int r = kill_and_compact(h, flag, res, capacity, res)) return r;
-  int32_t* ph = pin_reserve(h, nres, &rc);
-  if (rc) return rc;
-  (void)hipMemcpyAsync(ph, res, sizeof(int32_t) * nres, hipMemcpyDeviceToHost, h->s);
+  if (int r = select_flagged(h, "csel", flag, res + 3, res, P)) return r;
+  if (int r = kill_and_compact(h, m, flag, res, capacity, res)) return r;
+  const int32_t* ph = m.pin;
+  (void)hipMemcpyAsync(m.pin, res, sizeof(int32_t) * nres, hipMemcpyDeviceToHost, h->s);
   if (int r = sync(h)) return r;
   const int32_t n = ph[0];
   *n_cull = n;
@@ -1497,11 +1419,11 @@ int sfm_map_remove_points(sfm_map* h, int32_t n, const int32_t* pts3d_idx, int32
   if (!h) return mapfail(SFM_EINVAL, "NULL handle");
   if (n < 0) return mapfail(SFM_EINVAL, "negative size");
   if (n && !pts3d_idx) return mapfail(SFM_EINVAL, "NULL argument");
-  if (int rc = check_live(h, n, pts3d_idx)) return rc;
+  if (int rc = check_pts(h, n, pts3d_idx, true)) return rc;
   for (int32_t i = 1; i < n; ++i)
     if (pts3d_idx[i] <= pts3d_idx[i - 1])
       return mapfail(SFM_EINVAL, "the list must be ascending and distinct (at " + std::to_string(i) + ")");
-  const int P = h->n_pts;
+  const int P = h->n_pts();
   if (n == 0) {
     if (status && P) std::memset(status, 0, sizeof(int32_t) * size_t(P));
     return 0;
@@ -1509,18 +1431,19 @@ int sfm_map_remove_points(sfm_map* h, int32_t n, const int32_t* pts3d_idx, int32
   if (hipSetDevice(h->device) != hipSuccess) return mapfail(SFM_ENODEV, "hipSetDevice failed");
   int rc = 0;
   const size_t nres = 3 + 2 * size_t(P);
-  auto* res = static_cast<int32_t*>(scratch(h, "cres", sizeof(int32_t) * nres, &rc));
-  auto* flag = static_cast<uint8_t*>(scratch(h, "cflag", size_t(P), &rc));
-  auto* di = static_cast<int32_t*>(scratch(h, "vi", sizeof(int32_t) * size_t(n), &rc));
+  auto* res = scratch<int32_t>(h, "cres", nres, &rc);
+  auto* flag = scratch<uint8_t>(h, "cflag", size_t(P), &rc);
+  auto* di = scratch<int32_t>(h, "vi", size_t(n), &rc);
   if (rc) return rc;
+  const Removal m(h, nres);
+  if (m.rc) return m.rc;
   if (hipMemcpyAsync(di, pts3d_idx, sizeof(int32_t) * size_t(n), hipMemcpyHostToDevice, h->s) != hipSuccess)
     return mapfail(SFM_EIO, "upload failed");
   (void)hipMemsetAsync(flag, 0, size_t(P), h->s);
   k_flag_list<<<grid(n), 256, 0, h->s>>>(n, di, flag);
-  if (int r = kill_and_compact(h, flag, nullptr, 0, res)) return r;
-  int32_t* ph = pin_reserve(h, nres, &rc);
-  if (rc) return rc;
-  (void)hipMemcpyAsync(ph + 1, res + 1, sizeof(int32_t) * (nres - 1), hipMemcpyDeviceToHost, h->s);
+  if (int r = kill_and_compact(h, m, flag, nullptr, 0, res)) return r;
+  const int32_t* ph = m.pin;
+  (void)hipMemcpyAsync(m.pin + 1, res + 1, sizeof(int32_t) * (nres - 1), hipMemcpyDeviceToHost, h->s);
   if (int r = sync(h)) return r;
   compact_done(h, ph + 1);
   for (int32_t i = 0; i < n; ++i) h->live_h[size_t(pts3d_idx[i])] = 0;
@@ -1559,14 +1482,14 @@ namespace sfm {
 // synchronise before returning; this keeps the rule local).
 const double* map_points_dev(sfm_map* h, int32_t* n_pts, int* device) {
   (void)hipStreamSynchronize(h->s);
-  *n_pts = h->n_pts;
+  *n_pts = h->n_pts();
   *device = h->device;
-  return h->X.p;
+  return h->X();
 }
 
 // The points and live flags where they are (map_internal.h): no copy and no
 // synchronisation; the reader orders its stream after `stream` with an event.
 MapPointsView map_points_view(sfm_map* h) {
-  return MapPointsView{h->X.p, h->pt_live.p, h->n_pts, h->n_live, h->device, h->s};
+  return MapPointsView{h->X(), h->pt_live(), h->n_pts(), h->n_live, h->device, h->s};
 }
 }  // namespace sfm

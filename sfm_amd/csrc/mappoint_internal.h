@@ -65,4 +65,29 @@ void launch_project_rows(hipStream_t s, int n, const int* qidx, const double* X,
 // dst[k][0..W) = src[rows[k]][0..W)
 void launch_copy_desc_rows(hipStream_t s, int n, const int* rows, const uint64_t* src, int W, uint64_t* dst);
 
+// CMap::getRepresentativeDescriptors' choice (CMap.cpp:345-381) for k_repr
+// (match_kernels.hip: contiguous rows) and k_map_repr (map_store.hip: rows by
+// CSR).  One wave per point, lane l: of the point's k rows (row(r): row r's W
+// words) the one with the smallest sum of Hamming distances to all k, the
+// first on ties (integer sums).  Every lane returns it; k = 0: -1.
+template <int W, typename Row>
+__device__ inline int repr_row(int k, int l, Row row) {
+  unsigned long long key = ~0ull;  // (sum << 32 | row): the min is the first minimal row
+  for (int r = l; r - l < k; r += 64) {  // lane l owns rows l, l + 64, ...
+    uint64_t x[W];
+    const uint64_t* xr = row(r < k ? r : 0);
+#pragma unroll
+    for (int w = 0; w < W; ++w) x[w] = xr[w];
+    unsigned int sum = 0;
+    for (int q = 0; q < k; ++q) {
+      const uint64_t* y = row(q);  // wave-uniform: one line per instruction
+#pragma unroll
+      for (int w = 0; w < W; ++w) sum += __popcll(x[w] ^ y[w]);
+    }
+    if (r < k) key = min(key, (static_cast<unsigned long long>(sum) << 32) | unsigned(r));
+  }
+  for (int o = 32; o >= 1; o >>= 1) key = min(key, static_cast<unsigned long long>(__shfl_xor(key, o)));
+  return int(key & 0xffffffffu);
+}
+
 }  // namespace sfm

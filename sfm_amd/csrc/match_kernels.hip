@@ -285,20 +285,8 @@ __global__ __launch_bounds__(64) void k_repr(const uint64_t* __restrict__ d, con
   if (p >= n_pts) return;
   const int r0 = off[p], k = off[p + 1] - r0;
   const uint64_t* dp = d + size_t(r0) * W;
-  unsigned long long key = ~0ull;  // (sum << 32 | row): the min is the first minimal row
-  for (int r = l; r - l < k; r += 64) {
-    uint64_t x[W];
-#pragma unroll
-    for (int w = 0; w < W; ++w) x[w] = r < k ? dp[size_t(r) * W + w] : 0ull;
-    unsigned int sum = 0;
-    for (int q = 0; q < k; ++q) {
-#pragma unroll
-      for (int w = 0; w < W; ++w) sum += __popcll(x[w] ^ dp[size_t(q) * W + w]);
-    }
-    if (r < k) key = min(key, (static_cast<unsigned long long>(sum) << 32) | unsigned(r));
-  }
-  for (int o = 32; o >= 1; o >>= 1) key = min(key, static_cast<unsigned long long>(__shfl_xor(key, o)));
-  if (l == 0) best[p] = int(key & 0xffffffffu);
+  const int b = sfm::repr_row<W>(k, l, [dp](int r) { return dp + size_t(r) * W; });
+  if (l == 0) best[p] = b;
 }
 
 }  // namespace

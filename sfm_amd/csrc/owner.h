@@ -3,7 +3,10 @@
 // host sanitizer program (tests/asan) runs them over malloc / free.  The two
 // HIP memory policies, Stream and Event are in dev_mem.h.
 #pragma once
+#include <algorithm>
+#include <array>
 #include <cstddef>
+#include <cstdint>
 #include <map>
 #include <memory>
 #include <utility>
@@ -60,6 +63,54 @@ class Buf {
  private:
   void* p_ = nullptr;
   size_t bytes_ = 0;
+};
+
+// K columns that grow as one table (the map store's): one n and one cap, in
+// rows, and each column's bytes per row.  reserve() is the one keeper of
+// contents: it allocates EVERY new column first; if one allocation fails it
+// releases the new ones and returns Mem::alloc's code with the table as it
+// was (pointers, n, cap, contents).  Only then are the n live rows copied on
+// the stream, the stream drained and the columns swapped.  Growth: at least
+// the need, at least double, at least 1024 rows.  Rows past n are the caller's
+// to write and count after commit().  Beside Buf's hooks, Mem supplies
+//   static int copy(void* dst, const void* src, size_t bytes, Stream s)   (enqueued on s)
+template <typename Mem, int K>
+class RowTable {
+ public:
+  explicit RowTable(std::array<size_t, K> width) : width_(width) {}
+  RowTable(const RowTable&) = delete;
+  RowTable& operator=(const RowTable&) = delete;
+  ~RowTable() {
+    for (void* p : col_)
+      if (p) Mem::release(p);
+  }
+  int reserve(int64_t rows, typename Mem::Stream s) {
+    if (rows <= cap_) return 0;
+    const int64_t cap = std::max<int64_t>({rows, 2 * cap_, 1024});
+    std::array<void*, K> fresh{};
+    for (int c = 0; c < K; ++c)
+      if (const int rc = Mem::alloc(&fresh[c], size_t(cap) * width_[c])) {
+        while (c-- > 0) Mem::release(fresh[c]);
+        return rc;
+      }
+    for (int c = 0; c < K && n_; ++c) (void)Mem::copy(fresh[c], col_[c], size_t(n_) * width_[c], s);
+    if (cap_) (void)Mem::drain(s);
+    for (int c = 0; c < K; ++c)
+      if (col_[c]) Mem::release(col_[c]);
+    col_ = fresh, cap_ = cap;
+    return 0;
+  }
+  void commit(int64_t rows) { n_ += rows; }   // the rows written at n() .. n() + rows now count
+  void truncate(int64_t rows) { n_ = rows; }  // the first `rows` (<= n()) stay
+  int64_t n() const { return n_; }
+  int64_t cap() const { return cap_; }
+  template <typename T>
+  T* col(int c) const { return static_cast<T*>(col_[c]); }
+
+ private:
+  std::array<size_t, K> width_;
+  std::array<void*, K> col_{};
+  int64_t n_ = 0, cap_ = 0;
 };
 
 // Allocations re-used by size across problems (the bundle adjuster's): the

@@ -21,7 +21,12 @@
 //     restatement of the hand-kept one over seeded random scripts and at the
 //     literal edges, every allocation of a set-up failing in turn, and the
 //     order of stream waits and retirements over a large and a keyframe-sized
-//     set-up, a failing one and destroy;
+//     set-up, a failing one and destroy; and RowTable, the map store's
+//     tables: seeded random scripts of reserve / write / commit / truncate
+//     against a vector per column at the store's column widths, every
+//     allocation of a growth failing in turn (the table as it was, the new
+//     columns released, the next reserve succeeds), and the order all
+//     allocations, copies, drain, swap;
 //   * sfm_amd/csrc/ba_lm.h -- the LM trust-region state machine both loop
 //     drivers run: the oracle's 18 branch traces replayed through it
 //     (tests/golden/lm_replay.txt), and the branches no scene reaches from
@@ -427,19 +432,22 @@ static void check_plan() {
 // malloc / free with counters; allocation number fail_at (counted from 1) fails
 struct TestMem {
   using Stream = const char*;  // "drained" when non-null
-  static int allocs, releases, drains, fail_at;
+  static int allocs, releases, drains, copies, fail_at;
+  static bool trace;                      // log "alloc" / "release" too (the row table's order check)
   static size_t last_bytes;               // of the last successful allocation
   static std::vector<void*> released;     // in order
-  static std::vector<std::string> log;    // "drain <stream>" per drain; the pool's checks add their own entries
+  static std::vector<std::string> log;    // "drain <stream>" per drain, "copy" per copy; the pool's checks add their own entries
   static int alloc(void** p, size_t bytes) {
     if (++allocs == fail_at) return 7;
     *p = std::malloc(bytes);
     last_bytes = bytes;
+    if (trace) log.push_back("alloc");
     return *p ? 0 : 1;
   }
   static void release(void* p) {
     ++releases;
     released.push_back(p);
+    if (trace) log.push_back("release");
     std::free(p);
   }
   static int drain(Stream s) {
@@ -447,13 +455,21 @@ struct TestMem {
     log.push_back(std::string("drain ") + s);
     return 0;
   }
+  static int copy(void* dst, const void* src, size_t bytes, Stream) {
+    ++copies;
+    log.push_back("copy");
+    std::memcpy(dst, src, bytes);
+    return 0;
+  }
   static void reset_counts() {
-    allocs = releases = drains = fail_at = 0;
+    allocs = releases = drains = copies = fail_at = 0;
+    trace = false;
     released.clear();
     log.clear();
   }
 };
-int TestMem::allocs = 0, TestMem::releases = 0, TestMem::drains = 0, TestMem::fail_at = 0;
+int TestMem::allocs = 0, TestMem::releases = 0, TestMem::drains = 0, TestMem::copies = 0, TestMem::fail_at = 0;
+bool TestMem::trace = false;
 size_t TestMem::last_bytes = 0;
 std::vector<void*> TestMem::released;
 std::vector<std::string> TestMem::log;
@@ -842,6 +858,162 @@ static void check_pool_failure_and_drains() {
   }
   std::printf("  Pool: %d failing allocations leave it consistent; drains: large set-up 2, keyframe-sized 1, failure both streams, destroy ok\n",
               n_failed);
+}
+
+// ---- the map store's row tables (sfm::RowTable, owner.h) ----
+// The model: one std::vector of bytes per column, holding the committed rows.
+template <int K>
+struct TableCheck {
+  std::array<size_t, K> width;
+  sfm::RowTable<TestMem, K> t;
+  std::array<std::vector<uint8_t>, K> model;
+  int64_t n = 0, cap = 0;
+  uint32_t salt;
+  TableCheck(std::array<size_t, K> w, uint32_t seed) : width(w), t(w), salt(seed * 2654435761u) {}
+
+  // the table is the model: n, cap, every committed byte (ASan reads each column to its end)
+  void same() const {
+    CHECK(t.n() == n && t.cap() == cap);
+    for (int c = 0; c < K; ++c) {
+      CHECK(model[size_t(c)].size() == size_t(n) * width[size_t(c)]);
+      CHECK((cap == 0) == (t.template col<uint8_t>(c) == nullptr));
+      if (n) CHECK(std::memcmp(t.template col<uint8_t>(c), model[size_t(c)].data(), model[size_t(c)].size()) == 0);
+    }
+  }
+  int reserve(int64_t rows) {
+    const int rc = t.reserve(rows, "s");
+    if (!rc && rows > cap) cap = std::max<int64_t>({rows, 2 * cap, 1024});  // the documented rule, in rows
+    return rc;
+  }
+  // k rows past n (each cell one pseudo-random byte, repeated), counted only with `commit`
+  void write(int64_t k, bool commit) {
+    CHECK(n + k <= cap);
+    for (int c = 0; c < K; ++c)
+      for (int64_t r = n; r < n + k; ++r) {
+        salt = salt * 1664525u + 1013904223u;
+        std::memset(t.template col<uint8_t>(c) + size_t(r) * width[size_t(c)], int(salt >> 24), width[size_t(c)]);
+      }
+    if (!commit) return;
+    for (int c = 0; c < K; ++c) {
+      const uint8_t* p = t.template col<uint8_t>(c) + size_t(n) * width[size_t(c)];
+      model[size_t(c)].insert(model[size_t(c)].end(), p, p + size_t(k) * width[size_t(c)]);
+    }
+    t.commit(k);
+    n += k;
+  }
+  void truncate(int64_t rows) {
+    for (int c = 0; c < K; ++c) model[size_t(c)].resize(size_t(rows) * width[size_t(c)]);
+    t.truncate(rows);
+    n = rows;
+  }
+  std::array<void*, K> pointers() const {
+    std::array<void*, K> p;
+    for (int c = 0; c < K; ++c) p[size_t(c)] = t.template col<void>(c);
+    return p;
+  }
+};
+
+template <int K>
+static void check_table_script(std::array<size_t, K> width, uint32_t seed, int* n_growths) {
+  std::mt19937 rng(seed);
+  TableCheck<K> tc(width, seed);
+  tc.same();
+  const int steps = 8 + int(rng() % 16);
+  for (int k = 0; k < steps; ++k) {
+    const uint32_t op = rng() % 8;
+    if (op < 3) {  // a reserve at, next to or far from the capacity (also below n: a no-op)
+      const int64_t base[] = {0, tc.n, tc.cap, 2 * tc.cap, 1024};
+      const int64_t want = std::max<int64_t>(0, base[rng() % 5] + int64_t(rng() % 5) - 2 + (rng() % 8 == 0 ? 700 : 0));
+      const int64_t cap0 = tc.cap;
+      CHECK(tc.reserve(want) == 0);
+      *n_growths += tc.cap != cap0;
+    } else if (op < 7) {  // rows written into the room there is, most of them committed
+      const int64_t room = tc.cap - tc.n;
+      if (room) tc.write(rng() % 4 == 0 ? room : 1 + int64_t(rng() % uint32_t(std::min<int64_t>(room, 600))), rng() % 5 != 0);
+    } else if (tc.n) {  // a compaction's end: fewer rows count
+      tc.truncate(int64_t(rng() % uint32_t(tc.n + 1)));
+    }
+    tc.same();
+  }
+}
+
+// A growth of a K-column table with allocation 1 .. K failing in turn, then
+// the order of a successful growth's steps from TestMem's trace.
+template <int K>
+static void check_table_failures(std::array<size_t, K> width) {
+  TestMem::reset_counts();
+  {
+    TableCheck<K> tc(width, 77);
+    CHECK(tc.reserve(1) == 0 && tc.cap == 1024);
+    tc.write(1000, true);
+    for (int j = 1; j <= K; ++j) {
+      const auto before = tc.pointers();
+      // (TestMem counts a failed attempt as an allocation: j - 1 of them so far)
+      const int balance = TestMem::allocs - (j - 1) - TestMem::releases, allocs = TestMem::allocs;
+      const int copies = TestMem::copies, drains = TestMem::drains;
+      TestMem::fail_at = TestMem::allocs + j;
+      CHECK(tc.reserve(tc.cap + 1) == 7);
+      TestMem::fail_at = 0;
+      CHECK(tc.pointers() == before);
+      tc.same();  // n, cap and contents as they were
+      CHECK(TestMem::allocs == allocs + j && TestMem::allocs - j - TestMem::releases == balance);  // j - 1 new columns, released again
+      CHECK(TestMem::copies == copies && TestMem::drains == drains);  // nothing was enqueued or waited for
+      const int64_t cap0 = tc.cap;
+      CHECK(tc.reserve(tc.cap + 1) == 0 && tc.cap == 2 * cap0);        // the next reserve succeeds
+      tc.same();
+      tc.write(30, true);
+    }
+    // all allocations, then the copies, then the drain, then the swap (the old columns' release)
+    TestMem::log.clear();
+    TestMem::trace = true;
+    CHECK(tc.reserve(tc.cap + 1) == 0);
+    TestMem::trace = false;
+    std::vector<std::string> want;
+    for (const char* step : {"alloc", "copy"}) want.insert(want.end(), size_t(K), step);
+    want.push_back("drain s");
+    want.insert(want.end(), size_t(K), "release");
+    CHECK(TestMem::log == want);
+    tc.same();
+    // an empty table with columns: nothing to copy, the drain stays (the old columns may be in use)
+    tc.truncate(0);
+    TestMem::log.clear();
+    TestMem::trace = true;
+    CHECK(tc.reserve(tc.cap + 1) == 0);
+    TestMem::trace = false;
+    want.erase(want.begin() + K, want.begin() + 2 * K);
+    CHECK(TestMem::log == want);
+    // the first growth: columns only
+    TableCheck<K> fresh(width, 78);
+    TestMem::log.clear();
+    TestMem::trace = true;
+    CHECK(fresh.reserve(0) == 0 && TestMem::log.empty());  // nothing needed: nothing made
+    CHECK(fresh.reserve(5) == 0 && fresh.cap == 1024);
+    TestMem::trace = false;
+    CHECK(TestMem::log == std::vector<std::string>(size_t(K), "alloc"));
+    fresh.same();
+  }
+  CHECK(TestMem::allocs - K == TestMem::releases);  // the destructors released every column once (and the leak check)
+}
+
+static void check_row_table() {
+  int n_growths = 0, n_scripts = 0;
+  for (uint32_t seed = 0; seed < 3000; ++seed, ++n_scripts) {
+    TestMem::reset_counts();
+    const size_t W = size_t(1) << (seed % 7);  // the descriptor table's 8 W bytes, W = 1 .. 64
+    switch (seed % 3) {
+      case 0: check_table_script<4>({4, 4, 4, 1}, seed, &n_growths); break;       // observations
+      case 1: check_table_script<5>({24, 4, 4, 4, 1}, seed, &n_growths); break;   // points
+      default: check_table_script<2>({8 * W, 4}, seed, &n_growths); break;         // descriptor rows
+    }
+    CHECK(TestMem::allocs == TestMem::releases);
+  }
+  CHECK(n_growths > n_scripts);  // (growth is well exercised)
+  check_table_failures<4>({4, 4, 4, 1});
+  check_table_failures<5>({24, 4, 4, 4, 1});
+  check_table_failures<2>({512, 4});
+  std::printf("  RowTable: %d scripts of reserve / write / commit / truncate against a vector per column (%d growths); "
+              "each allocation of a growth failing in turn leaves it as it was; allocations, copies, drain, swap in order ok\n",
+              n_scripts, n_growths);
 }
 
 // ---- the LM trust-region state machine (sfm_amd/csrc/ba_lm.h) ----
@@ -1721,6 +1893,7 @@ int main() {
   check_owner();
   check_pool_rule();
   check_pool_failure_and_drains();
+  check_row_table();
 
   std::printf("asan: LM trust-region state machine (ba_lm.h)\n");
   check_lm_replay();
